@@ -9,10 +9,14 @@ executor slots + planner, then EVERY round (599): seed selection, seed occurrenc
 exchange (N>1), index build, index query + chaining, consensus, PAF.  Nothing is carried over between steps except the
 packed reads; the timed region is K consecutive jobs between two barriers.  `value` = PAF lines / wall time.
 The PCIe-inclusive rate (upload + packing of the ASCII reads added to every job) is reported beside it as
-`value_incl_upload`; the steady-state rate of the rounds alone as `rounds_only`.
-The PAF of the first job is checked against the committed oracle fixture (tests/golden_full/config2.json: SHA-256 over all
-3.9 M lines); every timed job must print the same number of lines.
-`roofline` describes the kernel with the largest accumulated time of a job.  Prints ONE JSON line on rank 0.
+`value_incl_upload`; the steady-state rate of the rounds alone as `rounds_only`.  Every timed job must print the same number
+of lines.  `roofline` describes the kernel with the largest accumulated time of a job.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the jobs and prints the line.  `--full` adds everything else, each outside the timed
+region: the first job's PAF against the committed oracle fixture (tests/golden_full/config2.json: SHA-256 over all 3.9 M lines)
+and the synthetic genome, the measured HBM stream rate, the legs (scan kernels, dense regime, the k = 10 job, `map` config 3),
+cpu_baseline and, for N > 1, the other multi-GPU layout (`alt_mode`).
+`--dump-outputs DIR` writes what the last timed job computed (its PAF as numbers, the reads' ignore flags) as .npy files.
 """
 import argparse
 import hashlib
@@ -27,6 +31,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 500000    # --dump-outputs: PAF lines kept row by row (a seeded sample when the job printed more)
+# secondary measurements that run with --full only, and their size there (0 = skip)
+FULL_DEFAULTS = {"cpu_rounds": 2, "scan_leg_rounds": 60, "dense_leg_rounds": 12, "dense_job": 1, "map_leg_repeats": 8}
 
 
 def launch_ranks(n):
@@ -74,21 +82,26 @@ def main():
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--seed-batch-size", type=int, default=10000)
     ap.add_argument("--max-rounds", type=int, default=-1, help="cut every job after this many rounds (experiments only)")
-    ap.add_argument("--cpu-rounds", type=int, default=2, help="oracle rounds timed for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and secondary measurement (fixture parity, ground truth, HBM stream rate, the legs, "
+                         "cpu_baseline, alt_mode); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64 / float32, at most 64 MB)")
+    ap.add_argument("--cpu-rounds", type=int, default=None, help="--full: oracle rounds timed for cpu_baseline (default 2, 0 = skip)")
     ap.add_argument("--slots", type=int, default=5, help="rounds executed concurrently per GPU (executor slots)")
-    ap.add_argument("--scan-leg-rounds", type=int, default=60,
-                    help="N=1: after the timed region, this many rounds with the scan kernels instead of the k-mer index "
+    ap.add_argument("--scan-leg-rounds", type=int, default=None,
+                    help="--full, N=1 (default 60): after the timed region, this many rounds with the scan kernels instead of the k-mer index "
                          "(reported as scan_kernels_leg with the count pass's achieved GB/s; 0 = skip)")
-    ap.add_argument("--dense-leg-rounds", type=int, default=12,
-                    help="N=1: after the timed region, this many rounds of the dense-seed regime (k=10) where the index query "
+    ap.add_argument("--dense-leg-rounds", type=int, default=None,
+                    help="--full, N=1 (default 12): after the timed region, this many rounds of the dense-seed regime (k=10) where the index query "
                          "carries real traffic (reported as index_query_dense; 0 = skip)")
-    ap.add_argument("--dense-job", type=int, default=1,
-                    help="N=1: after the timed region, ONE whole job with the command's default k = 10 on the same reads (every read indexed "
+    ap.add_argument("--dense-job", type=int, default=None,
+                    help="--full, N=1 (default 1): after the timed region, ONE whole job with the command's default k = 10 on the same reads (every read indexed "
                          "in every round), reported as overlap_default_k10_job with ground truth and first-16-round fixture parity (0 = skip)")
     ap.add_argument("--map-cpu-baseline", type=int, default=1,
                     help="map_config3: also time the oracle's mapper on the host (about 5 s, one core) as its cpu_baseline (0 = skip)")
-    ap.add_argument("--map-leg-repeats", type=int, default=8,
-                    help="N=1: after the timed region, BASELINE config 3 (`downpore map`: 50k reads x 8 kb against a 4.6 Mb circular "
+    ap.add_argument("--map-leg-repeats", type=int, default=None,
+                    help="--full, N=1 (default 8): after the timed region, BASELINE config 3 (`downpore map`: 50k reads x 8 kb against a 4.6 Mb circular "
                          "reference, k=11) this many times (value = the median of the runs after the first), reported as map_config3 with its PAF held to the oracle's fixture (0 = skip)")
     ap.add_argument("--mode", default="auto", choices=["auto", "round", "round-batch", "scan-shard"],
                     help="multi-GPU decomposition (N > 1).  scan-shard: every rank runs every round on its own read range and the "
@@ -98,6 +111,13 @@ def main():
                          "latency, so this is what scales while a GPU holds the reads and their k-mer index (9 B per base).  auto: "
                          "round if that fits in half of the GPU's memory, else scan-shard")
     args = ap.parse_args()
+    for name, size in FULL_DEFAULTS.items():
+        given = getattr(args, name)
+        if given and not args.full:
+            ap.error("--%s runs only with --full" % name.replace("_", "-"))
+        setattr(args, name, size if given is None and args.full else (given or 0))
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs writes what the last timed step computed: needs --steps >= 1")
 
     # --gpus N is the contract: N ranks, one per GPU.  Started under torch.distributed.run the ranks are there already
     # (WORLD_SIZE must then equal N); started plainly with N > 1 this process starts them itself - fresh child processes,
@@ -168,7 +188,7 @@ def main():
             # fits in half of the GPU's memory, the other one runs after it on the same reads and is reported as `alt_mode`.
             if 9 * N * L < hbm // 2:
                 args.mode = "round"
-                alt_mode_name = "scan-shard"
+                alt_mode_name = "scan-shard" if args.full else None
             else:
                 args.mode = "scan-shard"
     G = N * L // 20
@@ -201,8 +221,9 @@ def main():
     golden = golden_fixture(args)
     checks = {"fixture": golden["case"] if golden else None, "paf_sha256_matches_oracle_fixture": None, "jobs_with_equal_line_count": 0}
 
-    def job(verify=False):
-        """One whole job on the resident reads.  Returns (PAF lines, rounds, per-job kernel/phase totals, seconds of init)."""
+    def job(verify=False, capture=False):
+        """One whole job on the resident reads.  Returns (PAF lines, rounds, per-job kernel/phase totals, seconds of init).
+        capture: keep the job's PAF and ignore flags in res["outputs"] before the reset (its time in res["capture_s"])."""
         pipe.init()
         lines = rounds = 0
         t_prev = time.perf_counter()
@@ -227,13 +248,17 @@ def main():
             if golden is not None and args.max_rounds < 0:
                 checks["paf_sha256_matches_oracle_fixture"] = bool(hashlib.sha256(paf.encode()).hexdigest() == golden["paf_sha256"] and
                                                                    lines == golden["paf_lines"] and rounds == golden["rounds"])
+        if capture and rank == 0:
+            t_c = time.perf_counter()
+            res["outputs"] = (job_paf_bytes(pipe), reads.ignore())
+            res["capture_s"] = time.perf_counter() - t_c
         t_r = time.perf_counter()
         pipe.reset()
         res["reset_s"] = res.get("reset_s", 0.0) + (time.perf_counter() - t_r) if not verify else res.get("reset_s", 0.0)
         return lines, rounds, tot, t_init
 
     res = {}
-    verified = False
+    verified = not args.full  # (the first job's checks against the fixture and the genome run with --full)
     for _ in range(args.warmup):
         job(verify=not verified)
         verified = True
@@ -261,10 +286,10 @@ def main():
     acc, lines, rounds, t_init_sum, per_job, per_job_parts = {}, 0, 0, 0.0, [], []
     t_start = time.perf_counter()
     pcj = pc0
-    for _ in range(args.steps):
+    for i in range(args.steps):
         tj = time.perf_counter()
-        jl, jr, tot, ti = job()
-        per_job.append(time.perf_counter() - tj)
+        jl, jr, tot, ti = job(capture=args.dump_outputs is not None and i == args.steps - 1)
+        per_job.append(time.perf_counter() - tj - res.get("capture_s", 0.0))
         # (where a slow job lost its time: set-up, slots waiting for plans, the commit thread waiting for the formatters - ms)
         pcn = pipe_counters()
         per_job_parts.append([round(ti * 1e3, 2), round((pcn["slot_wait_for_plan_us"] - pcj["slot_wait_for_plan_us"]) / 1e3, 2),
@@ -279,10 +304,12 @@ def main():
             acc[key] = acc.get(key, 0.0) + v
         if lines == jl * len(per_job):
             checks["jobs_with_equal_line_count"] = len(per_job)
-    t_local = time.perf_counter() - t_start  # (this rank's own: before the barrier)
+    t_local = time.perf_counter() - t_start - res.get("capture_s", 0.0)  # (this rank's own: before the barrier)
     sync()
-    elapsed = time.perf_counter() - t_start
+    elapsed = time.perf_counter() - t_start - res.get("capture_s", 0.0)  # (--dump-outputs: the copy of the last job's output is not timed)
     cs1 = cpu_stat()
+    if "outputs" in res:
+        dump_outputs(args.dump_outputs, *res.pop("outputs"))
     # per-rank stage times of the timed jobs, gathered on rank 0 (so that a first multi-GPU run explains itself): set-up, rounds,
     # what this rank's planner and executor slots did
     pc1 = pipe_counters()
@@ -333,7 +360,7 @@ def main():
         map_leg = map_config3_leg(args.map_leg_repeats, cpu=bool(args.map_cpu_baseline))
 
     stream_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:  # measured HBM stream rate of this device (device-to-device copy, read + write counted), SURVEY 8(d)
             nb = 1 << 30
             a_ = torch.empty(nb, dtype=torch.uint8, device="cuda")
@@ -482,6 +509,41 @@ def k10_traffic():
         return {kk: v.get("hbm_bytes_per_launch") for kk, v in d.items() if v.get("hbm_bytes_per_launch")}
     except Exception:
         return None
+
+
+def job_paf_bytes(pipe):
+    """The whole PAF the job printed so far, as bytes."""
+    import ctypes as C
+    n = C.c_int64(0)
+    return C.string_at(pipe.H.dph_overlap_all_paf(pipe.h, C.byref(n)), n.value)
+
+
+def paf_table(paf):
+    """PAF text of the synthetic reads (names r%07d) as int64 rows of its 12 columns: query read, query length, start, end,
+    strand (1 = '+', 0 = '-'), target read, target length, start, end, matching bases, block length, mapping quality."""
+    text = paf.replace(b"\t+\t", b"\t1\t").replace(b"\t-\t", b"\t0\t").translate(None, b"r")
+    t = np.fromstring(text, dtype=np.int64, sep=" ") if paf.strip() else np.zeros(0, dtype=np.int64)
+    t = t.reshape(-1, 12)
+    assert len(t) == paf.count(b"\n"), "PAF with other than 12 numeric columns"
+    return t
+
+
+def dump_outputs(out_dir, paf, ignore):
+    """--dump-outputs: what one job computed, as .npy files of at most DUMP_LIMIT_BYTES together.
+    paf_lines_per_query_read  float64 [reads]     PAF lines of every query read (the whole PAF)
+    paf_column_sums           float64 [12]        every column of paf_table() summed over the whole PAF
+    paf_rows                  float64 [n, 12]     paf_table() rows: all of them, or a sample of DUMP_SAMPLE_ROWS (rng seed 0, in order)
+    ignore_flags              float32 [reads]     the reads' ignore flags at the end of the job"""
+    t = paf_table(paf)
+    per_read = np.bincount(t[:, 0], minlength=len(ignore)).astype(np.float64)
+    fixed = per_read.nbytes + 12 * 8 + ignore.size * 4 + 4 * 128  # (128: an .npy header)
+    keep = max(0, min(len(t), DUMP_SAMPLE_ROWS, (DUMP_LIMIT_BYTES - fixed) // (12 * 8)))
+    rows = t if keep == len(t) else t[np.sort(np.random.default_rng(0).choice(len(t), size=keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "paf_lines_per_query_read.npy"), per_read)
+    np.save(os.path.join(out_dir, "paf_column_sums.npy"), t.sum(axis=0).astype(np.float64))
+    np.save(os.path.join(out_dir, "paf_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "ignore_flags.npy"), ignore.astype(np.float32))
 
 
 def ground_truth(paf, off, starts, strands, k, sample=200000):

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ def _line(out):
 
 
 def test_bench_single_gpu_contract():
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-rounds", "0", "--scan-leg-rounds", "0",
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--cpu-rounds", "0", "--scan-leg-rounds", "0",
                         "--dense-leg-rounds", "0"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -28,11 +29,32 @@ def test_bench_single_gpu_contract():
     assert "workload" in d["config"]
 
 
+def test_bench_plain_run_times_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps jobs, runs none of the secondary measurements, and --dump-outputs writes the
+    last timed job's output: the whole config-2 PAF as per-read line counts (summing to the oracle fixture's line count)."""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _line(p.stdout)
+    assert d["steps"] == 2 and len(d["job_breakdown_s"]["per_job"]) == 2 and d["ms_per_step"] > 0
+    assert d["metric"].startswith("overlaps/sec") and d["unit"] == "overlaps/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["parity"]["paf_sha256_matches_oracle_fixture"] is None and d["ground_truth"] is None and "cpu_baseline" not in d
+    assert d["map_config3"] is None and d["overlap_default_k10_job"] is None and d["roofline"]["measured_stream_GBs"] is None
+    files = {f: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert set(files) == {"paf_lines_per_query_read.npy", "paf_column_sums.npy", "paf_rows.npy", "ignore_flags.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), f)) for f in files) <= 64 << 20
+    g = json.load(open(os.path.join(ROOT, "tests", "golden_full", "config2.json")))
+    per_read = files["paf_lines_per_query_read.npy"]
+    assert len(per_read) == g["generator"]["reads"] and per_read.sum() == g["paf_lines"] == d["paf_lines"] / 2
+    assert files["paf_rows.npy"].shape == (500000, 12) and files["ignore_flags.npy"].sum() == g["ignored_reads"]
+
+
 @pytest.mark.parametrize("mode", ["round", "scan-shard"])
 def test_bench_two_ranks_sharing_the_gpu(mode):
     env = dict(os.environ, DP_BENCH_SAME_DEVICE="1", DP_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29517", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-rounds", "0", "--mode", mode,
+                        "--master-port", "29517", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--cpu-rounds", "0", "--mode", mode,
                         "--slots", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -46,7 +68,7 @@ def test_bench_two_ranks_default_reports_both_layouts():
     `alt_mode`; each is held to the fixture on its own."""
     env = dict(os.environ, DP_BENCH_SAME_DEVICE="1", DP_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29518", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-rounds", "0", "--slots", "4"],
+                        "--master-port", "29518", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--cpu-rounds", "0", "--slots", "4"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -61,7 +83,7 @@ def test_bench_plain_launch_starts_its_own_ranks():
     process that has not touched the GPU), relays rank 0's line and the exit code."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DP_BENCH_SAME_DEVICE="1", DP_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-rounds", "0", "--mode", "round",
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--cpu-rounds", "0", "--mode", "round",
                         "--slots", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)
@@ -75,7 +97,7 @@ def test_bench_two_gpus_over_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29519", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-rounds", "0"],
+                        "--master-port", "29519", "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--cpu-rounds", "0"],
                        cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p.stdout)

@@ -9,7 +9,7 @@
 mkdir -p gpurun_out/r04; cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 R=gpurun_out/r04
 rm -rf $R/ktrace
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/ktrace -- python3 bench.py > $R/ktrace_bench.json 2> $R/ktrace_bench.err; echo "ktrace rc=$?"
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/ktrace -- python3 bench.py --full > $R/ktrace_bench.json 2> $R/ktrace_bench.err; echo "ktrace rc=$?"
 t=$(find $R/ktrace -name "*kernel_trace.csv" | head -1)
 [ -n "$t" ] && python3 tools/ktrace_digest.py $t > $R/bench_default_kernel_trace_digest.txt
 f=$(find $R/ktrace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $R/bench_default_kernel_stats.csv

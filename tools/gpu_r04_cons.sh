@@ -14,7 +14,7 @@ print("mean/max per phase (median over rounds): gather %s/%s trim %s/%s shared+r
 print("general steps per window: before scan %s scan %s selection %s update %s us | runs %s" % tuple(
     med(r"before the scan ([\d.]+) us, scan ([\d.]+), selection ([\d.]+), update ([\d.]+) \| scan runs ([\d.]+)", 5)))
 PY
-DP_CONS_DEBUG= python3 bench.py --steps 2 --warmup 1 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 2>/dev/null | python3 -c "
+DP_CONS_DEBUG= python3 bench.py --full --steps 2 --warmup 1 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('one slot: ms/round', j['rounds_only']['ms_per_round'], 'parity', j['parity']['paf_sha256_matches_oracle_fixture'], 'k_cons_ms per job', j['per_rank'][0]['kernel_ms_per_job']['k_cons_ms'])"

@@ -4,7 +4,7 @@ R=gpurun_out/r05; mkdir -p $R
 C="--gpus 1 --steps 12 --warmup 3 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --dense-job 0 --map-leg-repeats 0"
 for rep in $(seq 1 ${REPS:-3}); do
 for v in "$@"; do
-  env $v timeout 600 python bench.py $C > $R/ab12.json 2>/dev/null
+  env $v timeout 600 python bench.py --full $C > $R/ab12.json 2>/dev/null
   python3 - "$v" <<'PY'
 import json,sys
 d=json.loads([l for l in open('gpurun_out/r05/ab12.json') if l.startswith('{')][-1])

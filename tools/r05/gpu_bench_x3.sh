@@ -2,7 +2,7 @@
 # the driver's bench command three times on one box (last code state)
 R=gpurun_out/r05; mkdir -p $R
 for i in 1 2 3; do
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/bench_final_run$i.json 2>/dev/null
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $R/bench_final_run$i.json 2>/dev/null
 python3 - $i <<'PY'
 import json,sys
 i=sys.argv[1]

@@ -13,7 +13,7 @@ for v in 0 1; do
   rm -rf $R/kt1
 done
 for v in 0 1; do
-  DP_KX_BINS=$v DP_KX_ONESHOT_DEBUG=1 python3 bench.py --steps 1 --warmup 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 12 --map-leg-repeats 0 2> $R/dense_bins$v.err > $R/dense_bins$v.json
+  DP_KX_BINS=$v DP_KX_ONESHOT_DEBUG=1 python3 bench.py --full --steps 1 --warmup 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 12 --map-leg-repeats 0 2> $R/dense_bins$v.err > $R/dense_bins$v.json
   python3 - <<PY
 import json
 d=json.loads([l for l in open('$R/dense_bins$v.json') if l.startswith('{')][-1])

@@ -19,13 +19,13 @@ for v in before after before after; do
   if [ $v = before ]; then export DP_LIB_DIR=$PWD/downpore_amd/lib_before; else unset DP_LIB_DIR; fi
   DP_CONS_DEBUG=1 timeout 600 python3 bench.py --steps 1 --warmup 0 --max-rounds 40 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2> $R/cons_debug_$v.txt > /dev/null
   echo "$v: $(digest $R/cons_debug_$v.txt)"
-  timeout 600 python3 bench.py --steps 3 --warmup 1 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null | python3 -c "
+  timeout 600 python3 bench.py --full --steps 3 --warmup 1 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('   one slot: ms/round %.4f parity %s k_cons_ms per job %.2f' % (j['rounds_only']['ms_per_round'], j['parity']['paf_sha256_matches_oracle_fixture'], j['per_rank'][0]['kernel_ms_per_job']['k_cons_ms']))"
 done
 unset DP_LIB_DIR
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null > $R/bench_per_job_parts.json
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null > $R/bench_per_job_parts.json
 python3 - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r05/bench_per_job_parts.json') if l.startswith('{')][-1])

@@ -3,7 +3,7 @@
 R=gpurun_out/r05; mkdir -p $R
 timeout 2400 python -m pytest tests/ -x -q -m gpu --durations=8 > $R/gpu_suite_final.log 2>&1; echo "suite rc $?"; grep -E "passed|failed|error" $R/gpu_suite_final.log | tail -3
 for i in 1 2 3; do timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $R/smoke_$i.log 2>&1; echo "smoke $i rc $? $(tail -1 $R/smoke_$i.log)"; done
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/bench_driver_style.json 2> $R/bench_driver_style.err; echo "bench rc $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $R/bench_driver_style.json 2> $R/bench_driver_style.err; echo "bench rc $?"
 python3 - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r05/bench_driver_style.json') if l.startswith('{')][-1])

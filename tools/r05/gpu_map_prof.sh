@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-phase wave timers of map_kernel (PROF build) over config 3
 R=gpurun_out/r05; mkdir -p $R
-DP_LIB_DIR=$PWD/downpore_amd/lib_prof DP_MAP_PROF=1 DP_MAP_THREADS=1 timeout 600 python3 bench.py --steps 1 --warmup 0 --max-rounds 2 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --dense-job 0 --map-leg-repeats 1 --map-cpu-baseline 0 > $R/map_prof.json 2> $R/map_prof.err
+DP_LIB_DIR=$PWD/downpore_amd/lib_prof DP_MAP_PROF=1 DP_MAP_THREADS=1 timeout 600 python3 bench.py --full --steps 1 --warmup 0 --max-rounds 2 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --dense-job 0 --map-leg-repeats 1 --map-cpu-baseline 0 > $R/map_prof.json 2> $R/map_prof.err
 grep "map prof" $R/map_prof.err | head -3
 python3 - <<'PY'
 import re

@@ -4,7 +4,7 @@ R=gpurun_out/r05; mkdir -p $R
 DP_LIB_DIR=$PWD/downpore_amd/lib_p5 DP_CONS_DEBUG=1 timeout 600 python3 bench.py --steps 1 --warmup 0 --max-rounds 40 --slots 1 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2> $R/cons_p5.txt > /dev/null
 grep "contig+paf, us" $R/cons_p5.txt | tail -4
 grep "slowest window" $R/cons_p5.txt | tail -3
-timeout 600 python3 bench.py --gpus 1 --steps 30 --warmup 5 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null > $R/bench_per_job_parts.json
+timeout 600 python3 bench.py --full --gpus 1 --steps 30 --warmup 5 --cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0 --dense-job 0 2>/dev/null > $R/bench_per_job_parts.json
 python3 - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r05/bench_per_job_parts.json') if l.startswith('{')][-1])

@@ -12,7 +12,7 @@ PY
 done
 rm -f $R/slots.json
 for i in 1 2; do
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/bench_driver_style_$i.json 2> /dev/null; echo "bench rc $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $R/bench_driver_style_$i.json 2> /dev/null; echo "bench rc $?"
 python3 - $i <<'PY'
 import json,sys
 d=json.loads([l for l in open('gpurun_out/r05/bench_driver_style_%s.json' % sys.argv[1]) if l.startswith('{')][-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 R=gpurun_out/r06; mkdir -p $R
-timeout 900 python3 bench.py --steps 3 --warmup 1 --map-leg-repeats 0 --scan-leg-rounds 0 --cpu-rounds 0 > $R/bench_quick.json 2> $R/bench_quick.err; echo rc=$?
+timeout 900 python3 bench.py --full --steps 3 --warmup 1 --map-leg-repeats 0 --scan-leg-rounds 0 --cpu-rounds 0 > $R/bench_quick.json 2> $R/bench_quick.err; echo rc=$?
 python3 - <<'PY'
 import json
 j=json.loads([l for l in open("gpurun_out/r06/bench_quick.json") if l.startswith("{")][-1])

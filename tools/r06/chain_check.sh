@@ -5,11 +5,11 @@ timeout 900 python3 -m pytest tests/test_gpu_kernels.py tests/test_gpu_overlap_e
 timeout 600 python3 -m pytest tests/test_gpu_flag_matrix.py -m gpu -x -q 2>&1 | tail -3
 OFF="--cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --dense-job 0 --map-leg-repeats 0"
 for s in 1 5; do
-  timeout 300 python3 bench.py --k 10 --steps 2 --warmup 1 --slots $s $OFF > $R/k10_chainfix_slots$s.json 2> $R/k10_chainfix_slots$s.err; echo "k10 slots $s rc=$?"
+  timeout 300 python3 bench.py --full --k 10 --steps 2 --warmup 1 --slots $s $OFF > $R/k10_chainfix_slots$s.json 2> $R/k10_chainfix_slots$s.err; echo "k10 slots $s rc=$?"
 done
 for v in 1 9; do
-  DP_CHAIN_FULL_FROM=$v timeout 300 python3 bench.py --steps 5 --warmup 2 $OFF > $R/k13_fullfrom$v.json 2> $R/k13_fullfrom$v.err; echo "k13 full_from $v rc=$?"
-  DP_CHAIN_FULL_FROM=$v timeout 300 python3 bench.py --k 10 --steps 2 --warmup 1 $OFF > $R/k10_fullfrom$v.json 2> $R/k10_fullfrom$v.err; echo "k10 full_from $v rc=$?"
+  DP_CHAIN_FULL_FROM=$v timeout 300 python3 bench.py --full --steps 5 --warmup 2 $OFF > $R/k13_fullfrom$v.json 2> $R/k13_fullfrom$v.err; echo "k13 full_from $v rc=$?"
+  DP_CHAIN_FULL_FROM=$v timeout 300 python3 bench.py --full --k 10 --steps 2 --warmup 1 $OFF > $R/k10_fullfrom$v.json 2> $R/k10_fullfrom$v.err; echo "k10 full_from $v rc=$?"
 done
 python3 - <<'PY'
 import json,glob

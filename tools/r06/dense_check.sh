@@ -5,7 +5,7 @@ OFF="--cpu-rounds 0 --scan-leg-rounds 0 --dense-leg-rounds 0 --map-leg-repeats 0
 for v in 0 1 0 1; do
   for s in 1 5; do
     [ $v = 0 ] && export DP_KX_DENSE=0 || unset DP_KX_DENSE
-    timeout 300 python3 bench.py --steps 1 --warmup 1 --slots $s $OFF --dense-job 1 2>/dev/null | python3 -c "
+    timeout 300 python3 bench.py --full --steps 1 --warmup 1 --slots $s $OFF --dense-job 1 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 d=j['overlap_default_k10_job']
