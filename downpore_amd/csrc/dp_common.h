@@ -146,6 +146,16 @@ struct dp_ctx {
     bool map_stage_valid = false;  // dp_map_windows_shard: the query stage of the forward pass is reused by the reverse pass
     uint32_t word_base = 0, global_n_seqs = 0;  // dp_index_set_global: this index is the words [word_base, word_base + W) of a larger one
     DevBuf d_seqrefs, d_posting, d_seedsets, d_pmeta;  // pmeta: uint32 {count,start,end,lens} per seed
+    // the sparse layout of the same index (dp_index_build_sparse, dp_sparse.hip): sorted id lists instead of the two bit matrices
+    //   post_off uint64 [S + 1], post_ids uint32 [entries]: per seed, its chunks ascending
+    //   set_off  uint64 [M + 1], set_ids  uint32 [entries]: per chunk, its distinct seeds ascending
+    //   sp_segs: the chunks' segments, copied out of the scan buffer (window scans reuse that one)
+    bool index_sparse = false;
+    DevBuf d_sp_post_off, d_sp_post_ids, d_sp_set_off, d_sp_set_ids, d_sp_segs;
+    uint64_t sp_entries = 0;
+    dp_ctx* index_src = nullptr;  // dp_index_borrow: the context whose sparse index this one reads (its reads' owner)
+    DevBuf d_wlist;               // sparse map: the windows' seeds ascending, at qoff / 2
+    uint64_t map_regimes[4] = {0, 0, 0, 0};  // dp_map_windows queries by regime: 4/8-ladder, 16-ladder, exact count, more than 512 sets
 
     // ---- overlaps (A14..A8)
     DevBuf d_seeds_applied;     // the seed list currently written into d_bits / d_kmap (they are brought up to date lazily)
@@ -302,6 +312,13 @@ int dp_find_complete(dp_ctx* ctx, bool* reran);
 void dp_find_stats(const dp_ctx* ctx, double* query_ms, double* chain_ms, uint64_t* query_bytes, uint64_t* chain_bytes);
 int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t** d_qmeta_out,
                    uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out, uint32_t** d_qcnt_out = nullptr);
+// the context that holds the sparse index this one queries (itself, or the one it borrows from)
+static inline const dp_ctx* dp_index_of(const dp_ctx* ctx) { return ctx->index_src ? ctx->index_src : ctx; }
+// device bytes of a context's own sparse index (dp_sparse.hip)
+uint64_t dp_index_sparse_bytes(const dp_ctx* ctx);
+// dp_index_posting_row (side 0) / dp_index_seedset_row (side 1) of a sparse index: the row's ids expanded into words
+int dp_index_sparse_row(dp_ctx* ctx, int side, uint32_t row, uint64_t* words, uint32_t cap_words, uint32_t* n_words, uint32_t* count,
+                        uint32_t* start, uint32_t* end);
 
 // ---- device helpers ---------------------------------------------------------------------------------------
 // An entry of the resident k-mer position index (dp_kindex.hip; written by dp_kbuild.hip): fmt 8 = read << 32 | position in a

@@ -59,6 +59,27 @@ static __host__ __device__ inline size_t m_big_words(size_t qcap, size_t tcap) {
 }
 
 __device__ __forceinline__ bool m_contains(const u64* __restrict__ set, int32_t x) { return (set[x >> 6] >> (x & 63)) & 1ull; }
+// a sorted id list (the sparse index's seed-set rows, the windows' seed lists): membership by binary search
+struct MList {
+    const uint32_t* ids;
+    uint32_t n;
+};
+__device__ __forceinline__ bool m_has(const u64* __restrict__ set, int32_t x) { return m_contains(set, x); }
+__device__ __forceinline__ bool m_has(const MList& l, int32_t x) {
+    uint32_t lo = 0, hi = l.n;
+    while (lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (l.ids[m] < (uint32_t)x) lo = m + 1;
+        else hi = m;
+    }
+    return lo < l.n && l.ids[lo] == (uint32_t)x;
+}
+// map_kernel<BIG, true>: the sparse index's seed-set rows and the windows' seed lists (dp_index_build_sparse)
+struct MapSparse {
+    const uint64_t* set_off;
+    const uint32_t* set_ids;
+    const uint32_t* wl;  // window w's seeds ascending at wl + woff[w] / 2
+};
 
 // SeedSequence.Reduced (seeds/sequence.go:85-123).  Returns the number of reduced seeds or -1 if < minSeeds.
 // err bit 1: LDS capacity.
@@ -103,8 +124,8 @@ __device__ int m_reduce(const int32_t* __restrict__ seg, int n, const u64* __res
 // it is whitelisted and differs from the last KEPT seed; a whitelisted seed is dropped only when it equals the last kept one, which
 // then stays what it was - so "differs from the previous whitelisted seed" decides, and all lanes decide at once.  The gap written
 // before kept seed a (previous kept seed p, or -1) is sum_{t=p+1..a} gap_t + k (a - p - 1): prefix sums of the gaps.
-template <typename IDX>
-__device__ int m_reduce_wave(const int32_t* __restrict__ seg, int n, const u64* __restrict__ whitelist, int k, int minSeeds, int32_t* out,
+template <typename IDX, class SET>
+__device__ int m_reduce_wave(const int32_t* __restrict__ seg, int n, SET whitelist, int k, int minSeeds, int32_t* out,
                              IDX* index, int cap, uint32_t* err) {
     const int lane = dp_lane();
     const u64 below = (1ull << lane) - 1ull;
@@ -117,7 +138,7 @@ __device__ int m_reduce_wave(const int32_t* __restrict__ seg, int n, const u64* 
         const bool valid = sI < nS;
         const int seed = valid ? seg[2 * sI + 1] : -1;
         const int gap = valid ? seg[2 * sI] : 0;
-        const bool c = valid && m_contains(whitelist, seed);
+        const bool c = valid && m_has(whitelist, seed);
         const u64 cmask = __ballot(c);
         const u64 cb = cmask & below;
         const int srcC = cb ? 63 - __builtin_clzll(cb) : 0;
@@ -417,7 +438,7 @@ __device__ __forceinline__ uint32_t m_ld16_agent(const uint16_t* p) {
 }
 
 // cursor: [0] records, [1] ints, [2] error bits, [3] overflow flag, [8..9] algorithmic bytes
-template <bool BIG>
+template <bool BIG, bool SPARSE = false>
 __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __restrict__ wsegs, const u64* __restrict__ woff,
                                                            const uint32_t* __restrict__ wlen, uint32_t n_pairs,
                                                            const u64* __restrict__ wsets, const uint32_t* __restrict__ qmeta,
@@ -429,7 +450,7 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
                                                            int32_t* __restrict__ mb, uint32_t int_cap, uint32_t* __restrict__ cursor,
                                                            int phase, int32_t* __restrict__ thr_io, int one_lane,
                                                            const u64* __restrict__ words_read, unsigned long long* __restrict__ prof,
-                                                           uint32_t* __restrict__ big_ws, uint32_t big_q, uint32_t big_t) {
+                                                           uint32_t* __restrict__ big_ws, uint32_t big_q, uint32_t big_t, MapSparse sp) {
     // phase 2: both strands of every window pair, thresholds from the windows themselves (the whole index is here).
     // phase 0 / 1 (the index is one shard of the reference, dp_map_windows_shard): only the forward / only the reverse-complement
     // windows, starting from the thresholds the previous shard left in thr_io[pair][2] (< 0: none yet) and leaving its own there.
@@ -496,6 +517,7 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
             const int qN = (int)(woff[w + 1] - woff[w]);
             const int qLen = (int)wlen[w];
             const u64* qset = wsets + (uint64_t)w * SW;
+            const MList qlist = {SPARSE ? sp.wl + woff[w] / 2 : nullptr, (uint32_t)(qN / 2)};
             if (qmeta[4 * w + 0] < 5 || qmeta[4 * w + 2]) continue;  // Matches() returned nothing
             if (words_read) algb += 8ull * words_read[w];
             for (uint32_t wi = 0; wi < W; wi++) {
@@ -506,9 +528,18 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
                     const uint32_t t = wi * 64 + (uint32_t)b;
                     const u64* tset = seedsets + (uint64_t)t * SW;
                     int c = 0;
-                    for (uint32_t x = lane; x < SW; x += 64) c += __popcll(tset[x] & qset[x]);
+                    MList tlist = {nullptr, 0u};
+                    if constexpr (SPARSE) {
+                        // |chunk seeds ∩ window seeds|: the chunk's distinct seeds looked up in the window's list
+                        const uint64_t a = sp.set_off[t];
+                        tlist = {sp.set_ids + a, (uint32_t)(sp.set_off[t + 1] - a)};
+                        for (uint32_t x = lane; x < tlist.n; x += 64) c += m_has(qlist, (int32_t)tlist.ids[x]) ? 1 : 0;
+                        algb += 4ull * (tlist.n + qlist.n) + 4ull;
+                    } else {
+                        for (uint32_t x = lane; x < SW; x += 64) c += __popcll(tset[x] & qset[x]);
+                        algb += 16ull * SW + 4ull;
+                    }
                     c = wave_sum(c);
-                    algb += 16ull * SW + 4ull;
                     MP_TICK(0)  // candidate word walk + prefilter (two set rows per candidate)
                     if (c < thr[s]) continue;  // CountIntersectionTo(seedSet, min) < min (:521, :560)
                     const dp_seq_ref r = refs[t];
@@ -519,9 +550,16 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
                     uint32_t err = 0;
                     // Match (:361-394): s = seq.Reduced(querySet), q = query.Reduced(seqSet) - on all 64 lanes
                     const int minMatch = thr[s];
-                    const int nT = m_reduce_wave<uint16_t>(tSeg, tN, qset, k, minMatch, L.t, L.tIdx, L.tmax(), &err);
-                    MP_TICK(1)  // Reduced() of the target chunk
-                    const int nQ = nT < 0 ? -1 : m_reduce_wave<uint16_t>(qSeg, qN, tset, k, minMatch, L.q, L.qIdx, L.qmax(), &err);
+                    int nT, nQ;
+                    if constexpr (SPARSE) {
+                        nT = m_reduce_wave<uint16_t>(tSeg, tN, qlist, k, minMatch, L.t, L.tIdx, L.tmax(), &err);
+                        MP_TICK(1)  // Reduced() of the target chunk
+                        nQ = nT < 0 ? -1 : m_reduce_wave<uint16_t>(qSeg, qN, tlist, k, minMatch, L.q, L.qIdx, L.qmax(), &err);
+                    } else {
+                        nT = m_reduce_wave<uint16_t>(tSeg, tN, qset, k, minMatch, L.t, L.tIdx, L.tmax(), &err);
+                        MP_TICK(1)  // Reduced() of the target chunk
+                        nQ = nT < 0 ? -1 : m_reduce_wave<uint16_t>(qSeg, qN, tset, k, minMatch, L.q, L.qIdx, L.qmax(), &err);
+                    }
                     MP_TICK(2)  // Reduced() of the query window
                     // dynamicMatch: the probes on 64 lanes, the walk's decisions on lane 0 (DP_MAP_ONE_LANE=1: all of it on lane 0 as
                     // before round 4)
@@ -798,7 +836,8 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     uint32_t mc_n = 0;
     uint32_t* d_qcnt_unused = nullptr;
     int rc = DP_OK;
-    if (phase == 1 && ctx->map_stage_windows == nw && ctx->map_stage_valid) {
+    const bool reused = phase == 1 && ctx->map_stage_windows == nw && ctx->map_stage_valid;
+    if (reused) {
         // the reverse pass of a shard follows its forward pass on the same windows: the query stage's results are still there
         d_qmeta = (uint32_t*)ctx->d_qmeta.p;
     } else {
@@ -841,6 +880,11 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     }
 #endif
     const int one_lane = dp_tune("map_one_lane", 0) ? 1 : 0;  // (tests: dynamicMatch on one lane)
+    // a sparse index (its own or borrowed): seed-set rows, chunk views and segments from the index's context, window lists from the query stage
+    const bool sparse = ctx->index_sparse;
+    const dp_ctx* ix = dp_index_of(ctx);
+    MapSparse sp = {nullptr, nullptr, nullptr};
+    if (sparse) sp = {(const uint64_t*)ix->d_sp_set_off.p, (const uint32_t*)ix->d_sp_set_ids.p, (const uint32_t*)ctx->d_wlist.p};
     for (;;) {
         if (dev_reserve(ctx, ctx->d_mrec, (size_t)rec_cap * sizeof(MapRec))) return DP_ERR_HIP;
         if (dev_reserve(ctx, ctx->d_ma, (size_t)int_cap * 4)) return DP_ERR_HIP;
@@ -848,13 +892,26 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
         DP_HIP(hipMemsetAsync(ctx->d_cursor.p, 0, 64, ctx->stream));
         if (d_mprof) DP_HIP(hipMemsetAsync(d_mprof, 0, 16 * 8, ctx->stream));
         DP_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        if (!big)
+        if (sparse && !big)
+            hipLaunchKernelGGL((map_kernel<false, true>), dim3(blocks), dim3(64 * M_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev,
+                               (const uint32_t*)ctx->d_sched.p, n_pairs, (const u64*)nullptr, (const uint32_t*)d_qmeta, (const u64*)ctx->d_cand.p,
+                               (const dp_seq_ref*)ix->d_seqrefs.p, (const int32_t*)ix->d_sp_segs.p, (const u64*)nullptr, W, 0u, k, poolA, poolB,
+                               poolLen, (MapRec*)ctx->d_mrec.p, rec_cap, (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, int_cap,
+                               (uint32_t*)ctx->d_cursor.p, phase, d_thr, one_lane, (const u64*)d_words, d_mprof, (uint32_t*)nullptr, 0u, 0u, sp);
+        else if (sparse)
+            hipLaunchKernelGGL((map_kernel<true, true>), dim3(big_blocks), dim3(64 * M_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev,
+                               (const uint32_t*)ctx->d_sched.p, n_pairs, (const u64*)nullptr, (const uint32_t*)d_qmeta, (const u64*)ctx->d_cand.p,
+                               (const dp_seq_ref*)ix->d_seqrefs.p, (const int32_t*)ix->d_sp_segs.p, (const u64*)nullptr, W, 0u, k, poolA, poolB,
+                               poolLen, (MapRec*)ctx->d_mrec.p, rec_cap, (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, int_cap,
+                               (uint32_t*)ctx->d_cursor.p, phase, d_thr, one_lane, (const u64*)d_words, d_mprof, (uint32_t*)ctx->d_qbig.p, big_q,
+                               big_t, sp);
+        else if (!big)
             hipLaunchKernelGGL(map_kernel<false>, dim3(blocks), dim3(64 * M_WAVES), 0, ctx->stream, ctx->qsegs_dev,
                                ctx->qoff_dev, (const uint32_t*)ctx->d_sched.p, n_pairs, (const u64*)ctx->d_qsets.p,
                                (const uint32_t*)d_qmeta, (const u64*)ctx->d_cand.p, (const dp_seq_ref*)ctx->d_seqrefs.p,
                                (const int32_t*)ctx->d_segs.p, (const u64*)ctx->d_seedsets.p, W, SW, k, poolA, poolB, poolLen,
                                (MapRec*)ctx->d_mrec.p, rec_cap, (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, int_cap,
-                               (uint32_t*)ctx->d_cursor.p, phase, d_thr, one_lane, (const u64*)d_words, d_mprof, (uint32_t*)nullptr, 0u, 0u);
+                               (uint32_t*)ctx->d_cursor.p, phase, d_thr, one_lane, (const u64*)d_words, d_mprof, (uint32_t*)nullptr, 0u, 0u, sp);
         else
             hipLaunchKernelGGL(map_kernel<true>, dim3(big_blocks), dim3(64 * M_WAVES), 0, ctx->stream, ctx->qsegs_dev,
                                ctx->qoff_dev, (const uint32_t*)ctx->d_sched.p, n_pairs, (const u64*)ctx->d_qsets.p,
@@ -862,7 +919,7 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
                                (const int32_t*)ctx->d_segs.p, (const u64*)ctx->d_seedsets.p, W, SW, k, poolA, poolB, poolLen,
                                (MapRec*)ctx->d_mrec.p, rec_cap, (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, int_cap,
                                (uint32_t*)ctx->d_cursor.p, phase, d_thr, one_lane, (const u64*)d_words, d_mprof, (uint32_t*)ctx->d_qbig.p,
-                               big_q, big_t);
+                               big_q, big_t, sp);
         DP_HIP(hipGetLastError());
         DP_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
         DP_HIP(hipMemcpyAsync(cur, ctx->d_cursor.p, 64, hipMemcpyDeviceToHost, ctx->stream));
@@ -924,6 +981,11 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     DP_HIP(hipMemcpy(qm.data(), d_qmeta, (size_t)nw * 16, hipMemcpyDeviceToHost));
     for (uint32_t w = 0; w < nw; w++)
         if (qm[4 * w + 2] & 1) return dp_fail(ctx, DP_ERR_CAPACITY, "window with more than 65535 usable seeds");
+    // queries that reached the gather, by regime (dp_index_info): more than Q_MAXSETS (512) sets, else by minCount
+    if (!reused)
+        for (uint32_t w = 0; w < nw; w++)
+            if (qm[4 * w + 0] >= 5 && qm[4 * w + 2] == 0)
+                ctx->map_regimes[qm[4 * w + 0] > 512 ? 3 : qm[4 * w + 1] <= 12 ? 0 : qm[4 * w + 1] <= 24 ? 1 : 2]++;
     const uint32_t nm = cur[0], ni = cur[1];
     if (pin_reserve(ctx, ctx->h_mrec, (size_t)nm * sizeof(MapRec) + 16)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_ma, (size_t)ni * 4 + 16)) return DP_ERR_HIP;

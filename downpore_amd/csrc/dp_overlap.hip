@@ -188,6 +188,8 @@ int dp_index_build_impl(dp_ctx* ctx, const dp_seq_ref* seqs, uint32_t n_seqs) {
     ctx->word_base = 0;  // (a fresh index is a whole one until dp_index_set_global says otherwise)
     ctx->global_n_seqs = 0;
     ctx->chunks_on_device = false;
+    ctx->index_sparse = false;
+    ctx->index_src = nullptr;
     if (dev_reserve(ctx, ctx->d_seqrefs, (size_t)n_seqs * sizeof(dp_seq_ref) + 16)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_posting, (size_t)S * W * 8 + 64)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_seedsets, (size_t)n_seqs * SW * 8 + 64)) return DP_ERR_HIP;
@@ -513,6 +515,8 @@ static int index_chunked_launch(dp_ctx* ctx, int64_t chunk_size, int64_t overlap
     ctx->word_base = 0;
     ctx->global_n_seqs = 0;
     ctx->chunks_on_device = true;
+    ctx->index_sparse = false;
+    ctx->index_src = nullptr;
     if (dev_reserve(ctx, ctx->d_seqrefs, (size_t)cap * sizeof(dp_seq_ref) + 16)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_chunk_meta, (size_t)cap * sizeof(dp_seq_meta) + 16)) return DP_ERR_HIP;
     const uint32_t n_tiles = (n_survivors + 1023) / 1024;
@@ -723,6 +727,7 @@ extern "C" int dp_index_set_global(dp_ctx* ctx, const uint32_t* meta_global, uin
 extern "C" int dp_index_posting_row(dp_ctx* ctx, uint32_t seed, u64* words, uint32_t cap_words, uint32_t* n_words,
                                     uint32_t* count, uint32_t* start, uint32_t* end) {
     if (!ctx || seed >= ctx->n_seeds || cap_words < ctx->W) return DP_ERR_ARG;
+    if (ctx->index_sparse) return dp_index_sparse_row(ctx, 0, seed, words, cap_words, n_words, count, start, end);
     hipSetDevice(ctx->device);
     uint32_t meta[4];
     DP_HIP(hipMemcpy(words, (u64*)ctx->d_posting.p + (uint64_t)seed * ctx->W, (size_t)ctx->W * 8, hipMemcpyDeviceToHost));
@@ -735,6 +740,7 @@ extern "C" int dp_index_posting_row(dp_ctx* ctx, uint32_t seed, u64* words, uint
 }
 extern "C" int dp_index_seedset_row(dp_ctx* ctx, uint32_t seq, u64* words, uint32_t cap_words, uint32_t* n_words) {
     if (!ctx || seq >= ctx->n_seqs || cap_words < ctx->SW) return DP_ERR_ARG;
+    if (ctx->index_sparse) return dp_index_sparse_row(ctx, 1, seq, words, cap_words, n_words, nullptr, nullptr, nullptr);
     hipSetDevice(ctx->device);
     DP_HIP(hipMemcpy(words, (u64*)ctx->d_seedsets.p + (uint64_t)seq * ctx->SW, (size_t)ctx->SW * 8, hipMemcpyDeviceToHost));
     if (n_words) *n_words = ctx->SW;
@@ -893,6 +899,110 @@ __device__ __forceinline__ u64 q_ladder(const ST& S, const u64* __restrict__ pos
     return ((u64)hi[D - 1] << 32) | lo[D - 1];
 }
 
+// ---- the same query on a sparse index (dp_index_build_sparse): the ids of the live sets' rows, not their words -------------------
+// Every ladder of GetSharedIDs reduces to a count per id.  c = live sets that hold the id (a set that holds an id at word i is live
+// at i: drops come after a set's last word), p7 = the set at gather position 7 of the event that covers the id's word:
+//   minCount <= 4: c >= max(minCount, 1);  5 .. 12: c >= min(minCount, 8);
+//   >= 13: c' >= min(minCount, 16), c' = c - 1 when p7 holds the id and none of positions 0 .. 6 does (step 8 omits its ORQ);
+//   > 24: also c >= minCount (addSoftUnionIDs).
+// The query's live sets are merged tile by tile (SP_TILE ids, counters in LDS): each set keeps a cursor into its row, a tile starts at
+// the smallest id any cursor points at, so only tiles that hold ids are visited.  Candidates leave as the candidate row's words.
+#define SP_TILE 8192
+#define SP_P7 (1u << 30)
+#define SP_P06 (1u << 31)
+template <class ST>
+__device__ void q_sparse_ids(ST& S, uint32_t n, int minCount, int64_t w_lo, int64_t w_hi, uint32_t word_base, const u64* __restrict__ post_off,
+                             const uint32_t* __restrict__ post_ids, u64* __restrict__ cand_row, u64& gathered, int& nCand) {
+    __shared__ uint32_t cnt[SP_TILE];
+    __shared__ uint32_t red[Q_WAVES];
+    const int lane = dp_lane(), wave = threadIdx.x >> 6;
+    const uint32_t T = blockDim.x;
+    if (w_lo > w_hi) return;
+    const uint32_t lo = (uint32_t)((w_lo - (int64_t)word_base) * 64), hi = (uint32_t)((w_hi - (int64_t)word_base + 1) * 64);  // local ids
+    const bool ladder16 = minCount >= 13;
+    const uint32_t n_ev = ladder16 ? S.n_ev : 0;
+    // cursors: row-relative [first id >= lo, first id >= hi) in tmp_id / tmp_len (free once the gather order is recorded)
+    for (uint32_t j = threadIdx.x; j < n; j += T) {
+        const uint32_t s = S.setid[j];
+        const u64 a = post_off[s], b = post_off[s + 1];
+        u64 x = a, y = b;
+        while (x < y) {
+            const u64 m = (x + y) >> 1;
+            if (post_ids[m] < lo) x = m + 1;
+            else y = m;
+        }
+        const u64 c0 = x;
+        y = b;
+        while (x < y) {
+            const u64 m = (x + y) >> 1;
+            if (post_ids[m] < hi) x = m + 1;
+            else y = m;
+        }
+        S.tmp_id[j] = (uint32_t)(c0 - a);
+        S.tmp_len[j] = (uint32_t)(x - a);
+    }
+    __syncthreads();
+    for (uint32_t base = lo; base < hi;) {
+        uint32_t mn = 0xffffffffu;
+        for (uint32_t j = threadIdx.x; j < n; j += T)
+            if (S.tmp_id[j] < S.tmp_len[j]) mn = min(mn, post_ids[post_off[S.setid[j]] + S.tmp_id[j]]);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64));
+        if (lane == 0) red[wave] = mn;
+        __syncthreads();
+        mn = 0xffffffffu;
+        for (int w = 0; w < (int)(T >> 6); w++) mn = min(mn, red[w]);
+        if (mn == 0xffffffffu) break;  // (every block thread sees the same minimum)
+        const uint32_t tb = max(base, mn & ~63u), te = min(hi, tb + (uint32_t)SP_TILE);
+        for (uint32_t i = threadIdx.x; i < te - tb; i += T) cnt[i] = 0u;
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < n; j += T) {
+            const u64 a = post_off[S.setid[j]];
+            uint32_t c = S.tmp_id[j];
+            const uint32_t e = S.tmp_len[j];
+            for (; c < e; c++) {
+                const uint32_t id = post_ids[a + c];
+                if (id >= te) break;
+                atomicAdd(&cnt[id - tb], 1u);
+                gathered++;
+                if (ladder16) {
+                    // the event that covers this word: the last one at or before it
+                    const uint32_t iw = (id >> 6) + word_base;
+                    uint32_t x = 0, y = n_ev;
+                    while (y - x > 1) {
+                        const uint32_t m = (x + y) >> 1;
+                        if (S.ev_word[m] <= iw) x = m;
+                        else y = m;
+                    }
+                    bool p06 = false;
+#pragma unroll
+                    for (int p = 0; p < 7; p++) p06 |= S.ev_first8[x][p] == j;
+                    if (p06) atomicOr(&cnt[id - tb], SP_P06);
+                    else if (S.ev_first8[x][7] == j) atomicOr(&cnt[id - tb], SP_P7);
+                }
+            }
+            S.tmp_id[j] = c;
+        }
+        __syncthreads();
+        for (uint32_t x = wave; x < (te - tb) / 64; x += T >> 6) {
+            const uint32_t v = cnt[64 * x + lane];
+            const int c = (int)(v & 0xfffffu);
+            bool ok;
+            if (minCount <= 4) ok = c >= max(minCount, 1);
+            else if (minCount <= 12) ok = c >= min(minCount, 8);
+            else {
+                const int c2 = c - (((v & SP_P7) && !(v & SP_P06)) ? 1 : 0);
+                ok = c2 >= min(minCount, 16) && (minCount <= 24 || c >= minCount);
+            }
+            const u64 word = __ballot(ok);
+            if (lane == 0 && word) cand_row[(tb >> 6) + x] = word;
+            nCand += lane == 0 ? __popcll(word) : 0;
+        }
+        __syncthreads();
+        base = te;
+    }
+}
+
 // qmeta per query: {n_sets, minCount, status}; status bit0 = too many sets
 // One WORKGROUP per query: wave 0 prepares the set list (Matches' filter, the early-return cut, the 16-ladder's gather
 // order), then the Q_WAVES waves share the query's word range, 64 words per wave step, so that a dense index (W ~ 3 k words,
@@ -918,6 +1028,9 @@ struct query_kernel {
             body(qsegs, qoff, nq, posting, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt, word_base, n_seqs_dev, qsets, SW, dbg_flags, split, own_zero,
                  big_ws, big_stride);
     }
+    // SPARSE (query_sparse_kernel): `posting` is the sparse index's post_off, sp_ids its post_ids; the set list is prepared as in the
+    // heavy variant (every regime: the gather order is recorded for the 16-ladder's queries) and the light variant's qmeta is written
+    template <bool SPARSE = false>
     static __device__ void body(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff,
                                                              uint32_t nq, const u64* __restrict__ posting,
                                                              const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W,
@@ -926,7 +1039,8 @@ struct query_kernel {
                                                              u64* __restrict__ words_read, uint32_t* __restrict__ qcnt,
                                                              uint32_t word_base, const uint32_t* __restrict__ n_seqs_dev,
                                                              u64* __restrict__ qsets, uint32_t SW, uint32_t dbg_flags, uint32_t split,
-                                                             u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws, uint32_t big_stride) {
+                                                             u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws, uint32_t big_stride,
+                                                             const uint32_t* __restrict__ sp_ids = nullptr) {
     if (n_seqs_dev) n_seqs = *n_seqs_dev;  // (chunks made on the device: the host only knows an upper bound)
     // word_base: a shard of a larger index (dp_index_set_global) holds the words [word_base, word_base + W) of every set; pmeta
     // and n_seqs then describe the WHOLE sets (global windows, counts), so the filter, the early-return cut and the gather
@@ -1030,7 +1144,7 @@ struct query_kernel {
         if (n <= (uint32_t)Q_MAXSETS) status |= 4u;  // (the ordinary variants' query: nothing to do here)
         __threadfence();                             // (the lists are global memory: the other waves read them behind the barrier)
     }
-    if (!HEAVY && lane == 0 && part == 0 && !(BIG && (status & 4u))) {
+    if ((!HEAVY || SPARSE) && lane == 0 && part == 0 && !(BIG && (status & 4u))) {
         qmeta[4 * q + 0] = n;
         qmeta[4 * q + 1] = (uint32_t)minCount;
         qmeta[4 * q + 2] = status | (n >= mc_n ? 2u : 0u);
@@ -1129,6 +1243,24 @@ struct query_kernel {
     const int64_t i_last = sh_ilast;
     if (n < 5 || status || n >= mc_n) return;  // cand row stays zero
     if (dbg_flags & 1u) return;  // DP_QUERY_DEBUG=1 (timing experiments): the set-up alone, no posting word is read
+    if constexpr (SPARSE) {
+        u64 gathered = 0;  // (ids read)
+        int nCand = 0;
+        q_sparse_ids(S, n, minCount, max((int64_t)start, (int64_t)word_base), min(i_last, (int64_t)word_base + (int64_t)W - 1), word_base,
+                     posting, sp_ids, cand + (uint64_t)q * W, gathered, nCand);
+        gathered = (u64)wave_sum((int)gathered);
+        nCand = wave_sum(nCand);
+        if (lane == 0) {
+            atomicAdd(&sh_gathered, (unsigned long long)gathered);
+            atomicAdd(&sh_u[5], (uint32_t)nCand);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (sh_gathered) atomicAdd((unsigned long long*)&words_read[q], sh_gathered);
+            if (sh_u[5]) atomicAdd(&qcnt[q], sh_u[5]);
+        }
+        return;
+    }
     const bool ladder16 = minCount >= 13;
     if (ladder16 != HEAVY) return;  // (the other variant's query)
     const uint32_t n_ev = ladder16 ? S.n_ev : 0;
@@ -1241,6 +1373,52 @@ struct query_kernel {
         if (sh_u[5]) atomicAdd(&qcnt[q], sh_u[5]);
     }
 }
+};
+
+// the index query on a sparse index: one workgroup per query, every regime in one launch (the BIG variant behind it for the queries
+// with more than Q_MAXSETS sets, as in the dense stage)
+template <bool BIG>
+struct query_sparse_kernel {
+    enum { THREADS = 64 * Q_WAVES };
+    static __device__ void run(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, const u64* __restrict__ post_off,
+                               const uint32_t* __restrict__ post_ids, const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W,
+                               const int32_t* __restrict__ mc, uint32_t mc_n, u64* __restrict__ cand, uint32_t* __restrict__ qmeta,
+                               u64* __restrict__ words_read, uint32_t* __restrict__ qcnt, uint32_t word_base, uint32_t* __restrict__ big_ws,
+                               uint32_t big_stride) {
+        if (blockIdx.x < nq)
+            query_kernel<true, BIG>::template body<true>(qsegs, qoff, nq, post_off, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt,
+                                                         word_base, (const uint32_t*)nullptr, (u64*)nullptr, 0u, 0u, 1u, (u64*)nullptr, big_ws,
+                                                         big_stride, post_ids);
+    }
+};
+
+// the windows' seeds in ascending order (repeats kept: the map kernel only asks "is x among them"), at wl + qoff[w] / 2 - a window
+// of n seeds has 2 n + 1 segment ints, so the lists do not overlap.  One workgroup per window: the rank of seed i is the number of
+// seeds below it plus the equal ones in front of it.
+struct window_list_kernel {
+    enum { THREADS = 256, LDS_SEEDS = 2048 };
+    static __device__ void run(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, uint32_t* __restrict__ wl) {
+        __shared__ uint32_t a[LDS_SEEDS];
+        for (uint32_t w = blockIdx.x; w < nq; w += gridDim.x) {
+            const int32_t* seg = qsegs + qoff[w];
+            const uint32_t ns = (uint32_t)((qoff[w + 1] - qoff[w]) / 2);
+            uint32_t* out = wl + qoff[w] / 2;
+            const bool inLds = ns <= LDS_SEEDS;
+            if (inLds)
+                for (uint32_t i = threadIdx.x; i < ns; i += THREADS) a[i] = (uint32_t)seg[2 * i + 1];
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < ns; i += THREADS) {
+                const uint32_t v = inLds ? a[i] : (uint32_t)seg[2 * i + 1];
+                uint32_t r = 0;
+                for (uint32_t j = 0; j < ns; j++) {
+                    const uint32_t x = inLds ? a[j] : (uint32_t)seg[2 * j + 1];
+                    r += (x < v || (x == v && j < i)) ? 1u : 0u;
+                }
+                out[r] = v;
+            }
+            __syncthreads();
+        }
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2999,6 +3177,51 @@ extern "C" int dp_query_prestage(dp_ctx* ctx, const int32_t* q_segs, const uint6
 
 // Uploads the queries, builds their seed bitsets and runs the index query (Matches -> GetSharedIDs) for all of them.
 // Leaves d_qsegs/d_qoff/d_qsets/d_cand/d_qmeta on the device.  Events ev[4]/ev[5] bracket the query kernel.
+// dp_query_stage on a sparse index (the query block is staged already): candidate rows as in the dense stage, no seed bit rows -
+// the windows' seed lists (window_list_kernel) instead, whose size does not grow with the seed count
+static int query_stage_sparse(dp_ctx* ctx, uint32_t nq, const uint8_t* up, size_t up_off, size_t up_segs, size_t up_mc, bool on_device, uint32_t mc_n,
+                              uint32_t maxSeeds, uint32_t** d_qmeta_out, uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out,
+                              uint32_t** d_qcnt_out) {
+    const dp_ctx* ix = dp_index_of(ctx);
+    const uint32_t W = ctx->W, M = ctx->n_seqs;
+    const uint64_t nInts = up_segs / 4;
+    if (dev_reserve(ctx, ctx->d_qmeta, (size_t)nq * 16 + (size_t)nq * 8 + (size_t)nq * 4 + (size_t)mc_n * 4 + 64)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_wlist, (size_t)(nInts / 2 + 1) * 4 + 64)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
+    uint32_t* d_qmeta = (uint32_t*)ctx->d_qmeta.p;
+    u64* d_words = (u64*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 16);
+    uint32_t* d_qcnt = (uint32_t*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 24);
+    const int32_t* d_mc = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off + up_segs);
+    {
+        const dp_zero_region z[3] = {{ctx->d_cand.p, (size_t)nq * W * 8}, {d_qmeta, (size_t)nq * 28}, {ctx->d_cursor.p, C_CURSOR_BYTES}};
+        const dp_fetch_region f = {ctx->d_qsegs.p, up, up_off + up_segs + up_mc};
+        if (int rc = dp_zero_fetch_regions(ctx, z, 3, &f, on_device ? 0 : 1)) return rc;
+    }
+    DP_HIP(dp_mark(ctx, 4));
+    const uint32_t n_glob = ctx->global_n_seqs ? ctx->global_n_seqs : M;
+    dp_launch<query_sparse_kernel<false>>(ctx, dim3(nq), dim3(64 * Q_WAVES), ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ix->d_sp_post_off.p,
+                                          (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W, d_mc, mc_n,
+                                          (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)nullptr, 0u);
+    if (maxSeeds > Q_MAXSETS) {
+        const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
+        if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return DP_ERR_HIP;
+        dp_launch<query_sparse_kernel<true>>(ctx, dim3(nq), dim3(64 * Q_WAVES), ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ix->d_sp_post_off.p,
+                                             (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W, d_mc, mc_n,
+                                             (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)ctx->d_qbig.p, stride);
+    }
+    if (nq) dp_launch<window_list_kernel>(ctx, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), ctx->qsegs_dev, ctx->qoff_dev, nq,
+                                          (uint32_t*)ctx->d_wlist.p);
+    DP_HIP(hipGetLastError());
+    DP_HIP(dp_mark(ctx, 5));
+    *d_qmeta_out = d_qmeta;
+    *d_words_out = d_words;
+    *d_mc_out = (int32_t*)d_mc;
+    *mc_n_out = mc_n;
+    if (d_qcnt_out) *d_qcnt_out = d_qcnt;
+    return DP_OK;
+}
+
 int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t** d_qmeta_out,
                    uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out, uint32_t** d_qcnt_out) {
     const uint32_t W = ctx->W, SW = ctx->SW, M = ctx->n_seqs;
@@ -3028,6 +3251,8 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
     uint8_t* up = (uint8_t*)ctx->h_qup.p;
     ctx->qoff_dev = (const u64*)ctx->d_qsegs.p;
     ctx->qsegs_dev = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off);
+    if (ctx->index_sparse) return query_stage_sparse(ctx, nq, up, up_off, up_segs, up_mc, on_device, mc_n, maxSeeds, d_qmeta_out, d_words_out, d_mc_out,
+                                                     mc_n_out, d_qcnt_out);
     if (dev_reserve(ctx, ctx->d_qsets, (size_t)nq * SW * 8 + 64)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_qmeta, (size_t)nq * 16 + (size_t)nq * 8 + (size_t)nq * 4 + (size_t)mc_n * 4 + 64)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return DP_ERR_HIP;
@@ -3653,6 +3878,7 @@ extern "C" int dp_fetch_overlaps(dp_ctx* ctx, dp_match_batch* out) {
 extern "C" int dp_find_overlaps(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t n_queries,
                                 double hit_fraction, int k, uint32_t max_query_len, int want_candidates, dp_match_batch* out) {
     if (!ctx || !out || (n_queries && (!q_segs || !q_off))) return DP_ERR_ARG;
+    if (ctx->index_sparse) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps: the context holds a sparse index (overlap rounds index dense)");
     return dp_find_overlaps_impl(ctx, q_segs, q_off, n_queries, hit_fraction, k, max_query_len, want_candidates, out);
 }
 

@@ -755,12 +755,18 @@ struct MapParams {  // flag table commands/map.go:19-20
     int k = 11;
     i64 querySize = 1000, minLength = 500, chunkSize = 10000, seedRate = 40;
     int numWorkers = 4;
+    int indexLayout = 0;  // reference index: 0 = auto (sparse when the dense one would not fit the device), 1 = dense, 2 = sparse
 };
 struct MapStats {
     uint64_t n_chunks = 0, n_seeds = 0, n_windows = 0, n_chains = 0, n_batches = 0;
     double k_scan_ms = 0, k_map_ms = 0;
     double map_bytes = 0, scan_bytes = 0;  // algorithmic bytes: dp_map_windows' query + prefilter + chaining; packed bases of the windows scanned
     double t_setup_s = 0, t_scan_s = 0, t_chain_s = 0, t_host_s = 0;  // wall: indexing the reference / window scans / dp_map_windows / coroutines
+    // the reference index (dph_map_index_info): layout (1 dense, 2 sparse), device bytes of the indexes built, the dense estimate the
+    // layout was chosen by (every context / shard of the run), the device's total memory, seed hits in chunks, contexts that built an
+    // index, queries per regime (4/8-ladder, 16-ladder, exact count, more than 512 sets)
+    int64_t index_layout = 0, index_bytes = 0, dense_estimate = 0, device_total = 0, hits = 0, index_builds = 0;
+    int64_t regimes[4] = {0, 0, 0, 0};
 };
 // Runs the whole command on HIP device `device`: reference = first sequence of refSet (top-level, cache=false), reads
 // top-level.  paf receives the PAF lines (read order), errText the reference's stderr lines.

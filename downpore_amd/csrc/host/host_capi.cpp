@@ -910,16 +910,25 @@ extern "C" const char* dph_finalcheck(void* readsH, int k, int64_t overlapSize, 
 }
 
 // ---- `downpore map` ------------------------------------------------------------------------------------------------
-// params: circular,k,querySize,minLength,chunkSize,seedRate.  Returns a handle holding paf/err text, or NULL.
+// params: circular,k,querySize,minLength,chunkSize,seedRate[,index layout].  Returns a handle holding paf/err text, or NULL.
 namespace {
 struct MapH {
     std::string paf, err;
     MapStats st;
 };
 }  // namespace
-extern "C" void* dph_map_run(void* refH, void* readsH, const int64_t* params, int device) {
+extern "C" void* dph_map_run_ex(void* refH, void* readsH, const int64_t* params, int n_params, int device) {
+    if (!refH || !readsH || !params || (n_params != 6 && n_params != 7)) {
+        g_err = "dph_map_run_ex: bad arguments (6 or 7 parameters)";
+        return nullptr;
+    }
+    if (n_params == 7 && (params[6] < 0 || params[6] > 2)) {  // (refused before any device call)
+        g_err = "dph_map_run_ex: index layout " + std::to_string((long long)params[6]) + " (0 = auto, 1 = dense, 2 = sparse)";
+        return nullptr;
+    }
     MapH* h = new MapH();
     MapParams p;
+    p.indexLayout = n_params == 7 ? (int)params[6] : 0;
     p.circular = params[0] != 0;
     p.k = (int)params[1];
     p.querySize = params[2];
@@ -934,6 +943,9 @@ extern "C" void* dph_map_run(void* refH, void* readsH, const int64_t* params, in
         return nullptr;
     }
     return h;
+}
+extern "C" void* dph_map_run(void* refH, void* readsH, const int64_t* params, int device) {
+    return dph_map_run_ex(refH, readsH, params, 6, device);
 }
 extern "C" void dph_map_free(void* h) { delete (MapH*)h; }
 extern "C" const char* dph_map_paf(void* h, int64_t* n) {
@@ -950,6 +962,16 @@ extern "C" void dph_map_stats(void* h, double* out) {
     double v[] = {(double)s.n_chunks, (double)s.n_seeds, (double)s.n_windows, (double)s.n_chains, (double)s.n_batches, s.k_scan_ms,
                   s.k_map_ms, s.t_setup_s, s.t_scan_s, s.t_chain_s, s.t_host_s, s.map_bytes, s.scan_bytes};
     memcpy(out, v, sizeof v);
+}
+
+// out: layout, index bytes, dense estimate, device total memory, seed hits, contexts that built an index, queries per regime (4)
+extern "C" int dph_map_index_info(void* h, int64_t* out, int cap) {
+    const MapStats& s = ((MapH*)h)->st;
+    const int64_t v[] = {s.index_layout, s.index_bytes, s.dense_estimate, s.device_total, s.hits, s.index_builds,
+                         s.regimes[0], s.regimes[1], s.regimes[2], s.regimes[3]};
+    const int n = std::max(0, std::min(cap, (int)(sizeof v / sizeof v[0])));
+    memcpy(out, v, (size_t)n * sizeof(int64_t));
+    return n;
 }
 
 // ---- host-logic test hook (no GPU needed): the plan chain of a round-parallel run of `world` ranks whose planners each compute

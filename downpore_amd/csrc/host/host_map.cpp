@@ -590,6 +590,16 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     const int k = p.k;
     const i64 refLen = refSet.length(0);
     const char* ref = refSet.seq(0);
+    // positions in the reference travel as 32-bit signed ints (chunk offsets, the reverse strand, the PAF's target fields): a longer
+    // sequence is refused before anything is packed or allocated on the device
+    if (refLen > (i64)0x7fffffff) {
+        error = "map: the reference sequence is " + std::to_string((long long)refLen) + " bases long; at most 2147483647 are supported";
+        return DP_ERR_ARG;
+    }
+    if (p.indexLayout < 0 || p.indexLayout > 2) {
+        error = "map: reference index layout " + std::to_string(p.indexLayout) + " (0 = auto, 1 = dense, 2 = sparse)";
+        return DP_ERR_ARG;
+    }
     // ---- device read set: [0] reference, [1] circular join chunk, then (forward, reverse complement) of every read.  Its host
     // staging copy is made by a thread of its own while the device computes the reference's k-mer table
     std::vector<i64> off(1, 0);
@@ -879,18 +889,83 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     } shardGuard{shards};
     int nShards = 1;
     if (const char* e = getenv("DP_MAP_SHARDS")) nShards = std::max(1, atoi(e));
-    if (nShards > 1) {
-        std::vector<int> devs;
-        if (const char* e = getenv("DP_MAP_DEVICES")) {
-            for (const char* q = e; *q;) {
-                devs.push_back(atoi(q));
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
+    std::vector<int> devs;
+    if (const char* e = getenv("DP_MAP_DEVICES")) {
+        for (const char* q = e; *q;) {
+            devs.push_back(atoi(q));
+            while (*q && *q != ',') q++;
+            if (*q == ',') q++;
         }
-        if (devs.empty()) devs.push_back(device);
-        const uint32_t nChunks = (uint32_t)items.size(), S = (uint32_t)index.seedMap.size();
-        const uint32_t per = ((nChunks + (uint32_t)nShards - 1) / (uint32_t)nShards + 63) / 64 * 64;  // whole 64-chunk words
+    }
+    if (devs.empty()) devs.push_back(device);
+    const uint32_t nChunksAll = (uint32_t)items.size();
+    const uint32_t perShard = ((nChunksAll + (uint32_t)nShards - 1) / (uint32_t)nShards + 63) / 64 * 64;  // whole 64-chunk words
+    // mapper threads (each with a context of its own) when the index is not sharded
+    auto plannedThreads = [&]() -> size_t {
+        const char* e = getenv("DP_MAP_THREADS");
+        size_t n = (size_t)std::max(1, e ? atoi(e) : (hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3));
+        size_t perThread = 2048;  // (fewer reads than that per thread are not worth a context; DP_MAP_MIN_READS_PER_THREAD: test hook)
+        perThread = (size_t)std::max(1L, dph_tune("map_min_reads_per_thread", (long)perThread));
+        return std::min(n, std::max<size_t>(1, reads.size() / perThread));
+    };
+    // ---- the reference index's layout.  Dense: S x ceil(M/64) + M x ceil(S/64) words per context or shard; the estimate D sums them
+    // per device over every context / shard this run would build there.  Sparse (id lists, ~8 bytes per seed hit) when D exceeds a
+    // device's free memory less an eighth of its total: a run that close could already fail in its later allocations.  With the
+    // sparse layout the mapper threads' contexts borrow the one index instead of building their own.
+    bool sparseIndex = p.indexLayout == 2;
+    const uint64_t S64 = index.seedMap.size();
+    auto denseBytes = [&](uint64_t m) { return S64 * ((m + 63) / 64) * 8 + m * ((S64 + 63) / 64) * 8; };
+    // device bytes of an index of m chunks as dp_index_info counts them (the dense one without asking the device: its build is still queued)
+    auto indexBytes = [&](dp_ctx* c, uint64_t m) -> int64_t {
+        if (!sparseIndex) return (int64_t)(denseBytes(m) + 16 * S64 + (uint64_t)sizeof(dp_seq_ref) * m);
+        dp_index_info_t ii;
+        return dp_index_info(c, &ii) == 0 ? (int64_t)ii.device_bytes : 0;
+    };
+    {
+        std::vector<std::pair<int, uint64_t>> perDev;  // device, dense bytes
+        auto addDev = [&](int d, uint64_t b) {
+            for (auto& pd : perDev)
+                if (pd.first == d) return (void)(pd.second += b);
+            perDev.push_back({d, b});
+        };
+        if (nShards > 1) {
+            size_t i = 0;
+            for (uint32_t c0 = 0; c0 < nChunksAll; c0 += perShard, i++) addDev(devs[i % devs.size()], denseBytes(std::min(nChunksAll, c0 + perShard) - c0));
+        } else {
+            addDev(device, (uint64_t)plannedThreads() * denseBytes(nChunksAll));
+        }
+        uint64_t dTotal = 0;
+        bool over = false;
+        for (auto& pd : perDev) {
+            uint64_t fr = 0, tot = 0;
+            rc = dp_device_memory(pd.first, &fr, &tot);
+            if (rc) return fail(rc);
+            dTotal += pd.second;
+            if (pd.second + tot / 8 > fr) over = true;
+            if (pd.first == device && stats) stats->device_total = (int64_t)tot;
+        }
+        if (p.indexLayout == 0) sparseIndex = over;
+        if (stats) {
+            stats->dense_estimate = (int64_t)dTotal;
+            stats->index_layout = sparseIndex ? 2 : 1;
+            for (const dp_seq_ref& r : refs) stats->hits += r.n_seeds;
+        }
+        if (prof) fprintf(stderr, "[map setup] reference index: dense estimate %.3f GB over %zu device(s) -> %s\n", dTotal / 1e9, perDev.size(), sparseIndex ? "sparse" : "dense");
+    }
+    auto buildIndex = [&](dp_ctx* c, const dp_seq_ref* r, uint32_t n) {
+        const auto tb0 = std::chrono::steady_clock::now();
+        const int rc2 = sparseIndex ? dp_index_build_sparse(c, r, n) : dp_index_build(c, r, n);
+        if (prof) fprintf(stderr, "[map setup] %s index of %u chunks built in %.1f ms\n", sparseIndex ? "sparse" : "dense", n,
+                          1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count());
+        if (rc2 == 0 && stats) {
+            stats->index_bytes += indexBytes(c, n);
+            stats->index_builds++;
+        }
+        return rc2;
+    };
+    if (nShards > 1) {
+        const uint32_t nChunks = nChunksAll, S = (uint32_t)index.seedMap.size();
+        const uint32_t per = perShard;
         std::vector<uint32_t> global((size_t)S * 4), local((size_t)S * 4);
         for (uint32_t i = 0; i < S; i++) {  // NewIntSet(): count 0, start 1, end 0 (last + 1 = 1)
             global[4 * (size_t)i + 0] = 0;
@@ -921,7 +996,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             if (rc) return sfail(rc);
             std::vector<dp_seq_ref> lrefs(refs.begin() + sh.c0, refs.begin() + sh.c1);
             for (dp_seq_ref& r : lrefs) r.seg_off -= s0;
-            rc = dp_index_build(sc, lrefs.data(), (uint32_t)lrefs.size());
+            rc = buildIndex(sc, lrefs.data(), (uint32_t)lrefs.size());
             if (rc) return sfail(rc);
             rc = dp_index_meta(sc, local.data(), S);
             if (rc) return sfail(rc);
@@ -951,7 +1026,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             }
         }
     } else {
-        rc = dp_index_build(ctx, refs.data(), (uint32_t)refs.size());
+        rc = buildIndex(ctx, refs.data(), (uint32_t)refs.size());
         if (rc) return fail(rc);
     }
     // dp_scan below reuses the device scan buffer: keep the chunk segments in a dedicated import
@@ -1161,8 +1236,10 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         lap(2);
         const double tc0 = wallNow();
         if (shards.empty()) {
-            rc = dp_scan_import_segments(ctx, M.chunkSegs.data(), M.chunkSegs.size());
-            if (rc) return fail(rc);
+            if (!sparseIndex) {  // (the sparse index holds its own copy of the chunk segments)
+                rc = dp_scan_import_segments(ctx, M.chunkSegs.data(), M.chunkSegs.size());
+                if (rc) return fail(rc);
+            }
             dp_chain_batch cb;
             rc = dp_map_windows(ctx, wsegs.data(), woff.data(), wlen.data(), (uint32_t)witems.size(), k, &cb);
             if (rc) return fail(rc);
@@ -1200,16 +1277,11 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     };  // mapLoop
 
     size_t nThreads = 1;
-    if (shards.empty()) {
-        const char* e = getenv("DP_MAP_THREADS");
-        nThreads = (size_t)std::max(1, e ? atoi(e) : (hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3));
-        size_t perThread = 2048;  // (fewer reads than that per thread are not worth a context; DP_MAP_MIN_READS_PER_THREAD: test hook)
-        perThread = (size_t)std::max(1L, dph_tune("map_min_reads_per_thread", (long)perThread));
-        nThreads = std::min(nThreads, std::max<size_t>(1, reads.size() / perThread));
-    }
+    if (shards.empty()) nThreads = plannedThreads();
     nThreadsPlanned = nThreads;
     std::vector<LoopStats> lstats(nThreads);
     std::vector<dp_ctx*> tctx(nThreads, nullptr);
+    std::mutex infoMu;
     std::vector<MapperImpl> Ms(nThreads, M);  // (chunks[i].seg keep pointing into M.chunkSegs, which outlives the threads)
     tctx[0] = ctx;
     {
@@ -1223,9 +1295,15 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
                     const double ta = wallNow();
                     if (rc2 == 0) rc2 = dp_round_begin(tctx[t], k, index.seedMap.data(), (uint32_t)index.seedMap.size());
                     const double tb = wallNow();
-                    if (rc2 == 0) rc2 = dp_scan_import_segments(tctx[t], M.chunkSegs.data(), M.chunkSegs.size());
+                    if (rc2 == 0 && !sparseIndex) rc2 = dp_scan_import_segments(tctx[t], M.chunkSegs.data(), M.chunkSegs.size());
                     const double tc = wallNow();
-                    if (rc2 == 0) rc2 = dp_index_build(tctx[t], refs.data(), (uint32_t)refs.size());
+                    if (rc2 == 0 && sparseIndex) rc2 = dp_index_borrow(tctx[t], ctx);  // (the one sparse index, read-only)
+                    else if (rc2 == 0) rc2 = dp_index_build(tctx[t], refs.data(), (uint32_t)refs.size());
+                    if (rc2 == 0 && !sparseIndex && stats) {
+                        std::lock_guard<std::mutex> lk(infoMu);
+                        stats->index_bytes += indexBytes(tctx[t], refs.size());
+                        stats->index_builds++;
+                    }
                     if (prof) fprintf(stderr, "[map thread %zu] context %.2f ms, round begin %.2f, import %.2f, index %.2f\n", t, 1e3 * (ta - tt0), 1e3 * (tb - ta), 1e3 * (tc - tb), 1e3 * (wallNow() - tc));
                     if (rc2 != 0) {
                         ls.rc = rc2;
@@ -1242,6 +1320,16 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             });
         }
         for (auto& t : th) t.join();
+    }
+    if (stats) {  // queries per regime: every thread's context, or one shard (every shard answers every window)
+        std::vector<dp_ctx*> qc;
+        if (shards.empty()) qc = tctx;
+        else qc.push_back(shards[0].ctx);
+        for (dp_ctx* c : qc) {
+            dp_index_info_t ii;
+            if (c && dp_index_info(c, &ii) == 0)
+                for (int r = 0; r < 4; r++) stats->regimes[r] += (int64_t)ii.queries[r];
+        }
     }
     const double tJoin = wallNow();
     for (size_t t = 1; t < nThreads; t++)

@@ -49,13 +49,19 @@ class ChainBatch(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class IndexInfo(C.Structure):  # dp_index_info_t
+    _fields_ = [("layout", C.c_uint32), ("borrowed", C.c_uint32), ("n_seeds", C.c_uint32), ("n_seqs", C.c_uint32),
+                ("device_bytes", C.c_uint64), ("entries", C.c_uint64), ("queries", C.c_uint64 * 4)]
+
+
 #: every entry point include/downpore_hip.h declares (checked by the CPU-side symbol test)
 SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_priority", "dp_ctx_destroy", "dp_last_error", "dp_reads_upload", "dp_reads_packed",
            "dp_reads_count", "dp_reads_total_bases", "dp_kmer_histogram", "dp_kmer_values", "dp_round_begin", "dp_scan", "dp_scan_prepare", "dp_scan_reads", "dp_index_build",
            "dp_find_overlaps", "dp_query_prestage", "dp_map_windows", "dp_index_posting_row", "dp_index_seedset_row", "dp_scan_device_buffers",
            "dp_scan_import_segments", "dp_values_upload", "dp_select_seeds", "dp_reads_upload_rc", "dp_consensus_align", "dp_scan_release", "dp_consensus_paf", "dp_fetch_overlaps", "dp_select_windows", "dp_values_download",
     "dp_values_download_codes", "dp_values_download_codes8", "dp_index_build_chunked", "dp_index_prechain", "dp_index_prechained", "dp_index_chunks", "dp_scan_fetch_mode", "dp_scan_fetch_segments", "dp_set_stream_wait", "dp_set_kernel_timing", "dp_index_meta", "dp_index_set_global", "dp_map_windows_shard", "dp_single_seed_candidates", "dp_comm_unique_id", "dp_comm_init", "dp_comm_init_local", "dp_quality_upload",
-           "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors"]
+           "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
+           "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory"]
 
 _lib = None
 
@@ -265,6 +271,35 @@ class Context:
         refs["n_seeds"] = n_seeds
         self._chk(self.L.dp_index_build(self.h, refs.ctypes.data, len(refs)))
         self.n_seqs = len(refs)
+
+    def index_build_sparse(self, seg_off, n_seeds):
+        """The same index as id lists (dp_index_build_sparse); the row and meta calls answer alike."""
+        refs = np.zeros(len(seg_off), dtype=[("seg_off", np.uint64), ("n_seeds", np.uint32), ("reserved", np.uint32)])
+        refs["seg_off"] = seg_off
+        refs["n_seeds"] = n_seeds
+        self.L.dp_index_build_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._chk(self.L.dp_index_build_sparse(self.h, refs.ctypes.data, len(refs)))
+        self.n_seqs = len(refs)
+
+    def index_info(self):
+        """dp_index_info: layout ("none" / "dense" / "sparse"), borrowed, n_seeds, n_seqs, device_bytes, entries, queries[4]."""
+        info = IndexInfo()
+        self.L.dp_index_info.argtypes = [C.c_void_p, C.POINTER(IndexInfo)]
+        self._chk(self.L.dp_index_info(self.h, C.byref(info)))
+        return dict(layout={0: "none", 1: "dense", 2: "sparse"}[info.layout], borrowed=bool(info.borrowed), n_seeds=info.n_seeds,
+                    n_seqs=info.n_seqs, device_bytes=info.device_bytes, entries=info.entries, queries=list(info.queries))
+
+    def index_meta(self):
+        """dp_index_meta: the {count, first word, last word, last + 1} rows of every seed, uint32 [S, 4]."""
+        out = np.zeros((self.n_seeds, 4), dtype=np.uint32)
+        self.L.dp_index_meta.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._chk(self.L.dp_index_meta(self.h, out.ctypes.data, self.n_seeds))
+        return out
+
+    def index_set_global(self, meta_global, word_base, n_seqs_global):
+        m = np.ascontiguousarray(meta_global, dtype=np.uint32)
+        self.L.dp_index_set_global.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        self._chk(self.L.dp_index_set_global(self.h, m.ctypes.data, self.n_seeds, word_base, n_seqs_global))
 
     def posting_row(self, seed):
         W = max(1, (self.n_seqs + 63) // 64)

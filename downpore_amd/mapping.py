@@ -8,21 +8,40 @@ from .overlap import load_host
 
 MAP_STAT_FIELDS = ["n_chunks", "n_seeds", "n_windows", "n_chains", "n_batches", "k_scan_ms", "k_map_ms", "t_setup_s", "t_scan_s",
                    "t_chain_s", "t_host_s", "map_bytes", "scan_bytes"]
+#: dph_map_index_info's values, in order (the "index" entry of the stats)
+MAP_INDEX_FIELDS = ["layout", "index_bytes", "dense_estimate", "device_total", "hits", "index_builds", "q_ladder8", "q_ladder16",
+                    "q_exact", "q_big"]
+INDEX_LAYOUTS = {"auto": 0, "dense": 1, "sparse": 2}
 
 
-def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0):
+def index_layout_code(index):
+    """"auto" / "dense" / "sparse" (or 0 / 1 / 2) -> the layout code of dph_map_run_ex; anything else raises DpError."""
+    if isinstance(index, str) and index in INDEX_LAYOUTS:
+        return INDEX_LAYOUTS[index]
+    if isinstance(index, (int, np.integer)) and not isinstance(index, bool) and 0 <= int(index) <= 2:
+        return int(index)
+    raise DpError("map_reads: index must be 'auto', 'dense' or 'sparse' (0, 1, 2), not %r" % (index,))
+
+
+def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
+              index="auto"):
     """ref / reads: downpore_amd.overlap.Reads (reference loaded with min_len=0, reads with min_len=min_length; both are
-    treated as top-level sequences exactly like commands/map.go does).  Returns (paf, stderr_text, stats)."""
+    treated as top-level sequences exactly like commands/map.go does).  index: the reference index's layout ("auto" takes the
+    sparse one when the dense one would not fit the device; both give the same PAF).  Returns (paf, stderr_text, stats);
+    stats["index"] describes the index (MAP_INDEX_FIELDS, layout "dense" / "sparse")."""
+    layout = index_layout_code(index)
     H = load_host()
-    H.dph_map_run.restype = C.c_void_p
-    H.dph_map_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    H.dph_map_run_ex.restype = C.c_void_p
+    H.dph_map_run_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     H.dph_map_free.argtypes = [C.c_void_p]
     for f in (H.dph_map_paf, H.dph_map_errtext):
         f.restype = C.POINTER(C.c_char)
         f.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     H.dph_map_stats.argtypes = [C.c_void_p, C.c_void_p]
-    p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate], dtype=np.int64)
-    h = H.dph_map_run(ref.h, reads.h, p.ctypes.data, device)
+    H.dph_map_index_info.restype = C.c_int
+    H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout], dtype=np.int64)
+    h = H.dph_map_run_ex(ref.h, reads.h, p.ctypes.data, len(p), device)
     if not h:
         raise DpError("dph_map_run: " + H.dph_last_error(None).decode())
     n = C.c_int64(0)
@@ -30,5 +49,11 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     err = C.string_at(H.dph_map_errtext(h, C.byref(n)), n.value).decode()
     st = np.zeros(len(MAP_STAT_FIELDS), dtype=np.float64)
     H.dph_map_stats(h, st.ctypes.data)
+    ix = np.zeros(len(MAP_INDEX_FIELDS), dtype=np.int64)
+    got = H.dph_map_index_info(h, ix.ctypes.data, len(ix))
     H.dph_map_free(h)
-    return paf, err, dict(zip(MAP_STAT_FIELDS, st.tolist()))
+    stats = dict(zip(MAP_STAT_FIELDS, st.tolist()))
+    info = dict(zip(MAP_INDEX_FIELDS[:got], (int(v) for v in ix[:got])))
+    info["layout"] = {1: "dense", 2: "sparse"}.get(info.get("layout", 0), "none")
+    stats["index"] = info
+    return paf, err, stats

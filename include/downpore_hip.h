@@ -255,6 +255,32 @@ typedef struct {
 
 DP_API int dp_index_build(dp_ctx* ctx, const dp_seq_ref* seqs, uint32_t n_seqs);
 
+/* The same index in its sparse layout: per seed its distinct chunks, per chunk its distinct seeds, as ascending uint32 id lists
+ * (64-bit row offsets), plus the per-seed {count, first word, last word, last + 1} rows exactly as dp_index_build writes them
+ * (so dp_index_meta / dp_index_set_global work alike).  Device bytes: at most 8 H + 32 (S + M), H = the sum of n_seeds,
+ * S = seeds, M = n_seqs; the dense layout needs S ceil(M/64) 8 + M ceil(S/64) 8.  The sequences' segments are copied out of
+ * the scan buffer, so later dp_scan calls on the context do not disturb the index.  dp_map_windows / dp_map_windows_shard
+ * query either layout with the same results; dp_find_overlaps refuses a sparse context (DP_ERR_STATE): overlap rounds index
+ * dense.  dp_index_posting_row / dp_index_seedset_row answer on either layout (rows expanded into words). */
+DP_API int dp_index_build_sparse(dp_ctx* ctx, const dp_seq_ref* seqs, uint32_t n_seqs);
+/* A context made by dp_ctx_create_shared(src), after its dp_round_begin with src's seeds, reads src's sparse index instead of
+ * building one of its own (read-only; src must not build another index while borrowers map). */
+DP_API int dp_index_borrow(dp_ctx* ctx, dp_ctx* src);
+enum { DP_INDEX_NONE = 0, DP_INDEX_DENSE = 1, DP_INDEX_SPARSE = 2 };
+typedef struct {
+    uint32_t layout;        /* DP_INDEX_* */
+    uint32_t borrowed;      /* 1: the index is another context's (dp_index_borrow) */
+    uint32_t n_seeds;       /* S */
+    uint32_t n_seqs;        /* M */
+    uint64_t device_bytes;  /* bytes of the index's device buffers (offsets, id lists or bit matrices, pmeta, sequence views) */
+    uint64_t entries;       /* distinct (sequence, seed) pairs of a sparse index (0 for a dense one: the sum of dp_index_meta's counts) */
+    uint64_t queries[4];    /* windows dp_map_windows(_shard) queried on this context, by regime: 4/8-ladder (minCount <= 12),
+                             * 16-ladder (13 .. 24), exact count (> 24), more than 512 sets (the BIG tier) */
+} dp_index_info_t;
+DP_API int dp_index_info(dp_ctx* ctx, dp_index_info_t* out);
+/* Free and total memory of a device (free includes the blocks the library keeps parked for reuse). */
+DP_API int dp_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes);
+
 /* ---- A14 + A5 + A6 + A7 + A8: index query and overlap chaining ---------------------------------------------
  * Replaces overlapper.matchWorker (overlap/overlap.go:346-387) for all queries of a round:
  *   SeedIndex.Matches -> util.GetSharedIDs (+ getSoftUnion{4,8,16}Asm semantics incl. threshold saturation and

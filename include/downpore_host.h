@@ -133,10 +133,20 @@ DPH_API int dph_overlap_commit_blobs(void* h, const uint8_t* blobs, const uint64
  * kernel ms, seconds of set-up / window scans / dp_map_windows / host, algorithmic bytes of the map kernels (index query +
  * prefilter + chaining) and of the window scans (packed bases). */
 DPH_API void* dph_map_run(void* ref, void* reads, const int64_t* params, int device);
+/* dph_map_run with n_params = 6 (the same) or 7: params[6] = the reference index's layout, 0 = auto, 1 = dense, 2 = sparse
+ * (dp_index_build_sparse; mapper threads then borrow the one index).  Auto takes sparse when the dense estimate - S ceil(M/64) 8 +
+ * M ceil(S/64) 8 bytes summed over the contexts / shards the run builds on a device - exceeds that device's free memory less an
+ * eighth of its total.  Both layouts print the same PAF.  Another layout value is refused before any device call.  A reference
+ * sequence longer than 2^31 - 1 bases is refused (with its length in the error) before anything is allocated. */
+DPH_API void* dph_map_run_ex(void* ref, void* reads, const int64_t* params, int n_params, int device);
 DPH_API void dph_map_free(void* m);
 DPH_API const char* dph_map_paf(void* m, int64_t* n);
 DPH_API const char* dph_map_errtext(void* m, int64_t* n);
 DPH_API void dph_map_stats(void* m, double* out);
+/* The run's reference index: out[0..9] = layout (1 dense, 2 sparse), device bytes of the indexes built, the dense estimate D, the
+ * device's total memory, H (seed hits in chunks), contexts that built an index, then the queries by regime: 4/8-ladder (minCount
+ * <= 12), 16-ladder (13 .. 24), exact count (> 24), more than 512 sets.  Writes at most cap values; returns how many it wrote. */
+DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
 
 /* ---- test hooks (host logic without a GPU, counters) ------------------------------------------------------------------------ */
 DPH_API const char* dph_reads_dump(void* reads, int64_t* n);
