@@ -53,6 +53,8 @@ struct dp_ctx {
     int32_t pc_inset = 0;
     uint64_t pc_hits = 0, pc_misses = 0;
     std::vector<uint32_t> ss_host;  // dp_single_seed_candidates' result (ordinary host memory: read by a sequential host walk)
+    std::vector<uint64_t> qc_off;            // dp_query_candidates' result (ordinary host memory)
+    std::vector<uint32_t> qc_ids, qc_meta;
     uint32_t last_n_extra = 0;    // extra items of the last dp_scan_reads
     uint32_t kx_seq = 0;          // sequence number the sort pass of a one-go index step stores into h_total[15] when its output is complete
     uint32_t kx_maxlen = 0;       // longest read (hit records hold 24 bits of position)

@@ -849,8 +849,7 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     int32_t* d_thr = nullptr;
     if (thr_io) {
         if (dev_reserve(ctx, ctx->d_sa, (size_t)nw * 4 + 64)) return DP_ERR_HIP;
-        d_thr = (int32_t*)ctx->d_sa.p;
-        DP_HIP(hipMemcpyAsync(d_thr, thr_io, (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_thr = (int32_t*)ctx->d_sa.p;  // (filled from thr_io before every launch, below)
     }
     if (dev_reserve(ctx, ctx->d_cursor, 64)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_sched, (size_t)nw * 4 + 16)) return DP_ERR_HIP;
@@ -890,6 +889,9 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
         if (dev_reserve(ctx, ctx->d_ma, (size_t)int_cap * 4)) return DP_ERR_HIP;
         if (dev_reserve(ctx, ctx->d_mb, (size_t)int_cap * 4)) return DP_ERR_HIP;
         DP_HIP(hipMemsetAsync(ctx->d_cursor.p, 0, 64, ctx->stream));
+        // the kernel ratchets d_thr in place: a relaunch (grown buffers, the BIG variant) starts from the caller's thresholds again,
+        // which stay untouched in thr_io until the loop has ended
+        if (d_thr) DP_HIP(hipMemcpyAsync(d_thr, thr_io, (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
         if (d_mprof) DP_HIP(hipMemsetAsync(d_mprof, 0, 16 * 8, ctx->stream));
         DP_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
         if (sparse && !big)

@@ -3882,6 +3882,43 @@ extern "C" int dp_find_overlaps(dp_ctx* ctx, const int32_t* q_segs, const uint64
     return dp_find_overlaps_impl(ctx, q_segs, q_off, n_queries, hit_fraction, k, max_query_len, want_candidates, out);
 }
 
+// Matches() alone (test hook): the query stage on either layout, its candidate words and per-query words copied back and expanded
+extern "C" int dp_query_candidates(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t n_queries, double hit_fraction,
+                                   dp_candidate_batch* out) {
+    if (!ctx || !out || (n_queries && (!q_segs || !q_off))) return DP_ERR_ARG;
+    if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_query_candidates before dp_round_begin");
+    hipSetDevice(ctx->device);
+    memset(out, 0, sizeof(*out));
+    const uint32_t nq = n_queries, W = ctx->W;
+    ctx->qc_off.assign((size_t)nq + 1, 0);
+    ctx->qc_ids.clear();
+    ctx->qc_meta.assign((size_t)nq * 3 + 1, 0);
+    out->n_queries = nq;
+    out->cand_off = ctx->qc_off.data();
+    out->cand = ctx->qc_ids.data();
+    out->meta = ctx->qc_meta.data();
+    if (nq == 0 || ctx->n_seqs == 0) return DP_OK;
+    uint32_t* d_qmeta = nullptr;
+    u64* d_words = nullptr;
+    int32_t* d_mc = nullptr;
+    uint32_t mc_n = 0;
+    ctx->map_stage_valid = false;  // (the stage's buffers are those of dp_map_windows_shard's forward pass)
+    if (int rc = dp_query_stage(ctx, q_segs, q_off, nq, hit_fraction, &d_qmeta, &d_words, &d_mc, &mc_n, nullptr)) return rc;
+    std::vector<u64> cw((size_t)nq * W);
+    std::vector<uint32_t> qm((size_t)nq * 4);
+    DP_HIP(hipMemcpyAsync(cw.data(), ctx->d_cand.p, cw.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    DP_HIP(hipMemcpyAsync(qm.data(), d_qmeta, qm.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DP_HIP(dp_stream_sync(ctx));
+    for (uint32_t q = 0; q < nq; q++) {
+        for (int j = 0; j < 3; j++) ctx->qc_meta[3 * (size_t)q + j] = qm[4 * (size_t)q + j];
+        for (uint32_t wi = 0; wi < W; wi++)
+            for (u64 m = cw[(size_t)q * W + wi]; m; m &= m - 1) ctx->qc_ids.push_back(wi * 64 + (uint32_t)__builtin_ctzll(m));
+        ctx->qc_off[q + 1] = ctx->qc_ids.size();
+    }
+    out->cand = ctx->qc_ids.data();
+    return DP_OK;
+}
+
 // A19/A20 map flavour: implemented in dp_map.hip
 extern "C" int dp_map_windows(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_off, const uint32_t* w_len,
                               uint32_t n_windows, int k, dp_chain_batch* out) {

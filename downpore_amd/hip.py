@@ -46,7 +46,12 @@ class MatchBatch(C.Structure):
 class ChainBatch(C.Structure):
     _fields_ = [("n_chains", C.c_uint32), ("window", C.POINTER(C.c_uint32)), ("target", C.POINTER(C.c_uint32)),
                 ("off", C.POINTER(C.c_uint64)), ("match_a", C.POINTER(C.c_int32)), ("match_b", C.POINTER(C.c_int32)),
-                ("kernel_ms", C.c_double)]
+                ("kernel_ms", C.c_double), ("alg_bytes", C.c_double)]
+
+
+class CandidateBatch(C.Structure):  # dp_candidate_batch
+    _fields_ = [("n_queries", C.c_uint32), ("cand_off", C.POINTER(C.c_uint64)), ("cand", C.POINTER(C.c_uint32)),
+                ("meta", C.POINTER(C.c_uint32))]
 
 
 class IndexInfo(C.Structure):  # dp_index_info_t
@@ -61,7 +66,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_scan_import_segments", "dp_values_upload", "dp_select_seeds", "dp_reads_upload_rc", "dp_consensus_align", "dp_scan_release", "dp_consensus_paf", "dp_fetch_overlaps", "dp_select_windows", "dp_values_download",
     "dp_values_download_codes", "dp_values_download_codes8", "dp_index_build_chunked", "dp_index_prechain", "dp_index_prechained", "dp_index_chunks", "dp_scan_fetch_mode", "dp_scan_fetch_segments", "dp_set_stream_wait", "dp_set_kernel_timing", "dp_index_meta", "dp_index_set_global", "dp_map_windows_shard", "dp_single_seed_candidates", "dp_comm_unique_id", "dp_comm_init", "dp_comm_init_local", "dp_quality_upload",
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
-           "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory"]
+           "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates"]
 
 _lib = None
 
@@ -117,12 +122,18 @@ def _arr(p, n, dtype):
 class Context:
     """One GPU context (`dp_ctx`): reads resident in HBM + per-round seed/index state."""
 
-    def __init__(self, device=0):
+    def __init__(self, device=0, shared_from=None):
+        """shared_from: another Context whose resident reads this one borrows (dp_ctx_create_shared); close it before that one."""
         self.L = load_library()
         h = C.c_void_p()
-        rc = self.L.dp_ctx_create(device, C.byref(h))
-        if rc != 0:
-            raise DpError("dp_ctx_create failed (%d): %s" % (rc, self.L.dp_last_error(None).decode()))
+        if shared_from is not None:
+            rc = self.L.dp_ctx_create_shared(shared_from.h, C.byref(h))
+            if rc != 0:
+                raise DpError("dp_ctx_create_shared failed (%d): %s" % (rc, self.L.dp_last_error(shared_from.h).decode()))
+        else:
+            rc = self.L.dp_ctx_create(device, C.byref(h))
+            if rc != 0:
+                raise DpError("dp_ctx_create failed (%d): %s" % (rc, self.L.dp_last_error(None).decode()))
         self.h = h
 
     def close(self):
@@ -281,6 +292,12 @@ class Context:
         self._chk(self.L.dp_index_build_sparse(self.h, refs.ctypes.data, len(refs)))
         self.n_seqs = len(refs)
 
+    def index_borrow(self, src):
+        """dp_index_borrow: after round_begin with src's seeds, read src's sparse index instead of building one."""
+        self.L.dp_index_borrow.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(self.L.dp_index_borrow(self.h, src.h))
+        self.n_seqs = src.n_seqs
+
     def index_info(self):
         """dp_index_info: layout ("none" / "dense" / "sparse"), borrowed, n_seeds, n_seqs, device_bytes, entries, queries[4]."""
         info = IndexInfo()
@@ -337,6 +354,18 @@ class Context:
             res["cand"] = _arr(b.cand, int(co[-1]), np.uint32)
         return res
 
+    def query_candidates(self, q_segs, q_off, hit_fraction):
+        """dp_query_candidates: Matches() alone on either layout -> cand_off, cand (ascending ids per query, shard-local), meta
+        uint32 [n, 3] = {sets, minCount, status}."""
+        qs = np.ascontiguousarray(q_segs, dtype=np.int32)
+        qo = np.ascontiguousarray(q_off, dtype=np.uint64)
+        b = CandidateBatch()
+        self.L.dp_query_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.POINTER(CandidateBatch)]
+        self._chk(self.L.dp_query_candidates(self.h, qs.ctypes.data, qo.ctypes.data, len(qo) - 1, float(hit_fraction), C.byref(b)))
+        n = b.n_queries
+        co = _arr(b.cand_off, n + 1, np.uint64)
+        return dict(cand_off=co, cand=_arr(b.cand, int(co[-1]), np.uint32), meta=_arr(b.meta, 3 * n, np.uint32).reshape(-1, 3))
+
     # ---- A19 + A20
     def map_windows(self, w_segs, w_off, w_len, k):
         ws = np.ascontiguousarray(w_segs, dtype=np.int32)
@@ -344,8 +373,27 @@ class Context:
         wl = np.ascontiguousarray(w_len, dtype=np.uint32)
         b = ChainBatch()
         self._chk(self.L.dp_map_windows(self.h, ws.ctypes.data, wo.ctypes.data, wl.ctypes.data, len(wo) - 1, k, C.byref(b)))
+        return self._chains(b)
+
+    @staticmethod
+    def _chains(b):
         n = b.n_chains
         off = _arr(b.off, n + 1, np.uint64)
         tot = int(off[-1]) if n else 0
         return dict(window=_arr(b.window, n, np.uint32), target=_arr(b.target, n, np.uint32), off=off,
                     match_a=_arr(b.match_a, tot, np.int32), match_b=_arr(b.match_b, tot, np.int32), kernel_ms=b.kernel_ms)
+
+    def map_windows_shard(self, w_segs, w_off, w_len, k, phase, thr):
+        """dp_map_windows_shard: one strand (phase 0 forward, 1 reverse complement) of every window pair against this context's
+        shard.  thr: int32 [n_windows] minMatches / minRCMatches per pair (-1: the window's own).  Returns (chains, updated thr)."""
+        ws = np.ascontiguousarray(w_segs, dtype=np.int32)
+        wo = np.ascontiguousarray(w_off, dtype=np.uint64)
+        wl = np.ascontiguousarray(w_len, dtype=np.uint32)
+        t = np.array(thr, dtype=np.int32)
+        assert t.shape == (len(wo) - 1,)
+        b = ChainBatch()
+        self.L.dp_map_windows_shard.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                                C.POINTER(ChainBatch)]
+        self._chk(self.L.dp_map_windows_shard(self.h, ws.ctypes.data, wo.ctypes.data, wl.ctypes.data, len(wo) - 1, k, phase, t.ctypes.data,
+                                              C.byref(b)))
+        return self._chains(b), t

@@ -366,6 +366,21 @@ DP_API int dp_index_meta(dp_ctx* ctx, uint32_t* meta_out, uint32_t n_seeds);
 DP_API int dp_index_set_global(dp_ctx* ctx, const uint32_t* meta_global, uint32_t n_seeds, uint32_t word_base, uint32_t n_seqs_global);
 DP_API int dp_map_windows_shard(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_off, const uint32_t* w_len, uint32_t n_windows,
                          int k, int phase, int32_t* thr_io, dp_chain_batch* out);
+/* SeedIndex.Matches (seeds/seeds.go:335-353) alone, on either index layout (test hook: dp_find_overlaps refuses a sparse index and
+ * dp_map_windows returns chains only): the index query stage of dp_map_windows / dp_find_overlaps for queries given as segments
+ * (reference layout, as in dp_find_overlaps), and per query the ascending candidate ids - ids inside the shard when the context
+ * holds a shard (dp_index_set_global with word_base > 0: the shard's own words of the whole query) - and meta[3 q ..] = {sets that
+ * passed Matches' filter, minCount, status}; status != 0: the query exceeded a capacity of the stage (bit 0: more sets than it
+ * holds, bit 1: no minCount entry) and its candidates mean nothing.  The arrays are the library's (ordinary host memory, valid
+ * until the context's next dp_query_candidates or its destruction). */
+typedef struct {
+    uint32_t n_queries;
+    const uint64_t* cand_off; /* [n_queries + 1] offsets into cand */
+    const uint32_t* cand;
+    const uint32_t* meta;     /* [3 * n_queries] */
+} dp_candidate_batch;
+DP_API int dp_query_candidates(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t n_queries, double hit_fraction,
+                               dp_candidate_batch* out);
 /* The parallel part of SeedIndex.AddSingleSeeds (seeds/seeds.go:160-200; NewMapper calls it on the mapping reference,
  * mapping/mapping.go:67-109) for resident read `read` (a top-level sequence) and the resident value table of this k: for every
  * window of seed_rate bases - for (i = 0; i < len - seed_rate; i += seed_rate) - its best-valued k-mer (what the reference adds as a

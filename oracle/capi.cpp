@@ -497,10 +497,13 @@ const char* dpo_overlap_trace_paf(void* hh, int64_t round, int64_t* n) {
 // ---- map command -----------------------------------------------------------------------------
 struct MapH {
     MapResult res;
+    MapTrace trace;
+    std::map<std::pair<int64_t, int>, std::vector<int64_t>> cache;
 };
 // params: circular,k,querySize,minLength(unused here: applied when the read set was loaded),chunkSize,seedRate
-void* dpo_map_run(void* refSet, void* reads, const int64_t* params) {
+static void* mapRun(void* refSet, void* reads, const int64_t* params, int64_t maxCalls) {
     MapH* h = new MapH();
+    h->trace.maxCalls = maxCalls;
     int rc = guard([&] {
         MapParams p;
         p.circular = params[0] != 0;
@@ -509,13 +512,68 @@ void* dpo_map_run(void* refSet, void* reads, const int64_t* params) {
         p.minLength = params[3];
         p.chunkSize = params[4];
         p.seedRate = params[5];
-        h->res = runMap(((ReadSetH*)refSet)->set, ((ReadSetH*)reads)->set, p);
+        h->res = runMap(((ReadSetH*)refSet)->set, ((ReadSetH*)reads)->set, p, maxCalls >= 0 ? &h->trace : nullptr);
     });
     if (rc != 0) {
         delete h;
         return nullptr;
     }
     return h;
+}
+void* dpo_map_run(void* refSet, void* reads, const int64_t* params) { return mapRun(refSet, reads, params, -1); }
+// the same run with a trace of its first max_calls performMapping calls (dpo_map_trace)
+void* dpo_map_run_traced(void* refSet, void* reads, const int64_t* params, int64_t max_calls) {
+    return mapRun(refSet, reads, params, max_calls < 0 ? 0 : max_calls);
+}
+// Trace fields.  Nested fields come as (flat, offsets) pairs: field f = flat data, f+100 = offsets.
+//  call -1 (the run): 0 seedKmers | 1 scalars {performMapping calls made, calls traced} | 20 indexedSegments
+//  call i: 2 seedQuery segments | 3 rcQuery segments | 4 scalars {seedQuery length, rcQuery length} | 5 matchingIndices
+//          | 6 matchingRCIndices | 7 chain strand (0 forward, 1 reverse complement) | 8 chain target | 23 MatchA | 24 MatchB
+const int64_t* dpo_map_trace(void* hh, int64_t call, int field, int64_t* n) {
+    MapH* h = (MapH*)hh;
+    const MapTrace& t = h->trace;
+    if (call < -1 || call >= (int64_t)t.callTraces.size()) {
+        *n = -1;
+        return nullptr;
+    }
+    auto key = std::make_pair(call, field);
+    auto it = h->cache.find(key);
+    if (it == h->cache.end()) {
+        std::vector<i64> d, o;
+        const int base = field >= 100 ? field - 100 : field;
+        bool ok = true;
+        if (call < 0) {
+            switch (base) {
+                case 0: d = t.seedKmers; break;
+                case 1: d = {t.calls, (i64)t.callTraces.size()}; break;
+                case 20: flat(t.indexedSegments, d, o); break;
+                default: ok = false;
+            }
+        } else {
+            const MapCallTrace& c = t.callTraces[(size_t)call];
+            switch (base) {
+                case 2: d = c.fwdSegments; break;
+                case 3: d = c.rcSegments; break;
+                case 4: d = {c.length, c.rcLength}; break;
+                case 5: d = c.candidates; break;
+                case 6: d = c.rcCandidates; break;
+                case 7: d = c.chainStrand; break;
+                case 8: d = c.chainTarget; break;
+                case 23: flat(c.chainA, d, o); break;
+                case 24: flat(c.chainB, d, o); break;
+                default: ok = false;
+            }
+        }
+        if (!ok) {
+            *n = -1;
+            return nullptr;
+        }
+        h->cache[std::make_pair(call, base)] = d;
+        h->cache[std::make_pair(call, base + 100)] = o;
+        it = h->cache.find(key);
+    }
+    *n = (int64_t)it->second.size();
+    return it->second.data();
 }
 void dpo_map_free(void* h) { delete (MapH*)h; }
 const char* dpo_map_paf(void* h, int64_t* n) {

@@ -365,6 +365,28 @@ std::vector<Mapping*> Mapper::performMapping(const PackedSeq& query) {
     std::vector<u64> matchingIndices = index.matches(seedQuery, 0.25);
     std::vector<u64> matchingRCIndices = index.matches(rcQuery, 0.25);
     std::vector<Mapping*> results;
+    // trace (tests): what this call hands to and takes from the part of it that the product runs on the device
+    MapCallTrace* tc = nullptr;
+    if (trace) {
+        if ((i64)trace->callTraces.size() < trace->maxCalls) {
+            trace->callTraces.emplace_back();
+            tc = &trace->callTraces.back();
+            tc->fwdSegments.assign(seedQuery->seg(), seedQuery->seg() + seedQuery->n);
+            tc->rcSegments.assign(rcQuery->seg(), rcQuery->seg() + rcQuery->n);
+            tc->length = seedQuery->length;
+            tc->rcLength = rcQuery->length;
+            tc->candidates.assign(matchingIndices.begin(), matchingIndices.end());
+            tc->rcCandidates.assign(matchingRCIndices.begin(), matchingRCIndices.end());
+        }
+        trace->calls++;
+    }
+    auto traceChain = [&](i64 strand, u64 idx, const SeedMatch& sm) {
+        if (!tc) return;
+        tc->chainStrand.push_back(strand);
+        tc->chainTarget.push_back((i64)idx);
+        tc->chainA.push_back(sm.MatchA);
+        tc->chainB.push_back(sm.MatchB);
+    };
     i64 maxSeed = 0;
     for (i64 i = 0; i < seedQuery->numSeeds(); i++)
         if (seedQuery->getSeed(i) > maxSeed) maxSeed = seedQuery->getSeed(i);
@@ -394,6 +416,7 @@ std::vector<Mapping*> Mapper::performMapping(const PackedSeq& query) {
             mp->RC = false;
             mp->ids = ids;
             results.push_back(mp);
+            traceChain(0, idx, sm);
             i64 limit = ((i64)sm.MatchA.size() * 4) / 5;
             if (limit > minMatches) minMatches = limit;
             if (limit > minRCMatches) minRCMatches = limit;
@@ -425,6 +448,7 @@ std::vector<Mapping*> Mapper::performMapping(const PackedSeq& query) {
             mp->RC = true;
             mp->ids = ids;
             results.push_back(mp);
+            traceChain(1, idx, sm);
             i64 limit = ((i64)sm.MatchA.size() * 4) / 5;
             if (limit > minRCMatches) minRCMatches = limit;
         }
@@ -450,7 +474,7 @@ std::vector<Mapping*> Mapper::performMapping(const PackedSeq& query) {
 }
 
 // commands/map.go:33-116
-MapResult runMap(FastaSet& refSet, FastaSet& reads, const MapParams& p) {
+MapResult runMap(FastaSet& refSet, FastaSet& reads, const MapParams& p, MapTrace* trace) {
     MapResult res;
     if (refSet.size() == 0) throw std::runtime_error("oracle: empty reference");
     PackedSeq reference = refSet.cached[0];  // cache=false: top-level sequence
@@ -458,6 +482,11 @@ MapResult runMap(FastaSet& refSet, FastaSet& reads, const MapParams& p) {
     std::vector<double> values = kmerValues(counts, p.k);
     res.err += "K-mer counting complete. Preparing to start indexing and querying...\n";
     Mapper mapper(reference, p.circular, p.k, values.data(), p.seedRate, p.querySize, p.chunkSize);
+    if (trace) {
+        mapper.trace = trace;
+        trace->seedKmers = mapper.index.seedMap;
+        for (SeedSequence* s : mapper.index.sequences) trace->indexedSegments.emplace_back(s->seg(), s->seg() + s->n);
+    }
     i64 unmapped = 0, mapped = 0, multiple = 0, total = 0;
     const size_t arenaBase = mapper.index.arena.seqs.size();
     for (size_t id = 0; id < reads.size(); id++) {

@@ -307,8 +307,24 @@ struct Mapping {
 };
 bool mappingsConsistent(const Mapping* left, i64 leftQueryLen, const Mapping* right, bool circular, i64 referenceLength);  // mapping.go:131-160
 std::vector<Mapping*> removeDominated(std::vector<Mapping*> open, const std::vector<Mapping*>* extendedIn, i64 queryLen);  // mapping.go:387-428
+// What a `map` run hands to and takes from the device part of performMapping (tests compare it with the product's kernels).
+struct MapCallTrace {
+    std::vector<i64> fwdSegments, rcSegments;      // seedQuery, rcQuery (seeds are seed ids)
+    i64 length = 0, rcLength = 0;                  // their SeedSequence lengths
+    std::vector<i64> candidates, rcCandidates;     // matchingIndices, matchingRCIndices as Matches(.., 0.25) returned them
+    std::vector<i64> chainStrand, chainTarget;     // chains appended to `results` before the sort and de-overlap, in append order
+    std::vector<std::vector<i64>> chainA, chainB;  // their MatchA / MatchB
+};
+struct MapTrace {
+    i64 maxCalls = 0;                              // performMapping calls to record
+    i64 calls = 0;                                 // performMapping calls made
+    std::vector<i64> seedKmers;                    // seedMap after NewMapper (k-mers in seed-id order)
+    std::vector<std::vector<i64>> indexedSegments; // the indexed chunks
+    std::vector<MapCallTrace> callTraces;
+};
 struct Mapper {
     SeedIndex index;
+    MapTrace* trace = nullptr;
     PackedSeq reference;
     i64 edgeSize;
     bool circular;
@@ -328,7 +344,7 @@ struct Mapper {
                  bool& matchedNil);                                        // :305
 };
 struct MapResult { std::string paf, err; };
-MapResult runMap(FastaSet& refSet, FastaSet& reads, const MapParams& p);
+MapResult runMap(FastaSet& refSet, FastaSet& reads, const MapParams& p, MapTrace* trace = nullptr);
 
 // Go sort.Sort stand-in (see header note): insertion sort for n<=12, stable sort otherwise.
 template <class T, class Less>

@@ -115,6 +115,10 @@ def lib():
         L.dpo_map_run.restype = vp
         L.dpo_map_run.argtypes = [vp, vp, i64p]
         L.dpo_map_free.argtypes = [vp]
+        L.dpo_map_run_traced.restype = vp
+        L.dpo_map_run_traced.argtypes = [vp, vp, i64p, C.c_int64]
+        L.dpo_map_trace.restype = i64p
+        L.dpo_map_trace.argtypes = [vp, C.c_int64, C.c_int, i64p]
         _lib = L
     return _lib
 
@@ -252,6 +256,11 @@ def kmer_value(s):
 class IntSet:
     def __init__(self, cap=None):
         self.h = lib().dpo_set_new() if cap is None else lib().dpo_set_new_cap(cap)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().dpo_set_free(self.h)
+            self.h = None
 
     def add(self, x):
         lib().dpo_set_add(self.h, x)
@@ -422,3 +431,42 @@ def map_run(ref, reads, circular=True, k=11, query_size=1000, min_length=500, ch
     err = _bytes(lib().dpo_map_err, h).decode()
     lib().dpo_map_free(h)
     return paf, err
+
+
+class MapRun:
+    """map_run with a trace of the first max_calls calls of performMapping: what each call hands to and takes from the part of it the
+    product runs on the device.  trace(name): the run's seedKmers, scalars {calls made, calls traced}, indexedSegments (data, offsets);
+    call(i): that call's windows, window lengths, candidate lists and chains."""
+    RUN_FIELDS = dict(seedKmers=0, scalars=1, indexedSegments=20)
+    CALL_FIELDS = dict(fwdSegments=2, rcSegments=3, lengths=4, candidates=5, rcCandidates=6, chainStrand=7, chainTarget=8, matchA=23,
+                       matchB=24)
+
+    def __init__(self, ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, max_calls=0):
+        p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate], dtype=np.int64)
+        self.h = lib().dpo_map_run_traced(ref.h, reads.h, ptr(p, i64p), max_calls)
+        if not self.h:
+            raise RuntimeError(lib().dpo_last_error().decode())
+        self.k = k
+        self.paf = _bytes(lib().dpo_map_paf, self.h).decode()
+        self.err = _bytes(lib().dpo_map_err, self.h).decode()
+        self.calls_made, self.n_calls = (int(x) for x in self._field(-1, 1))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().dpo_map_free(self.h)
+            self.h = None
+
+    def _field(self, call, f):
+        n = C.c_int64(0)
+        p = lib().dpo_map_trace(self.h, call, f, C.byref(n))
+        assert n.value >= 0, (call, f)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.int64)
+
+    def _get(self, call, f):
+        return self._field(call, f) if f < 20 else (self._field(call, f), self._field(call, f + 100))
+
+    def trace(self, name):
+        return self._get(-1, self.RUN_FIELDS[name])
+
+    def call(self, i):
+        return {name: self._get(i, f) for name, f in self.CALL_FIELDS.items()}

@@ -445,8 +445,9 @@ def test_select_seeds_matches_addseeds(ctx, k, L, e):
             assert got == want[i].tolist(), (num_seeds, wins[i])
 
 
-def _index_from_sets(ctx, k, member):
-    """member[s][i] truthy <=> sequence i holds seed s.  Builds the device index for it; returns the oracle IntSets."""
+def _index_from_sets(ctx, k, member, build="index_build"):
+    """member[s][i] truthy <=> sequence i holds seed s.  Builds the device index for it (build: the Context method that does,
+    index_build or index_build_sparse); returns the oracle IntSets."""
     S, M = len(member), len(member[0])
     ctx.round_begin(k, np.arange(S, dtype=np.uint32) * 37 + 5)  # any S distinct k-mers
     segs, offs, nseeds = [], [0], []
@@ -459,7 +460,7 @@ def _index_from_sets(ctx, k, member):
         offs.append(len(segs))
         nseeds.append(len(mine))
     ctx.import_segments(np.array(segs, dtype=np.int32))
-    ctx.index_build(np.array(offs[:-1], dtype=np.uint64), np.array(nseeds, dtype=np.uint32))
+    getattr(ctx, build)(np.array(offs[:-1], dtype=np.uint64), np.array(nseeds, dtype=np.uint32))
     sets = [O.IntSet() for _ in range(S)]
     for s in range(S):
         for i in reversed(range(M)):  # IndexSequences adds in descending sequence order (seeds.go:373-381)
