@@ -47,6 +47,7 @@ struct ReadSet {
     bool isFastq = false;
     const uint8_t* quality(size_t r) const { return (!qual.empty() && hasQual[r]) ? (const uint8_t*)qual.data() + off[r] : nullptr; }
     std::vector<uint8_t> ignore;   // SetIgnore flags (seqio.go:375); planner lanes read them while a commit sets them: flagLoad / flagStore
+    std::vector<int32_t> frontTrim, backTrim;  // SetFrontTrim / SetBackTrim (seqio.go:378-386); empty until a trim run sizes them
     bool himem = true;             // cached views (seqio.go:115) vs top-level re-reads (:158)
     size_t maxNameLen = 0;         // longest name (PAF line buffers are sized from it)
     size_t size() const { return names.size(); }
@@ -773,6 +774,42 @@ struct MapStats {
 size_t releaseMapStaging();  // dph_release_caches: the staging block kept for the process's next map command
 int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
            MapStats* stats, std::string& error);
+
+// ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------
+struct TrimParams {  // flag table commands/trim.go:17-20 (the flags of the middle-adapter search are parsed by the CLI and not used)
+    int k = 6;
+    i64 checkReads = 10000;
+    int adapterThreshold = 90, extraEdgeTrim = 5;
+    bool tagAdapters = true, requirePairs = false, determineAdapters = true;
+    int verbosity = 1;
+};
+// setupIndex (trim.go:57-99) as dp_trim_setup takes it: front adapters first, then back
+struct TrimIndex {
+    int k = 0;
+    uint32_t nFront = 0, nBack = 0, nSeeds = 0;
+    std::vector<uint16_t> kmerSeed;  // 4^k, 0xffff = not a seed
+    std::vector<int32_t> segs;       // NewAllSeedSequence segments
+    std::vector<uint64_t> segOff;
+    std::vector<int32_t> lengths, pairs;
+    std::vector<uint8_t> isBarcode;
+};
+struct TrimResult {
+    std::string out, errText;             // what Write prints; the log.Println lines without their timestamps
+    std::vector<std::string> names;       // the reads' names after tagging (SetName, :501)
+    std::vector<int32_t> table;           // per read: front_trim, back_trim, ignore, front adapter index or -1, back adapter index or -1
+    std::vector<std::string> frontNames, backNames;  // the adapters after determination, in the trimmer's order
+    std::vector<uint64_t> counts;         // frontCounts then backCounts
+    i64 seen = 0, none = 0;               // seenCount, noCount
+    double t_determine = 0, t_extract = 0, t_apply = 0, t_write = 0;  // host wall seconds
+    double k_determine_ms = 0, upload_ms = 0, kernel_ms = 0, download_ms = 0, bytes_up = 0, bytes_down = 0;  // the trim pass's device calls
+};
+bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error);
+// the whole edge stage on HIP device `device`; reads receives ignore / frontTrim / backTrim.  0, or < 0 with `error` (-2: no read of 200 bases)
+int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error);
+int applyTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+              size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error);
+void trimWrite(const ReadSet& reads, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out);
+int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::string& dir, std::string& error);  // files written, or < 0
 
 // ---- flag table helpers (commands/command.go:18-74, downpore.go:34-51) -------------------------------------------
 struct ArgTable {

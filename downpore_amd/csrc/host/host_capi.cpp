@@ -974,6 +974,126 @@ extern "C" int dph_map_index_info(void* h, int64_t* out, int cap) {
     return n;
 }
 
+// ---- `downpore trim`, edge stage -----------------------------------------------------------------------------------
+// params: k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity
+namespace {
+struct TrimH {
+    ReadSet* reads = nullptr;
+    TrimResult res;
+    std::string adapters;
+};
+bool trimParamsFrom(const int64_t* params, int n, TrimParams& p) {
+    if (!params || n != 8) return false;
+    p.k = (int)params[0];
+    p.checkReads = params[1];
+    p.adapterThreshold = (int)params[2];
+    p.extraEdgeTrim = (int)params[3];
+    p.tagAdapters = params[4] != 0;
+    p.requirePairs = params[5] != 0;
+    p.determineAdapters = params[6] != 0;
+    p.verbosity = (int)params[7];
+    return true;
+}
+}  // namespace
+extern "C" void* dph_trim_run(void* readsH, void* frontH, void* backH, const int64_t* params, int n_params, int device) {
+    TrimParams p;
+    if (!readsH || !frontH || !backH || !trimParamsFrom(params, n_params, p)) {
+        g_err = "dph_trim_run: bad arguments (8 parameters)";
+        return nullptr;
+    }
+    TrimH* h = new TrimH();
+    h->reads = &((ReadsH*)readsH)->set;
+    std::string error;
+    if (runTrim(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, device, h->res, error) != 0) {
+        g_err = error;
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+extern "C" void* dph_trim_apply(void* readsH, void* frontH, void* backH, const int64_t* params, int n_params, const uint8_t* enabled,
+                                const int32_t* recs, int64_t n_rec_reads, const uint64_t* counts) {
+    TrimParams p;
+    if (!readsH || !frontH || !backH || !trimParamsFrom(params, n_params, p) || n_rec_reads < 0 || (n_rec_reads && !recs) || !counts) {
+        g_err = "dph_trim_apply: bad arguments (8 parameters)";
+        return nullptr;
+    }
+    static_assert(sizeof(dp_trim_rec) == 6 * sizeof(int32_t), "edge records are six int32");
+    TrimH* h = new TrimH();
+    h->reads = &((ReadsH*)readsH)->set;
+    std::string error;
+    if (applyTrim(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, h->res,
+                  error) != 0) {
+        g_err = error;
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+extern "C" void dph_trim_free(void* h) { delete (TrimH*)h; }
+extern "C" const char* dph_trim_output(void* h, int64_t* n) {
+    *n = (int64_t)((TrimH*)h)->res.out.size();
+    return ((TrimH*)h)->res.out.data();
+}
+extern "C" const char* dph_trim_errtext(void* h, int64_t* n) {
+    *n = (int64_t)((TrimH*)h)->res.errText.size();
+    return ((TrimH*)h)->res.errText.data();
+}
+extern "C" int64_t dph_trim_table(void* h, int32_t* out, int64_t cap_reads) {
+    const std::vector<int32_t>& t = ((TrimH*)h)->res.table;
+    const int64_t n = std::min<int64_t>(cap_reads, (int64_t)t.size() / 5);
+    if (out && n > 0) memcpy(out, t.data(), (size_t)n * 5 * sizeof(int32_t));
+    return (int64_t)t.size() / 5;
+}
+// "F\tname\tcount\n" per front adapter, then "B\t..." per back adapter, in the trimmer's order after determination
+extern "C" const char* dph_trim_adapters(void* h, int64_t* n) {
+    TrimH* t = (TrimH*)h;
+    t->adapters.clear();
+    const TrimResult& r = t->res;
+    for (size_t i = 0; i < r.frontNames.size(); i++) t->adapters += "F\t" + r.frontNames[i] + "\t" + std::to_string(r.counts[i]) + "\n";
+    for (size_t i = 0; i < r.backNames.size(); i++)
+        t->adapters += "B\t" + r.backNames[i] + "\t" + std::to_string(r.counts[r.frontNames.size() + i]) + "\n";
+    *n = (int64_t)t->adapters.size();
+    return t->adapters.data();
+}
+// out[16]: seen, none, reads, front adapters, back adapters, determine s, end extraction s, upload ms, kernel ms, download ms,
+// host apply s, write s, determine kernel ms, bytes up, bytes down, 0
+extern "C" void dph_trim_stats(void* h, double* out) {
+    const TrimH* t = (const TrimH*)h;
+    const TrimResult& r = t->res;
+    const double v[16] = {(double)r.seen, (double)r.none, (double)t->reads->size(), (double)r.frontNames.size(), (double)r.backNames.size(),
+                          r.t_determine, r.t_extract, r.upload_ms, r.kernel_ms, r.download_ms, r.t_apply, r.t_write, r.k_determine_ms,
+                          r.bytes_up, r.bytes_down, 0.0};
+    memcpy(out, v, sizeof v);
+}
+extern "C" int dph_trim_demultiplex(void* h, const char* dir) {
+    TrimH* t = (TrimH*)h;
+    std::string error;
+    const int rc = trimDemultiplex(*t->reads, t->res, dir ? dir : ".", error);
+    if (rc < 0) g_err = error;
+    return rc;
+}
+// setupIndex as dp_trim_setup takes it.  kmer_seed[4^k]; segs[seg_cap]; seg_off[n + 1]; lengths, is_barcode, pairs[n] with
+// n = front + back adapters.  Returns the number of seeds, or -1 (dph_last_error(NULL)); seg_cap too small: -2 - seg_off[n] ints are needed.
+extern "C" int64_t dph_trim_index(void* frontH, void* backH, int k, uint16_t* kmer_seed, int32_t* segs, int64_t seg_cap, uint64_t* seg_off,
+                                  int32_t* lengths, uint8_t* is_barcode, int32_t* pairs) {
+    TrimIndex ix;
+    std::string error;
+    if (!frontH || !backH || !trimBuildIndex(((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, k, ix, error)) {
+        g_err = error.empty() ? "dph_trim_index: bad arguments" : error;
+        return -1;
+    }
+    const size_t n = ix.lengths.size();
+    memcpy(seg_off, ix.segOff.data(), (n + 1) * sizeof(uint64_t));
+    if ((int64_t)ix.segs.size() > seg_cap) return -2;
+    memcpy(kmer_seed, ix.kmerSeed.data(), ix.kmerSeed.size() * 2);
+    memcpy(segs, ix.segs.data(), ix.segs.size() * 4);
+    memcpy(lengths, ix.lengths.data(), n * 4);
+    memcpy(is_barcode, ix.isBarcode.data(), n);
+    memcpy(pairs, ix.pairs.data(), n * 4);
+    return (int64_t)ix.nSeeds;
+}
+
 // ---- host-logic test hook (no GPU needed): the plan chain of a round-parallel run of `world` ranks whose planners each compute
 // only the plans of their own rounds (Planner::setOwnership) and guess where the rounds in between end.  Every simulated rank has
 // its own copy of the read set (its own flags), its own window cache (host producer) and planner; the driver plays the commit:

@@ -1,8 +1,10 @@
 // `downpore` command-line front end of the product: same commands, flag names, defaults, aliases, stderr lines and
-// PAF columns as the reference for the path in scope (downpore.go:34-92; commands/overlap.go:22-29; commands/map.go:17-22).
+// PAF columns as the reference for the path in scope (downpore.go:34-92; commands/overlap.go:22-29; commands/map.go:17-22;
+// commands/trim.go:16-50).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 
 #include "host_util.hpp"
 
@@ -86,9 +88,73 @@ static int runOverlap(ArgTable& t) {
     return 0;
 }
 
+// log.Println's default prefix ("2006/01/02 15:04:05 ") in front of every line of a run's log text
+static void printLog(const std::string& text) {
+    char stamp[32];
+    const time_t t = time(nullptr);
+    struct tm tmv;
+    localtime_r(&t, &tmv);
+    strftime(stamp, sizeof stamp, "%Y/%m/%d %H:%M:%S ", &tmv);
+    size_t at = 0;
+    while (at < text.size()) {
+        size_t e = text.find('\n', at);
+        if (e == std::string::npos) e = text.size();
+        fprintf(stderr, "%s%.*s\n", stamp, (int)(e - at), text.data() + at);
+        at = e + 1;
+    }
+}
+
+static int runTrimCommand(ArgTable& t) {  // commands/trim.go:32-50
+    bool ok = true;
+    TrimParams p;
+    p.k = (int)parseInt(t.args["k"], ok);
+    p.checkReads = parseInt(t.args["check_reads"], ok);
+    p.adapterThreshold = (int)parseInt(t.args["adapter_threshold"], ok);
+    p.extraEdgeTrim = (int)parseInt(t.args["extra_end_trim"], ok);
+    p.verbosity = (int)parseInt(t.args["verbosity"], ok);
+    p.tagAdapters = parseBool(t.args["tag_adapters"]);
+    p.requirePairs = parseBool(t.args["require_pairs"]);
+    p.determineAdapters = parseBool(t.args["determine_adapters"]);
+    // parsed and accepted; they belong to the search for adapters in the middle of reads, or change nothing in the result
+    parseInt(t.args["chunk_size"], ok);
+    parseInt(t.args["middle_threshold"], ok);
+    parseInt(t.args["extra_middle_trim"], ok);
+    parseInt(t.args["num_workers"], ok);
+    if (!ok) return 1;
+    if (t.args["front_adapters"].empty() || t.args["back_adapters"].empty()) {
+        fprintf(stderr, "downpore trim: -front_adapters and -back_adapters are required (the adapter lists are not shipped with this build)\n");
+        return 1;
+    }
+    fprintf(stderr, "downpore trim: the search for adapters in the middle of reads is not part of this build; reads are end-trimmed only\n");
+    ReadSet front, back, reads;
+    std::string err;
+    if (!ReadSet::fromFile(t.args["front_adapters"], 0, false, front, err) || !ReadSet::fromFile(t.args["back_adapters"], 0, false, back, err) ||
+        !ReadSet::fromFile(t.args["input"], 50, parseBool(t.args["himem"]), reads, err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return 1;
+    }
+    TrimResult res;
+    std::string error;
+    const int rc = runTrim(reads, front, back, p, 0, res, error);
+    printLog(res.errText);
+    if (rc != 0) {
+        fprintf(stderr, "downpore: %s\n", error.c_str());
+        return 2;
+    }
+    if (!t.args["demultiplex"].empty()) {
+        if (trimDemultiplex(reads, res, t.args["demultiplex"], error) < 0) {
+            fprintf(stderr, "downpore: %s\n", error.c_str());
+            return 2;
+        }
+    } else {
+        fwrite(res.out.data(), 1, res.out.size(), stdout);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     setenv("GPU_MAX_HW_QUEUES", "8", 0);  // one hardware queue per executor slot's stream (the runtime's default is 4)
-    ArgTable ov, mp;
+    ArgTable ov, mp, tr;
     ov.make({"overlap_size", "k", "num_seeds", "seed_batch_size", "chunk_size", "query_batch_size", "min_hits", "num_workers",
              "input", "seed_values", "himem"},
             {"1000", "10", "15", "10000", "10000", "20000", "0.25", "4", "", "", "true"},
@@ -104,13 +170,25 @@ int main(int argc, char** argv) {
              "Whether the reference genome is circular", "Length of seeds in bases", "The number of bases to query at a time",
              "The minimum sequence size to generate queries from", "The number of bases for reference index chunks",
              "The maximum number of bases between seeds in the reference", "The number of worker process to use for mapping"});
+    tr.make({"input", "k", "chunk_size", "middle_threshold", "discard_middle", "check_reads", "adapter_threshold", "extra_end_trim",
+             "extra_middle_trim", "tag_adapters", "verbosity", "front_adapters", "back_adapters", "num_workers", "himem", "demultiplex",
+             "require_pairs", "determine_adapters"},
+            {"", "6", "5000", "85", "false", "10000", "90", "5", "100", "true", "1", "", "", "4", "false", "", "false", "true"},
+            {"Fasta/fastq/gzip input file", "k-mer size to use when matching adapters", "Split long reads into chunks of this size when indexing",
+             "% identity for matching adapters that split reads", "Whether to keep halves of split reads",
+             "Number of reads to use to determine which adapters are present", "% identity required at check_adapters stage",
+             "Number of bases to remove around adapters at read edges", "Number of bases to remove around read-splitting adapters",
+             "Whether to add adapter names to output sequence names", "Level (0-2) of output to stderr", "Fasta/fastq file containing front adapters",
+             "Fasta/fastq file containing back adapters", "Number of threads to use", "Whether to cache all reads in memory",
+             "A path to demultiplex to, otherwise write sequences to stdout", "Whether front/back adapters with the same name must appear together",
+             "Whether to use a fixed set of adapters or to search for those present"});
     if (argc == 1) {
-        printf("Available commands:\n help <command> Describe the command and its arguments\n overlap\n map\n");
+        printf("Available commands:\n help <command> Describe the command and its arguments\n overlap\n map\n trim\n");
         return 0;
     }
     std::string cmd = argv[1];
     if (cmd == "help") {
-        ArgTable* t = argc > 2 && !strcmp(argv[2], "overlap") ? &ov : argc > 2 && !strcmp(argv[2], "map") ? &mp : nullptr;
+        ArgTable* t = argc > 2 && !strcmp(argv[2], "overlap") ? &ov : argc > 2 && !strcmp(argv[2], "map") ? &mp : argc > 2 && !strcmp(argv[2], "trim") ? &tr : nullptr;
         if (!t) {
             printf("Usage: downpore help <command>\nTo see a list of available commands just run downpore\n");
             return 0;
@@ -159,6 +237,13 @@ int main(int argc, char** argv) {
         fwrite(paf.data(), 1, paf.size(), stdout);
         fwrite(errText.data(), 1, errText.size(), stderr);
         return 0;
+    }
+    if (cmd == "trim") {
+        if (!tr.parse(argc, argv, err)) {
+            fprintf(stderr, "%s\n", err.c_str());
+            return 1;
+        }
+        return runTrimCommand(tr);
     }
     printf("Available commands:\n help <command> Describe the command and its arguments\n");
     return 0;

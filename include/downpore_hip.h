@@ -558,6 +558,43 @@ DP_API int dp_scan_fetch_segments(dp_ctx* ctx, const int32_t** segs_out, uint64_
 /* Replace the device-resident scan output with externally gathered segments (host pointer). */
 DP_API int dp_scan_import_segments(dp_ctx* ctx, const int32_t* segs, uint64_t n_segs);
 
+/* ---- `trim`, edge stage (trim/trim.go:272-513): adapters and barcodes in the first and last 150 bases of every read -------------
+ * A dp_trim handle holds one adapter index on one device (its own stream; one host thread per handle) from dp_trim_setup to
+ * dp_trim_release.  dp_trim_error(t) gives the text of the handle's last failure, dp_trim_error(NULL) that of the calling thread's
+ * last failed dp_trim_setup.
+ *
+ * dp_trim_setup: k in 3..8 (DP_ERR_ARG otherwise: ShortKmers holds a k-mer in 16 bits, sequence/sequence.go:482).  kmer_seed: the
+ * index's k-mer -> seed id table, 4^k entries, 0xffff = not a seed; n_seeds <= 16384.  The adapters come front first, then back:
+ * segs / seg_off[n_front + n_back + 1] are their NewAllSeedSequence segments (seeds/seeds.go:204-237: [gap, seed, ..., gap]),
+ * lengths their bases, is_barcode "the name starts with Barcode" (trim.go:377), pair_ids (may be NULL) pairsFront / pairsBack
+ * (:81-98) - held with the index; pairing itself is the caller's rule (:471-485).  The device builds one seed-set bit row per
+ * adapter.  An adapter longer than DP_TRIM_MAX_ADAPTER bases is refused with DP_ERR_CAPACITY (the text names the limit), one with
+ * fewer than two distinct k-mers with DP_ERR_ARG (the reference divides by the set's size).
+ *
+ * dp_trim_edges: ends = n_reads x 2 x 150 ASCII bases (read r: its first 150 bases, then its last 150); one wave per end.
+ *   DP_TRIM_MODE_TRIM: findMatches (:354-428) with Match's minMatch and the chain-length test at min_match (the reference: 3).
+ *     recs[2 r] is read r's front end against the front adapters, recs[2 r + 1] its back end against the back adapters, each as
+ *     findMatches leaves its variables BEFORE the ambiguity rule of :423-427 (the caller applies it: ambiguous -> found = 0,
+ *     best_match = 0); best_match indexes the side's own adapter list.  Every reported match adds one to its adapter's count;
+ *     counts (may be NULL) receives the n_front + n_back totals accumulated since the set-up.
+ *   DP_TRIM_MODE_DETERMINE: isNewFullMatch (:326-352) with `threshold`; minMatch is each adapter's own size / 2 - 1.  enabled
+ *     (may be NULL) receives the n_front + n_back flags OR-ed over every determine call since the set-up.  recs is not written.
+ *   times_ms (may be NULL): [3] = upload, kernel, download of this call, from events on the handle's stream. */
+typedef struct dp_trim dp_trim;
+typedef struct {
+    int32_t earliest, latest, found, best_match, ambiguous, best_ident;
+} dp_trim_rec;
+#define DP_TRIM_EDGE 150
+#define DP_TRIM_MAX_ADAPTER 512
+enum { DP_TRIM_MODE_TRIM = 0, DP_TRIM_MODE_DETERMINE = 1 };
+DP_API int dp_trim_setup(int device, int k, const uint16_t* kmer_seed, uint32_t n_seeds, uint32_t n_front, uint32_t n_back,
+                         const int32_t* segs, const uint64_t* seg_off, const int32_t* lengths, const uint8_t* is_barcode,
+                         const int32_t* pair_ids, dp_trim** out);
+DP_API int dp_trim_edges(dp_trim* t, const uint8_t* ends, uint32_t n_reads, int mode, int min_match, int threshold, dp_trim_rec* recs,
+                         uint64_t* counts, uint8_t* enabled, double* times_ms);
+DP_API void dp_trim_release(dp_trim* t);
+DP_API const char* dp_trim_error(const dp_trim* t);
+
 #ifdef __cplusplus
 }
 #endif

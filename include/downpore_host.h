@@ -148,6 +148,38 @@ DPH_API void dph_map_stats(void* m, double* out);
  * <= 12), 16-ladder (13 .. 24), exact count (> 24), more than 512 sets.  Writes at most cap values; returns how many it wrote. */
 DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
 
+/* ---- `downpore trim`, edge stage (commands/trim.go:32-50, trim/trim.go:272-513, sequence/seqio.go:375-523) --------------------
+ * reads: a read set loaded with min_len 50 (commands/trim.go:35); front / back: the adapter files loaded with min_len 0.  The read
+ * set must outlive the handle; a run overwrites its ignore flags and trims.
+ * params[8] = k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity.
+ * dph_trim_run: adapter determination, end trimming and the writer on HIP device `device`; NULL on failure - k outside 3..8, an
+ * adapter beyond the device's limits, no read of 200 bases ("no reads long enough to trim").
+ * dph_trim_apply: the same outputs without a device, from what a caller that drives dp_trim_edges itself has in hand: enabled (NULL:
+ * no determination ran) = the determine flags over the front then the back adapters as loaded; recs = six int32 (dp_trim_rec) per
+ * end, two ends per read of 200 bases and more in read order, and counts = matches per adapter - both in the order of the adapter
+ * lists AFTER determination (the backwards swap-remove of trim.go:294-322).
+ * dph_trim_output: the trimmed FASTA / FASTQ text; dph_trim_errtext: the reference's log lines without their timestamps.
+ * dph_trim_table: int32[reads][5] = front_trim, back_trim, ignore, front adapter index or -1, back adapter index or -1; returns the
+ * number of reads.  dph_trim_adapters: "F|B <tab> name <tab> matches" lines, the adapters after determination in the trimmer's order.
+ * dph_trim_stats: out[16] = seen, none, reads, front adapters, back adapters, determination s, end extraction s, upload ms, kernel
+ * ms, download ms, host apply s, write s, determination kernel ms, bytes up, bytes down, 0.
+ * dph_trim_demultiplex: <dir>/<label>.fasta|.fastq per barcode label (seqio.go:460-523); returns the number of files or < 0.
+ * dph_trim_index: setupIndex (trim.go:57-99) in the layout dp_trim_setup takes - kmer_seed[4^k], segs[seg_cap], seg_off[n + 1],
+ * lengths / is_barcode / pairs[n], n = front + back adapters; returns the number of seeds, -1 on error, -2 when seg_cap is below the
+ * seg_off[n] ints needed. */
+DPH_API void* dph_trim_run(void* reads, void* front, void* back, const int64_t* params, int n_params, int device);
+DPH_API void* dph_trim_apply(void* reads, void* front, void* back, const int64_t* params, int n_params, const uint8_t* enabled,
+                             const int32_t* recs, int64_t n_rec_reads, const uint64_t* counts);
+DPH_API void dph_trim_free(void* t);
+DPH_API const char* dph_trim_output(void* t, int64_t* n);
+DPH_API const char* dph_trim_errtext(void* t, int64_t* n);
+DPH_API int64_t dph_trim_table(void* t, int32_t* out, int64_t cap_reads);
+DPH_API const char* dph_trim_adapters(void* t, int64_t* n);
+DPH_API void dph_trim_stats(void* t, double* out);
+DPH_API int dph_trim_demultiplex(void* t, const char* dir);
+DPH_API int64_t dph_trim_index(void* front, void* back, int k, uint16_t* kmer_seed, int32_t* segs, int64_t seg_cap, uint64_t* seg_off,
+                               int32_t* lengths, uint8_t* is_barcode, int32_t* pairs);
+
 /* ---- test hooks (host logic without a GPU, counters) ------------------------------------------------------------------------ */
 DPH_API const char* dph_reads_dump(void* reads, int64_t* n);
 DPH_API void dph_values_from_counts(uint64_t* counts, int k, double* out);
