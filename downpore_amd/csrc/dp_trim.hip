@@ -284,6 +284,20 @@ struct dp_trim {
     size_t ends_cap = 0;          // read ends the batch buffers hold
     std::vector<int32_t> pairs;   // the pair ids as uploaded (pairing is the host's rule, trim.go:471-485)
     std::string err;
+    // ---- the middle stage (dp_trim_scan_chunks / dp_trim_search)
+    dp_ctx* ctx = nullptr;             // the context whose index build and query stage (SeedIndex.Matches) the search drives
+    std::vector<uint32_t> seed_kmers;  // seed id -> k-mer (dp_round_begin)
+    std::vector<int32_t> h_fsegs;      // the front adapters' segments and offsets as dp_query_candidates takes them
+    std::vector<uint64_t> h_foff;
+    std::vector<int32_t> h_alen;
+    void *d_cbases = nullptr, *d_coff = nullptr, *d_ccount = nullptr, *d_csegoff = nullptr, *d_pairs = nullptr, *d_mrecs = nullptr, *d_mover = nullptr,
+         *d_mcnt = nullptr;
+    size_t cbases_cap = 0, chunks_cap = 0, pairs_cap = 0, mrecs_cap = 0;
+    uint32_t n_chunks = 0;
+    std::vector<uint32_t> c_count;     // seeds per scanned chunk
+    std::vector<uint64_t> c_segoff;    // [n_chunks + 1] offsets of the chunks' segments in the context's scan buffer
+    std::vector<dp_trim_mid_rec> m_recs;
+    std::vector<uint32_t> m_over;
 };
 static thread_local std::string g_trim_err;
 
@@ -305,8 +319,9 @@ extern "C" void dp_trim_release(dp_trim* t) {
     hipSetDevice(t->device);
     if (t->stream) hipStreamSynchronize(t->stream);
     for (void* p : {t->d_table, t->d_segs, t->d_off, t->d_len, t->d_bar, t->d_size, t->d_rows, t->d_rowsT, t->d_counts, t->d_enabled, t->d_pool,
-                    t->d_err, t->d_ends, t->d_recs})
+                    t->d_err, t->d_ends, t->d_recs, t->d_cbases, t->d_coff, t->d_ccount, t->d_csegoff, t->d_pairs, t->d_mrecs, t->d_mover, t->d_mcnt})
         if (p) dp_dev_free(p);
+    if (t->ctx) dp_ctx_destroy(t->ctx);
     for (hipEvent_t e : t->ev)
         if (e) hipEventDestroy(e);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -375,6 +390,12 @@ extern "C" int dp_trim_setup(int device, int k, const uint16_t* kmer_seed, uint3
     t->SW = (n_seeds + 63) / 64;
     t->qcap = std::max<uint32_t>(64u, ((uint32_t)longest + 31u) & ~31u);
     if (pair_ids) t->pairs.assign(pair_ids, pair_ids + nA);
+    t->seed_kmers.assign(n_seeds, 0);
+    for (size_t i = 0; i < nK; i++)
+        if (kmer_seed[i] != TR_NONE) t->seed_kmers[kmer_seed[i]] = (uint32_t)i;
+    t->h_fsegs.assign(segs, segs + off32[n_front]);
+    t->h_foff.assign(seg_off, seg_off + n_front + 1);
+    t->h_alen.assign(lengths, lengths + nA);
     TR_HIP(hipSetDevice(device));
     TR_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     for (hipEvent_t& e : t->ev) TR_HIP(hipEventCreate(&e));
@@ -477,5 +498,392 @@ extern "C" int dp_trim_edges(dp_trim* t, const uint8_t* ends, uint32_t n_reads, 
         TR_HIP(hipMemcpy(en.data(), t->d_enabled, (size_t)nA * 4, hipMemcpyDeviceToHost));
         for (uint32_t a = 0; a < nA; a++) enabled[a] = en[a] ? 1 : 0;
     }
+    return DP_OK;
+}
+
+
+// ---- the middle stage: chunk scan, chunk index, candidates and the (front adapter, chunk) matching -----------------------------------
+// Trim's second half (trim/trim.go:151-217) and findSplit's search (:519-530).  The centres of the edge-trimmed reads arrive as
+// chunks of ASCII bases; chunk_scan_kernel is step 1 of trim_edge_kernel for a chunk of any length (NewSeedSequence, seeds.go:33-50:
+// one wave per chunk, ballot + prefix over 64 k-mer positions at a time), first counting, then writing [gap, seed, ..., gap] into the
+// scan buffer of a dp_ctx the handle owns.  That context's dense index build (seed-set rows, posting matrix, pmeta) and its query
+// stage - the exact GetSharedIDs emulation behind dp_query_candidates - give Matches(ad, 0.2) for every front adapter;
+// trim_mid_kernel then runs Match for every (candidate chunk, front adapter) pair.
+#define MID_TCAP 1024  // reduced seeds of a chunk a wave's LDS slice holds; a pair beyond it is listed for the host's exact Match
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void chunk_scan_kernel(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n_chunks, int k,
+                                                         const uint16_t* __restrict__ table, uint32_t* __restrict__ counts,
+                                                         const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs) {
+    const int lane = dp_lane();
+    const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), waves = gridDim.x * (blockDim.x >> 6);
+    const u64 below = (1ull << lane) - 1ull;
+    for (uint32_t c = gw; c < n_chunks; c += waves) {
+        const uint8_t* src = bases + off[c];
+        const long long len = (long long)(off[c + 1] - off[c]);
+        const long long nK = len - k + 1;
+        const uint32_t cap = WRITE ? counts[c] : 0u;
+        int32_t* seg = WRITE ? segs + segoff[c] : nullptr;
+        uint32_t nE = 0;
+        long long lastPos = -1;
+        for (long long pb = 0; pb < nK; pb += 64) {
+            const long long p = pb + lane;
+            uint32_t sid = TR_NONE;
+            if (p < nK) {
+                uint32_t km = 0;
+                for (int j = 0; j < k; j++) {
+                    const uint32_t b = src[p + j];
+                    km = (km << 2) | (((b >> 1) ^ ((b & 4) >> 2)) & 3);
+                }
+                sid = table[km];
+            }
+            const bool is = sid != TR_NONE;
+            const u64 m = __ballot(is);
+            if (WRITE && is) {
+                const u64 mb = m & below;
+                const long long prev = mb ? pb + 63 - __builtin_clzll(mb) : lastPos;
+                const uint32_t j = nE + (uint32_t)__popcll(mb);
+                if (j < cap) {
+                    seg[2 * (size_t)j] = (int32_t)(p - (prev < 0 ? 0 : prev + k));  // kmerIndex - prev (sequence.go:316-318)
+                    seg[2 * (size_t)j + 1] = (int32_t)sid;
+                }
+            }
+            nE += (uint32_t)__popcll(m);
+            if (m) lastPos = pb + 63 - __builtin_clzll(m);
+        }
+        if (lane == 0) {
+            if (WRITE) {
+                if (nE == cap) seg[2 * (size_t)nE] = (int32_t)(len - (lastPos < 0 ? 0 : lastPos + k));  // len - prev (:323)
+            } else {
+                counts[c] = nE;
+            }
+        }
+    }
+}
+
+struct MidGeom {
+    int k;
+    uint32_t SW, SWc, qcap, wave_words, n_pairs, rec_cap;
+    int threshold;
+};
+static __host__ __device__ inline uint32_t mid_wave_words(uint32_t qcap) {
+    return (2 * MID_TCAP + 2) + (2 * qcap + 2) + (qcap + 2) + MID_TCAP / 2 + (qcap + 2) / 2 * 2 + 2;
+}
+
+// One wave per (chunk, front adapter) pair, pairs in chunk-major order so that the waves of a workgroup read one chunk's segments
+// together.  cnt[0] = records appended, cnt[1] = pairs listed for the host.
+__global__ __launch_bounds__(64 * TR_WAVES) void trim_mid_kernel(
+    const uint2* __restrict__ pairs, MidGeom G, const dp_seq_ref* __restrict__ refs, const int32_t* __restrict__ csegs, const u64* __restrict__ csets,
+    const int32_t* __restrict__ asegs, const uint32_t* __restrict__ aoff, const int32_t* __restrict__ alen, const u64* __restrict__ rows,
+    dp_trim_mid_rec* __restrict__ recs, uint32_t* __restrict__ over, uint32_t* __restrict__ cnt, uint16_t* __restrict__ poolA,
+    uint16_t* __restrict__ poolB, uint16_t* __restrict__ poolLen) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tr_lds[];
+    __shared__ TrimL sh[TR_WAVES];
+    const int lane = dp_lane();
+    const int wv = threadIdx.x >> 6;
+    const int k = G.k;
+    const uint32_t qcap = G.qcap;
+    TrimL& L = sh[wv];
+    {
+        uint32_t* p = tr_lds + (size_t)wv * G.wave_words;
+        int32_t* t = (int32_t*)p;
+        p += 2 * MID_TCAP + 2;
+        int32_t* q = (int32_t*)p;
+        p += 2 * qcap + 2;
+        int32_t* hc = (int32_t*)p;
+        p += qcap + 2;
+        uint16_t* tI = (uint16_t*)p;
+        p += MID_TCAP / 2;
+        uint16_t* qI = (uint16_t*)p;
+        p += (qcap + 2) / 2;
+        uint16_t* hl = (uint16_t*)p;
+        if (lane == 0) {
+            L.t = t;
+            L.q = q;
+            L.headChain = hc;
+            L.tIdx = tI;
+            L.qIdx = qI;
+            L.headLen = hl;
+        }
+    }
+    __syncthreads();
+    const uint32_t gw = blockIdx.x * TR_WAVES + wv, waves = gridDim.x * TR_WAVES;
+    MChainPool P;
+    P.stride = qcap;
+    P.a = poolA + (size_t)gw * M_CHAINS * qcap;
+    P.b = poolB + (size_t)gw * M_CHAINS * qcap;
+    uint16_t* chainLen = poolLen + (size_t)gw * M_CHAINS;
+    for (uint32_t pi = gw; pi < G.n_pairs; pi += waves) {
+        const uint2 pr = pairs[pi];  // x = indexed chunk, y = front adapter
+        const dp_seq_ref ref = refs[pr.x];
+        const int32_t* cSeg = csegs + ref.seg_off;
+        const int cN = 2 * (int)ref.n_seeds + 1;
+        const uint32_t ai = pr.y;
+        const int32_t* aSeg = asegs + aoff[ai];
+        const int aN = (int)(aoff[ai + 1] - aoff[ai]);
+        const int minMatch = (aN / 2) / 5;  // ad.GetNumSeeds() / 5 (trim.go:519)
+        uint32_t err = ref.n_seeds > 0xffffu ? 1u : 0u;  // (seed indices travel in 16 bits)
+        int nGood = 0;
+        if (!err) {
+            // Match (seeds/sequence.go:361-394): the chunk reduced to the adapter's seeds, the adapter to the chunk's
+            const int nT = m_reduce_wave<uint16_t>(cSeg, cN, (const u64*)(rows + (size_t)ai * G.SW), k, minMatch, L.t, L.tIdx, MID_TCAP, &err);
+            const int nQ = nT < 0 ? -1 : m_reduce_wave<uint16_t>(aSeg, aN, (const u64*)(csets + (size_t)pr.x * G.SWc), k, minMatch, L.q, L.qIdx, (int)qcap, &err);
+            if (nT >= 0 && nQ >= 0) nGood = m_dynamic_match_wave(L, 2 * nQ + 1, 2 * nT + 1, minMatch, k, P, chainLen, &err);
+        }
+        err = (uint32_t)__builtin_amdgcn_readfirstlane((int)err);
+        if (lane == 0) {
+            if (err) {
+                over[atomicAdd(&cnt[1], 1u)] = pi;  // (the list holds every pair)
+            } else {
+                for (int g = 0; g < nGood; g++) {
+                    const int ch = L.good[g];
+                    const int len = chainLen[ch];
+                    const uint16_t* ca = P.A(ch);
+                    const uint16_t* cb = P.B(ch);
+                    // GetBasesCovered's countA (:830-858): SeqA = the adapter
+                    int countA = len * k, prevA = L.qIdx[ca[0]];
+                    for (int i = 1; i < len; i++) {
+                        const int s = L.qIdx[ca[i]];
+                        int d1 = aSeg[prevA * 2 + 2];
+                        for (int j = prevA + 2; j <= s; j++) d1 += aSeg[j * 2] + k;
+                        if (d1 < 0) countA += d1;
+                        prevA = s;
+                    }
+                    if ((countA * 100) / alen[ai] < G.threshold) continue;  // trim.go:528
+                    const uint32_t at = atomicAdd(&cnt[0], 1u);
+                    if (at < G.rec_cap) {
+                        dp_trim_mid_rec r;
+                        r.adapter = (int32_t)ai;
+                        r.chunk = (int32_t)pr.x;
+                        r.ordinal = g;
+                        r.start_rel = tr_seed_offset(cSeg, L.tIdx[cb[0]], k) - tr_seed_offset(aSeg, L.qIdx[ca[0]], k);  // :541
+                        r.covered = countA;
+                        r.chain_len = len;
+                        recs[at] = r;
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+#define TR_CTX(call)                                                                                            \
+    do {                                                                                                        \
+        const int rc_ = (call);                                                                                 \
+        if (rc_ != DP_OK) return tr_fail(t, rc_, std::string("dp_trim: " #call ": ") + dp_last_error(t->ctx)); \
+    } while (0)
+
+static int tr_mid_ctx(dp_trim* t) {
+    if (t->k < 4) return tr_fail(t, DP_ERR_ARG, "dp_trim: the middle stage needs k >= 4 (the chunk index is a dp_ctx round index)");
+    if (!t->ctx) {
+        const int rc = dp_ctx_create(t->device, &t->ctx);
+        if (rc != DP_OK) return tr_fail(t, rc, std::string("dp_trim: dp_ctx_create: ") + dp_last_error(nullptr));
+        TR_CTX(dp_round_begin(t->ctx, t->k, t->seed_kmers.data(), t->n_seeds));
+    }
+    return DP_OK;
+}
+
+extern "C" int dp_trim_scan_chunks(dp_trim* t, const uint8_t* bases, const uint64_t* off, uint32_t n_chunks, uint32_t* n_seeds_out,
+                                   double* times_ms) {
+    if (!t) return tr_fail(nullptr, DP_ERR_ARG, "dp_trim_scan_chunks: null handle");
+    const bool own = false;
+    if (n_chunks && (!bases || !off)) return tr_fail(t, DP_ERR_ARG, "dp_trim_scan_chunks: bad arguments");
+    for (uint32_t c = 0; c < n_chunks; c++)
+        if (off[c + 1] < off[c]) return tr_fail(t, DP_ERR_ARG, "dp_trim_scan_chunks: chunk offsets must ascend");
+    if (int rc = tr_mid_ctx(t)) return rc;
+    TR_HIP(hipSetDevice(t->device));
+    if (times_ms) times_ms[0] = times_ms[1] = 0;
+    t->n_chunks = 0;
+    t->c_count.assign(n_chunks, 0);
+    t->c_segoff.assign((size_t)n_chunks + 1, 0);
+    t->ctx->n_segs = 0;
+    if (!n_chunks) return DP_OK;
+    hipStream_t st = t->ctx->stream;
+    const size_t nb = off[n_chunks] - off[0];
+    if (nb > t->cbases_cap) {
+        if (t->d_cbases) dp_dev_free(t->d_cbases);
+        t->d_cbases = nullptr;
+        t->cbases_cap = 0;
+        TR_HIP(dp_dev_malloc(&t->d_cbases, nb + nb / 4 + 64));
+        t->cbases_cap = nb + nb / 4;
+    }
+    if (n_chunks > t->chunks_cap) {
+        for (void** p : {&t->d_coff, &t->d_ccount, &t->d_csegoff}) {
+            if (*p) dp_dev_free(*p);
+            *p = nullptr;
+        }
+        t->chunks_cap = 0;
+        const size_t cap = (size_t)n_chunks + n_chunks / 4 + 1024;
+        TR_HIP(dp_dev_malloc(&t->d_coff, (cap + 1) * 8 + 64));
+        TR_HIP(dp_dev_malloc(&t->d_ccount, cap * 4 + 64));
+        TR_HIP(dp_dev_malloc(&t->d_csegoff, (cap + 1) * 8 + 64));
+        t->chunks_cap = cap;
+    }
+    std::vector<uint64_t> rel((size_t)n_chunks + 1);
+    for (uint32_t c = 0; c <= n_chunks; c++) rel[c] = off[c] - off[0];
+    TR_HIP(hipEventRecord(t->ev[0], st));
+    TR_HIP(hipMemcpyAsync(t->d_cbases, bases + off[0], nb, hipMemcpyHostToDevice, st));
+    TR_HIP(hipMemcpyAsync(t->d_coff, rel.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
+    TR_HIP(hipEventRecord(t->ev[1], st));
+    const uint32_t blocks = std::min<uint32_t>(4096, (n_chunks + 3) / 4);
+    hipLaunchKernelGGL(chunk_scan_kernel<false>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)t->d_cbases, (const uint64_t*)t->d_coff, n_chunks, t->k,
+                       (const uint16_t*)t->d_table, (uint32_t*)t->d_ccount, (const uint64_t*)nullptr, (int32_t*)nullptr);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipMemcpyAsync(t->c_count.data(), t->d_ccount, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, st));
+    TR_HIP(hipStreamSynchronize(st));
+    for (uint32_t c = 0; c < n_chunks; c++) t->c_segoff[c + 1] = t->c_segoff[c] + 2ull * t->c_count[c] + 1;
+    const uint64_t total = t->c_segoff[n_chunks];
+    if (dev_reserve(t->ctx, t->ctx->d_segs, (size_t)total * 4 + 64)) return tr_fail(t, DP_ERR_HIP, std::string("dp_trim_scan_chunks: ") + dp_last_error(t->ctx));
+    TR_HIP(hipMemcpyAsync(t->d_csegoff, t->c_segoff.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(chunk_scan_kernel<true>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)t->d_cbases, (const uint64_t*)t->d_coff, n_chunks, t->k,
+                       (const uint16_t*)t->d_table, (uint32_t*)t->d_ccount, (const uint64_t*)t->d_csegoff, (int32_t*)t->ctx->d_segs.p);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipEventRecord(t->ev[2], st));
+    TR_HIP(hipStreamSynchronize(st));
+    t->ctx->n_segs = total;
+    t->n_chunks = n_chunks;
+    if (times_ms)
+        for (int i = 0; i < 2; i++) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]) == hipSuccess) times_ms[i] = ms;
+        }
+    if (n_seeds_out) memcpy(n_seeds_out, t->c_count.data(), (size_t)n_chunks * 4);
+    return DP_OK;
+}
+
+extern "C" int dp_trim_chunk_segments(dp_trim* t, uint32_t chunk, int32_t* out, uint64_t cap, uint64_t* n) {
+    if (!t || !n) return tr_fail(t, DP_ERR_ARG, "dp_trim_chunk_segments: bad arguments");
+    const bool own = false;
+    if (chunk >= t->n_chunks) return tr_fail(t, DP_ERR_ARG, "dp_trim_chunk_segments: no such chunk in the last scan");
+    *n = t->c_segoff[chunk + 1] - t->c_segoff[chunk];
+    if (!out || cap < *n) return DP_OK;
+    TR_HIP(hipSetDevice(t->device));
+    TR_HIP(hipMemcpy(out, (const int32_t*)t->ctx->d_segs.p + t->c_segoff[chunk], (size_t)*n * 4, hipMemcpyDeviceToHost));
+    return DP_OK;
+}
+
+extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, int mid_threshold, dp_trim_mid_batch* out) {
+    if (!t || !out) return tr_fail(t, DP_ERR_ARG, "dp_trim_search: bad arguments");
+    const bool own = false;
+    memset(out, 0, sizeof(*out));
+    t->m_recs.clear();
+    t->m_over.clear();
+    if (n_sel && !sel) return tr_fail(t, DP_ERR_ARG, "dp_trim_search: bad arguments");
+    if (!n_sel || !t->n_front) return DP_OK;
+    if (!t->ctx || !t->n_chunks) return tr_fail(t, DP_ERR_STATE, "dp_trim_search before dp_trim_scan_chunks");
+    TR_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->ctx->stream;
+    std::vector<dp_seq_ref> refs(n_sel);
+    for (uint32_t i = 0; i < n_sel; i++) {
+        if (sel[i] >= t->n_chunks || (i && sel[i] <= sel[i - 1])) return tr_fail(t, DP_ERR_ARG, "dp_trim_search: the chunks must be ascending ids of the last scan");
+        refs[i].seg_off = t->c_segoff[sel[i]];
+        refs[i].n_seeds = t->c_count[sel[i]];
+        refs[i].reserved = 0;
+    }
+    // AddSequence + IndexSequences, then Matches(ad, 0.2) of every front adapter (trim.go:187, :520)
+    TR_HIP(hipEventRecord(t->ev[0], st));
+    TR_CTX(dp_index_build(t->ctx, refs.data(), n_sel));
+    TR_HIP(hipEventRecord(t->ev[1], st));
+    dp_candidate_batch cb;
+    TR_CTX(dp_query_candidates(t->ctx, t->h_fsegs.data(), t->h_foff.data(), t->n_front, 0.2, &cb));
+    TR_HIP(hipEventRecord(t->ev[2], st));
+    for (uint32_t a = 0; a < t->n_front; a++)
+        if (cb.meta[3 * a + 2]) return tr_fail(t, DP_ERR_CAPACITY, "dp_trim_search: front adapter " + std::to_string(a) + " exceeds a capacity of the index query");
+    const uint64_t n_pairs64 = cb.cand_off[t->n_front];
+    if (n_pairs64 > 0x7fffffffull) return tr_fail(t, DP_ERR_CAPACITY, "dp_trim_search: more than 2^31 candidate pairs in one batch");
+    const uint32_t n_pairs = (uint32_t)n_pairs64;
+    out->n_pairs = n_pairs;
+    if (n_pairs) {
+        // chunk-major pair list: a counting sort of the per-adapter candidate lists by chunk
+        std::vector<uint32_t> start((size_t)n_sel + 1, 0);
+        for (uint64_t i = 0; i < n_pairs64; i++) start[cb.cand[i] + 1]++;
+        for (uint32_t i = 0; i < n_sel; i++) start[i + 1] += start[i];
+        std::vector<uint2> pairs(n_pairs);
+        for (uint32_t a = 0; a < t->n_front; a++)
+            for (uint64_t i = cb.cand_off[a]; i < cb.cand_off[a + 1]; i++) pairs[start[cb.cand[i]]++] = make_uint2(cb.cand[i], a);
+        if (n_pairs > t->pairs_cap) {
+            for (void** p : {&t->d_pairs, &t->d_mover}) {
+                if (*p) dp_dev_free(*p);
+                *p = nullptr;
+            }
+            t->pairs_cap = 0;
+            const size_t cap = (size_t)n_pairs + n_pairs / 4 + 1024;
+            TR_HIP(dp_dev_malloc(&t->d_pairs, cap * 8 + 64));
+            TR_HIP(dp_dev_malloc(&t->d_mover, cap * 4 + 64));
+            t->pairs_cap = cap;
+        }
+        if (!t->d_mcnt) TR_HIP(dp_dev_malloc(&t->d_mcnt, 64));
+        TR_HIP(hipMemcpyAsync(t->d_pairs, pairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
+        MidGeom G;
+        G.k = t->k;
+        G.SW = t->SW;
+        G.SWc = t->ctx->SW;
+        G.qcap = t->qcap;
+        G.wave_words = (mid_wave_words(t->qcap) + 1u) & ~1u;
+        G.n_pairs = n_pairs;
+        G.threshold = mid_threshold;
+        const size_t lds = (size_t)TR_WAVES * G.wave_words * 4;
+        TR_HIP(hipFuncSetAttribute((const void*)trim_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // the record buffer is sized from a guess - nearly every pair emits nothing - and the launch repeated when it was too small
+        size_t rec_cap = std::max<size_t>(1024, n_pairs / 64);
+        if (const char* e = getenv("DP_TRIM_MID_REC_CAP")) rec_cap = std::max<long>(1, atol(e));
+        const uint32_t blocks = std::min<uint32_t>(t->waves / TR_WAVES, (n_pairs + TR_WAVES - 1) / TR_WAVES);
+        const size_t poolElems = (size_t)t->waves * M_CHAINS * t->qcap;
+        uint16_t* poolA = (uint16_t*)t->d_pool;
+        TR_HIP(hipEventRecord(t->ev[2], st));
+        for (;;) {
+            if (rec_cap > t->mrecs_cap) {
+                if (t->d_mrecs) dp_dev_free(t->d_mrecs);
+                t->d_mrecs = nullptr;
+                t->mrecs_cap = 0;
+                TR_HIP(dp_dev_malloc(&t->d_mrecs, rec_cap * sizeof(dp_trim_mid_rec) + 64));
+                t->mrecs_cap = rec_cap;
+            }
+            G.rec_cap = (uint32_t)std::min<size_t>(rec_cap, 0x7fffffffu);
+            TR_HIP(hipMemsetAsync(t->d_mcnt, 0, 64, st));
+            hipLaunchKernelGGL(trim_mid_kernel, dim3(blocks), dim3(64 * TR_WAVES), lds, st, (const uint2*)t->d_pairs, G, (const dp_seq_ref*)t->ctx->d_seqrefs.p,
+                               (const int32_t*)t->ctx->d_segs.p, (const u64*)t->ctx->d_seedsets.p, (const int32_t*)t->d_segs, (const uint32_t*)t->d_off,
+                               (const int32_t*)t->d_len, (const u64*)t->d_rows, (dp_trim_mid_rec*)t->d_mrecs, (uint32_t*)t->d_mover, (uint32_t*)t->d_mcnt, poolA,
+                               poolA + poolElems, poolA + 2 * poolElems);
+            TR_HIP(hipGetLastError());
+            uint32_t cnt[2] = {0, 0};
+            TR_HIP(hipMemcpyAsync(cnt, t->d_mcnt, 8, hipMemcpyDeviceToHost, st));
+            TR_HIP(hipStreamSynchronize(st));
+            out->launches++;
+            if (cnt[0] > G.rec_cap) {
+                rec_cap = (size_t)cnt[0] + cnt[0] / 8 + 16;
+                continue;
+            }
+            t->m_recs.resize(cnt[0]);
+            t->m_over.resize(std::min<uint32_t>(cnt[1], n_pairs));
+            if (cnt[0]) TR_HIP(hipMemcpyAsync(t->m_recs.data(), t->d_mrecs, (size_t)cnt[0] * sizeof(dp_trim_mid_rec), hipMemcpyDeviceToHost, st));
+            if (!t->m_over.empty()) TR_HIP(hipMemcpyAsync(t->m_over.data(), t->d_mover, t->m_over.size() * 4, hipMemcpyDeviceToHost, st));
+            TR_HIP(hipEventRecord(t->ev[3], st));
+            TR_HIP(hipStreamSynchronize(st));
+            break;
+        }
+        // records name the caller's chunk ids; the overflow list becomes (chunk, adapter) pairs
+        for (dp_trim_mid_rec& r : t->m_recs) r.chunk = (int32_t)sel[r.chunk];
+        std::vector<uint32_t> ov;
+        for (uint32_t pi : t->m_over) {
+            ov.push_back(sel[pairs[pi].x]);
+            ov.push_back(pairs[pi].y);
+        }
+        t->m_over.swap(ov);
+        std::sort(t->m_recs.begin(), t->m_recs.end(), [](const dp_trim_mid_rec& a, const dp_trim_mid_rec& b) {
+            if (a.adapter != b.adapter) return a.adapter < b.adapter;
+            if (a.chunk != b.chunk) return a.chunk < b.chunk;
+            return a.ordinal < b.ordinal;
+        });
+    }
+    out->n_recs = (uint32_t)t->m_recs.size();
+    out->recs = t->m_recs.data();
+    out->n_overflow = (uint32_t)(t->m_over.size() / 2);
+    out->overflow = t->m_over.data();
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess) out->index_ms = ms;
+    if (hipEventElapsedTime(&ms, t->ev[1], t->ev[2]) == hipSuccess) out->query_ms = ms;
+    if (n_pairs && hipEventElapsedTime(&ms, t->ev[2], t->ev[3]) == hipSuccess) out->kernel_ms = ms;
     return DP_OK;
 }

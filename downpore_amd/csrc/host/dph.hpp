@@ -776,12 +776,28 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
            MapStats* stats, std::string& error);
 
 // ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------
-struct TrimParams {  // flag table commands/trim.go:17-20 (the flags of the middle-adapter search are parsed by the CLI and not used)
+struct TrimParams {  // flag table commands/trim.go:17-20
     int k = 6;
     i64 checkReads = 10000;
     int adapterThreshold = 90, extraEdgeTrim = 5;
     bool tagAdapters = true, requirePairs = false, determineAdapters = true;
     int verbosity = 1;
+    // the middle-adapter stage (Trim's second half, trim.go:151-256); off: the edge stage alone, as before
+    bool middle = false;
+    i64 chunkSize = 5000;
+    int middleThreshold = 85, extraMiddleTrim = 100;
+    bool discardMiddle = false;
+    i64 flushSeeds = 300000000;  // the `totalCount > 300000000` of trim.go:186
+};
+// a chunk of the middle stage's plan (trim.go:165-184), in the coordinates of the edge-trimmed read
+struct TrimChunk {
+    uint32_t read;
+    int32_t start, end;
+    uint8_t remainder;  // "add the entire remainder" (:166-171): indexed whatever its seed count
+};
+// a match of a front adapter in a chunk that passed the identity test of trim.go:527-530 (six int32, as the device emits them)
+struct TrimMidRec {
+    int32_t adapter, chunk, ordinal, startRel, covered, chainLen;  // chunk: position in the plan; startRel: GetSeedOffset(MatchB[0]) - ad.GetSeedOffset(MatchA[0])
 };
 // setupIndex (trim.go:57-99) as dp_trim_setup takes it: front adapters first, then back
 struct TrimIndex {
@@ -802,12 +818,32 @@ struct TrimResult {
     i64 seen = 0, none = 0;               // seenCount, noCount
     double t_determine = 0, t_extract = 0, t_apply = 0, t_write = 0;  // host wall seconds
     double k_determine_ms = 0, upload_ms = 0, kernel_ms = 0, download_ms = 0, bytes_up = 0, bytes_down = 0;  // the trim pass's device calls
+    // ---- the middle stage
+    std::vector<int32_t> plan;            // per planned chunk: read, start, end, remainder, seeds, indexed
+    std::vector<int32_t> splits;          // per live entry of ids (trim.go:227-256): read, aEnd, bStart, kept halves (bit 0 left, bit 1 right)
+    std::vector<std::string> extraNames, extraBases, extraQuals;  // AddSequence (seqio.go:396-399) in the order added; quals as written (phred + 33)
+    std::vector<int32_t> applied;         // the records applied, in canonical order (six int32 each)
+    i64 midChunks = 0, midSeeds = 0, midBatches = 0, midPairs = 0, midRecords = 0, midOverflowPairs = 0, midOutOfRange = 0;
+    double mid_upload_ms = 0, mid_scan_ms = 0, mid_index_ms = 0, mid_query_ms = 0, mid_kernel_ms = 0;
 };
+void trimChunkPlan(i64 length, i64 chunkSize, uint32_t read, std::vector<TrimChunk>& out);  // appends; chunkSize > 100
+// SeedSequence.Match (seeds/sequence.go:361-576) of one (chunk, front adapter) pair on the host + the identity test of trim.go:527-530; appends
+void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
+                   std::vector<TrimMidRec>& out);
 bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error);
 // the whole edge stage on HIP device `device`; reads receives ignore / frontTrim / backTrim.  0, or < 0 with `error` (-2: no read of 200 bases)
 int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error);
 int applyTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
               size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error);
+// the same with the middle stage's device results supplied too (p.middle): seedCounts[planned chunks] and midRecs, in any order
+struct TrimMidInput {
+    const int32_t* seedCounts = nullptr;
+    size_t nChunks = 0;
+    const TrimMidRec* recs = nullptr;
+    size_t nRecs = 0;
+};
+int applyTrimMid(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+                 size_t nRecReads, const uint64_t* counts, const TrimMidInput& mid, TrimResult& res, std::string& error);
 void trimWrite(const ReadSet& reads, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out);
 int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::string& dir, std::string& error);  // files written, or < 0
 

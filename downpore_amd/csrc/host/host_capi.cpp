@@ -983,7 +983,15 @@ struct TrimH {
     std::string adapters;
 };
 bool trimParamsFrom(const int64_t* params, int n, TrimParams& p) {
-    if (!params || n != 8) return false;
+    if (!params || (n != 8 && n != 14)) return false;
+    if (n == 14) {  // the middle stage's six follow the edge stage's eight
+        p.middle = params[8] != 0;
+        p.chunkSize = params[9];
+        p.middleThreshold = (int)params[10];
+        p.extraMiddleTrim = (int)params[11];
+        p.discardMiddle = params[12] != 0;
+        p.flushSeeds = params[13];
+    }
     p.k = (int)params[0];
     p.checkReads = params[1];
     p.adapterThreshold = (int)params[2];
@@ -998,7 +1006,7 @@ bool trimParamsFrom(const int64_t* params, int n, TrimParams& p) {
 extern "C" void* dph_trim_run(void* readsH, void* frontH, void* backH, const int64_t* params, int n_params, int device) {
     TrimParams p;
     if (!readsH || !frontH || !backH || !trimParamsFrom(params, n_params, p)) {
-        g_err = "dph_trim_run: bad arguments (8 parameters)";
+        g_err = "dph_trim_run: bad arguments (8 parameters, or 14 with the middle stage's)";
         return nullptr;
     }
     TrimH* h = new TrimH();
@@ -1029,6 +1037,82 @@ extern "C" void* dph_trim_apply(void* readsH, void* frontH, void* backH, const i
         return nullptr;
     }
     return h;
+}
+// dph_trim_apply with the middle stage (params[14], middle != 0): seed_counts[n_chunks] per planned chunk and mid_recs = six int32 per
+// match that passed the identity test (adapter, chunk, ordinal, start_rel, covered, chain length), in any order
+extern "C" void* dph_trim_apply_mid(void* readsH, void* frontH, void* backH, const int64_t* params, int n_params, const uint8_t* enabled,
+                                    const int32_t* recs, int64_t n_rec_reads, const uint64_t* counts, const int32_t* seed_counts, int64_t n_chunks,
+                                    const int32_t* mid_recs, int64_t n_mid_recs) {
+    TrimParams p;
+    if (!readsH || !frontH || !backH || !trimParamsFrom(params, n_params, p) || n_params != 14 || n_rec_reads < 0 || (n_rec_reads && !recs) || !counts ||
+        n_chunks < 0 || (n_chunks && !seed_counts) || n_mid_recs < 0 || (n_mid_recs && !mid_recs)) {
+        g_err = "dph_trim_apply_mid: bad arguments (14 parameters)";
+        return nullptr;
+    }
+    static_assert(sizeof(TrimMidRec) == 6 * sizeof(int32_t), "middle records are six int32");
+    TrimH* h = new TrimH();
+    h->reads = &((ReadsH*)readsH)->set;
+    std::string error;
+    TrimMidInput mid;
+    mid.seedCounts = seed_counts;
+    mid.nChunks = (size_t)n_chunks;
+    mid.recs = (const TrimMidRec*)mid_recs;
+    mid.nRecs = (size_t)n_mid_recs;
+    if (applyTrimMid(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, mid,
+                     h->res, error) != 0) {
+        g_err = error;
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+// the chunk loop of trim.go:165-184 for one served length: out[3 i ..] = start, end, is-remainder; returns the number of chunks, -1: chunk_size <= 100
+extern "C" int64_t dph_trim_chunk_plan(int64_t length, int64_t chunk_size, int32_t* out, int64_t cap) {
+    if (chunk_size <= 100) {
+        g_err = "trim: -chunk_size must be larger than 100 (the chunks advance by chunk_size - 100 bases)";
+        return -1;
+    }
+    std::vector<TrimChunk> plan;
+    trimChunkPlan(length, chunk_size, 0, plan);
+    for (size_t i = 0; i < plan.size() && (int64_t)i < cap; i++) {
+        out[3 * i] = plan[i].start;
+        out[3 * i + 1] = plan[i].end;
+        out[3 * i + 2] = plan[i].remainder;
+    }
+    return (int64_t)plan.size();
+}
+// which: 0 the chunk plan (6 per chunk: read, start, end, remainder, seeds, indexed), 1 the splits (4 each: read, aEnd, bStart, kept
+// halves), 2 the applied records (6 each); returns the number of int32 (out may be NULL)
+extern "C" int64_t dph_trim_mid_ints(void* h, int which, int32_t* out, int64_t cap) {
+    const TrimResult& r = ((TrimH*)h)->res;
+    const std::vector<int32_t>& v = which == 0 ? r.plan : which == 1 ? r.splits : r.applied;
+    if (out) memcpy(out, v.data(), (size_t)std::min<int64_t>(cap, (int64_t)v.size()) * sizeof(int32_t));
+    return (int64_t)v.size();
+}
+// the names of the halves added for split reads, one per line, in the order added (their sequences close dph_trim_output's text)
+extern "C" const char* dph_trim_extras(void* h, int64_t* n) {
+    TrimH* t = (TrimH*)h;
+    t->adapters.clear();
+    for (const std::string& s : t->res.extraNames) t->adapters += s + "\n";
+    *n = (int64_t)t->adapters.size();
+    return t->adapters.data();
+}
+// out[12]: chunks, seeds, batches, candidate pairs, records applied, overflow pairs, out-of-range halves, upload / scan / index / query /
+// kernel ms
+extern "C" void dph_trim_mid_stats(void* h, double* out) {
+    const TrimResult& r = ((TrimH*)h)->res;
+    const double v[12] = {(double)r.midChunks, (double)r.midSeeds, (double)r.midBatches, (double)r.midPairs, (double)r.midRecords, (double)r.midOverflowPairs,
+                          (double)r.midOutOfRange, r.mid_upload_ms, r.mid_scan_ms, r.mid_index_ms, r.mid_query_ms, r.mid_kernel_ms};
+    memcpy(out, v, sizeof v);
+}
+// test hook: the host's exact Match of one (chunk, front adapter) pair - what the pairs beyond the kernel's working set are given
+// to - with the identity test of trim.go:527-530; out = six int32 per passing match (adapter and chunk as passed in); returns their number
+extern "C" int64_t dph_hand_trim_match(const int32_t* chunk_segs, int n_chunk, const int32_t* adapter_segs, int n_adapter, int adapter_len, int n_seeds,
+                                       int k, int threshold, int adapter, int chunk, int32_t* out, int64_t cap) {
+    std::vector<TrimMidRec> recs;
+    trimHostMatch(chunk_segs, n_chunk, adapter_segs, n_adapter, adapter_len, n_seeds, k, threshold, adapter, chunk, recs);
+    for (size_t i = 0; i < recs.size() && (int64_t)i < cap; i++) memcpy(out + 6 * i, &recs[i], sizeof(TrimMidRec));
+    return (int64_t)recs.size();
 }
 extern "C" void dph_trim_free(void* h) { delete (TrimH*)h; }
 extern "C" const char* dph_trim_output(void* h, int64_t* n) {

@@ -115,17 +115,24 @@ static int runTrimCommand(ArgTable& t) {  // commands/trim.go:32-50
     p.tagAdapters = parseBool(t.args["tag_adapters"]);
     p.requirePairs = parseBool(t.args["require_pairs"]);
     p.determineAdapters = parseBool(t.args["determine_adapters"]);
-    // parsed and accepted; they belong to the search for adapters in the middle of reads, or change nothing in the result
-    parseInt(t.args["chunk_size"], ok);
-    parseInt(t.args["middle_threshold"], ok);
-    parseInt(t.args["extra_middle_trim"], ok);
-    parseInt(t.args["num_workers"], ok);
+    // the flags of the search for adapters in the middle of reads: in force with DP_TRIM_MIDDLE=1, else parsed and accepted
+    const char* midEnv = getenv("DP_TRIM_MIDDLE");
+    p.middle = midEnv && midEnv[0] && strcmp(midEnv, "0") != 0;
+    p.chunkSize = parseInt(t.args["chunk_size"], ok);
+    p.middleThreshold = (int)parseInt(t.args["middle_threshold"], ok);
+    p.extraMiddleTrim = (int)parseInt(t.args["extra_middle_trim"], ok);
+    p.discardMiddle = parseBool(t.args["discard_middle"]);
+    parseInt(t.args["num_workers"], ok);  // (changes nothing in the result)
     if (!ok) return 1;
+    if (p.middle && p.chunkSize <= 100) {
+        fprintf(stderr, "downpore trim: -chunk_size must be larger than 100 (the chunks advance by chunk_size - 100 bases)\n");
+        return 1;
+    }
     if (t.args["front_adapters"].empty() || t.args["back_adapters"].empty()) {
         fprintf(stderr, "downpore trim: -front_adapters and -back_adapters are required (the adapter lists are not shipped with this build)\n");
         return 1;
     }
-    fprintf(stderr, "downpore trim: the search for adapters in the middle of reads is not part of this build; reads are end-trimmed only\n");
+    if (!p.middle) fprintf(stderr, "downpore trim: the search for adapters in the middle of reads is not part of this build; reads are end-trimmed only\n");
     ReadSet front, back, reads;
     std::string err;
     if (!ReadSet::fromFile(t.args["front_adapters"], 0, false, front, err) || !ReadSet::fromFile(t.args["back_adapters"], 0, false, back, err) ||

@@ -1,12 +1,17 @@
 // trim.Trimmer, edge stage (trim/trim.go:13-132, 259-513; commands/trim.go:32-50): adapter determination, end trimming, tagging,
 // pairing, stats, the trimmed FASTA / FASTQ writer and demultiplexing (sequence/seqio.go:375-523).  The matching itself - findMatches
 // and isNewFullMatch for every read end - runs on the device (dp_trim_edges); what stays here is the sequential logic around it.
-// The search for adapters in the middle of reads (Trim's second half and findSplit, :151-257, :515-591) is not part of this build.
+// The middle stage (Trim's second half and findSplit, :151-257, :515-591): the chunk plan, the flush batches, findSplit's rules over
+// the matches a matching stage reports, the halves of split reads (AddSequence, sendExtras: seqio.go:81-104, 396-399).
 //
-// Canonical semantics where the reference depends on goroutine scheduling: one worker, so reads are judged and written in file order.
+// Canonical semantics where the reference depends on goroutine scheduling: one worker, so reads are judged and written in file order;
+// in the middle stage front adapters in list order, each to completion, within an adapter the chunks in ascending index order, within
+// a pair the matches in Match's return order.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
+
+#include <functional>
 
 #include "host_util.hpp"
 
@@ -77,6 +82,19 @@ bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex&
     return true;
 }
 
+// the chunk loop of trim.go:165-184 for a served (edge-trimmed) read of `length` bases
+void trimChunkPlan(i64 length, i64 chunkSize, uint32_t read, std::vector<TrimChunk>& out) {
+    const i64 longestAdapter = 100, edgeSize = 150;
+    for (i64 i = edgeSize; i < length - edgeSize - longestAdapter; i += chunkSize - longestAdapter) {
+        if (i > length - (chunkSize * 3) / 2 - edgeSize) {  // add the entire remainder
+            out.push_back(TrimChunk{read, (int32_t)i, (int32_t)(length - edgeSize), 1});
+            break;
+        }
+        const i64 endPoint = std::min(i + chunkSize, length - edgeSize);
+        out.push_back(TrimChunk{read, (int32_t)i, (int32_t)endPoint, 0});
+    }
+}
+
 namespace {
 // a ReadSet holding the chosen adapters of another one, in the given order
 ReadSet pickAdapters(const ReadSet& src, const std::vector<size_t>& order) {
@@ -129,8 +147,15 @@ void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
 }
 
 // trimWorker's arithmetic on the device's records (trim.go:464-510), PrintStats (:260-268) and Write (seqio.go:401-458)
+int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const TrimMidInput& in, TrimResult& res, bool& flushed, std::string& error);
+void writeExtras(const ReadSet& reads, const TrimResult& res, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out);
+
+// the middle stage's matching results made on demand, once the edge trims stand (the device path)
+typedef std::function<int(std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& recs)> MidProducer;
+
 int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimIndex& ix, const TrimParams& p, const std::vector<uint32_t>& eligible,
-               const dp_trim_rec* recs, const uint64_t* counts, TrimResult& res, std::string& error) {
+               const dp_trim_rec* recs, const uint64_t* counts, TrimResult& res, std::string& error, const TrimMidInput* mid = nullptr,
+               const MidProducer* producer = nullptr) {
     const double t0 = now();
     const size_t n = reads.size();
     reads.frontTrim.assign(n, 0);
@@ -185,6 +210,28 @@ int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const 
     res.frontNames = front.names;
     res.backNames = back.names;
     res.counts.assign(counts, counts + front.size() + back.size());
+    std::vector<int32_t> madeCounts;
+    std::vector<TrimMidRec> madeRecs;
+    TrimMidInput made;
+    if (producer) {
+        if (int rc = (*producer)(madeCounts, madeRecs)) return rc;
+        made.seedCounts = madeCounts.data();
+        made.nChunks = madeCounts.size();
+        made.recs = madeRecs.data();
+        made.nRecs = madeRecs.size();
+        mid = &made;
+    }
+    if (mid) {
+        bool flushed = false;
+        if (int rc = trimMiddle(reads, front, p, *mid, res, flushed, error)) return rc;
+        if (flushed) std::fill(res.counts.begin(), res.counts.end(), 0);  // setupIndex() after a flush zeroes frontCounts / backCounts (:78-79, :202)
+        for (size_t r = 0; r < n; r++) {
+            res.table[5 * r] = reads.frontTrim[r];
+            res.table[5 * r + 1] = reads.backTrim[r];
+            res.table[5 * r + 2] = reads.ignore[r];
+        }
+        counts = res.counts.data();
+    }
     res.t_apply = now() - t0;
     // PrintStats: with seenCount == 0 the reference divides by zero
     if (res.seen == 0) {
@@ -201,7 +248,520 @@ int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const 
     const double t1 = now();
     res.out.clear();
     trimWrite(reads, res.names, nullptr, res.out);
+    writeExtras(reads, res, res.extraNames, nullptr, res.out);
     res.t_write = now() - t1;
+    return 0;
+}
+
+// a half of a split read as the writers print it (seqio.go:401-435): extras follow the file's reads in the order added (sendExtras)
+void writeExtras(const ReadSet& reads, const TrimResult& res, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out) {
+    for (size_t e = 0; e < res.extraNames.size(); e++) {
+        if (keep && !(*keep)[e]) continue;
+        out += reads.isFastq ? '@' : '>';
+        out += names[e];
+        out += '\n';
+        out += res.extraBases[e];
+        out += '\n';
+        if (reads.isFastq) {
+            out += "+\n";
+            out += res.extraQuals[e];
+            out += '\n';
+        }
+    }
+}
+
+// ---- the middle stage -----------------------------------------------------------------------------------------------------------
+struct MidSplit {  // sequenceSplit (trim.go:42-46); live = the pointer is not nil
+    bool live = false;
+    i64 aEnd = 0, bStart = 0;
+};
+
+struct MidBatchRange {
+    size_t lo, hi;  // planned chunks [lo, hi)
+    i64 totalBases;
+};
+struct MidPlan {
+    std::vector<TrimChunk> plan;
+    std::vector<i64> servedLen;       // -1: the read was ignored when the second pass began
+    std::vector<size_t> firstChunk;   // [reads + 1]
+    std::vector<MidBatchRange> batches;
+};
+const i64 kLongestAdapter = 100, kMinSeeds = 4;  // :153, :155
+
+// the plan over what the second GetSequences() serves: the non-ignored reads with their edge trims applied (seqio.go:138-187)
+bool midBuildPlan(const ReadSet& reads, const TrimParams& p, MidPlan& mp, std::string& error) {
+    if (p.chunkSize <= kLongestAdapter) {
+        error = "trim: -chunk_size must be larger than 100 (the chunks advance by chunk_size - 100 bases)";
+        return false;
+    }
+    const size_t n = reads.size();
+    mp.servedLen.assign(n, -1);
+    mp.firstChunk.assign(n + 1, 0);
+    for (size_t r = 0; r < n; r++) {
+        mp.firstChunk[r] = mp.plan.size();
+        if (reads.ignore[r]) continue;
+        mp.servedLen[r] = reads.length(r) - reads.frontTrim[r] - reads.backTrim[r];
+        trimChunkPlan(mp.servedLen[r], p.chunkSize, (uint32_t)r, mp.plan);
+    }
+    mp.firstChunk[n] = mp.plan.size();
+    return true;
+}
+// the flush batches (:186-203, :206): a batch ends after the READ that takes totalCount over the threshold; returns "a flush happened"
+bool midCutBatches(const TrimParams& p, const int32_t* seedCounts, MidPlan& mp) {
+    bool flushed = false;
+    i64 totalCount = 0, totalBases = 0;
+    size_t lo = 0;
+    mp.batches.clear();
+    for (size_t r = 0; r + 1 < mp.firstChunk.size(); r++) {
+        if (mp.servedLen[r] < 0) continue;
+        totalBases += mp.servedLen[r] - kEdgeSize * 2;  // :164
+        for (size_t c = mp.firstChunk[r]; c < mp.firstChunk[r + 1]; c++) totalCount += seedCounts[c];
+        if (totalCount > p.flushSeeds) {
+            mp.batches.push_back(MidBatchRange{lo, mp.firstChunk[r + 1], totalBases});
+            lo = mp.firstChunk[r + 1];
+            totalCount = totalBases = 0;
+            flushed = true;
+        }
+    }
+    if (totalCount > 0) mp.batches.push_back(MidBatchRange{lo, mp.plan.size(), totalBases});
+    return flushed;
+}
+
+int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const TrimMidInput& in, TrimResult& res, bool& flushed, std::string& error) {
+    const size_t n = reads.size();
+    const i64 longestAdapter = kLongestAdapter, minSeeds = kMinSeeds, minSeqLength = 500;  // :153-155, :517
+    MidPlan mp;
+    if (!midBuildPlan(reads, p, mp, error)) return -1;
+    const std::vector<TrimChunk>& plan = mp.plan;
+    const std::vector<i64>& servedLen = mp.servedLen;
+    const std::vector<size_t>& firstChunk = mp.firstChunk;
+    if (in.nChunks != plan.size()) {
+        error = "trim: " + std::to_string(in.nChunks) + " seed counts for " + std::to_string(plan.size()) + " planned chunks";
+        return -1;
+    }
+    res.midChunks = (i64)plan.size();
+    res.plan.resize(plan.size() * 6);
+    flushed = midCutBatches(p, in.seedCounts, mp);
+    const std::vector<MidBatchRange>& batches = mp.batches;
+    std::vector<uint32_t> batchOf(plan.size(), 0);
+    {
+        (void)firstChunk;
+        for (size_t c = 0; c < plan.size(); c++) {
+            const i64 seeds = in.seedCounts[c];
+            res.midSeeds += seeds;
+            const bool indexed = plan[c].remainder || seeds >= minSeeds;
+            const int32_t row[6] = {(int32_t)plan[c].read, plan[c].start, plan[c].end, plan[c].remainder, (int32_t)seeds, indexed ? 1 : 0};
+            std::copy(row, row + 6, res.plan.begin() + 6 * (long)c);
+        }
+        for (size_t b = 0; b < batches.size(); b++)
+            for (size_t c = batches[b].lo; c < batches[b].hi; c++) batchOf[c] = (uint32_t)b;
+        // (chunks behind the last batch - a tail whose seeds sum to 0 - are never searched)
+        for (size_t c = batches.empty() ? 0 : batches.back().hi; c < plan.size(); c++) batchOf[c] = 0xffffffffu;
+    }
+    res.midBatches = (i64)batches.size();
+    // the records in canonical order: batch, adapter, chunk, ordinal
+    std::vector<TrimMidRec> recs;
+    for (size_t i = 0; i < in.nRecs; i++) {
+        const TrimMidRec& r = in.recs[i];
+        if (r.adapter < 0 || (size_t)r.adapter >= front.size() || r.chunk < 0 || (size_t)r.chunk >= plan.size()) {
+            error = "trim: a middle record names an adapter or a chunk beyond the lists";
+            return -1;
+        }
+        if (batchOf[(size_t)r.chunk] == 0xffffffffu || !res.plan[6 * (size_t)r.chunk + 5]) {
+            error = "trim: a middle record names a chunk that was not indexed";
+            return -1;
+        }
+        recs.push_back(r);
+    }
+    std::stable_sort(recs.begin(), recs.end(), [&](const TrimMidRec& a, const TrimMidRec& b) {
+        const uint32_t ba = batchOf[(size_t)a.chunk], bb = batchOf[(size_t)b.chunk];
+        if (ba != bb) return ba < bb;
+        if (a.adapter != b.adapter) return a.adapter < b.adapter;
+        if (a.chunk != b.chunk) return a.chunk < b.chunk;
+        return a.ordinal < b.ordinal;
+    });
+    // findSplit's rules (:527-586)
+    std::vector<MidSplit> splits(n + 1);
+    std::vector<i64> ids;
+    size_t at = 0;
+    for (size_t b = 0; b < batches.size(); b++) {
+        if (p.verbosity > 0)
+            logLine(res.errText, "Searching " + std::to_string(batches[b].totalBases / 1000000) + " MB of sequences for splitting based on " +
+                                     std::to_string(front.size()) + " adapters");
+        for (; at < recs.size() && batchOf[(size_t)recs[at].chunk] == b; at++) {
+            const TrimMidRec& m = recs[at];
+            const i64 adLen = front.length((size_t)m.adapter);
+            if (((i64)m.covered * 100) / adLen < p.middleThreshold) continue;  // :528
+            res.applied.insert(res.applied.end(), {m.adapter, m.chunk, m.ordinal, m.startRel, m.covered, m.chainLen});
+            const TrimChunk& c = plan[(size_t)m.chunk];
+            const size_t id = c.read;
+            const i64 frontTrim = reads.frontTrim[id], backTrim = reads.backTrim[id];  // :538-539
+            // the chunk is SubSequence(start, end) of the served read: offset = start, Len = end - start, and - `end--` comes before
+            // the inset is taken (sequence.go:353-370) - inset = served length - end + 1
+            const i64 start = (i64)c.start + m.startRel;           // :541
+            const i64 seqLen = servedLen[id] + 1 - backTrim;       // :542
+            MidSplit& split = splits[id];
+            if (start < minSeqLength + frontTrim) {  // :543 just crop the front off
+                const i64 newTrim = start + adLen + p.extraMiddleTrim;
+                if (newTrim + minSeqLength < seqLen) {
+                    if (newTrim > frontTrim) {
+                        reads.frontTrim[id] = (int32_t)newTrim;
+                        if (split.live) {  // update the existing split
+                            split.aEnd -= newTrim - frontTrim;
+                            split.bStart -= newTrim - frontTrim;
+                        }
+                    }
+                    if (p.tagAdapters) res.names[id] = front.names[(size_t)m.adapter] + "_" + res.names[id];
+                } else {
+                    split.live = false;  // in case of existing split that is no longer valid
+                    reads.ignore[id] = 1;
+                }
+            } else if (start + minSeqLength + adLen > seqLen) {  // :560 crop off the tail
+                const i64 newTrim = seqLen - start + p.extraMiddleTrim;
+                if (newTrim > backTrim) reads.backTrim[id] = (int32_t)newTrim;
+            } else if (split.live) {  // :568-574
+                split.aEnd = std::min(split.aEnd, start - p.extraMiddleTrim - frontTrim);
+                split.bStart = std::max(split.bStart, start + adLen + p.extraMiddleTrim - frontTrim);
+            } else {  // :579-583
+                split.live = true;
+                split.aEnd = start - p.extraMiddleTrim - frontTrim;
+                split.bStart = start + adLen + p.extraMiddleTrim - frontTrim;
+                ids.push_back((i64)id);  // (an id whose split was dropped and made again is listed twice, as in the reference)
+            }
+        }
+    }
+    res.midRecords = (i64)res.applied.size() / 6;
+    if (p.verbosity > 0) logLine(res.errText, std::to_string(ids.size()) + " sequences require splitting");  // :218-220
+    // :222-256 over the reads re-read with the trims as they stand now
+    auto bases = [&](size_t id, i64 lo, i64 hi) {
+        std::string t((size_t)(hi - lo), 'A');
+        const char* s = reads.seq(id) + reads.frontTrim[id] + lo;
+        for (i64 j = 0; j < hi - lo; j++) t[(size_t)j] = "ACGT"[baseCode((unsigned char)s[j])];
+        return t;
+    };
+    auto quals = [&](size_t id, i64 lo, i64 hi) {
+        std::string t;
+        if (const uint8_t* q = reads.isFastq ? reads.quality(id) : nullptr)
+            for (i64 j = lo; j < hi; j++) t += (char)(uint8_t)(q[reads.frontTrim[id] + j] + 33);
+        return t;
+    };
+    for (i64 idv : ids) {
+        const size_t id = (size_t)idv;
+        const MidSplit& split = splits[id];
+        if (!split.live) continue;
+        const i64 len = reads.length(id) - reads.frontTrim[id] - reads.backTrim[id];
+        int kept = 0;
+        if (!p.discardMiddle) {
+            std::string report = "Splitting read " + std::to_string(id) + " into";
+            if (split.aEnd > kEdgeSize) {
+                const i64 e = std::min(split.aEnd, len);  // SubSequence clamps its end (:354-356)
+                res.extraNames.push_back(res.names[id] + "_(left)");
+                res.extraBases.push_back(bases(id, 0, e));
+                res.extraQuals.push_back(quals(id, 0, e));
+                report += ": 0 - " + std::to_string(split.aEnd) + " and ";
+                kept |= 1;
+            } else {
+                report += " ignored short left hand side and ";
+            }
+            if (len - split.bStart > kEdgeSize) {
+                if (split.bStart < 0) {  // SubSequence would slice out of range (the reference panics or reads past its bytes)
+                    res.midOutOfRange++;
+                    logLine(res.errText, "Skipping the right hand side of read " + std::to_string(id) + ": its start " + std::to_string(split.bStart) + " is out of range");
+                    report += " out of range right hand side";
+                } else {
+                    res.extraNames.push_back(res.names[id] + "_(right)");
+                    res.extraBases.push_back(bases(id, split.bStart, len));
+                    res.extraQuals.push_back(quals(id, split.bStart, len));
+                    report += std::to_string(split.bStart) + " - " + std::to_string(len);
+                    kept |= 2;
+                }
+            } else {
+                report += " ignored short right hand side";
+            }
+            if (p.verbosity > 1) {
+                logLine(res.errText, report);
+                if (split.aEnd >= 0 && split.bStart < len && split.bStart - split.aEnd - (i64)p.extraMiddleTrim * 2 <= longestAdapter)
+                    logLine(res.errText, bases(id, split.aEnd + p.extraMiddleTrim, std::min(split.bStart - p.extraMiddleTrim, len)));
+            }
+        }
+        res.splits.insert(res.splits.end(), {(int32_t)id, (int32_t)split.aEnd, (int32_t)split.bStart, kept});
+        reads.ignore[id] = 1;  // :255
+    }
+    return 0;
+}
+
+// ---- SeedSequence.Match on the host (seeds/sequence.go:85-123, 361-576), for the pairs the device lists as beyond its working set --
+// Reduced (:85-123): the seeds of `seg` that are in the whitelist and differ from the seed kept before them; index = their positions
+int hostReduced(const int32_t* seg, int n, const std::vector<uint64_t>& wl, int k, int minSeeds, std::vector<int32_t>& out, std::vector<int>& index) {
+    auto has = [&](int x) { return (wl[(size_t)x >> 6] >> (x & 63)) & 1ull; };
+    int count = 0, prev = -1;
+    for (int i = 1; i < n; i += 2) {
+        const int next = seg[i];
+        if (next != prev && has(next)) {
+            count++;
+            prev = next;
+        }
+    }
+    if (count < minSeeds) return -1;
+    out.assign((size_t)count * 2 + 1, 0);
+    index.assign((size_t)count, 0);
+    int offset = seg[0], j = 0;
+    prev = -1;
+    for (int i = 1; i < n; i += 2) {
+        const int seed = seg[i];
+        if (prev != seed && has(seed)) {
+            out[(size_t)j] = offset;
+            out[(size_t)j + 1] = seed;
+            index[(size_t)j / 2] = i / 2;
+            j += 2;
+            offset = seg[i + 1];
+            prev = seed;
+        } else {
+            offset += seg[i + 1] + k;
+        }
+    }
+    out[(size_t)j] = offset;
+    return count;
+}
+struct HostChains {
+    std::vector<std::vector<int>> a, b;  // chain -> seed indices of the reduced query / target
+    std::vector<int> headChain, headLen;
+};
+// extendChain (:476-576); as = reduced query, bs = reduced target
+void hostExtend(HostChains& C, const std::vector<int32_t>& as, const std::vector<int32_t>& bs, int aIndex, int bIndex, int k, int cur) {
+    const int an = (int)as.size(), bn = (int)bs.size();
+    std::vector<int>&ca = C.a[(size_t)cur], &cb = C.b[(size_t)cur];
+    int offsetA = as[(size_t)aIndex + 1], offsetB = bs[(size_t)bIndex + 1];
+    aIndex += 2;
+    bIndex += 2;
+    while (aIndex < an && bIndex < bn) {
+        int aSeedIndex = aIndex / 2;
+        int minBOffset, maxBOffset;
+        if (offsetA < 0) {
+            minBOffset = -k;
+            maxBOffset = 0;
+        } else {
+            minBOffset = (offsetA * 2) / 3 - k;
+            maxBOffset = (offsetA * 3) / 2 + k;
+        }
+        while (maxBOffset < offsetB) {
+            offsetA += as[(size_t)aIndex + 1] + k;
+            aIndex += 2;
+            if (aIndex >= an) return;
+            aSeedIndex = aIndex / 2;
+            minBOffset = (offsetA * 2) / 3 - k;
+            maxBOffset = (offsetA * 3) / 2 + k;
+        }
+        while (offsetB < minBOffset) {
+            offsetB += bs[(size_t)bIndex + 1] + k;
+            bIndex += 2;
+            if (bIndex >= bn) return;
+        }
+        const int oldBIndex = bIndex, oldBOffset = offsetB;
+        bool matched = false;
+        const int seedA = as[(size_t)aIndex];
+        while (offsetB <= maxBOffset) {
+            if (seedA == bs[(size_t)bIndex]) {
+                const int hc = C.headChain[(size_t)aSeedIndex];
+                if (hc >= 0) {
+                    const int hl = C.headLen[(size_t)aSeedIndex];
+                    if (bIndex / 2 == C.b[(size_t)hc][(size_t)hl - 1] && hl > (int)ca.size()) return;  // they have a better chain already
+                }
+                ca.push_back(aSeedIndex);
+                cb.push_back(bIndex / 2);
+                C.headChain[(size_t)aSeedIndex] = cur;
+                C.headLen[(size_t)aSeedIndex] = (int)ca.size();
+                offsetA = as[(size_t)aIndex + 1];
+                offsetB = bs[(size_t)bIndex + 1];
+                aIndex += 2;
+                bIndex += 2;
+                matched = true;
+                break;
+            }
+            offsetB += bs[(size_t)bIndex + 1] + k;
+            bIndex += 2;
+            if (bIndex >= bn) break;
+        }
+        if (!matched) {
+            offsetA += as[(size_t)aIndex + 1] + k;
+            aIndex += 2;
+            offsetB = oldBOffset;
+            bIndex = oldBIndex;
+        }
+    }
+}
+// dynamicMatch (:401-471): the good chains in the reference's return order
+std::vector<int> hostDynamicMatch(HostChains& C, const std::vector<int32_t>& qs, const std::vector<int32_t>& ss, int minMatch, int k) {
+    if (minMatch == 0) minMatch = 1;
+    const int qn = (int)qs.size(), sn = (int)ss.size(), nq = qn / 2;
+    C.headChain.assign((size_t)nq, -1);
+    C.headLen.assign((size_t)nq, 0);
+    std::vector<int> good;
+    for (int qIndex = 1; qIndex < qn - minMatch * 2 + 2; qIndex += 2) {
+        if (qs[(size_t)qIndex - 1] < 0 && qIndex > 1 && qs[(size_t)qIndex + 1] < 0 && qs[(size_t)qIndex] == qs[(size_t)qIndex - 2] && qs[(size_t)qIndex] == qs[(size_t)qIndex + 2])
+            continue;
+        const int qsi = qIndex / 2;
+        if (C.headChain[(size_t)qsi] >= 0) continue;
+        int prevSeed = -1;
+        for (int i = 1; i < sn - minMatch * 2 + 2; i += 2) {
+            const int nextSeed = ss[(size_t)i];
+            const int hc = C.headChain[(size_t)qsi];
+            if (nextSeed == qs[(size_t)qIndex] && nextSeed != prevSeed && (hc < 0 || C.b[(size_t)hc][(size_t)C.headLen[(size_t)qsi] - 1] != i / 2)) {
+                const int c = (int)C.a.size();
+                C.a.push_back({qsi});
+                C.b.push_back({i / 2});
+                C.headChain[(size_t)qsi] = c;
+                C.headLen[(size_t)qsi] = 1;
+                hostExtend(C, qs, ss, qIndex, i, k, c);
+                const int len = (int)C.a[(size_t)c].size();
+                if (len >= minMatch) {
+                    const int nextLength = (len * 2) / 3;
+                    if (nextLength > minMatch) {
+                        minMatch = nextLength;
+                        for (int j = (int)good.size() - 1; j >= 0; j--)
+                            if ((int)C.a[(size_t)good[(size_t)j]].size() < nextLength) {
+                                good[(size_t)j] = good.back();
+                                good.pop_back();
+                            }
+                    }
+                    good.push_back(c);
+                    int remaining = 0;
+                    for (int x = 0; x < nq; x++) remaining += C.headChain[(size_t)x] < 0;
+                    if (remaining < len) return good;
+                }
+            }
+            prevSeed = nextSeed;
+        }
+    }
+    return good;
+}
+// Match(ad, adSet, chunkSet, minMatch, k) of one (chunk, front adapter) pair and the identity test of trim.go:527-530
+void hostMatchPair(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
+                   std::vector<TrimMidRec>& out) {
+    std::vector<uint64_t> aSet(((size_t)nSeeds + 63) / 64, 0), cSet(aSet.size(), 0);
+    for (int i = 1; i < aN; i += 2) aSet[(size_t)aSeg[i] >> 6] |= 1ull << (aSeg[i] & 63);
+    for (int i = 1; i < cN; i += 2) cSet[(size_t)cSeg[i] >> 6] |= 1ull << (cSeg[i] & 63);
+    const int minMatch = (aN / 2) / 5;
+    std::vector<int32_t> t, q;
+    std::vector<int> tIdx, qIdx;
+    if (hostReduced(cSeg, cN, aSet, k, minMatch, t, tIdx) < 0) return;
+    if (hostReduced(aSeg, aN, cSet, k, minMatch, q, qIdx) < 0) return;
+    HostChains C;
+    const std::vector<int> good = hostDynamicMatch(C, q, t, minMatch, k);
+    auto seedOffset = [&](const int32_t* seg, int index) {  // GetSeedOffset (seeds/sequence.go:1239-1246)
+        index = index * 2 + 1;
+        int o = seg[0];
+        for (int i = 2; i < index; i += 2) o += seg[i] + k;
+        return o;
+    };
+    for (size_t g = 0; g < good.size(); g++) {
+        const std::vector<int>&ca = C.a[(size_t)good[g]], &cb = C.b[(size_t)good[g]];
+        const int len = (int)ca.size();
+        int countA = len * k, prevA = qIdx[(size_t)ca[0]];  // GetBasesCovered's countA (:830-858)
+        for (int i = 1; i < len; i++) {
+            const int s = qIdx[(size_t)ca[(size_t)i]];
+            int d1 = aSeg[prevA * 2 + 2];
+            for (int j = prevA + 2; j <= s; j++) d1 += aSeg[j * 2] + k;
+            if (d1 < 0) countA += d1;
+            prevA = s;
+        }
+        if ((countA * 100) / adLen < threshold) continue;
+        out.push_back(TrimMidRec{adapter, chunk, (int32_t)g, seedOffset(cSeg, tIdx[(size_t)cb[0]]) - seedOffset(aSeg, qIdx[(size_t)ca[0]]), countA, len});
+    }
+}
+
+}  // namespace
+void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
+                   std::vector<TrimMidRec>& out) {
+    hostMatchPair(cSeg, cN, aSeg, aN, adLen, nSeeds, k, threshold, adapter, chunk, out);
+}
+namespace {
+// the middle stage's device half: scan every planned chunk for its seed count, cut the flush batches, then per batch scan -> index ->
+// candidates -> matching kernel, and the host's Match for the pairs the kernel listed
+int midDevice(dp_trim* h, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& recs,
+              TrimResult& res, std::string& error) {
+    MidPlan mp;
+    if (!midBuildPlan(reads, p, mp, error)) return -1;
+    const size_t nC = mp.plan.size();
+    seedCounts.assign(nC, 0);
+    recs.clear();
+    if (!nC || !ix.nFront) return 0;
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> cnt;
+    double tms[2];
+    // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device
+    auto scan = [&](size_t lo, size_t hi) -> bool {
+        off.assign(1, 0);
+        for (size_t c = lo; c < hi; c++) off.push_back(off.back() + (uint64_t)(mp.plan[c].end - mp.plan[c].start));
+        bases.resize((size_t)off.back() + 1);
+        for (size_t c = lo; c < hi; c++) {
+            const TrimChunk& ch = mp.plan[c];
+            memcpy(bases.data() + off[c - lo], reads.seq(ch.read) + reads.frontTrim[ch.read] + ch.start, (size_t)(ch.end - ch.start));
+        }
+        cnt.assign(hi - lo, 0);
+        if (dp_trim_scan_chunks(h, bases.data(), off.data(), (uint32_t)(hi - lo), cnt.data(), tms) != 0) {
+            error = std::string("trim: ") + dp_trim_error(h);
+            return false;
+        }
+        res.mid_upload_ms += tms[0];
+        res.mid_scan_ms += tms[1];
+        res.bytes_up += (double)off.back();
+        for (size_t c = lo; c < hi; c++) seedCounts[c] = (int32_t)cnt[c - lo];
+        return true;
+    };
+    const uint64_t groupBases = (uint64_t)1 << 28;
+    size_t scannedLo = 0, scannedHi = 0;  // what the device holds segments of
+    for (size_t lo = 0; lo < nC;) {
+        size_t hi = lo;
+        uint64_t b = 0;
+        while (hi < nC && (hi == lo || b + (uint64_t)(mp.plan[hi].end - mp.plan[hi].start) <= groupBases)) b += (uint64_t)(mp.plan[hi].end - mp.plan[hi].start), hi++;
+        if (!scan(lo, hi)) return -1;
+        scannedLo = lo;
+        scannedHi = hi;
+        lo = hi;
+    }
+    midCutBatches(p, seedCounts.data(), mp);
+    std::vector<uint32_t> sel;
+    std::vector<int32_t> cseg;
+    for (const MidBatchRange& bt : mp.batches) {
+        if (bt.lo != scannedLo || bt.hi != scannedHi) {
+            if (!scan(bt.lo, bt.hi)) return -1;
+            scannedLo = bt.lo;
+            scannedHi = bt.hi;
+        }
+        sel.clear();
+        for (size_t c = bt.lo; c < bt.hi; c++)
+            if (mp.plan[c].remainder || seedCounts[c] >= kMinSeeds) sel.push_back((uint32_t)(c - bt.lo));
+        dp_trim_mid_batch mb;
+        if (dp_trim_search(h, sel.data(), (uint32_t)sel.size(), p.middleThreshold, &mb) != 0) {
+            error = std::string("trim: ") + dp_trim_error(h);
+            return -1;
+        }
+        res.midPairs += mb.n_pairs;
+        res.midOverflowPairs += mb.n_overflow;
+        res.mid_index_ms += mb.index_ms;
+        res.mid_query_ms += mb.query_ms;
+        res.mid_kernel_ms += mb.kernel_ms;
+        res.bytes_down += (double)mb.n_recs * sizeof(dp_trim_mid_rec);
+        static_assert(sizeof(dp_trim_mid_rec) == sizeof(TrimMidRec), "device and host records are the same six int32");
+        for (uint32_t i = 0; i < mb.n_recs; i++) {
+            const dp_trim_mid_rec& r = mb.recs[i];
+            recs.push_back(TrimMidRec{r.adapter, (int32_t)(r.chunk + (int32_t)bt.lo), r.ordinal, r.start_rel, r.covered, r.chain_len});
+        }
+        const std::vector<uint32_t> over(mb.overflow, mb.overflow + 2 * (size_t)mb.n_overflow);  // (the handle's arrays go with its next call)
+        for (size_t i = 0; i < over.size(); i += 2) {
+            const uint32_t c = over[i], a = over[i + 1];
+            uint64_t n = 0;
+            cseg.resize(2 * (size_t)seedCounts[bt.lo + c] + 1);
+            if (dp_trim_chunk_segments(h, c, cseg.data(), cseg.size(), &n) != 0 || n != cseg.size()) {
+                error = std::string("trim: ") + dp_trim_error(h);
+                return -1;
+            }
+            hostMatchPair(cseg.data(), (int)cseg.size(), ix.segs.data() + ix.segOff[a], (int)(ix.segOff[a + 1] - ix.segOff[a]), ix.lengths[a], (int)ix.nSeeds, ix.k,
+                          p.middleThreshold, (int32_t)a, (int32_t)(bt.lo + c), recs);
+        }
+    }
     return 0;
 }
 
@@ -267,11 +827,31 @@ int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::stri
         names[r] = n.substr(pos + 1);
         keep[li][r] = 1;
     }
+    // the halves of split reads follow the file's reads (sendExtras)
+    std::vector<std::string> extraNames = res.extraNames;
+    std::vector<std::vector<uint8_t>> keepExtra(labels.size(), std::vector<uint8_t>(extraNames.size(), 0));
+    for (size_t e = 0; e < extraNames.size(); e++) {
+        const std::string n = extraNames[e];
+        if (!isBarcodeName(n)) continue;
+        const size_t pos = n.find('_');
+        if (pos == std::string::npos) continue;
+        const std::string label = n.substr(0, pos);
+        size_t li = 0;
+        while (li < labels.size() && labels[li] != label) li++;
+        if (li == labels.size()) {
+            labels.push_back(label);
+            keep.emplace_back(reads.size(), 0);
+            keepExtra.emplace_back(extraNames.size(), 0);
+        }
+        extraNames[e] = n.substr(pos + 1);
+        keepExtra[li][e] = 1;
+    }
     const char* ext = reads.isFastq ? ".fastq" : ".fasta";
     for (size_t li = 0; li < labels.size(); li++) {
         const std::string path = dir + "/" + labels[li] + ext;
         std::string text;
         trimWrite(reads, names, &keep[li], text);
+        writeExtras(reads, res, extraNames, &keepExtra[li], text);
         const int fd = open(path.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0755);
         if (fd < 0) {
             error = "Unable to open file for writing:" + path;
@@ -295,8 +875,8 @@ int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::stri
 // The device-free half: DetermineAdapters' compaction from caller-supplied flags (enabled == nullptr: none ran), then trimWorker,
 // PrintStats and Write from caller-supplied edge records of the eligible reads (in read order) and per-adapter match counts, both
 // in the order of the COMPACTED adapter lists.
-int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-              size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error) {
+static int applyTrimImpl(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+                         size_t nRecReads, const uint64_t* counts, const TrimMidInput* mid, TrimResult& res, std::string& error) {
     res = TrimResult();
     ReadSet front = front0, back = back0;
     if (enabled) {
@@ -313,7 +893,15 @@ int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const
         error = "trim: " + std::to_string(nRecReads) + " edge record pairs for " + std::to_string(eligible.size()) + " reads of 200 bases and more";
         return -1;
     }
-    return finishTrim(reads, front, back, ix, p, eligible, recs, counts, res, error);
+    return finishTrim(reads, front, back, ix, p, eligible, recs, counts, res, error, mid);
+}
+int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+              size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error) {
+    return applyTrimImpl(reads, front0, back0, p, enabled, recs, nRecReads, counts, nullptr, res, error);
+}
+int applyTrimMid(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+                 size_t nRecReads, const uint64_t* counts, const TrimMidInput& mid, TrimResult& res, std::string& error) {
+    return applyTrimImpl(reads, front0, back0, p, enabled, recs, nRecReads, counts, p.middle ? &mid : nullptr, res, error);
 }
 
 int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, int device, TrimResult& res, std::string& error) {
@@ -371,8 +959,16 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
             res.bytes_down += (double)(2 * eb.reads.size() * sizeof(dp_trim_rec));
         }
     }
-    if (h) dp_trim_release(h);
-    return finishTrim(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error);
+    if (!p.middle || !h) {
+        if (h) dp_trim_release(h);
+        return finishTrim(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error);
+    }
+    const MidProducer producer = [&](std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& midRecs) {
+        return midDevice(h, reads, ix, p, seedCounts, midRecs, res, error);
+    };
+    const int rc = finishTrim(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error, nullptr, &producer);
+    dp_trim_release(h);
+    return rc;
 }
 
 }  // namespace dph

@@ -13,6 +13,12 @@ TRIM_STAT_FIELDS = ["seen", "none", "reads", "front_adapters", "back_adapters", 
 TRIM_TABLE_FIELDS = ["front_trim", "back_trim", "ignore", "front_adapter", "back_adapter"]
 #: fields of one edge record (dp_trim_rec)
 TRIM_REC_FIELDS = ["earliest", "latest", "found", "best_match", "ambiguous", "best_ident"]
+#: the middle stage's stats, columns of its plan / split / record tables
+TRIM_MID_STAT_FIELDS = ["mid_chunks", "mid_seeds", "mid_batches", "mid_pairs", "mid_records", "mid_overflow_pairs", "mid_out_of_range",
+                        "mid_upload_ms", "mid_scan_ms", "mid_index_ms", "mid_query_ms", "mid_kernel_ms"]
+TRIM_PLAN_FIELDS = ["read", "start", "end", "remainder", "seeds", "indexed"]
+TRIM_SPLIT_FIELDS = ["read", "a_end", "b_start", "kept"]
+TRIM_MID_REC_FIELDS = ["adapter", "chunk", "ordinal", "start_rel", "covered", "chain_len"]
 EDGE = 150
 MODE_TRIM, MODE_DETERMINE = 0, 1
 
@@ -34,12 +40,26 @@ def _host():
     H.dph_trim_demultiplex.argtypes = [vp, C.c_char_p]
     H.dph_trim_index.restype = C.c_int64
     H.dph_trim_index.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp]
+    H.dph_trim_apply_mid.restype = vp
+    H.dph_trim_apply_mid.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64]
+    H.dph_trim_chunk_plan.restype = C.c_int64
+    H.dph_trim_chunk_plan.argtypes = [C.c_int64, C.c_int64, vp, C.c_int64]
+    H.dph_trim_mid_ints.restype = C.c_int64
+    H.dph_trim_mid_ints.argtypes = [vp, C.c_int, vp, C.c_int64]
+    H.dph_trim_extras.restype = C.POINTER(C.c_char)
+    H.dph_trim_extras.argtypes = [vp, C.POINTER(C.c_int64)]
+    H.dph_trim_mid_stats.argtypes = [vp, vp]
     return H
 
 
 def _params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity):
     return np.array([k, check_reads, adapter_threshold, extra_end_trim, 1 if tag_adapters else 0, 1 if require_pairs else 0,
                      1 if determine_adapters else 0, verbosity], dtype=np.int64)
+
+
+def _mid_params(edge, chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds):
+    return np.concatenate([edge, np.array([1, chunk_size, middle_threshold, extra_middle_trim, 1 if discard_middle else 0, flush_seeds],
+                                          dtype=np.int64)])
 
 
 class TrimResult:
@@ -58,6 +78,18 @@ class TrimResult:
         st = np.zeros(16, dtype=np.float64)
         H.dph_trim_stats(h, st.ctypes.data)
         self.stats = dict(zip(TRIM_STAT_FIELDS, st.tolist()))
+        # the middle stage (empty / zero when it did not run)
+        def ints(which, width):
+            m = H.dph_trim_mid_ints(h, which, None, 0)
+            a = np.zeros(m, dtype=np.int32)
+            H.dph_trim_mid_ints(h, which, a.ctypes.data, m)
+            return a.reshape(-1, width)
+
+        self.plan, self.splits, self.applied = ints(0, 6), ints(1, 4), ints(2, 6)
+        self.extras = C.string_at(H.dph_trim_extras(h, C.byref(n)), n.value).decode().splitlines()
+        ms = np.zeros(12, dtype=np.float64)
+        H.dph_trim_mid_stats(h, ms.ctypes.data)
+        self.stats.update(zip(TRIM_MID_STAT_FIELDS, ms.tolist()))
         self._H, self._h = H, h
 
     def __iter__(self):
@@ -84,12 +116,18 @@ class TrimResult:
 
 
 def trim_reads(reads, front, back, k=6, check_reads=10000, adapter_threshold=90, extra_end_trim=5, tag_adapters=True,
-               require_pairs=False, determine_adapters=True, device=0, verbosity=1):
+               require_pairs=False, determine_adapters=True, device=0, verbosity=1, middle=False, chunk_size=5000, middle_threshold=85,
+               extra_middle_trim=100, discard_middle=False, flush_seeds=300_000_000):
     """reads: downpore_amd.overlap.Reads loaded with min_len=50 (commands/trim.go:35); front / back: the adapter files as Reads
     with min_len=0.  Runs adapter determination, end trimming and the writer on the GPU and returns a TrimResult (output text,
-    stderr text, per-read table, stats); keep `reads` alive while the result is in use.  There is no CPU fallback."""
+    stderr text, per-read table, stats); keep `reads` alive while the result is in use.  There is no CPU fallback.
+    middle=True adds the search for front adapters in the middle of reads (trim/trim.go:151-256): reads are cropped or split, the
+    halves of split reads follow the file's reads as <name>_(left) / <name>_(right) (TrimResult.splits / .extras; needs k >= 4).
+    middle=False is the edge stage alone."""
     H = _host()
     p = _params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity)
+    if middle:
+        p = _mid_params(p, chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds)
     h = H.dph_trim_run(reads.h, front.h, back.h, p.ctypes.data, len(p), device)
     if not h:
         raise DpError("dph_trim_run: " + H.dph_last_error(None).decode())
@@ -112,6 +150,39 @@ def trim_apply(reads, front, back, recs, counts, enabled=None, k=6, check_reads=
     return TrimResult(H, h)
 
 
+def trim_apply_middle(reads, front, back, recs, counts, seed_counts, mid_recs, enabled=None, k=6, check_reads=10000, adapter_threshold=90,
+                      extra_end_trim=5, tag_adapters=True, require_pairs=False, verbosity=1, chunk_size=5000, middle_threshold=85,
+                      extra_middle_trim=100, discard_middle=False, flush_seeds=300_000_000):
+    """trim_apply followed by the middle stage's sequential half (dph_trim_apply_mid), without a device: seed_counts = seeds of every
+    planned chunk (trim_chunk_plan over the edge-trimmed reads, in file order), mid_recs int32 [n, 6] (TRIM_MID_REC_FIELDS) = the matches
+    that passed the identity test, in any order."""
+    H = _host()
+    p = _mid_params(_params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, enabled is not None, verbosity),
+                    chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds)
+    r = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, 6)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    en = None if enabled is None else np.ascontiguousarray(enabled, dtype=np.uint8)
+    sc = np.ascontiguousarray(seed_counts, dtype=np.int32)
+    mr = np.ascontiguousarray(mid_recs, dtype=np.int32).reshape(-1, 6)
+    h = H.dph_trim_apply_mid(reads.h, front.h, back.h, p.ctypes.data, len(p), None if en is None else en.ctypes.data, r.ctypes.data,
+                             len(r) // 2, c.ctypes.data, sc.ctypes.data, len(sc), mr.ctypes.data, len(mr))
+    if not h:
+        raise DpError("dph_trim_apply_mid: " + H.dph_last_error(None).decode())
+    return TrimResult(H, h)
+
+
+def trim_chunk_plan(length, chunk_size):
+    """The chunks the middle stage cuts from an edge-trimmed read of `length` bases (trim/trim.go:165-184): int32 [n, 3] =
+    start, end, is-remainder.  chunk_size <= 100 is refused (the reference's loop would not end)."""
+    H = _host()
+    n = H.dph_trim_chunk_plan(length, chunk_size, None, 0)
+    if n < 0:
+        raise DpError("dph_trim_chunk_plan: " + H.dph_last_error(None).decode())
+    out = np.zeros((max(n, 1), 3), dtype=np.int32)
+    H.dph_trim_chunk_plan(length, chunk_size, out.ctypes.data, n)
+    return out[:n]
+
+
 def trim_index(front, back, k):
     """setupIndex (trim/trim.go:57-99) as dp_trim_setup takes it: dict of kmer_seed, n_seeds, segs, seg_off, lengths, is_barcode,
     pairs, n_front, n_back."""
@@ -132,6 +203,12 @@ def trim_index(front, back, k):
                 n_front=len(front), n_back=len(back), k=k)
 
 
+class MidBatch(C.Structure):
+    """dp_trim_mid_batch"""
+    _fields_ = [("n_recs", C.c_uint32), ("recs", C.c_void_p), ("n_overflow", C.c_uint32), ("overflow", C.POINTER(C.c_uint32)),
+                ("n_pairs", C.c_uint32), ("launches", C.c_uint32), ("index_ms", C.c_double), ("query_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class TrimDevice:
     """One adapter index on the device (dp_trim_setup .. dp_trim_release)."""
 
@@ -144,6 +221,9 @@ class TrimDevice:
         L.dp_trim_release.restype = None
         L.dp_trim_error.restype = C.c_char_p
         L.dp_trim_error.argtypes = [vp]
+        L.dp_trim_scan_chunks.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
+        L.dp_trim_chunk_segments.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.dp_trim_search.argtypes = [vp, vp, C.c_uint32, C.c_int, C.POINTER(MidBatch)]
         self.L = L
         self.n_adapters = index["n_front"] + index["n_back"]
         ix = {key: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for key, v in index.items()}
@@ -168,6 +248,43 @@ class TrimDevice:
         if rc != 0:
             raise DpError("dp_trim_edges failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
         return (recs, counts, times) if mode == MODE_TRIM else (enabled, times)
+
+    def scan_chunks(self, chunks):
+        """dp_trim_scan_chunks: chunks = a list of ASCII base strings (or bytes) -> (seeds per chunk uint32, times_ms [upload, scan]).
+        The segments stay on the device for chunk_segments / search until the next scan."""
+        raw = [c.encode() if isinstance(c, str) else bytes(c) for c in chunks]
+        off = np.zeros(len(raw) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c) for c in raw], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)
+        counts = np.zeros(len(raw), dtype=np.uint32)
+        times = np.zeros(2, dtype=np.float64)
+        rc = self.L.dp_trim_scan_chunks(self.h, bases.ctypes.data, off.ctypes.data, len(raw), counts.ctypes.data, times.ctypes.data)
+        if rc != 0:
+            raise DpError("dp_trim_scan_chunks failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        return counts, times
+
+    def chunk_segments(self, chunk):
+        """The [gap, seed, ..., gap] segments of one chunk of the last scan (int32)."""
+        n = C.c_uint64(0)
+        rc = self.L.dp_trim_chunk_segments(self.h, chunk, None, 0, C.byref(n))
+        out = np.zeros(max(int(n.value), 1), dtype=np.int32)
+        if rc == 0:
+            rc = self.L.dp_trim_chunk_segments(self.h, chunk, out.ctypes.data, len(out), C.byref(n))
+        if rc != 0:
+            raise DpError("dp_trim_chunk_segments failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        return out[:int(n.value)]
+
+    def search(self, sel, middle_threshold=85):
+        """dp_trim_search over the chunks `sel` (ascending ids of the last scan) -> dict(recs int32 [n, 6] (TRIM_MID_REC_FIELDS, sorted
+        by adapter, chunk, ordinal), overflow uint32 [m, 2] (chunk, adapter), pairs, launches, index_ms, query_ms, kernel_ms)."""
+        s = np.ascontiguousarray(sel, dtype=np.uint32)
+        b = MidBatch()
+        rc = self.L.dp_trim_search(self.h, s.ctypes.data, len(s), middle_threshold, C.byref(b))
+        if rc != 0:
+            raise DpError("dp_trim_search failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        recs = np.ctypeslib.as_array(C.cast(b.recs, C.POINTER(C.c_int32)), shape=(b.n_recs, 6)).copy() if b.n_recs else np.zeros((0, 6), dtype=np.int32)
+        over = np.ctypeslib.as_array(b.overflow, shape=(b.n_overflow, 2)).copy() if b.n_overflow else np.zeros((0, 2), dtype=np.uint32)
+        return dict(recs=recs, overflow=over, pairs=b.n_pairs, launches=b.launches, index_ms=b.index_ms, query_ms=b.query_ms, kernel_ms=b.kernel_ms)
 
     def close(self):
         if getattr(self, "h", None):

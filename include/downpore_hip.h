@@ -593,6 +593,35 @@ DP_API int dp_trim_setup(int device, int k, const uint16_t* kmer_seed, uint32_t 
 DP_API int dp_trim_edges(dp_trim* t, const uint8_t* ends, uint32_t n_reads, int mode, int min_match, int threshold, dp_trim_rec* recs,
                          uint64_t* counts, uint8_t* enabled, double* times_ms);
 DP_API void dp_trim_release(dp_trim* t);
+/* ---- `trim`, middle stage (trim/trim.go:151-217, 515-530): front adapters in the centres of the edge-trimmed reads ----------------
+ * dp_trim_scan_chunks: NewSeedSequence (seeds/seeds.go:33-50) of n_chunks chunks given as ASCII bases, chunk c = bases[off[c] ..
+ * off[c + 1]) (the host cuts them from the trimmed reads: trim.go:165-184).  n_seeds_out[c] = the chunk's seeds; the segments
+ * [gap, seed, ..., gap] stay on the device until the handle's next scan.  times_ms[2] = upload, scan.  Needs k >= 4 (DP_ERR_ARG).
+ * dp_trim_chunk_segments: test hook - the segments of one chunk of the last scan (*n ints; copied when cap >= *n).
+ * dp_trim_search: AddSequence + IndexSequences over the chunks sel[0 .. n_sel) of the last scan (ascending ids), Matches(ad, 0.2) for
+ * every front adapter - the index build and query stage of a dp_ctx the handle owns, i.e. the same GetSharedIDs emulation
+ * dp_query_candidates exposes - and SeedSequence.Match(ad, adSet, chunkSet, ad.GetNumSeeds() / 5, k) for every (candidate chunk,
+ * front adapter) pair, one wave per pair.  Every match with GetBasesCovered's identity * 100 / ad.Len() >= mid_threshold gives one
+ * record; records come back sorted by adapter, chunk, ordinal (Match's return order).  A pair whose reduced chunk, chains or good
+ * list exceed the wave's working set is not matched on the device: it is listed in overflow (chunk, adapter per pair) for the caller's
+ * exact host Match.  The record buffer is sized from a guess and the launch repeated when it was too small (DP_TRIM_MID_REC_CAP
+ * forces the first capacity; launches counts them).  The arrays are the handle's, valid until its next search. */
+typedef struct {
+    int32_t adapter, chunk, ordinal, start_rel, covered, chain_len;
+} dp_trim_mid_rec;
+typedef struct {
+    uint32_t n_recs;
+    const dp_trim_mid_rec* recs;
+    uint32_t n_overflow;
+    const uint32_t* overflow; /* [2 * n_overflow]: chunk, front adapter */
+    uint32_t n_pairs;         /* candidate pairs: the sum of Matches' list lengths over the front adapters */
+    uint32_t launches;        /* launches of the matching kernel (> 1: the record buffer was too small) */
+    double index_ms, query_ms, kernel_ms;
+} dp_trim_mid_batch;
+DP_API int dp_trim_scan_chunks(dp_trim* t, const uint8_t* bases, const uint64_t* off, uint32_t n_chunks, uint32_t* n_seeds_out,
+                               double* times_ms);
+DP_API int dp_trim_chunk_segments(dp_trim* t, uint32_t chunk, int32_t* out, uint64_t cap, uint64_t* n);
+DP_API int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, int mid_threshold, dp_trim_mid_batch* out);
 DP_API const char* dp_trim_error(const dp_trim* t);
 
 #ifdef __cplusplus

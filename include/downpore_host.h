@@ -180,6 +180,36 @@ DPH_API int dph_trim_demultiplex(void* t, const char* dir);
 DPH_API int64_t dph_trim_index(void* front, void* back, int k, uint16_t* kmer_seed, int32_t* segs, int64_t seg_cap, uint64_t* seg_off,
                                int32_t* lengths, uint8_t* is_barcode, int32_t* pairs);
 
+/* ---- `downpore trim`, middle stage (trim/trim.go:151-256, 515-591; sequence/seqio.go:81-104, 302-323, 396-399) ----------------
+ * The search for front adapters in the middle of reads: every edge-trimmed read's centre is cut into chunks (dph_trim_chunk_plan:
+ * out[3 i ..] = start, end, is-remainder of the chunks of one served length, in the coordinates of the trimmed read; -1 when
+ * chunk_size <= 100, where the reference's loop does not end), the chunks are scanned for adapter seeds and matched against every
+ * front adapter, and findSplit's rules crop the front, crop the tail or split the read; the halves of split reads follow the file's
+ * reads in the output as <name>_(left) / <name>_(right).
+ * params[14] = the edge stage's eight, then middle (0: off, exactly the eight-parameter behaviour), chunk_size, middle_threshold,
+ * extra_middle_trim, discard_middle, flush_seeds (the reference's 300000000: a batch of chunks is searched after the read that takes
+ * the batch's seed count over it; after such a flush PrintStats reports the edge counts as 0, as the reference does).
+ * dph_trim_apply_mid: dph_trim_apply with the middle stage's device results supplied: seed_counts[n_chunks] = seeds of every planned
+ * chunk (reads in file order, chunks in position order) and mid_recs = six int32 per match that passed the identity test - front
+ * adapter, chunk (position in the plan), ordinal of the match within the pair, GetSeedOffset(MatchB[0]) - ad.GetSeedOffset(MatchA[0]),
+ * bases covered, chain length - in any order: they are applied batch by batch, adapter by adapter, in chunk and ordinal order.
+ * dph_trim_mid_ints: which = 0 the plan (read, start, end, remainder, seeds, indexed per chunk), 1 the splits (read, aEnd, bStart,
+ * kept halves: bit 0 left, bit 1 right), 2 the records applied; returns the number of int32.  dph_trim_extras: the halves' names,
+ * one per line.  dph_trim_mid_stats: out[12] = chunks, seeds, batches, candidate pairs, records applied, overflow pairs,
+ * out-of-range halves (a right half whose start is negative is skipped, counted and named in the log), upload / scan / index /
+ * query / kernel ms. */
+DPH_API void* dph_trim_apply_mid(void* reads, void* front, void* back, const int64_t* params, int n_params, const uint8_t* enabled,
+                                 const int32_t* recs, int64_t n_rec_reads, const uint64_t* counts, const int32_t* seed_counts,
+                                 int64_t n_chunks, const int32_t* mid_recs, int64_t n_mid_recs);
+DPH_API int64_t dph_trim_chunk_plan(int64_t length, int64_t chunk_size, int32_t* out, int64_t cap);
+DPH_API int64_t dph_trim_mid_ints(void* t, int which, int32_t* out, int64_t cap);
+DPH_API const char* dph_trim_extras(void* t, int64_t* n);
+DPH_API void dph_trim_mid_stats(void* t, double* out);
+/* test hook: the exact host Match that the (chunk, front adapter) pairs beyond the matching kernel's working set are given to, with
+ * the identity test; segments as [gap, seed, ..., gap]; out = six int32 per passing match; returns their number */
+DPH_API int64_t dph_hand_trim_match(const int32_t* chunk_segs, int n_chunk, const int32_t* adapter_segs, int n_adapter, int adapter_len,
+                                    int n_seeds, int k, int threshold, int adapter, int chunk, int32_t* out, int64_t cap);
+
 /* ---- test hooks (host logic without a GPU, counters) ------------------------------------------------------------------------ */
 DPH_API const char* dph_reads_dump(void* reads, int64_t* n);
 DPH_API void dph_values_from_counts(uint64_t* counts, int k, double* out);
