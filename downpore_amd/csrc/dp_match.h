@@ -1,5 +1,5 @@
 // Seed-space chaining on one wave, shared by the kernels that run SeedSequence.Match (seeds/sequence.go:361-394) on the device:
-// map_kernel (dp_map.hip) and trim_edge_kernel (dp_trim.hip).  Reduced (:85-123), dynamicMatch (:401-471), extendChain (:476-576)
+// map_kernel (dp_map.hip), trim_edge_kernel and trim_mid_kernel (dp_trim.hip).  Reduced (:85-123), dynamicMatch (:401-471), extendChain (:476-576)
 // and the set membership tests they use.  The working set type LT supplies q / t (reduced query / target segments), qIdx / tIdx,
 // headChain / headLen and good[M_GOOD]; chain storage is an HBM pool of M_CHAINS fixed-stride slots per wave (MChainPool).
 #pragma once

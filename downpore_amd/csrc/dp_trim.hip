@@ -42,10 +42,28 @@ struct TrimGeom {
     uint32_t table_bytes;  // bytes of the k-mer table copied into LDS (0: read through L2)
     uint32_t wave_words;   // 4-byte words of a wave's LDS slice
 };
-// a wave's slice: [set u64 x SW][eseg][t][q][headChain][tIdx][qIdx][headLen][codes]
-static __host__ __device__ inline uint32_t tr_wave_words(uint32_t SW, uint32_t qcap) {
-    return 2 * SW + (2 * TR_TCAP + 2) * 2 + (2 * qcap + 2) + (qcap + 2) + TR_TCAP / 2 + (qcap + 2) / 2 * 2 + TR_TCAP / 4 + 2;
+// The chaining working set for a target of tcap and a query of qcap reduced seeds, in 4-byte words from `base`: the one list of its
+// fields.  Returns the words it takes; with L it also points L's arrays at them.
+static __host__ __device__ inline uint32_t tr_chain_set(uint32_t tcap, uint32_t qcap, uint32_t* base = nullptr, TrimL* L = nullptr) {
+    uint32_t w = 0;
+#define TR_FIELD(name, words)                               \
+    do {                                                    \
+        if (L) L->name = (decltype(L->name))(base + w);     \
+        w += (words);                                       \
+    } while (0)
+    TR_FIELD(t, 2 * tcap + 2);
+    TR_FIELD(q, 2 * qcap + 2);
+    TR_FIELD(headChain, qcap + 2);
+    TR_FIELD(tIdx, tcap / 2);
+    TR_FIELD(qIdx, (qcap + 2) / 2);
+    TR_FIELD(headLen, (qcap + 2) / 2);
+#undef TR_FIELD
+    return w;
 }
+// a wave's slice in trim_edge_kernel: [set u64 x SW][eseg][the chaining working set][codes], and two words to spare
+#define TR_ESEG_WORDS (2 * TR_TCAP + 2)
+#define TR_CODE_WORDS (TR_TCAP / 4)
+static inline uint32_t tr_wave_words(uint32_t SW, uint32_t qcap) { return 2 * SW + TR_ESEG_WORDS + tr_chain_set(TR_TCAP, qcap) + TR_CODE_WORDS + 2; }
 
 // one thread per adapter: its seed-set row (row-major for Reduced's whitelist probes, transposed for the prefilter) and size
 __global__ void trim_rows_kernel(const int32_t* __restrict__ segs, const uint32_t* __restrict__ seg_off, uint32_t nA, uint32_t SW,
@@ -79,6 +97,50 @@ __device__ __forceinline__ int tr_seed_offset_from_end(const int32_t* seg, int n
     return o;
 }
 
+// NewSeedSequence's segment emission (seeds.go:33-50, sequence.go:308-324) for the 64 k-mer positions pb .. pb + 63: the lane's
+// position pb + lane holds seed `sid` (TR_NONE: none).  The seed that is the j-th of the sequence gets its [gap, seed] at seg[2 j]
+// when j < cap; nE (seeds so far) and lastPos (k-mer index of the last one, -1: none yet) advance.  POS: int for a read end, 64 bits
+// for a chunk of any length.
+template <typename POS>
+__device__ __forceinline__ void tr_scan_step(uint32_t sid, POS pb, int k, uint32_t& nE, POS& lastPos, int32_t* seg, uint32_t cap) {
+    const bool is = sid != TR_NONE;
+    const u64 m = __ballot(is);
+    if (is) {
+        const u64 mb = m & ((1ull << dp_lane()) - 1ull);
+        const POS prev = mb ? pb + 63 - __builtin_clzll(mb) : lastPos;
+        const uint32_t j = nE + (uint32_t)__popcll(mb);
+        if (j < cap) {
+            seg[2 * (size_t)j] = (int32_t)(pb + dp_lane() - (prev < 0 ? 0 : prev + k));  // kmerIndex - prev (sequence.go:316-318)
+            seg[2 * (size_t)j + 1] = (int32_t)sid;
+        }
+    }
+    nE += (uint32_t)__popcll(m);
+    if (m) lastPos = pb + 63 - __builtin_clzll(m);
+}
+
+// GetBasesCovered's countA (seeds/sequence.go:830-858) of a chain of len links: SeqA = the adapter, ca = its links into the reduced adapter
+__device__ __forceinline__ int tr_count_a(const int32_t* aSeg, const uint16_t* qIdx, const uint16_t* ca, int len, int k) {
+    int countA = len * k, prevA = qIdx[ca[0]];
+    for (int i = 1; i < len; i++) {
+        const int s = qIdx[ca[i]];
+        int d1 = aSeg[prevA * 2 + 2];
+        for (int j = prevA + 2; j <= s; j++) d1 += aSeg[j * 2] + k;
+        if (d1 < 0) countA += d1;
+        prevA = s;
+    }
+    return countA;
+}
+
+// wave gw's part of the chain pool (dp_match.h): M_CHAINS slots of qcap links in each of two arrays, and the chains' lengths
+__device__ __forceinline__ MChainPool tr_wave_pool(uint32_t gw, uint32_t qcap, uint16_t* poolA, uint16_t* poolB, uint16_t* poolLen, uint16_t** chainLen) {
+    MChainPool P;
+    P.stride = qcap;
+    P.a = poolA + (size_t)gw * M_CHAINS * qcap;
+    P.b = poolB + (size_t)gw * M_CHAINS * qcap;
+    *chainLen = poolLen + (size_t)gw * M_CHAINS;
+    return P;
+}
+
 // errbits: 1 reduced sequence beyond its array, 2 chain pool, 4 good-chain list (dp_match.h)
 __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
     const uint8_t* __restrict__ ends, uint32_t n_ends, TrimGeom G, const uint16_t* __restrict__ table, const int32_t* __restrict__ asegs,
@@ -102,40 +164,13 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
     uint32_t* base = tr_lds + G.table_bytes / 4 + (size_t)wv * G.wave_words;
     u64* set = (u64*)base;
     int32_t* eseg = (int32_t*)(base + 2 * SW);
-    uint8_t* codes;
+    uint32_t* chain = base + 2 * SW + TR_ESEG_WORDS;
     TrimL& L = sh[wv];
-    {
-        uint32_t* p = base + 2 * SW + (2 * TR_TCAP + 2);
-        int32_t* t = (int32_t*)p;
-        p += 2 * TR_TCAP + 2;
-        int32_t* q = (int32_t*)p;
-        p += 2 * qcap + 2;
-        int32_t* hc = (int32_t*)p;
-        p += qcap + 2;
-        uint16_t* tI = (uint16_t*)p;
-        p += TR_TCAP / 2;
-        uint16_t* qI = (uint16_t*)p;
-        p += (qcap + 2) / 2;
-        uint16_t* hl = (uint16_t*)p;
-        p += (qcap + 2) / 2;
-        codes = (uint8_t*)p;
-        if (lane == 0) {
-            L.t = t;
-            L.q = q;
-            L.headChain = hc;
-            L.tIdx = tI;
-            L.qIdx = qI;
-            L.headLen = hl;
-        }
-    }
+    uint8_t* codes = (uint8_t*)(chain + tr_chain_set(TR_TCAP, qcap, chain, lane == 0 ? &L : nullptr));
     __syncthreads();
     const uint32_t gw = blockIdx.x * TR_WAVES + wv, waves = gridDim.x * TR_WAVES;
-    MChainPool P;
-    P.stride = qcap;
-    P.a = poolA + (size_t)gw * M_CHAINS * qcap;
-    P.b = poolB + (size_t)gw * M_CHAINS * qcap;
-    uint16_t* chainLen = poolLen + (size_t)gw * M_CHAINS;
-    const u64 below = (1ull << lane) - 1ull;
+    uint16_t* chainLen;
+    const MChainPool P = tr_wave_pool(gw, qcap, poolA, poolB, poolLen, &chainLen);
     const int nK = TR_EDGE - k + 1;
     uint32_t err = 0;
     for (uint32_t e = gw; e < n_ends; e += waves) {
@@ -147,7 +182,8 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
         }
         for (uint32_t w = lane; w < SW; w += 64) set[w] = 0;
         __builtin_amdgcn_wave_barrier();
-        int nE = 0, lastPos = -1;  // seeds so far, k-mer index of the last one
+        uint32_t nE = 0;
+        int lastPos = -1;
         for (int pb = 0; pb < nK; pb += 64) {
             const int p = pb + lane;
             uint32_t sid = TR_NONE;
@@ -156,22 +192,12 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
                 for (int j = 0; j < k; j++) km = (km << 2) | codes[p + j];
                 sid = tab[km];
             }
-            const bool is = sid != TR_NONE;
-            if (is) atomicOr((uint32_t*)set + (sid >> 5), 1u << (sid & 31));
-            const u64 m = __ballot(is);
-            if (is) {
-                const u64 mb = m & below;
-                const int prev = mb ? pb + 63 - __builtin_clzll(mb) : lastPos;
-                const int j = nE + __popcll(mb);
-                eseg[2 * j] = p - (prev < 0 ? 0 : prev + k);  // kmerIndex - prev (sequence.go:316-318)
-                eseg[2 * j + 1] = (int32_t)sid;
-            }
-            nE += __popcll(m);
-            if (m) lastPos = pb + 63 - __builtin_clzll(m);
+            if (sid != TR_NONE) atomicOr((uint32_t*)set + (sid >> 5), 1u << (sid & 31));
+            tr_scan_step(sid, pb, k, nE, lastPos, eseg, TR_TCAP);
         }
         if (lane == 0) eseg[2 * nE] = TR_EDGE - (lastPos < 0 ? 0 : lastPos + k);  // len - prev (:323)
         __builtin_amdgcn_wave_barrier();
-        const int eN = 2 * nE + 1;
+        const int eN = 2 * (int)nE + 1;
         // ---- 2..4. the adapters of this end's side, in order
         const uint32_t side = e & 1u;
         const uint32_t a0 = side ? G.n_front : 0u, nSide = side ? G.n_back : G.n_front;
@@ -206,16 +232,7 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
                         if (len < (mode == 0 ? min_match : minHits)) continue;  // :374 / :342
                         const uint16_t* ca = P.A(ch);
                         const uint16_t* cb = P.B(ch);
-                        // GetBasesCovered's countA (:830-858): SeqA = the adapter
-                        int countA = len * k, prevA = L.qIdx[ca[0]];
-                        for (int i = 1; i < len; i++) {
-                            const int s = L.qIdx[ca[i]];
-                            int d1 = aSeg[prevA * 2 + 2];
-                            for (int j = prevA + 2; j <= s; j++) d1 += aSeg[j * 2] + k;
-                            if (d1 < 0) countA += d1;
-                            prevA = s;
-                        }
-                        const int identity = (countA * 100) / alen[ai];
+                        const int identity = (tr_count_a(aSeg, L.qIdx, ca, len, k) * 100) / alen[ai];
                         if (mode == 1) {
                             if (identity >= threshold) enabled[ai] = 1u;  // :344-346
                             continue;
@@ -272,6 +289,9 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the device buffers of a handle: the adapter index (set-up), the edge stage's batch, the middle stage's chunks, pairs and records
+enum TrBuf { TB_TABLE, TB_SEGS, TB_OFF, TB_LEN, TB_BAR, TB_SIZE, TB_ROWS, TB_ROWST, TB_COUNTS, TB_ENABLED, TB_POOL, TB_ERR, TB_ENDS, TB_RECS,
+             TB_CBASES, TB_COFF, TB_CCOUNT, TB_CSEGOFF, TB_PAIRS, TB_MRECS, TB_MOVER, TB_MCNT, TB_N };
 struct dp_trim {
     int device = 0, k = 0;
     uint32_t n_front = 0, n_back = 0, n_seeds = 0, SW = 0, qcap = 0, waves = 0;
@@ -279,9 +299,9 @@ struct dp_trim {
     TrimGeom G;
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void *d_table = nullptr, *d_segs = nullptr, *d_off = nullptr, *d_len = nullptr, *d_bar = nullptr, *d_size = nullptr, *d_rows = nullptr,
-         *d_rowsT = nullptr, *d_counts = nullptr, *d_enabled = nullptr, *d_pool = nullptr, *d_err = nullptr, *d_ends = nullptr, *d_recs = nullptr;
-    size_t ends_cap = 0;          // read ends the batch buffers hold
+    DevBuf buf[TB_N];             // the handle's device memory (tr_reserve)
+    template <typename T>
+    T* dev(TrBuf b) const { return (T*)buf[b].p; }
     std::vector<int32_t> pairs;   // the pair ids as uploaded (pairing is the host's rule, trim.go:471-485)
     std::string err;
     // ---- the middle stage (dp_trim_scan_chunks / dp_trim_search)
@@ -290,9 +310,6 @@ struct dp_trim {
     std::vector<int32_t> h_fsegs;      // the front adapters' segments and offsets as dp_query_candidates takes them
     std::vector<uint64_t> h_foff;
     std::vector<int32_t> h_alen;
-    void *d_cbases = nullptr, *d_coff = nullptr, *d_ccount = nullptr, *d_csegoff = nullptr, *d_pairs = nullptr, *d_mrecs = nullptr, *d_mover = nullptr,
-         *d_mcnt = nullptr;
-    size_t cbases_cap = 0, chunks_cap = 0, pairs_cap = 0, mrecs_cap = 0;
     uint32_t n_chunks = 0;
     std::vector<uint32_t> c_count;     // seeds per scanned chunk
     std::vector<uint64_t> c_segoff;    // [n_chunks + 1] offsets of the chunks' segments in the context's scan buffer
@@ -312,15 +329,33 @@ static int tr_fail(dp_trim* t, int code, const std::string& what, hipError_t e =
     return code;
 }
 
+// A buffer that holds `bytes`: one that is too small is freed and replaced by one of `grown` bytes (the caller's head room; 0: bytes)
+// and 64 of pad.  The contents do not survive.
+static hipError_t tr_reserve(dp_trim* t, TrBuf which, size_t bytes, size_t grown = 0) {
+    DevBuf& b = t->buf[which];
+    if (b.p && bytes <= b.cap) return hipSuccess;
+    if (b.p) dp_dev_free(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    grown = std::max(grown, bytes);
+    const hipError_t e = dp_dev_malloc(&b.p, grown + 64);
+    if (e == hipSuccess) b.cap = grown;
+    return e;
+}
+// elapsed ms between ev[i] and ev[i + 1], or 0
+static double tr_ms(const dp_trim* t, int i) {
+    float ms = 0;
+    return hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]) == hipSuccess ? ms : 0;
+}
+
 extern "C" const char* dp_trim_error(const dp_trim* t) { return t ? t->err.c_str() : g_trim_err.c_str(); }
 
 extern "C" void dp_trim_release(dp_trim* t) {
     if (!t) return;
     hipSetDevice(t->device);
     if (t->stream) hipStreamSynchronize(t->stream);
-    for (void* p : {t->d_table, t->d_segs, t->d_off, t->d_len, t->d_bar, t->d_size, t->d_rows, t->d_rowsT, t->d_counts, t->d_enabled, t->d_pool,
-                    t->d_err, t->d_ends, t->d_recs, t->d_cbases, t->d_coff, t->d_ccount, t->d_csegoff, t->d_pairs, t->d_mrecs, t->d_mover, t->d_mcnt})
-        if (p) dp_dev_free(p);
+    for (DevBuf& b : t->buf)
+        if (b.p) dp_dev_free(b.p);
     if (t->ctx) dp_ctx_destroy(t->ctx);
     for (hipEvent_t e : t->ev)
         if (e) hipEventDestroy(e);
@@ -400,27 +435,27 @@ extern "C" int dp_trim_setup(int device, int k, const uint16_t* kmer_seed, uint3
     TR_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     for (hipEvent_t& e : t->ev) TR_HIP(hipEventCreate(&e));
     const size_t nSegs = off32[nA];
-    TR_HIP(dp_dev_malloc(&t->d_table, nK * 2 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_segs, nSegs * 4 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_off, ((size_t)nA + 1) * 4 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_len, (size_t)nA * 4 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_bar, (size_t)nA + 64));
-    TR_HIP(dp_dev_malloc(&t->d_size, (size_t)nA * 4 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_rows, (size_t)nA * t->SW * 8 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_rowsT, (size_t)nA * t->SW * 8 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_counts, (size_t)nA * 8 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_enabled, (size_t)nA * 4 + 64));
-    TR_HIP(dp_dev_malloc(&t->d_err, 64));
-    TR_HIP(hipMemcpyAsync(t->d_table, kmer_seed, nK * 2, hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipMemcpyAsync(t->d_segs, segs, nSegs * 4, hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipMemcpyAsync(t->d_off, off32.data(), ((size_t)nA + 1) * 4, hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipMemcpyAsync(t->d_len, lengths, (size_t)nA * 4, hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipMemcpyAsync(t->d_bar, is_barcode, (size_t)nA, hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipMemsetAsync(t->d_rows, 0, (size_t)nA * t->SW * 8, t->stream));
-    TR_HIP(hipMemsetAsync(t->d_counts, 0, (size_t)nA * 8, t->stream));
-    TR_HIP(hipMemsetAsync(t->d_enabled, 0, (size_t)nA * 4, t->stream));
-    hipLaunchKernelGGL(trim_rows_kernel, dim3((nA + 63) / 64), dim3(64), 0, t->stream, (const int32_t*)t->d_segs, (const uint32_t*)t->d_off, nA, t->SW,
-                       (u64*)t->d_rows, (u64*)t->d_rowsT, (int32_t*)t->d_size);
+    TR_HIP(tr_reserve(t, TB_TABLE, nK * 2));
+    TR_HIP(tr_reserve(t, TB_SEGS, nSegs * 4));
+    TR_HIP(tr_reserve(t, TB_OFF, ((size_t)nA + 1) * 4));
+    TR_HIP(tr_reserve(t, TB_LEN, (size_t)nA * 4));
+    TR_HIP(tr_reserve(t, TB_BAR, (size_t)nA));
+    TR_HIP(tr_reserve(t, TB_SIZE, (size_t)nA * 4));
+    TR_HIP(tr_reserve(t, TB_ROWS, (size_t)nA * t->SW * 8));
+    TR_HIP(tr_reserve(t, TB_ROWST, (size_t)nA * t->SW * 8));
+    TR_HIP(tr_reserve(t, TB_COUNTS, (size_t)nA * 8));
+    TR_HIP(tr_reserve(t, TB_ENABLED, (size_t)nA * 4));
+    TR_HIP(tr_reserve(t, TB_ERR, 64));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_TABLE].p, kmer_seed, nK * 2, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_SEGS].p, segs, nSegs * 4, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_OFF].p, off32.data(), ((size_t)nA + 1) * 4, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_LEN].p, lengths, (size_t)nA * 4, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_BAR].p, is_barcode, (size_t)nA, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipMemsetAsync(t->buf[TB_ROWS].p, 0, (size_t)nA * t->SW * 8, t->stream));
+    TR_HIP(hipMemsetAsync(t->buf[TB_COUNTS].p, 0, (size_t)nA * 8, t->stream));
+    TR_HIP(hipMemsetAsync(t->buf[TB_ENABLED].p, 0, (size_t)nA * 4, t->stream));
+    hipLaunchKernelGGL(trim_rows_kernel, dim3((nA + 63) / 64), dim3(64), 0, t->stream, t->dev<const int32_t>(TB_SEGS), t->dev<const uint32_t>(TB_OFF), nA, t->SW,
+                       t->dev<u64>(TB_ROWS), t->dev<u64>(TB_ROWST), t->dev<int32_t>(TB_SIZE));
     TR_HIP(hipGetLastError());
     // the edge kernel's LDS: the table (k <= 6) + four wave slices sized from the longest adapter
     t->G.k = k;
@@ -437,7 +472,7 @@ extern "C" int dp_trim_setup(int device, int k, const uint16_t* kmer_seed, uint3
     size_t waves = std::min<size_t>(2048, ((size_t)1 << 30) / per_wave);
     waves = std::max<size_t>(TR_WAVES, waves / TR_WAVES * TR_WAVES);
     t->waves = (uint32_t)waves;
-    TR_HIP(dp_dev_malloc(&t->d_pool, waves * per_wave + 64));
+    TR_HIP(tr_reserve(t, TB_POOL, waves * per_wave));
     TR_HIP(hipStreamSynchronize(t->stream));
     *out = t;
     return DP_OK;
@@ -455,47 +490,37 @@ extern "C" int dp_trim_edges(dp_trim* t, const uint8_t* ends, uint32_t n_reads, 
     const uint32_t nA = t->n_front + t->n_back, n_ends = 2 * n_reads;
     if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0;
     if (n_ends) {
-        if (n_ends > t->ends_cap) {
-            if (t->d_ends) dp_dev_free(t->d_ends);
-            if (t->d_recs) dp_dev_free(t->d_recs);
-            t->d_ends = t->d_recs = nullptr;
-            t->ends_cap = 0;
-            const size_t cap = std::max<size_t>(n_ends, 1u << 16);
-            TR_HIP(dp_dev_malloc(&t->d_ends, cap * TR_EDGE + 64));
-            TR_HIP(dp_dev_malloc(&t->d_recs, cap * sizeof(dp_trim_rec) + 64));
-            t->ends_cap = cap;
-        }
-        TR_HIP(hipMemsetAsync(t->d_err, 0, 64, t->stream));
+        const size_t cap = std::max<size_t>(n_ends, 1u << 16);  // read ends the batch buffers hold once they grow
+        TR_HIP(tr_reserve(t, TB_ENDS, (size_t)n_ends * TR_EDGE, cap * TR_EDGE));
+        TR_HIP(tr_reserve(t, TB_RECS, (size_t)n_ends * sizeof(dp_trim_rec), cap * sizeof(dp_trim_rec)));
+        TR_HIP(hipMemsetAsync(t->buf[TB_ERR].p, 0, 64, t->stream));
         TR_HIP(hipEventRecord(t->ev[0], t->stream));
-        TR_HIP(hipMemcpyAsync(t->d_ends, ends, (size_t)n_ends * TR_EDGE, hipMemcpyHostToDevice, t->stream));
+        TR_HIP(hipMemcpyAsync(t->buf[TB_ENDS].p, ends, (size_t)n_ends * TR_EDGE, hipMemcpyHostToDevice, t->stream));
         TR_HIP(hipEventRecord(t->ev[1], t->stream));
         const uint32_t blocks = std::min<uint32_t>(t->waves / TR_WAVES, (n_ends + TR_WAVES - 1) / TR_WAVES);
         const size_t poolElems = (size_t)t->waves * M_CHAINS * t->qcap;
-        uint16_t* poolA = (uint16_t*)t->d_pool;
-        hipLaunchKernelGGL(trim_edge_kernel, dim3(blocks), dim3(64 * TR_WAVES), t->lds_bytes, t->stream, (const uint8_t*)t->d_ends, n_ends, t->G,
-                           (const uint16_t*)t->d_table, (const int32_t*)t->d_segs, (const uint32_t*)t->d_off, (const int32_t*)t->d_len,
-                           (const uint8_t*)t->d_bar, (const int32_t*)t->d_size, (const u64*)t->d_rows, (const u64*)t->d_rowsT, mode, min_match,
-                           threshold, (dp_trim_rec*)t->d_recs, (unsigned long long*)t->d_counts, (uint32_t*)t->d_enabled, poolA, poolA + poolElems,
-                           poolA + 2 * poolElems, (uint32_t*)t->d_err);
+        uint16_t* poolA = t->dev<uint16_t>(TB_POOL);
+        hipLaunchKernelGGL(trim_edge_kernel, dim3(blocks), dim3(64 * TR_WAVES), t->lds_bytes, t->stream, t->dev<const uint8_t>(TB_ENDS), n_ends, t->G,
+                           t->dev<const uint16_t>(TB_TABLE), t->dev<const int32_t>(TB_SEGS), t->dev<const uint32_t>(TB_OFF), t->dev<const int32_t>(TB_LEN),
+                           t->dev<const uint8_t>(TB_BAR), t->dev<const int32_t>(TB_SIZE), t->dev<const u64>(TB_ROWS), t->dev<const u64>(TB_ROWST), mode, min_match,
+                           threshold, t->dev<dp_trim_rec>(TB_RECS), t->dev<unsigned long long>(TB_COUNTS), t->dev<uint32_t>(TB_ENABLED), poolA, poolA + poolElems,
+                           poolA + 2 * poolElems, t->dev<uint32_t>(TB_ERR));
         TR_HIP(hipGetLastError());
         TR_HIP(hipEventRecord(t->ev[2], t->stream));
         uint32_t errbits = 0;
-        if (mode == DP_TRIM_MODE_TRIM) TR_HIP(hipMemcpyAsync(recs, t->d_recs, (size_t)n_ends * sizeof(dp_trim_rec), hipMemcpyDeviceToHost, t->stream));
-        TR_HIP(hipMemcpyAsync(&errbits, t->d_err, 4, hipMemcpyDeviceToHost, t->stream));
+        if (mode == DP_TRIM_MODE_TRIM) TR_HIP(hipMemcpyAsync(recs, t->buf[TB_RECS].p, (size_t)n_ends * sizeof(dp_trim_rec), hipMemcpyDeviceToHost, t->stream));
+        TR_HIP(hipMemcpyAsync(&errbits, t->buf[TB_ERR].p, 4, hipMemcpyDeviceToHost, t->stream));
         TR_HIP(hipEventRecord(t->ev[3], t->stream));
         TR_HIP(hipStreamSynchronize(t->stream));
         if (times_ms)
-            for (int i = 0; i < 3; i++) {
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]) == hipSuccess) times_ms[i] = ms;
-            }
+            for (int i = 0; i < 3; i++) times_ms[i] = tr_ms(t, i);
         if (errbits) return tr_fail(t, DP_ERR_CAPACITY, "dp_trim_edges: chaining exceeded a device capacity (bits " + std::to_string(errbits) +
                                                             ": 1 reduced sequence, 2 chain pool, 4 good-chain list)");
     }
-    if (counts) TR_HIP(hipMemcpy(counts, t->d_counts, (size_t)nA * 8, hipMemcpyDeviceToHost));
+    if (counts) TR_HIP(hipMemcpy(counts, t->buf[TB_COUNTS].p, (size_t)nA * 8, hipMemcpyDeviceToHost));
     if (enabled) {
         std::vector<uint32_t> en(nA);
-        TR_HIP(hipMemcpy(en.data(), t->d_enabled, (size_t)nA * 4, hipMemcpyDeviceToHost));
+        TR_HIP(hipMemcpy(en.data(), t->buf[TB_ENABLED].p, (size_t)nA * 4, hipMemcpyDeviceToHost));
         for (uint32_t a = 0; a < nA; a++) enabled[a] = en[a] ? 1 : 0;
     }
     return DP_OK;
@@ -517,7 +542,6 @@ __global__ __launch_bounds__(256) void chunk_scan_kernel(const uint8_t* __restri
                                                          const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs) {
     const int lane = dp_lane();
     const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), waves = gridDim.x * (blockDim.x >> 6);
-    const u64 below = (1ull << lane) - 1ull;
     for (uint32_t c = gw; c < n_chunks; c += waves) {
         const uint8_t* src = bases + off[c];
         const long long len = (long long)(off[c + 1] - off[c]);
@@ -537,19 +561,8 @@ __global__ __launch_bounds__(256) void chunk_scan_kernel(const uint8_t* __restri
                 }
                 sid = table[km];
             }
-            const bool is = sid != TR_NONE;
-            const u64 m = __ballot(is);
-            if (WRITE && is) {
-                const u64 mb = m & below;
-                const long long prev = mb ? pb + 63 - __builtin_clzll(mb) : lastPos;
-                const uint32_t j = nE + (uint32_t)__popcll(mb);
-                if (j < cap) {
-                    seg[2 * (size_t)j] = (int32_t)(p - (prev < 0 ? 0 : prev + k));  // kmerIndex - prev (sequence.go:316-318)
-                    seg[2 * (size_t)j + 1] = (int32_t)sid;
-                }
-            }
-            nE += (uint32_t)__popcll(m);
-            if (m) lastPos = pb + 63 - __builtin_clzll(m);
+            if (WRITE) tr_scan_step(sid, pb, k, nE, lastPos, seg, cap);
+            else nE += (uint32_t)__popcll(__ballot(sid != TR_NONE));  // the counting pass
         }
         if (lane == 0) {
             if (WRITE) {
@@ -566,9 +579,6 @@ struct MidGeom {
     uint32_t SW, SWc, qcap, wave_words, n_pairs, rec_cap;
     int threshold;
 };
-static __host__ __device__ inline uint32_t mid_wave_words(uint32_t qcap) {
-    return (2 * MID_TCAP + 2) + (2 * qcap + 2) + (qcap + 2) + MID_TCAP / 2 + (qcap + 2) / 2 * 2 + 2;
-}
 
 // One wave per (chunk, front adapter) pair, pairs in chunk-major order so that the waves of a workgroup read one chunk's segments
 // together.  cnt[0] = records appended, cnt[1] = pairs listed for the host.
@@ -584,35 +594,11 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_mid_kernel(
     const int k = G.k;
     const uint32_t qcap = G.qcap;
     TrimL& L = sh[wv];
-    {
-        uint32_t* p = tr_lds + (size_t)wv * G.wave_words;
-        int32_t* t = (int32_t*)p;
-        p += 2 * MID_TCAP + 2;
-        int32_t* q = (int32_t*)p;
-        p += 2 * qcap + 2;
-        int32_t* hc = (int32_t*)p;
-        p += qcap + 2;
-        uint16_t* tI = (uint16_t*)p;
-        p += MID_TCAP / 2;
-        uint16_t* qI = (uint16_t*)p;
-        p += (qcap + 2) / 2;
-        uint16_t* hl = (uint16_t*)p;
-        if (lane == 0) {
-            L.t = t;
-            L.q = q;
-            L.headChain = hc;
-            L.tIdx = tI;
-            L.qIdx = qI;
-            L.headLen = hl;
-        }
-    }
+    tr_chain_set(MID_TCAP, qcap, tr_lds + (size_t)wv * G.wave_words, lane == 0 ? &L : nullptr);
     __syncthreads();
     const uint32_t gw = blockIdx.x * TR_WAVES + wv, waves = gridDim.x * TR_WAVES;
-    MChainPool P;
-    P.stride = qcap;
-    P.a = poolA + (size_t)gw * M_CHAINS * qcap;
-    P.b = poolB + (size_t)gw * M_CHAINS * qcap;
-    uint16_t* chainLen = poolLen + (size_t)gw * M_CHAINS;
+    uint16_t* chainLen;
+    const MChainPool P = tr_wave_pool(gw, qcap, poolA, poolB, poolLen, &chainLen);
     for (uint32_t pi = gw; pi < G.n_pairs; pi += waves) {
         const uint2 pr = pairs[pi];  // x = indexed chunk, y = front adapter
         const dp_seq_ref ref = refs[pr.x];
@@ -640,15 +626,7 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_mid_kernel(
                     const int len = chainLen[ch];
                     const uint16_t* ca = P.A(ch);
                     const uint16_t* cb = P.B(ch);
-                    // GetBasesCovered's countA (:830-858): SeqA = the adapter
-                    int countA = len * k, prevA = L.qIdx[ca[0]];
-                    for (int i = 1; i < len; i++) {
-                        const int s = L.qIdx[ca[i]];
-                        int d1 = aSeg[prevA * 2 + 2];
-                        for (int j = prevA + 2; j <= s; j++) d1 += aSeg[j * 2] + k;
-                        if (d1 < 0) countA += d1;
-                        prevA = s;
-                    }
+                    const int countA = tr_count_a(aSeg, L.qIdx, ca, len, k);
                     if ((countA * 100) / alen[ai] < G.threshold) continue;  // trim.go:528
                     const uint32_t at = atomicAdd(&cnt[0], 1u);
                     if (at < G.rec_cap) {
@@ -701,53 +679,36 @@ extern "C" int dp_trim_scan_chunks(dp_trim* t, const uint8_t* bases, const uint6
     if (!n_chunks) return DP_OK;
     hipStream_t st = t->ctx->stream;
     const size_t nb = off[n_chunks] - off[0];
-    if (nb > t->cbases_cap) {
-        if (t->d_cbases) dp_dev_free(t->d_cbases);
-        t->d_cbases = nullptr;
-        t->cbases_cap = 0;
-        TR_HIP(dp_dev_malloc(&t->d_cbases, nb + nb / 4 + 64));
-        t->cbases_cap = nb + nb / 4;
-    }
-    if (n_chunks > t->chunks_cap) {
-        for (void** p : {&t->d_coff, &t->d_ccount, &t->d_csegoff}) {
-            if (*p) dp_dev_free(*p);
-            *p = nullptr;
-        }
-        t->chunks_cap = 0;
-        const size_t cap = (size_t)n_chunks + n_chunks / 4 + 1024;
-        TR_HIP(dp_dev_malloc(&t->d_coff, (cap + 1) * 8 + 64));
-        TR_HIP(dp_dev_malloc(&t->d_ccount, cap * 4 + 64));
-        TR_HIP(dp_dev_malloc(&t->d_csegoff, (cap + 1) * 8 + 64));
-        t->chunks_cap = cap;
-    }
+    TR_HIP(tr_reserve(t, TB_CBASES, nb, nb + nb / 4));
+    const size_t cap = (size_t)n_chunks + n_chunks / 4 + 1024;  // chunks the three per-chunk arrays hold once they grow
+    TR_HIP(tr_reserve(t, TB_COFF, ((size_t)n_chunks + 1) * 8, (cap + 1) * 8));
+    TR_HIP(tr_reserve(t, TB_CCOUNT, (size_t)n_chunks * 4, cap * 4));
+    TR_HIP(tr_reserve(t, TB_CSEGOFF, ((size_t)n_chunks + 1) * 8, (cap + 1) * 8));
     std::vector<uint64_t> rel((size_t)n_chunks + 1);
     for (uint32_t c = 0; c <= n_chunks; c++) rel[c] = off[c] - off[0];
     TR_HIP(hipEventRecord(t->ev[0], st));
-    TR_HIP(hipMemcpyAsync(t->d_cbases, bases + off[0], nb, hipMemcpyHostToDevice, st));
-    TR_HIP(hipMemcpyAsync(t->d_coff, rel.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_CBASES].p, bases + off[0], nb, hipMemcpyHostToDevice, st));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_COFF].p, rel.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
     TR_HIP(hipEventRecord(t->ev[1], st));
     const uint32_t blocks = std::min<uint32_t>(4096, (n_chunks + 3) / 4);
-    hipLaunchKernelGGL(chunk_scan_kernel<false>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)t->d_cbases, (const uint64_t*)t->d_coff, n_chunks, t->k,
-                       (const uint16_t*)t->d_table, (uint32_t*)t->d_ccount, (const uint64_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(chunk_scan_kernel<false>, dim3(blocks), dim3(256), 0, st, t->dev<const uint8_t>(TB_CBASES), t->dev<const uint64_t>(TB_COFF), n_chunks, t->k,
+                       t->dev<const uint16_t>(TB_TABLE), t->dev<uint32_t>(TB_CCOUNT), (const uint64_t*)nullptr, (int32_t*)nullptr);
     TR_HIP(hipGetLastError());
-    TR_HIP(hipMemcpyAsync(t->c_count.data(), t->d_ccount, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, st));
+    TR_HIP(hipMemcpyAsync(t->c_count.data(), t->buf[TB_CCOUNT].p, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, st));
     TR_HIP(hipStreamSynchronize(st));
     for (uint32_t c = 0; c < n_chunks; c++) t->c_segoff[c + 1] = t->c_segoff[c] + 2ull * t->c_count[c] + 1;
     const uint64_t total = t->c_segoff[n_chunks];
     if (dev_reserve(t->ctx, t->ctx->d_segs, (size_t)total * 4 + 64)) return tr_fail(t, DP_ERR_HIP, std::string("dp_trim_scan_chunks: ") + dp_last_error(t->ctx));
-    TR_HIP(hipMemcpyAsync(t->d_csegoff, t->c_segoff.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(chunk_scan_kernel<true>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)t->d_cbases, (const uint64_t*)t->d_coff, n_chunks, t->k,
-                       (const uint16_t*)t->d_table, (uint32_t*)t->d_ccount, (const uint64_t*)t->d_csegoff, (int32_t*)t->ctx->d_segs.p);
+    TR_HIP(hipMemcpyAsync(t->buf[TB_CSEGOFF].p, t->c_segoff.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(chunk_scan_kernel<true>, dim3(blocks), dim3(256), 0, st, t->dev<const uint8_t>(TB_CBASES), t->dev<const uint64_t>(TB_COFF), n_chunks, t->k,
+                       t->dev<const uint16_t>(TB_TABLE), t->dev<uint32_t>(TB_CCOUNT), t->dev<const uint64_t>(TB_CSEGOFF), (int32_t*)t->ctx->d_segs.p);
     TR_HIP(hipGetLastError());
     TR_HIP(hipEventRecord(t->ev[2], st));
     TR_HIP(hipStreamSynchronize(st));
     t->ctx->n_segs = total;
     t->n_chunks = n_chunks;
     if (times_ms)
-        for (int i = 0; i < 2; i++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]) == hipSuccess) times_ms[i] = ms;
-        }
+        for (int i = 0; i < 2; i++) times_ms[i] = tr_ms(t, i);
     if (n_seeds_out) memcpy(n_seeds_out, t->c_count.data(), (size_t)n_chunks * 4);
     return DP_OK;
 }
@@ -802,25 +763,17 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
         std::vector<uint2> pairs(n_pairs);
         for (uint32_t a = 0; a < t->n_front; a++)
             for (uint64_t i = cb.cand_off[a]; i < cb.cand_off[a + 1]; i++) pairs[start[cb.cand[i]]++] = make_uint2(cb.cand[i], a);
-        if (n_pairs > t->pairs_cap) {
-            for (void** p : {&t->d_pairs, &t->d_mover}) {
-                if (*p) dp_dev_free(*p);
-                *p = nullptr;
-            }
-            t->pairs_cap = 0;
-            const size_t cap = (size_t)n_pairs + n_pairs / 4 + 1024;
-            TR_HIP(dp_dev_malloc(&t->d_pairs, cap * 8 + 64));
-            TR_HIP(dp_dev_malloc(&t->d_mover, cap * 4 + 64));
-            t->pairs_cap = cap;
-        }
-        if (!t->d_mcnt) TR_HIP(dp_dev_malloc(&t->d_mcnt, 64));
-        TR_HIP(hipMemcpyAsync(t->d_pairs, pairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
+        const size_t cap = (size_t)n_pairs + n_pairs / 4 + 1024;  // pairs the list and the overflow list hold once they grow
+        TR_HIP(tr_reserve(t, TB_PAIRS, (size_t)n_pairs * 8, cap * 8));
+        TR_HIP(tr_reserve(t, TB_MOVER, (size_t)n_pairs * 4, cap * 4));
+        TR_HIP(tr_reserve(t, TB_MCNT, 64));
+        TR_HIP(hipMemcpyAsync(t->buf[TB_PAIRS].p, pairs.data(), (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
         MidGeom G;
         G.k = t->k;
         G.SW = t->SW;
         G.SWc = t->ctx->SW;
         G.qcap = t->qcap;
-        G.wave_words = (mid_wave_words(t->qcap) + 1u) & ~1u;
+        G.wave_words = (tr_chain_set(MID_TCAP, t->qcap) + 2 + 1u) & ~1u;  // (a wave's slice: the working set and two words to spare)
         G.n_pairs = n_pairs;
         G.threshold = mid_threshold;
         const size_t lds = (size_t)TR_WAVES * G.wave_words * 4;
@@ -830,25 +783,19 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
         if (const char* e = getenv("DP_TRIM_MID_REC_CAP")) rec_cap = std::max<long>(1, atol(e));
         const uint32_t blocks = std::min<uint32_t>(t->waves / TR_WAVES, (n_pairs + TR_WAVES - 1) / TR_WAVES);
         const size_t poolElems = (size_t)t->waves * M_CHAINS * t->qcap;
-        uint16_t* poolA = (uint16_t*)t->d_pool;
+        uint16_t* poolA = t->dev<uint16_t>(TB_POOL);
         TR_HIP(hipEventRecord(t->ev[2], st));
         for (;;) {
-            if (rec_cap > t->mrecs_cap) {
-                if (t->d_mrecs) dp_dev_free(t->d_mrecs);
-                t->d_mrecs = nullptr;
-                t->mrecs_cap = 0;
-                TR_HIP(dp_dev_malloc(&t->d_mrecs, rec_cap * sizeof(dp_trim_mid_rec) + 64));
-                t->mrecs_cap = rec_cap;
-            }
+            TR_HIP(tr_reserve(t, TB_MRECS, rec_cap * sizeof(dp_trim_mid_rec)));
             G.rec_cap = (uint32_t)std::min<size_t>(rec_cap, 0x7fffffffu);
-            TR_HIP(hipMemsetAsync(t->d_mcnt, 0, 64, st));
-            hipLaunchKernelGGL(trim_mid_kernel, dim3(blocks), dim3(64 * TR_WAVES), lds, st, (const uint2*)t->d_pairs, G, (const dp_seq_ref*)t->ctx->d_seqrefs.p,
-                               (const int32_t*)t->ctx->d_segs.p, (const u64*)t->ctx->d_seedsets.p, (const int32_t*)t->d_segs, (const uint32_t*)t->d_off,
-                               (const int32_t*)t->d_len, (const u64*)t->d_rows, (dp_trim_mid_rec*)t->d_mrecs, (uint32_t*)t->d_mover, (uint32_t*)t->d_mcnt, poolA,
+            TR_HIP(hipMemsetAsync(t->buf[TB_MCNT].p, 0, 64, st));
+            hipLaunchKernelGGL(trim_mid_kernel, dim3(blocks), dim3(64 * TR_WAVES), lds, st, t->dev<const uint2>(TB_PAIRS), G, (const dp_seq_ref*)t->ctx->d_seqrefs.p,
+                               (const int32_t*)t->ctx->d_segs.p, (const u64*)t->ctx->d_seedsets.p, t->dev<const int32_t>(TB_SEGS), t->dev<const uint32_t>(TB_OFF),
+                               t->dev<const int32_t>(TB_LEN), t->dev<const u64>(TB_ROWS), t->dev<dp_trim_mid_rec>(TB_MRECS), t->dev<uint32_t>(TB_MOVER), t->dev<uint32_t>(TB_MCNT), poolA,
                                poolA + poolElems, poolA + 2 * poolElems);
             TR_HIP(hipGetLastError());
             uint32_t cnt[2] = {0, 0};
-            TR_HIP(hipMemcpyAsync(cnt, t->d_mcnt, 8, hipMemcpyDeviceToHost, st));
+            TR_HIP(hipMemcpyAsync(cnt, t->buf[TB_MCNT].p, 8, hipMemcpyDeviceToHost, st));
             TR_HIP(hipStreamSynchronize(st));
             out->launches++;
             if (cnt[0] > G.rec_cap) {
@@ -857,8 +804,8 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
             }
             t->m_recs.resize(cnt[0]);
             t->m_over.resize(std::min<uint32_t>(cnt[1], n_pairs));
-            if (cnt[0]) TR_HIP(hipMemcpyAsync(t->m_recs.data(), t->d_mrecs, (size_t)cnt[0] * sizeof(dp_trim_mid_rec), hipMemcpyDeviceToHost, st));
-            if (!t->m_over.empty()) TR_HIP(hipMemcpyAsync(t->m_over.data(), t->d_mover, t->m_over.size() * 4, hipMemcpyDeviceToHost, st));
+            if (cnt[0]) TR_HIP(hipMemcpyAsync(t->m_recs.data(), t->buf[TB_MRECS].p, (size_t)cnt[0] * sizeof(dp_trim_mid_rec), hipMemcpyDeviceToHost, st));
+            if (!t->m_over.empty()) TR_HIP(hipMemcpyAsync(t->m_over.data(), t->buf[TB_MOVER].p, t->m_over.size() * 4, hipMemcpyDeviceToHost, st));
             TR_HIP(hipEventRecord(t->ev[3], st));
             TR_HIP(hipStreamSynchronize(st));
             break;
@@ -881,9 +828,8 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
     out->recs = t->m_recs.data();
     out->n_overflow = (uint32_t)(t->m_over.size() / 2);
     out->overflow = t->m_over.data();
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess) out->index_ms = ms;
-    if (hipEventElapsedTime(&ms, t->ev[1], t->ev[2]) == hipSuccess) out->query_ms = ms;
-    if (n_pairs && hipEventElapsedTime(&ms, t->ev[2], t->ev[3]) == hipSuccess) out->kernel_ms = ms;
+    out->index_ms = tr_ms(t, 0);
+    out->query_ms = tr_ms(t, 1);
+    if (n_pairs) out->kernel_ms = tr_ms(t, 2);
     return DP_OK;
 }

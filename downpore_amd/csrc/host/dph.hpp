@@ -833,17 +833,16 @@ void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int
 bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error);
 // the whole edge stage on HIP device `device`; reads receives ignore / frontTrim / backTrim.  0, or < 0 with `error` (-2: no read of 200 bases)
 int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error);
-int applyTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-              size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error);
-// the same with the middle stage's device results supplied too (p.middle): seedCounts[planned chunks] and midRecs, in any order
+// the middle stage's matching results: seedCounts[planned chunks] and the matches, in any order
 struct TrimMidInput {
     const int32_t* seedCounts = nullptr;
     size_t nChunks = 0;
     const TrimMidRec* recs = nullptr;
     size_t nRecs = 0;
 };
-int applyTrimMid(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-                 size_t nRecReads, const uint64_t* counts, const TrimMidInput& mid, TrimResult& res, std::string& error);
+// the device-free half from caller-supplied edge records; mid (may be null) adds the middle stage's sequential half when p.middle
+int applyTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+              size_t nRecReads, const uint64_t* counts, const TrimMidInput* mid, TrimResult& res, std::string& error);
 void trimWrite(const ReadSet& reads, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out);
 int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::string& dir, std::string& error);  // files written, or < 0
 

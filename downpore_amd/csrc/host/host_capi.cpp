@@ -1030,8 +1030,8 @@ extern "C" void* dph_trim_apply(void* readsH, void* frontH, void* backH, const i
     TrimH* h = new TrimH();
     h->reads = &((ReadsH*)readsH)->set;
     std::string error;
-    if (applyTrim(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, h->res,
-                  error) != 0) {
+    if (applyTrim(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, nullptr,
+                  h->res, error) != 0) {
         g_err = error;
         delete h;
         return nullptr;
@@ -1058,8 +1058,8 @@ extern "C" void* dph_trim_apply_mid(void* readsH, void* frontH, void* backH, con
     mid.nChunks = (size_t)n_chunks;
     mid.recs = (const TrimMidRec*)mid_recs;
     mid.nRecs = (size_t)n_mid_recs;
-    if (applyTrimMid(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, mid,
-                     h->res, error) != 0) {
+    if (applyTrim(*h->reads, ((ReadsH*)frontH)->set, ((ReadsH*)backH)->set, p, enabled, (const dp_trim_rec*)recs, (size_t)n_rec_reads, counts, &mid,
+                  h->res, error) != 0) {
         g_err = error;
         delete h;
         return nullptr;

@@ -11,91 +11,23 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <functional>
-
 #include "host_util.hpp"
 
 namespace dph {
 
 namespace {
-const int kEdgeSize = 150;  // trim.go:432,453
+const int kEdgeSize = 150;        // edgeSize: the bases of a read end that are searched (trim.go:432,453)
+const int kMinEdgeLength = 200;   // a shorter read keeps its ends (:434 / :455)
+const i64 kLongestAdapter = 100;  // longestAdapter (:153)
+const i64 kMinSeeds = 4;          // minSeeds: a chunk with fewer is not indexed (:155)
+const i64 kMinSeqLength = 500;    // minSeqLength of findSplit (:517)
 
 void logLine(std::string& err, const std::string& s) {  // log.Println without the timestamp (the CLI adds it)
     err += s;
     err += '\n';
 }
 bool isBarcodeName(const std::string& n) { return n.compare(0, 7, "Barcode") == 0; }  // strings.HasPrefix(name, "Barcode") :377
-}  // namespace
 
-// setupIndex (trim.go:57-99): NewAllSeedSequence of every front, then every back adapter (seeds/seeds.go:204-237) - seed ids in order
-// of first occurrence - and pairsFront / pairsBack by name
-bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error) {
-    if (k < 3 || k > 8) {
-        error = "trim: k = " + std::to_string(k) + " is outside 3..8 (ShortKmers holds a k-mer in 16 bits)";
-        return false;
-    }
-    ix = TrimIndex();
-    ix.k = k;
-    ix.nFront = (uint32_t)front.size();
-    ix.nBack = (uint32_t)back.size();
-    ix.kmerSeed.assign((size_t)1 << (2 * k), (uint16_t)0xffff);
-    ix.segOff.push_back(0);
-    const uint32_t mask = (uint32_t)(((size_t)1 << (2 * k)) - 1);
-    for (const ReadSet* set : {&front, &back}) {
-        for (size_t a = 0; a < set->size(); a++) {
-            const char* s = set->seq(a);
-            const i64 len = set->length(a);
-            int prev = 0, kmerIndex = 0;
-            uint32_t kmer = 0;
-            for (i64 i = 0; i < k - 1 && i < len; i++) kmer = (kmer << 2) | baseCode((unsigned char)s[i]);  // KmerAt(0, k) >> 2 (:212)
-            for (i64 i = k - 1; i < len; i++) {
-                kmer = ((kmer << 2) | baseCode((unsigned char)s[i])) & mask;
-                if (ix.kmerSeed[kmer] == 0xffff) {  // :217-226
-                    if (ix.nSeeds >= 0xffff) {
-                        error = "trim: more than 65534 distinct adapter k-mers";
-                        return false;
-                    }
-                    ix.kmerSeed[kmer] = (uint16_t)ix.nSeeds++;
-                }
-                ix.segs.push_back(kmerIndex - prev);
-                ix.segs.push_back((int32_t)ix.kmerSeed[kmer]);
-                prev = kmerIndex + k;
-                kmerIndex++;
-            }
-            ix.segs.push_back(0);  // :233
-            ix.segOff.push_back((uint64_t)ix.segs.size());
-            ix.lengths.push_back((int32_t)len);
-            ix.isBarcode.push_back(isBarcodeName(set->names[a]) ? 1 : 0);
-        }
-    }
-    // :81-98
-    int pairID = 1;
-    ix.pairs.assign(front.size() + back.size(), -1);
-    for (size_t i = 0; i < front.size(); i++)
-        for (size_t j = 0; j < back.size(); j++)
-            if (back.names[j] == front.names[i]) {
-                ix.pairs[i] = pairID;
-                ix.pairs[front.size() + j] = pairID;
-                pairID++;
-                break;
-            }
-    return true;
-}
-
-// the chunk loop of trim.go:165-184 for a served (edge-trimmed) read of `length` bases
-void trimChunkPlan(i64 length, i64 chunkSize, uint32_t read, std::vector<TrimChunk>& out) {
-    const i64 longestAdapter = 100, edgeSize = 150;
-    for (i64 i = edgeSize; i < length - edgeSize - longestAdapter; i += chunkSize - longestAdapter) {
-        if (i > length - (chunkSize * 3) / 2 - edgeSize) {  // add the entire remainder
-            out.push_back(TrimChunk{read, (int32_t)i, (int32_t)(length - edgeSize), 1});
-            break;
-        }
-        const i64 endPoint = std::min(i + chunkSize, length - edgeSize);
-        out.push_back(TrimChunk{read, (int32_t)i, (int32_t)endPoint, 0});
-    }
-}
-
-namespace {
 // a ReadSet holding the chosen adapters of another one, in the given order
 ReadSet pickAdapters(const ReadSet& src, const std::vector<size_t>& order) {
     ReadSet out;
@@ -134,10 +66,13 @@ struct EdgeBatch {
     std::vector<uint32_t> reads;  // eligible reads (>= 200 bases, :434 / :455), in read order
     std::vector<uint8_t> ends;    // 2 x 150 ASCII bases per eligible read
 };
-void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
-    b.reads.clear();
+void eligibleReads(const ReadSet& reads, size_t lo, size_t hi, std::vector<uint32_t>& out) {
+    out.clear();
     for (size_t r = lo; r < hi; r++)
-        if (reads.length(r) >= kEdgeSize + 50) b.reads.push_back((uint32_t)r);
+        if (reads.length(r) >= kMinEdgeLength) out.push_back((uint32_t)r);
+}
+void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
+    eligibleReads(reads, lo, hi, b.reads);
     b.ends.resize(b.reads.size() * 2 * kEdgeSize);
     for (size_t i = 0; i < b.reads.size(); i++) {
         const size_t r = b.reads[i];
@@ -146,17 +81,10 @@ void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
     }
 }
 
-// trimWorker's arithmetic on the device's records (trim.go:464-510), PrintStats (:260-268) and Write (seqio.go:401-458)
-int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const TrimMidInput& in, TrimResult& res, bool& flushed, std::string& error);
-void writeExtras(const ReadSet& reads, const TrimResult& res, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out);
-
-// the middle stage's matching results made on demand, once the edge trims stand (the device path)
-typedef std::function<int(std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& recs)> MidProducer;
-
-int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimIndex& ix, const TrimParams& p, const std::vector<uint32_t>& eligible,
-               const dp_trim_rec* recs, const uint64_t* counts, TrimResult& res, std::string& error, const TrimMidInput* mid = nullptr,
-               const MidProducer* producer = nullptr) {
-    const double t0 = now();
+// trimWorker's arithmetic on the device's records (trim.go:464-510): frontTrim / backTrim / ignore of the reads, their names after
+// tagging, seen / none, the table's adapter columns, and the adapters with their counts
+bool applyEdgeRecords(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimIndex& ix, const TrimParams& p, const std::vector<uint32_t>& eligible,
+                      const dp_trim_rec* recs, const uint64_t* counts, TrimResult& res, std::string& error) {
     const size_t n = reads.size();
     reads.frontTrim.assign(n, 0);
     reads.backTrim.assign(n, 0);
@@ -176,7 +104,7 @@ int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const 
         bool foundEnd = !b.ambiguous && b.found;
         if ((foundStart && (matchIndex < 0 || (size_t)matchIndex >= front.size())) || (foundEnd && (backMatchIndex < 0 || (size_t)backMatchIndex >= back.size()))) {
             error = "trim: an edge record names an adapter beyond the list";
-            return -1;
+            return false;
         }
         if (p.requirePairs) {  // :471-485
             const int fp = foundStart ? ix.pairs[matchIndex] : -1;
@@ -202,55 +130,19 @@ int finishTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const 
         res.table[5 * r + 3] = foundStart ? matchIndex : -1;
         res.table[5 * r + 4] = foundEnd ? backMatchIndex : -1;
     }
-    for (size_t r = 0; r < n; r++) {
+    res.frontNames = front.names;
+    res.backNames = back.names;
+    res.counts.assign(counts, counts + front.size() + back.size());
+    return true;
+}
+
+// the table's trim columns, from the reads as the stages left them
+void fillTable(const ReadSet& reads, TrimResult& res) {
+    for (size_t r = 0; r < reads.size(); r++) {
         res.table[5 * r] = reads.frontTrim[r];
         res.table[5 * r + 1] = reads.backTrim[r];
         res.table[5 * r + 2] = reads.ignore[r];
     }
-    res.frontNames = front.names;
-    res.backNames = back.names;
-    res.counts.assign(counts, counts + front.size() + back.size());
-    std::vector<int32_t> madeCounts;
-    std::vector<TrimMidRec> madeRecs;
-    TrimMidInput made;
-    if (producer) {
-        if (int rc = (*producer)(madeCounts, madeRecs)) return rc;
-        made.seedCounts = madeCounts.data();
-        made.nChunks = madeCounts.size();
-        made.recs = madeRecs.data();
-        made.nRecs = madeRecs.size();
-        mid = &made;
-    }
-    if (mid) {
-        bool flushed = false;
-        if (int rc = trimMiddle(reads, front, p, *mid, res, flushed, error)) return rc;
-        if (flushed) std::fill(res.counts.begin(), res.counts.end(), 0);  // setupIndex() after a flush zeroes frontCounts / backCounts (:78-79, :202)
-        for (size_t r = 0; r < n; r++) {
-            res.table[5 * r] = reads.frontTrim[r];
-            res.table[5 * r + 1] = reads.backTrim[r];
-            res.table[5 * r + 2] = reads.ignore[r];
-        }
-        counts = res.counts.data();
-    }
-    res.t_apply = now() - t0;
-    // PrintStats: with seenCount == 0 the reference divides by zero
-    if (res.seen == 0) {
-        logLine(res.errText, "no reads long enough to trim");
-        error = "trim: no reads long enough to trim (the ends are searched in reads of 200 bases and more)";
-        return -2;
-    }
-    for (size_t i = 0; i < front.size(); i++)
-        logLine(res.errText, "Front adapter: " + front.names[i] + " \t " + std::to_string((i64)(counts[i] * 100) / res.seen) + " %");
-    for (size_t i = 0; i < back.size(); i++)
-        logLine(res.errText, "Back adapter: " + back.names[i] + " \t " + std::to_string((i64)(counts[front.size() + i] * 100) / res.seen) + " %");
-    logLine(res.errText, std::to_string((res.none * 100) / res.seen) + " % with no adapters found.");
-    logLine(res.errText, "Writing trimmed sequences...");  // commands/trim.go:44
-    const double t1 = now();
-    res.out.clear();
-    trimWrite(reads, res.names, nullptr, res.out);
-    writeExtras(reads, res, res.extraNames, nullptr, res.out);
-    res.t_write = now() - t1;
-    return 0;
 }
 
 // a half of a split read as the writers print it (seqio.go:401-435): extras follow the file's reads in the order added (sendExtras)
@@ -270,6 +162,28 @@ void writeExtras(const ReadSet& reads, const TrimResult& res, const std::vector<
     }
 }
 
+// PrintStats (trim.go:260-268) and Write (seqio.go:401-458)
+int reportAndWrite(const ReadSet& reads, const ReadSet& front, const ReadSet& back, TrimResult& res, std::string& error) {
+    // PrintStats: with seenCount == 0 the reference divides by zero
+    if (res.seen == 0) {
+        logLine(res.errText, "no reads long enough to trim");
+        error = "trim: no reads long enough to trim (the ends are searched in reads of 200 bases and more)";
+        return -2;
+    }
+    for (size_t i = 0; i < front.size(); i++)
+        logLine(res.errText, "Front adapter: " + front.names[i] + " \t " + std::to_string((i64)(res.counts[i] * 100) / res.seen) + " %");
+    for (size_t i = 0; i < back.size(); i++)
+        logLine(res.errText, "Back adapter: " + back.names[i] + " \t " + std::to_string((i64)(res.counts[front.size() + i] * 100) / res.seen) + " %");
+    logLine(res.errText, std::to_string((res.none * 100) / res.seen) + " % with no adapters found.");
+    logLine(res.errText, "Writing trimmed sequences...");  // commands/trim.go:44
+    const double t1 = now();
+    res.out.clear();
+    trimWrite(reads, res.names, nullptr, res.out);
+    writeExtras(reads, res, res.extraNames, nullptr, res.out);
+    res.t_write = now() - t1;
+    return 0;
+}
+
 // ---- the middle stage -----------------------------------------------------------------------------------------------------------
 struct MidSplit {  // sequenceSplit (trim.go:42-46); live = the pointer is not nil
     bool live = false;
@@ -286,7 +200,7 @@ struct MidPlan {
     std::vector<size_t> firstChunk;   // [reads + 1]
     std::vector<MidBatchRange> batches;
 };
-const i64 kLongestAdapter = 100, kMinSeeds = 4;  // :153, :155
+const uint32_t kNoBatch = 0xffffffffu;
 
 // the plan over what the second GetSequences() serves: the non-ignored reads with their edge trims applied (seqio.go:138-187)
 bool midBuildPlan(const ReadSet& reads, const TrimParams& p, MidPlan& mp, std::string& error) {
@@ -327,49 +241,39 @@ bool midCutBatches(const TrimParams& p, const int32_t* seedCounts, MidPlan& mp) 
     return flushed;
 }
 
-int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const TrimMidInput& in, TrimResult& res, bool& flushed, std::string& error) {
-    const size_t n = reads.size();
-    const i64 longestAdapter = kLongestAdapter, minSeeds = kMinSeeds, minSeqLength = 500;  // :153-155, :517
-    MidPlan mp;
-    if (!midBuildPlan(reads, p, mp, error)) return -1;
-    const std::vector<TrimChunk>& plan = mp.plan;
-    const std::vector<i64>& servedLen = mp.servedLen;
-    const std::vector<size_t>& firstChunk = mp.firstChunk;
-    if (in.nChunks != plan.size()) {
-        error = "trim: " + std::to_string(in.nChunks) + " seed counts for " + std::to_string(plan.size()) + " planned chunks";
-        return -1;
+// the plan table of the result (six int32 per chunk) and the batch every chunk is searched in (kNoBatch: never)
+std::vector<uint32_t> midPlanTable(const MidPlan& mp, const int32_t* seedCounts, TrimResult& res) {
+    res.midChunks = (i64)mp.plan.size();
+    res.midBatches = (i64)mp.batches.size();
+    res.plan.resize(mp.plan.size() * 6);
+    for (size_t c = 0; c < mp.plan.size(); c++) {
+        const i64 seeds = seedCounts[c];
+        res.midSeeds += seeds;
+        const bool indexed = mp.plan[c].remainder || seeds >= kMinSeeds;
+        const int32_t row[6] = {(int32_t)mp.plan[c].read, mp.plan[c].start, mp.plan[c].end, mp.plan[c].remainder, (int32_t)seeds, indexed ? 1 : 0};
+        std::copy(row, row + 6, res.plan.begin() + 6 * (long)c);
     }
-    res.midChunks = (i64)plan.size();
-    res.plan.resize(plan.size() * 6);
-    flushed = midCutBatches(p, in.seedCounts, mp);
-    const std::vector<MidBatchRange>& batches = mp.batches;
-    std::vector<uint32_t> batchOf(plan.size(), 0);
-    {
-        (void)firstChunk;
-        for (size_t c = 0; c < plan.size(); c++) {
-            const i64 seeds = in.seedCounts[c];
-            res.midSeeds += seeds;
-            const bool indexed = plan[c].remainder || seeds >= minSeeds;
-            const int32_t row[6] = {(int32_t)plan[c].read, plan[c].start, plan[c].end, plan[c].remainder, (int32_t)seeds, indexed ? 1 : 0};
-            std::copy(row, row + 6, res.plan.begin() + 6 * (long)c);
-        }
-        for (size_t b = 0; b < batches.size(); b++)
-            for (size_t c = batches[b].lo; c < batches[b].hi; c++) batchOf[c] = (uint32_t)b;
-        // (chunks behind the last batch - a tail whose seeds sum to 0 - are never searched)
-        for (size_t c = batches.empty() ? 0 : batches.back().hi; c < plan.size(); c++) batchOf[c] = 0xffffffffu;
-    }
-    res.midBatches = (i64)batches.size();
-    // the records in canonical order: batch, adapter, chunk, ordinal
+    // (chunks behind the last batch - a tail whose seeds sum to 0 - are never searched)
+    std::vector<uint32_t> batchOf(mp.plan.size(), kNoBatch);
+    for (size_t b = 0; b < mp.batches.size(); b++)
+        for (size_t c = mp.batches[b].lo; c < mp.batches[b].hi; c++) batchOf[c] = (uint32_t)b;
+    return batchOf;
+}
+
+// findSplit's rules (trim.go:527-586) over the records in canonical order - batch, adapter, chunk, ordinal: crops go into the reads'
+// trims, the splits into `splits` (one per read) and, in the order made, `ids`
+bool midFindSplits(ReadSet& reads, const ReadSet& front, const TrimParams& p, const MidPlan& mp, const std::vector<uint32_t>& batchOf, const TrimMidInput& in,
+                   TrimResult& res, std::vector<MidSplit>& splits, std::vector<i64>& ids, std::string& error) {
     std::vector<TrimMidRec> recs;
     for (size_t i = 0; i < in.nRecs; i++) {
         const TrimMidRec& r = in.recs[i];
-        if (r.adapter < 0 || (size_t)r.adapter >= front.size() || r.chunk < 0 || (size_t)r.chunk >= plan.size()) {
+        if (r.adapter < 0 || (size_t)r.adapter >= front.size() || r.chunk < 0 || (size_t)r.chunk >= mp.plan.size()) {
             error = "trim: a middle record names an adapter or a chunk beyond the lists";
-            return -1;
+            return false;
         }
-        if (batchOf[(size_t)r.chunk] == 0xffffffffu || !res.plan[6 * (size_t)r.chunk + 5]) {
+        if (batchOf[(size_t)r.chunk] == kNoBatch || !res.plan[6 * (size_t)r.chunk + 5]) {
             error = "trim: a middle record names a chunk that was not indexed";
-            return -1;
+            return false;
         }
         recs.push_back(r);
     }
@@ -380,30 +284,27 @@ int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const 
         if (a.chunk != b.chunk) return a.chunk < b.chunk;
         return a.ordinal < b.ordinal;
     });
-    // findSplit's rules (:527-586)
-    std::vector<MidSplit> splits(n + 1);
-    std::vector<i64> ids;
     size_t at = 0;
-    for (size_t b = 0; b < batches.size(); b++) {
+    for (size_t b = 0; b < mp.batches.size(); b++) {
         if (p.verbosity > 0)
-            logLine(res.errText, "Searching " + std::to_string(batches[b].totalBases / 1000000) + " MB of sequences for splitting based on " +
+            logLine(res.errText, "Searching " + std::to_string(mp.batches[b].totalBases / 1000000) + " MB of sequences for splitting based on " +
                                      std::to_string(front.size()) + " adapters");
         for (; at < recs.size() && batchOf[(size_t)recs[at].chunk] == b; at++) {
             const TrimMidRec& m = recs[at];
             const i64 adLen = front.length((size_t)m.adapter);
             if (((i64)m.covered * 100) / adLen < p.middleThreshold) continue;  // :528
             res.applied.insert(res.applied.end(), {m.adapter, m.chunk, m.ordinal, m.startRel, m.covered, m.chainLen});
-            const TrimChunk& c = plan[(size_t)m.chunk];
+            const TrimChunk& c = mp.plan[(size_t)m.chunk];
             const size_t id = c.read;
             const i64 frontTrim = reads.frontTrim[id], backTrim = reads.backTrim[id];  // :538-539
             // the chunk is SubSequence(start, end) of the served read: offset = start, Len = end - start, and - `end--` comes before
             // the inset is taken (sequence.go:353-370) - inset = served length - end + 1
             const i64 start = (i64)c.start + m.startRel;           // :541
-            const i64 seqLen = servedLen[id] + 1 - backTrim;       // :542
+            const i64 seqLen = mp.servedLen[id] + 1 - backTrim;    // :542
             MidSplit& split = splits[id];
-            if (start < minSeqLength + frontTrim) {  // :543 just crop the front off
+            if (start < kMinSeqLength + frontTrim) {  // :543 just crop the front off
                 const i64 newTrim = start + adLen + p.extraMiddleTrim;
-                if (newTrim + minSeqLength < seqLen) {
+                if (newTrim + kMinSeqLength < seqLen) {
                     if (newTrim > frontTrim) {
                         reads.frontTrim[id] = (int32_t)newTrim;
                         if (split.live) {  // update the existing split
@@ -416,7 +317,7 @@ int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const 
                     split.live = false;  // in case of existing split that is no longer valid
                     reads.ignore[id] = 1;
                 }
-            } else if (start + minSeqLength + adLen > seqLen) {  // :560 crop off the tail
+            } else if (start + kMinSeqLength + adLen > seqLen) {  // :560 crop off the tail
                 const i64 newTrim = seqLen - start + p.extraMiddleTrim;
                 if (newTrim > backTrim) reads.backTrim[id] = (int32_t)newTrim;
             } else if (split.live) {  // :568-574
@@ -431,8 +332,11 @@ int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const 
         }
     }
     res.midRecords = (i64)res.applied.size() / 6;
-    if (p.verbosity > 0) logLine(res.errText, std::to_string(ids.size()) + " sequences require splitting");  // :218-220
-    // :222-256 over the reads re-read with the trims as they stand now
+    return true;
+}
+
+// trim.go:222-256 over the reads re-read with the trims as they stand now: the halves of the split reads become extras
+void midEmitHalves(ReadSet& reads, const TrimParams& p, const std::vector<MidSplit>& splits, const std::vector<i64>& ids, TrimResult& res) {
     auto bases = [&](size_t id, i64 lo, i64 hi) {
         std::string t((size_t)(hi - lo), 'A');
         const char* s = reads.seq(id) + reads.frontTrim[id] + lo;
@@ -480,14 +384,31 @@ int trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, const 
             }
             if (p.verbosity > 1) {
                 logLine(res.errText, report);
-                if (split.aEnd >= 0 && split.bStart < len && split.bStart - split.aEnd - (i64)p.extraMiddleTrim * 2 <= longestAdapter)
+                if (split.aEnd >= 0 && split.bStart < len && split.bStart - split.aEnd - (i64)p.extraMiddleTrim * 2 <= kLongestAdapter)
                     logLine(res.errText, bases(id, split.aEnd + p.extraMiddleTrim, std::min(split.bStart - p.extraMiddleTrim, len)));
             }
         }
         res.splits.insert(res.splits.end(), {(int32_t)id, (int32_t)split.aEnd, (int32_t)split.bStart, kept});
         reads.ignore[id] = 1;  // :255
     }
-    return 0;
+}
+
+// The middle stage's sequential half over the plan `mp` of the edge-trimmed reads and the matching stage's results: crops, splits and
+// extras.  setupIndex() after a flush zeroes frontCounts / backCounts (trim.go:78-79, :202), so the stats lines then print zeros.
+bool trimMiddle(ReadSet& reads, const ReadSet& front, const TrimParams& p, MidPlan& mp, const TrimMidInput& in, TrimResult& res, std::string& error) {
+    if (in.nChunks != mp.plan.size()) {
+        error = "trim: " + std::to_string(in.nChunks) + " seed counts for " + std::to_string(mp.plan.size()) + " planned chunks";
+        return false;
+    }
+    const bool flushed = midCutBatches(p, in.seedCounts, mp);
+    const std::vector<uint32_t> batchOf = midPlanTable(mp, in.seedCounts, res);
+    std::vector<MidSplit> splits(reads.size() + 1);
+    std::vector<i64> ids;
+    if (!midFindSplits(reads, front, p, mp, batchOf, in, res, splits, ids, error)) return false;
+    if (p.verbosity > 0) logLine(res.errText, std::to_string(ids.size()) + " sequences require splitting");  // :218-220
+    midEmitHalves(reads, p, splits, ids, res);
+    if (flushed) std::fill(res.counts.begin(), res.counts.end(), 0);
+    return true;
 }
 
 // ---- SeedSequence.Match on the host (seeds/sequence.go:85-123, 361-576), for the pairs the device lists as beyond its working set --
@@ -635,8 +556,182 @@ std::vector<int> hostDynamicMatch(HostChains& C, const std::vector<int32_t>& qs,
     }
     return good;
 }
+// a device call's outcome: false with the handle's (h == nullptr: the set-up's) error text
+bool devOk(bool ok, const dp_trim* h, std::string& error) {
+    if (!ok) error = std::string("trim: ") + dp_trim_error(h);
+    return ok;
+}
+typedef std::unique_ptr<dp_trim, void (*)(dp_trim*)> TrimDev;
+TrimDev setupDevice(const TrimIndex& ix, int device, std::string& error) {
+    dp_trim* h = nullptr;
+    const int rc = dp_trim_setup(device, ix.k, ix.kmerSeed.data(), ix.nSeeds, ix.nFront, ix.nBack, ix.segs.data(), ix.segOff.data(), ix.lengths.data(),
+                                 ix.isBarcode.data(), ix.pairs.data(), &h);
+    devOk(rc == 0 && h, nullptr, error);
+    return TrimDev(h, dp_trim_release);
+}
+
+// the middle stage's device half over the plan `mp`: scan every planned chunk for its seed count, cut the flush batches, then per batch
+// scan -> index -> candidates -> matching kernel, and the host's Match for the pairs the kernel listed
+bool midDevice(dp_trim* h, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, MidPlan& mp, std::vector<int32_t>& seedCounts,
+               std::vector<TrimMidRec>& recs, TrimResult& res, std::string& error) {
+    const size_t nC = mp.plan.size();
+    seedCounts.assign(nC, 0);
+    recs.clear();
+    if (!nC || !ix.nFront) return true;
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> cnt;
+    double tms[2];
+    // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device
+    auto scan = [&](size_t lo, size_t hi) -> bool {
+        off.assign(1, 0);
+        for (size_t c = lo; c < hi; c++) off.push_back(off.back() + (uint64_t)(mp.plan[c].end - mp.plan[c].start));
+        bases.resize((size_t)off.back() + 1);
+        for (size_t c = lo; c < hi; c++) {
+            const TrimChunk& ch = mp.plan[c];
+            memcpy(bases.data() + off[c - lo], reads.seq(ch.read) + reads.frontTrim[ch.read] + ch.start, (size_t)(ch.end - ch.start));
+        }
+        cnt.assign(hi - lo, 0);
+        if (!devOk(dp_trim_scan_chunks(h, bases.data(), off.data(), (uint32_t)(hi - lo), cnt.data(), tms) == 0, h, error)) return false;
+        res.mid_upload_ms += tms[0];
+        res.mid_scan_ms += tms[1];
+        res.bytes_up += (double)off.back();
+        for (size_t c = lo; c < hi; c++) seedCounts[c] = (int32_t)cnt[c - lo];
+        return true;
+    };
+    const uint64_t groupBases = (uint64_t)1 << 28;
+    size_t scannedLo = 0, scannedHi = 0;  // what the device holds segments of
+    for (size_t lo = 0; lo < nC;) {
+        size_t hi = lo;
+        uint64_t b = 0;
+        while (hi < nC && (hi == lo || b + (uint64_t)(mp.plan[hi].end - mp.plan[hi].start) <= groupBases)) b += (uint64_t)(mp.plan[hi].end - mp.plan[hi].start), hi++;
+        if (!scan(lo, hi)) return false;
+        scannedLo = lo;
+        scannedHi = hi;
+        lo = hi;
+    }
+    midCutBatches(p, seedCounts.data(), mp);
+    std::vector<uint32_t> sel;
+    std::vector<int32_t> cseg;
+    for (const MidBatchRange& bt : mp.batches) {
+        if (bt.lo != scannedLo || bt.hi != scannedHi) {
+            if (!scan(bt.lo, bt.hi)) return false;
+            scannedLo = bt.lo;
+            scannedHi = bt.hi;
+        }
+        sel.clear();
+        for (size_t c = bt.lo; c < bt.hi; c++)
+            if (mp.plan[c].remainder || seedCounts[c] >= kMinSeeds) sel.push_back((uint32_t)(c - bt.lo));
+        dp_trim_mid_batch mb;
+        if (!devOk(dp_trim_search(h, sel.data(), (uint32_t)sel.size(), p.middleThreshold, &mb) == 0, h, error)) return false;
+        res.midPairs += mb.n_pairs;
+        res.midOverflowPairs += mb.n_overflow;
+        res.mid_index_ms += mb.index_ms;
+        res.mid_query_ms += mb.query_ms;
+        res.mid_kernel_ms += mb.kernel_ms;
+        res.bytes_down += (double)mb.n_recs * sizeof(dp_trim_mid_rec);
+        static_assert(sizeof(dp_trim_mid_rec) == sizeof(TrimMidRec), "device and host records are the same six int32");
+        for (uint32_t i = 0; i < mb.n_recs; i++) {
+            const dp_trim_mid_rec& r = mb.recs[i];
+            recs.push_back(TrimMidRec{r.adapter, (int32_t)(r.chunk + (int32_t)bt.lo), r.ordinal, r.start_rel, r.covered, r.chain_len});
+        }
+        const std::vector<uint32_t> over(mb.overflow, mb.overflow + 2 * (size_t)mb.n_overflow);  // (the handle's arrays go with its next call)
+        for (size_t i = 0; i < over.size(); i += 2) {
+            const uint32_t c = over[i], a = over[i + 1];
+            uint64_t n = 0;
+            cseg.resize(2 * (size_t)seedCounts[bt.lo + c] + 1);
+            if (!devOk(dp_trim_chunk_segments(h, c, cseg.data(), cseg.size(), &n) == 0 && n == cseg.size(), h, error)) return false;
+            trimHostMatch(cseg.data(), (int)cseg.size(), ix.segs.data() + ix.segOff[a], (int)(ix.segOff[a + 1] - ix.segOff[a]), ix.lengths[a], (int)ix.nSeeds, ix.k,
+                          p.middleThreshold, (int32_t)a, (int32_t)(bt.lo + c), recs);
+        }
+    }
+    return true;
+}
+
+// Demultiplex's bookkeeping for one name (seqio.go:460-523): a name that starts with "Barcode" loses its label, which is found in or
+// added to `labels`; returns the label's index, -1 for a name without one
+int demuxLabel(std::string& name, std::vector<std::string>& labels) {
+    if (!isBarcodeName(name)) return -1;
+    const size_t pos = name.find('_');
+    if (pos == std::string::npos) return -1;
+    const std::string label = name.substr(0, pos);
+    size_t li = 0;
+    while (li < labels.size() && labels[li] != label) li++;
+    if (li == labels.size()) labels.push_back(label);
+    name = name.substr(pos + 1);
+    return (int)li;
+}
+}  // namespace
+
+// setupIndex (trim.go:57-99): NewAllSeedSequence of every front, then every back adapter (seeds/seeds.go:204-237) - seed ids in order
+// of first occurrence - and pairsFront / pairsBack by name
+bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error) {
+    if (k < 3 || k > 8) {
+        error = "trim: k = " + std::to_string(k) + " is outside 3..8 (ShortKmers holds a k-mer in 16 bits)";
+        return false;
+    }
+    ix = TrimIndex();
+    ix.k = k;
+    ix.nFront = (uint32_t)front.size();
+    ix.nBack = (uint32_t)back.size();
+    ix.kmerSeed.assign((size_t)1 << (2 * k), (uint16_t)0xffff);
+    ix.segOff.push_back(0);
+    const uint32_t mask = (uint32_t)(((size_t)1 << (2 * k)) - 1);
+    for (const ReadSet* set : {&front, &back}) {
+        for (size_t a = 0; a < set->size(); a++) {
+            const char* s = set->seq(a);
+            const i64 len = set->length(a);
+            int prev = 0, kmerIndex = 0;
+            uint32_t kmer = 0;
+            for (i64 i = 0; i < k - 1 && i < len; i++) kmer = (kmer << 2) | baseCode((unsigned char)s[i]);  // KmerAt(0, k) >> 2 (:212)
+            for (i64 i = k - 1; i < len; i++) {
+                kmer = ((kmer << 2) | baseCode((unsigned char)s[i])) & mask;
+                if (ix.kmerSeed[kmer] == 0xffff) {  // :217-226
+                    if (ix.nSeeds >= 0xffff) {
+                        error = "trim: more than 65534 distinct adapter k-mers";
+                        return false;
+                    }
+                    ix.kmerSeed[kmer] = (uint16_t)ix.nSeeds++;
+                }
+                ix.segs.push_back(kmerIndex - prev);
+                ix.segs.push_back((int32_t)ix.kmerSeed[kmer]);
+                prev = kmerIndex + k;
+                kmerIndex++;
+            }
+            ix.segs.push_back(0);  // :233
+            ix.segOff.push_back((uint64_t)ix.segs.size());
+            ix.lengths.push_back((int32_t)len);
+            ix.isBarcode.push_back(isBarcodeName(set->names[a]) ? 1 : 0);
+        }
+    }
+    // :81-98
+    int pairID = 1;
+    ix.pairs.assign(front.size() + back.size(), -1);
+    for (size_t i = 0; i < front.size(); i++)
+        for (size_t j = 0; j < back.size(); j++)
+            if (back.names[j] == front.names[i]) {
+                ix.pairs[i] = pairID;
+                ix.pairs[front.size() + j] = pairID;
+                pairID++;
+                break;
+            }
+    return true;
+}
+
+// the chunk loop of trim.go:165-184 for a served (edge-trimmed) read of `length` bases
+void trimChunkPlan(i64 length, i64 chunkSize, uint32_t read, std::vector<TrimChunk>& out) {
+    for (i64 i = kEdgeSize; i < length - kEdgeSize - kLongestAdapter; i += chunkSize - kLongestAdapter) {
+        if (i > length - (chunkSize * 3) / 2 - kEdgeSize) {  // add the entire remainder
+            out.push_back(TrimChunk{read, (int32_t)i, (int32_t)(length - kEdgeSize), 1});
+            break;
+        }
+        const i64 endPoint = std::min<i64>(i + chunkSize, length - kEdgeSize);
+        out.push_back(TrimChunk{read, (int32_t)i, (int32_t)endPoint, 0});
+    }
+}
+
 // Match(ad, adSet, chunkSet, minMatch, k) of one (chunk, front adapter) pair and the identity test of trim.go:527-530
-void hostMatchPair(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
+void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
                    std::vector<TrimMidRec>& out) {
     std::vector<uint64_t> aSet(((size_t)nSeeds + 63) / 64, 0), cSet(aSet.size(), 0);
     for (int i = 1; i < aN; i += 2) aSet[(size_t)aSeg[i] >> 6] |= 1ull << (aSeg[i] & 63);
@@ -669,119 +764,6 @@ void hostMatchPair(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int
         out.push_back(TrimMidRec{adapter, chunk, (int32_t)g, seedOffset(cSeg, tIdx[(size_t)cb[0]]) - seedOffset(aSeg, qIdx[(size_t)ca[0]]), countA, len});
     }
 }
-
-}  // namespace
-void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int adLen, int nSeeds, int k, int threshold, int32_t adapter, int32_t chunk,
-                   std::vector<TrimMidRec>& out) {
-    hostMatchPair(cSeg, cN, aSeg, aN, adLen, nSeeds, k, threshold, adapter, chunk, out);
-}
-namespace {
-// the middle stage's device half: scan every planned chunk for its seed count, cut the flush batches, then per batch scan -> index ->
-// candidates -> matching kernel, and the host's Match for the pairs the kernel listed
-int midDevice(dp_trim* h, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& recs,
-              TrimResult& res, std::string& error) {
-    MidPlan mp;
-    if (!midBuildPlan(reads, p, mp, error)) return -1;
-    const size_t nC = mp.plan.size();
-    seedCounts.assign(nC, 0);
-    recs.clear();
-    if (!nC || !ix.nFront) return 0;
-    std::vector<uint8_t> bases;
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> cnt;
-    double tms[2];
-    // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device
-    auto scan = [&](size_t lo, size_t hi) -> bool {
-        off.assign(1, 0);
-        for (size_t c = lo; c < hi; c++) off.push_back(off.back() + (uint64_t)(mp.plan[c].end - mp.plan[c].start));
-        bases.resize((size_t)off.back() + 1);
-        for (size_t c = lo; c < hi; c++) {
-            const TrimChunk& ch = mp.plan[c];
-            memcpy(bases.data() + off[c - lo], reads.seq(ch.read) + reads.frontTrim[ch.read] + ch.start, (size_t)(ch.end - ch.start));
-        }
-        cnt.assign(hi - lo, 0);
-        if (dp_trim_scan_chunks(h, bases.data(), off.data(), (uint32_t)(hi - lo), cnt.data(), tms) != 0) {
-            error = std::string("trim: ") + dp_trim_error(h);
-            return false;
-        }
-        res.mid_upload_ms += tms[0];
-        res.mid_scan_ms += tms[1];
-        res.bytes_up += (double)off.back();
-        for (size_t c = lo; c < hi; c++) seedCounts[c] = (int32_t)cnt[c - lo];
-        return true;
-    };
-    const uint64_t groupBases = (uint64_t)1 << 28;
-    size_t scannedLo = 0, scannedHi = 0;  // what the device holds segments of
-    for (size_t lo = 0; lo < nC;) {
-        size_t hi = lo;
-        uint64_t b = 0;
-        while (hi < nC && (hi == lo || b + (uint64_t)(mp.plan[hi].end - mp.plan[hi].start) <= groupBases)) b += (uint64_t)(mp.plan[hi].end - mp.plan[hi].start), hi++;
-        if (!scan(lo, hi)) return -1;
-        scannedLo = lo;
-        scannedHi = hi;
-        lo = hi;
-    }
-    midCutBatches(p, seedCounts.data(), mp);
-    std::vector<uint32_t> sel;
-    std::vector<int32_t> cseg;
-    for (const MidBatchRange& bt : mp.batches) {
-        if (bt.lo != scannedLo || bt.hi != scannedHi) {
-            if (!scan(bt.lo, bt.hi)) return -1;
-            scannedLo = bt.lo;
-            scannedHi = bt.hi;
-        }
-        sel.clear();
-        for (size_t c = bt.lo; c < bt.hi; c++)
-            if (mp.plan[c].remainder || seedCounts[c] >= kMinSeeds) sel.push_back((uint32_t)(c - bt.lo));
-        dp_trim_mid_batch mb;
-        if (dp_trim_search(h, sel.data(), (uint32_t)sel.size(), p.middleThreshold, &mb) != 0) {
-            error = std::string("trim: ") + dp_trim_error(h);
-            return -1;
-        }
-        res.midPairs += mb.n_pairs;
-        res.midOverflowPairs += mb.n_overflow;
-        res.mid_index_ms += mb.index_ms;
-        res.mid_query_ms += mb.query_ms;
-        res.mid_kernel_ms += mb.kernel_ms;
-        res.bytes_down += (double)mb.n_recs * sizeof(dp_trim_mid_rec);
-        static_assert(sizeof(dp_trim_mid_rec) == sizeof(TrimMidRec), "device and host records are the same six int32");
-        for (uint32_t i = 0; i < mb.n_recs; i++) {
-            const dp_trim_mid_rec& r = mb.recs[i];
-            recs.push_back(TrimMidRec{r.adapter, (int32_t)(r.chunk + (int32_t)bt.lo), r.ordinal, r.start_rel, r.covered, r.chain_len});
-        }
-        const std::vector<uint32_t> over(mb.overflow, mb.overflow + 2 * (size_t)mb.n_overflow);  // (the handle's arrays go with its next call)
-        for (size_t i = 0; i < over.size(); i += 2) {
-            const uint32_t c = over[i], a = over[i + 1];
-            uint64_t n = 0;
-            cseg.resize(2 * (size_t)seedCounts[bt.lo + c] + 1);
-            if (dp_trim_chunk_segments(h, c, cseg.data(), cseg.size(), &n) != 0 || n != cseg.size()) {
-                error = std::string("trim: ") + dp_trim_error(h);
-                return -1;
-            }
-            hostMatchPair(cseg.data(), (int)cseg.size(), ix.segs.data() + ix.segOff[a], (int)(ix.segOff[a + 1] - ix.segOff[a]), ix.lengths[a], (int)ix.nSeeds, ix.k,
-                          p.middleThreshold, (int32_t)a, (int32_t)(bt.lo + c), recs);
-        }
-    }
-    return 0;
-}
-
-#define TRIM_DEV(call, h)                                     \
-    do {                                                      \
-        if ((call) != 0) {                                    \
-            error = std::string("trim: ") + dp_trim_error(h); \
-            if (h) dp_trim_release(h);                        \
-            return -1;                                        \
-        }                                                     \
-    } while (0)
-
-dp_trim* setupDevice(const TrimIndex& ix, int device) {
-    dp_trim* h = nullptr;
-    dp_trim_setup(device, ix.k, ix.kmerSeed.data(), ix.nSeeds, ix.nFront, ix.nBack, ix.segs.data(), ix.segOff.data(), ix.lengths.data(),
-                  ix.isBarcode.data(), ix.pairs.data(), &h);
-    return h;
-}
-}  // namespace
-
 // fastaWriter / fastqWriter with fullNames (seqio.go:401-435) over the non-ignored reads in file order; keep (may be null) selects reads
 void trimWrite(const ReadSet& reads, const std::vector<std::string>& names, const std::vector<uint8_t>* keep, std::string& out) {
     for (size_t r = 0; r < reads.size(); r++) {
@@ -808,50 +790,22 @@ void trimWrite(const ReadSet& reads, const std::vector<std::string>& names, cons
 // Demultiplex (seqio.go:460-523): reads whose name starts with "Barcode" go to <label><ext> with the label cut off their name; a file
 // that exists is replaced (the reference opens without truncating and leaves the tail of a longer old file in place)
 int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::string& dir, std::string& error) {
+    // labels in the order first seen: over the reads, then over the halves of split reads that follow them (sendExtras)
     std::vector<std::string> labels;
-    std::vector<std::vector<uint8_t>> keep;
-    std::vector<std::string> names = res.names;
-    for (size_t r = 0; r < reads.size(); r++) {
-        if (reads.ignore[r]) continue;
-        const std::string n = names[r];
-        if (!isBarcodeName(n)) continue;
-        const size_t pos = n.find('_');
-        if (pos == std::string::npos) continue;
-        const std::string label = n.substr(0, pos);
-        size_t li = 0;
-        while (li < labels.size() && labels[li] != label) li++;
-        if (li == labels.size()) {
-            labels.push_back(label);
-            keep.emplace_back(reads.size(), 0);
-        }
-        names[r] = n.substr(pos + 1);
-        keep[li][r] = 1;
-    }
-    // the halves of split reads follow the file's reads (sendExtras)
-    std::vector<std::string> extraNames = res.extraNames;
-    std::vector<std::vector<uint8_t>> keepExtra(labels.size(), std::vector<uint8_t>(extraNames.size(), 0));
-    for (size_t e = 0; e < extraNames.size(); e++) {
-        const std::string n = extraNames[e];
-        if (!isBarcodeName(n)) continue;
-        const size_t pos = n.find('_');
-        if (pos == std::string::npos) continue;
-        const std::string label = n.substr(0, pos);
-        size_t li = 0;
-        while (li < labels.size() && labels[li] != label) li++;
-        if (li == labels.size()) {
-            labels.push_back(label);
-            keep.emplace_back(reads.size(), 0);
-            keepExtra.emplace_back(extraNames.size(), 0);
-        }
-        extraNames[e] = n.substr(pos + 1);
-        keepExtra[li][e] = 1;
-    }
+    std::vector<std::string> names = res.names, extraNames = res.extraNames;
+    std::vector<int> labelOf(reads.size(), -1), extraLabelOf(extraNames.size(), -1);
+    for (size_t r = 0; r < reads.size(); r++)
+        if (!reads.ignore[r]) labelOf[r] = demuxLabel(names[r], labels);
+    for (size_t e = 0; e < extraNames.size(); e++) extraLabelOf[e] = demuxLabel(extraNames[e], labels);
     const char* ext = reads.isFastq ? ".fastq" : ".fasta";
+    std::vector<uint8_t> keep(reads.size()), keepExtra(extraNames.size());
     for (size_t li = 0; li < labels.size(); li++) {
         const std::string path = dir + "/" + labels[li] + ext;
+        for (size_t r = 0; r < reads.size(); r++) keep[r] = labelOf[r] == (int)li;
+        for (size_t e = 0; e < extraNames.size(); e++) keepExtra[e] = extraLabelOf[e] == (int)li;
         std::string text;
-        trimWrite(reads, names, &keep[li], text);
-        writeExtras(reads, res, extraNames, &keepExtra[li], text);
+        trimWrite(reads, names, &keep, text);
+        writeExtras(reads, res, extraNames, &keepExtra, text);
         const int fd = open(path.c_str(), O_CREAT | O_WRONLY | O_TRUNC, 0755);
         if (fd < 0) {
             error = "Unable to open file for writing:" + path;
@@ -874,9 +828,9 @@ int trimDemultiplex(const ReadSet& reads, const TrimResult& res, const std::stri
 
 // The device-free half: DetermineAdapters' compaction from caller-supplied flags (enabled == nullptr: none ran), then trimWorker,
 // PrintStats and Write from caller-supplied edge records of the eligible reads (in read order) and per-adapter match counts, both
-// in the order of the COMPACTED adapter lists.
-static int applyTrimImpl(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-                         size_t nRecReads, const uint64_t* counts, const TrimMidInput* mid, TrimResult& res, std::string& error) {
+// in the order of the COMPACTED adapter lists; with mid and p.middle, the middle stage's sequential half over its matching results too.
+int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
+              size_t nRecReads, const uint64_t* counts, const TrimMidInput* mid, TrimResult& res, std::string& error) {
     res = TrimResult();
     ReadSet front = front0, back = back0;
     if (enabled) {
@@ -887,21 +841,20 @@ static int applyTrimImpl(ReadSet& reads, const ReadSet& front0, const ReadSet& b
     if (!trimBuildIndex(front, back, p.k, ix, error)) return -1;
     if (p.verbosity > 0) logLine(res.errText, "Trimming ends and indexing all sequences against " + std::to_string(front.size()) + " adapters...");
     std::vector<uint32_t> eligible;
-    for (size_t r = 0; r < reads.size(); r++)
-        if (reads.length(r) >= kEdgeSize + 50) eligible.push_back((uint32_t)r);
+    eligibleReads(reads, 0, reads.size(), eligible);
     if (eligible.size() != nRecReads) {
         error = "trim: " + std::to_string(nRecReads) + " edge record pairs for " + std::to_string(eligible.size()) + " reads of 200 bases and more";
         return -1;
     }
-    return finishTrim(reads, front, back, ix, p, eligible, recs, counts, res, error, mid);
-}
-int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-              size_t nRecReads, const uint64_t* counts, TrimResult& res, std::string& error) {
-    return applyTrimImpl(reads, front0, back0, p, enabled, recs, nRecReads, counts, nullptr, res, error);
-}
-int applyTrimMid(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, const uint8_t* enabled, const dp_trim_rec* recs,
-                 size_t nRecReads, const uint64_t* counts, const TrimMidInput& mid, TrimResult& res, std::string& error) {
-    return applyTrimImpl(reads, front0, back0, p, enabled, recs, nRecReads, counts, p.middle ? &mid : nullptr, res, error);
+    const double t0 = now();
+    if (!applyEdgeRecords(reads, front, back, ix, p, eligible, recs, counts, res, error)) return -1;
+    if (mid && p.middle) {
+        MidPlan mp;
+        if (!midBuildPlan(reads, p, mp, error) || !trimMiddle(reads, front, p, mp, *mid, res, error)) return -1;
+    }
+    fillTable(reads, res);
+    res.t_apply = now() - t0;
+    return reportAndWrite(reads, front, back, res, error);
 }
 
 int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, int device, TrimResult& res, std::string& error) {
@@ -917,16 +870,16 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         const size_t nCheck = (size_t)std::max<i64>(0, std::min<i64>(p.checkReads, (i64)reads.size()));
         std::vector<uint8_t> enabled(front0.size() + back0.size(), 0);
         if (!enabled.empty()) {
-            dp_trim* h = setupDevice(ix, device);
-            TRIM_DEV(h ? 0 : 1, h);
+            const TrimDev h = setupDevice(ix, device, error);
+            if (!h) return -1;
             for (size_t lo = 0; lo < nCheck; lo += batchReads) {
                 extractEnds(reads, lo, std::min(nCheck, lo + batchReads), eb);
-                TRIM_DEV(dp_trim_edges(h, eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr,
-                                       enabled.data(), tms),
-                         h);
+                if (!devOk(dp_trim_edges(h.get(), eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr,
+                                         enabled.data(), tms) == 0,
+                           h.get(), error))
+                    return -1;
                 res.k_determine_ms += tms[1];
             }
-            dp_trim_release(h);
         }
         front = pickAdapters(front0, compactAdapters(front0, enabled.data(), "front", p.verbosity, res.errText));
         back = pickAdapters(back0, compactAdapters(back0, enabled.data() + front0.size(), "back", p.verbosity, res.errText));
@@ -938,10 +891,10 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
     std::vector<uint32_t> eligible;
     std::vector<dp_trim_rec> recs;
     std::vector<uint64_t> counts(nA, 0);
-    dp_trim* h = nullptr;
+    TrimDev h(nullptr, dp_trim_release);
     if (nA) {
-        h = setupDevice(ix, device);
-        TRIM_DEV(h ? 0 : 1, h);
+        h = setupDevice(ix, device, error);
+        if (!h) return -1;
     }
     for (size_t lo = 0; lo < reads.size(); lo += batchReads) {
         const double t0 = now();
@@ -951,7 +904,9 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         eligible.insert(eligible.end(), eb.reads.begin(), eb.reads.end());
         recs.resize(2 * eligible.size(), dp_trim_rec{kEdgeSize, 0, 0, 0, 0, 0});  // (no adapters at all: what findMatches returns)
         if (h && !eb.reads.empty()) {
-            TRIM_DEV(dp_trim_edges(h, eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms), h);
+            if (!devOk(dp_trim_edges(h.get(), eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms) == 0,
+                       h.get(), error))
+                return -1;
             res.upload_ms += tms[0];
             res.kernel_ms += tms[1];
             res.download_ms += tms[2];
@@ -959,16 +914,24 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
             res.bytes_down += (double)(2 * eb.reads.size() * sizeof(dp_trim_rec));
         }
     }
-    if (!p.middle || !h) {
-        if (h) dp_trim_release(h);
-        return finishTrim(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error);
+    const double t0 = now();
+    if (!applyEdgeRecords(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error)) return -1;
+    if (p.middle && h) {  // the matching results are made once the edge trims stand
+        MidPlan mp;
+        std::vector<int32_t> seedCounts;
+        std::vector<TrimMidRec> midRecs;
+        if (!midBuildPlan(reads, p, mp, error) || !midDevice(h.get(), reads, ix, p, mp, seedCounts, midRecs, res, error)) return -1;
+        TrimMidInput mid;
+        mid.seedCounts = seedCounts.data();
+        mid.nChunks = seedCounts.size();
+        mid.recs = midRecs.data();
+        mid.nRecs = midRecs.size();
+        if (!trimMiddle(reads, front, p, mp, mid, res, error)) return -1;
     }
-    const MidProducer producer = [&](std::vector<int32_t>& seedCounts, std::vector<TrimMidRec>& midRecs) {
-        return midDevice(h, reads, ix, p, seedCounts, midRecs, res, error);
-    };
-    const int rc = finishTrim(reads, front, back, ix, p, eligible, recs.data(), counts.data(), res, error, nullptr, &producer);
-    dp_trim_release(h);
-    return rc;
+    fillTable(reads, res);
+    res.t_apply = now() - t0;
+    h.reset();
+    return reportAndWrite(reads, front, back, res, error);
 }
 
 }  // namespace dph

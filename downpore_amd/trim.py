@@ -134,20 +134,29 @@ def trim_reads(reads, front, back, k=6, check_reads=10000, adapter_threshold=90,
     return TrimResult(H, h)
 
 
+def _apply(reads, front, back, recs, counts, enabled, p, middle=None):
+    """dph_trim_apply, or dph_trim_apply_mid when middle = (seed_counts, mid_recs)"""
+    H = _host()
+    r = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, 6)
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    en = None if enabled is None else np.ascontiguousarray(enabled, dtype=np.uint8)
+    f, more = H.dph_trim_apply, []
+    if middle is not None:
+        sc = np.ascontiguousarray(middle[0], dtype=np.int32)
+        mr = np.ascontiguousarray(middle[1], dtype=np.int32).reshape(-1, 6)
+        f, more = H.dph_trim_apply_mid, [sc.ctypes.data, len(sc), mr.ctypes.data, len(mr)]
+    h = f(reads.h, front.h, back.h, p.ctypes.data, len(p), None if en is None else en.ctypes.data, r.ctypes.data, len(r) // 2, c.ctypes.data, *more)
+    if not h:
+        raise DpError(f.__name__ + ": " + H.dph_last_error(None).decode())
+    return TrimResult(H, h)
+
+
 def trim_apply(reads, front, back, recs, counts, enabled=None, k=6, check_reads=10000, adapter_threshold=90, extra_end_trim=5,
                tag_adapters=True, require_pairs=False, verbosity=1):
     """The device-free half (dph_trim_apply): recs int32 [2 * eligible reads, 6] and counts as dp_trim_edges returns them for the
     adapter lists after determination; enabled: the determine flags over the adapters as loaded, or None."""
-    H = _host()
     p = _params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, enabled is not None, verbosity)
-    r = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, 6)
-    c = np.ascontiguousarray(counts, dtype=np.uint64)
-    en = None if enabled is None else np.ascontiguousarray(enabled, dtype=np.uint8)
-    h = H.dph_trim_apply(reads.h, front.h, back.h, p.ctypes.data, len(p), None if en is None else en.ctypes.data, r.ctypes.data,
-                         len(r) // 2, c.ctypes.data)
-    if not h:
-        raise DpError("dph_trim_apply: " + H.dph_last_error(None).decode())
-    return TrimResult(H, h)
+    return _apply(reads, front, back, recs, counts, enabled, p)
 
 
 def trim_apply_middle(reads, front, back, recs, counts, seed_counts, mid_recs, enabled=None, k=6, check_reads=10000, adapter_threshold=90,
@@ -156,19 +165,9 @@ def trim_apply_middle(reads, front, back, recs, counts, seed_counts, mid_recs, e
     """trim_apply followed by the middle stage's sequential half (dph_trim_apply_mid), without a device: seed_counts = seeds of every
     planned chunk (trim_chunk_plan over the edge-trimmed reads, in file order), mid_recs int32 [n, 6] (TRIM_MID_REC_FIELDS) = the matches
     that passed the identity test, in any order."""
-    H = _host()
     p = _mid_params(_params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, enabled is not None, verbosity),
                     chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds)
-    r = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, 6)
-    c = np.ascontiguousarray(counts, dtype=np.uint64)
-    en = None if enabled is None else np.ascontiguousarray(enabled, dtype=np.uint8)
-    sc = np.ascontiguousarray(seed_counts, dtype=np.int32)
-    mr = np.ascontiguousarray(mid_recs, dtype=np.int32).reshape(-1, 6)
-    h = H.dph_trim_apply_mid(reads.h, front.h, back.h, p.ctypes.data, len(p), None if en is None else en.ctypes.data, r.ctypes.data,
-                             len(r) // 2, c.ctypes.data, sc.ctypes.data, len(sc), mr.ctypes.data, len(mr))
-    if not h:
-        raise DpError("dph_trim_apply_mid: " + H.dph_last_error(None).decode())
-    return TrimResult(H, h)
+    return _apply(reads, front, back, recs, counts, enabled, p, (seed_counts, mid_recs))
 
 
 def trim_chunk_plan(length, chunk_size):
@@ -231,9 +230,12 @@ class TrimDevice:
         rc = L.dp_trim_setup(device, ix["k"], ix["kmer_seed"].ctypes.data, ix["n_seeds"], ix["n_front"], ix["n_back"], ix["segs"].ctypes.data,
                              ix["seg_off"].ctypes.data, ix["lengths"].ctypes.data, ix["is_barcode"].ctypes.data, ix["pairs"].ctypes.data,
                              C.byref(h))
-        if rc != 0:
-            raise DpError("dp_trim_setup failed (%d): %s" % (rc, L.dp_trim_error(None).decode()))
+        self._check(rc, "dp_trim_setup")
         self.h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise DpError("%s failed (%d): %s" % (what, rc, self.L.dp_trim_error(getattr(self, "h", None)).decode()))  # (no handle: the set-up's text)
 
     def edges(self, ends, mode=MODE_TRIM, min_match=3, threshold=90):
         """ends: uint8 [reads, 2, 150] ASCII.  Trim mode -> (recs int32 [2 * reads, 6], counts uint64, times_ms); determine mode ->
@@ -245,8 +247,7 @@ class TrimDevice:
         times = np.zeros(3, dtype=np.float64)
         rc = self.L.dp_trim_edges(self.h, e.ctypes.data, len(e), mode, min_match, threshold, recs.ctypes.data, counts.ctypes.data,
                                   enabled.ctypes.data, times.ctypes.data)
-        if rc != 0:
-            raise DpError("dp_trim_edges failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        self._check(rc, "dp_trim_edges")
         return (recs, counts, times) if mode == MODE_TRIM else (enabled, times)
 
     def scan_chunks(self, chunks):
@@ -259,8 +260,7 @@ class TrimDevice:
         counts = np.zeros(len(raw), dtype=np.uint32)
         times = np.zeros(2, dtype=np.float64)
         rc = self.L.dp_trim_scan_chunks(self.h, bases.ctypes.data, off.ctypes.data, len(raw), counts.ctypes.data, times.ctypes.data)
-        if rc != 0:
-            raise DpError("dp_trim_scan_chunks failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        self._check(rc, "dp_trim_scan_chunks")
         return counts, times
 
     def chunk_segments(self, chunk):
@@ -270,8 +270,7 @@ class TrimDevice:
         out = np.zeros(max(int(n.value), 1), dtype=np.int32)
         if rc == 0:
             rc = self.L.dp_trim_chunk_segments(self.h, chunk, out.ctypes.data, len(out), C.byref(n))
-        if rc != 0:
-            raise DpError("dp_trim_chunk_segments failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        self._check(rc, "dp_trim_chunk_segments")
         return out[:int(n.value)]
 
     def search(self, sel, middle_threshold=85):
@@ -280,8 +279,7 @@ class TrimDevice:
         s = np.ascontiguousarray(sel, dtype=np.uint32)
         b = MidBatch()
         rc = self.L.dp_trim_search(self.h, s.ctypes.data, len(s), middle_threshold, C.byref(b))
-        if rc != 0:
-            raise DpError("dp_trim_search failed (%d): %s" % (rc, self.L.dp_trim_error(self.h).decode()))
+        self._check(rc, "dp_trim_search")
         recs = np.ctypeslib.as_array(C.cast(b.recs, C.POINTER(C.c_int32)), shape=(b.n_recs, 6)).copy() if b.n_recs else np.zeros((0, 6), dtype=np.int32)
         over = np.ctypeslib.as_array(b.overflow, shape=(b.n_overflow, 2)).copy() if b.n_overflow else np.zeros((0, 2), dtype=np.uint32)
         return dict(recs=recs, overflow=over, pairs=b.n_pairs, launches=b.launches, index_ms=b.index_ms, query_ms=b.query_ms, kernel_ms=b.kernel_ms)
