@@ -471,6 +471,188 @@ extern "C" int dp_single_seed_candidates(dp_ctx* ctx, uint32_t read, int k, int6
     return DP_OK;
 }
 
+// ---- the same two passes over a RUN of resident sequences that share one seed index (`map -all_sequences`).  The windows of all
+// sequences are numbered in sequence order; window w finds its sequence in the prefix table win_off (the last c with win_off[c] <= w)
+// and takes that sequence's own length, skipBack and packed base address, so bases beyond a sequence's end read as zero whatever
+// follows it in d_packed.  "Best of ANY window" - the one `bits` table - is over the windows of every sequence.
+struct SsSeq {
+    unsigned long long boff;  // byte offset of the sequence in d_packed
+    long long len;
+};
+struct SsMulti {
+    const SsSeq* seqs;
+    const uint32_t* win_off;  // [n_seqs + 1]
+    uint32_t n_seqs, n_windows;
+    long long seed_rate;
+    int k;
+};
+// geometry of window w within its own sequence; returns the window's first base
+__device__ __forceinline__ long long ss_locate(const SsMulti& M, uint32_t w, SsGeom* G, unsigned long long* boff) {
+    uint32_t lo = 0, hi = M.n_seqs;  // invariant: win_off[lo] <= w < win_off[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (M.win_off[mid] <= w) lo = mid;
+        else hi = mid;
+    }
+    const SsSeq s = M.seqs[lo];
+    G->len = s.len;
+    G->seed_rate = M.seed_rate;
+    G->k = M.k;
+    G->skip_back = 4 - (int)(s.len % 4);
+    G->n_windows = M.n_windows;
+    *boff = s.boff;
+    return (long long)(w - M.win_off[lo]) * M.seed_rate;
+}
+__global__ void ss_best_multi_kernel(const uint8_t* __restrict__ packed_all, SsMulti M, const double* __restrict__ values,
+                                     uint32_t* __restrict__ best, uint32_t* __restrict__ bits) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= M.n_windows) return;
+    SsGeom G;
+    unsigned long long boff;
+    const long long i = ss_locate(M, w, &G, &boff), end = i + G.seed_rate;
+    const uint8_t* __restrict__ packed = packed_all + boff;
+    const uint32_t mask = (uint32_t)(((unsigned long long)1 << (2 * G.k)) - 1);
+    uint32_t km = 0;
+    for (int j = 0; j < G.k; j++) km = (km << 2) | ss_code(packed, i + j, G.len);
+    double bv = values[km];
+    uint32_t bk = km;
+    for (long long j = i + G.k; j < end; j++) {
+        km = ((km << 2) | ss_code(packed, j, G.len)) & mask;
+        const double v = values[km];
+        if (v > bv) {
+            bv = v;
+            bk = km;
+        }
+    }
+    best[w] = bk;
+    atomicOr(&bits[bk >> 5], 1u << (bk & 31));
+}
+template <bool WRITE>
+__global__ void ss_cand_multi_kernel(const uint8_t* __restrict__ packed_all, SsMulti M, const uint32_t* __restrict__ bits,
+                                     uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off, uint32_t* __restrict__ cand) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= M.n_windows) return;
+    SsGeom G;
+    unsigned long long boff;
+    const long long i = ss_locate(M, w, &G, &boff);
+    const uint8_t* __restrict__ packed = packed_all + boff;
+    long long p0, P;
+    ss_region(G, i, &p0, &P);
+    const uint32_t mask = (uint32_t)(((unsigned long long)1 << (2 * G.k)) - 1);
+    uint32_t km = 0, n = 0;
+    const uint32_t at = WRITE ? off[w] : 0u;
+    for (int j = 0; j < G.k; j++) km = (km << 2) | ss_code(packed, p0 + j, G.len);
+    for (long long j = 0; j < P; j++) {
+        if (j) km = ((km << 2) | ss_code(packed, p0 + j + G.k - 1, G.len)) & mask;
+        if ((bits[km >> 5] >> (km & 31)) & 1u) {
+            if (WRITE) cand[at + n] = km;
+            n++;
+        }
+    }
+    if (!WRITE) cnt[w] = n;
+}
+
+extern "C" int dp_single_seed_candidates_multi(dp_ctx* ctx, uint32_t first_read, uint32_t n_reads, int k, int64_t seed_rate,
+                                               dp_single_seed_multi_batch* out) {
+    if (!ctx || !out || k < 4 || k > 15 || seed_rate < 1)
+        return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_single_seed_candidates_multi: bad arguments") : DP_ERR_ARG;
+    if (n_reads == 0 || first_read >= ctx->n_reads || n_reads > ctx->n_reads - first_read)
+        return dp_fail(ctx, DP_ERR_ARG, "dp_single_seed_candidates_multi: read range out of range");
+    const dp_ctx* src = ctx->owner ? ctx->owner : ctx;
+    const size_t nk = (size_t)1 << (2 * k);
+    if (!src->d_values.p || src->n_values != nk)
+        return dp_fail(ctx, DP_ERR_STATE, "dp_single_seed_candidates_multi: no value table of this k resident");
+    hipSetDevice(ctx->device);
+    memset(out, 0, sizeof(*out));
+    // per sequence: for (i = 0; i < len - seed_rate; i += seed_rate); the prefix table also goes back to the caller
+    std::vector<SsSeq> seqs(n_reads);
+    std::vector<uint32_t> winOff((size_t)n_reads + 1, 0);
+    unsigned long long windows = 0;
+    for (uint32_t c = 0; c < n_reads; c++) {
+        seqs[c].boff = src->h_boff[first_read + c];
+        seqs[c].len = (long long)src->h_len[first_read + c];
+        const long long span = seqs[c].len - seed_rate;
+        if (span > 0) windows += (unsigned long long)((span + seed_rate - 1) / seed_rate);
+        if (windows > 0xffffffffull) return dp_fail(ctx, DP_ERR_ARG, "dp_single_seed_candidates_multi: 2^32 or more seed windows");
+        winOff[c + 1] = (uint32_t)windows;
+    }
+    const uint32_t nw = (uint32_t)windows;
+    const size_t headWords = (size_t)n_reads + 1;
+    if (!nw) {
+        ctx->ss_host.assign(winOff.begin(), winOff.end());
+        out->n_reads = n_reads;
+        out->win_off = ctx->ss_host.data();
+        return DP_OK;
+    }
+    void *d_bits = nullptr, *d_best = nullptr, *d_cnt = nullptr, *d_off = nullptr, *d_cand = nullptr, *d_tmp = nullptr, *d_seqs = nullptr,
+         *d_woff = nullptr;
+    auto cleanup = [&] {
+        for (void* p : {d_bits, d_best, d_cnt, d_off, d_cand, d_tmp, d_seqs, d_woff})
+            if (p) dp_dev_free(p);
+    };
+#define DSS(x)                                                                              \
+    do {                                                                                    \
+        hipError_t e_ = (x);                                                                \
+        if (e_ != hipSuccess) {                                                             \
+            cleanup();                                                                      \
+            return dp_fail(ctx, DP_ERR_HIP, "dp_single_seed_candidates_multi: " #x, e_);    \
+        }                                                                                   \
+    } while (0)
+    const uint32_t blocks = (nw + 255) / 256;
+    DSS(dp_dev_malloc(&d_bits, nk / 8 + 64));
+    DSS(dp_dev_malloc(&d_best, (size_t)nw * 4));
+    DSS(dp_dev_malloc(&d_cnt, ((size_t)nw + 1) * 4));
+    DSS(dp_dev_malloc(&d_off, ((size_t)nw + 1) * 4));
+    DSS(dp_dev_malloc(&d_seqs, (size_t)n_reads * sizeof(SsSeq)));
+    DSS(dp_dev_malloc(&d_woff, headWords * 4));
+    DSS(hipMemcpyAsync(d_seqs, seqs.data(), (size_t)n_reads * sizeof(SsSeq), hipMemcpyHostToDevice, ctx->stream));
+    DSS(hipMemcpyAsync(d_woff, winOff.data(), headWords * 4, hipMemcpyHostToDevice, ctx->stream));
+    DSS(hipMemsetAsync(d_bits, 0, nk / 8 + 64, ctx->stream));
+    DSS(hipMemsetAsync(d_cnt, 0, ((size_t)nw + 1) * 4, ctx->stream));
+    SsMulti M;
+    M.seqs = (const SsSeq*)d_seqs;
+    M.win_off = (const uint32_t*)d_woff;
+    M.n_seqs = n_reads;
+    M.n_windows = nw;
+    M.seed_rate = seed_rate;
+    M.k = k;
+    const uint8_t* packed = (const uint8_t*)src->d_packed.p;
+    hipLaunchKernelGGL(ss_best_multi_kernel, dim3(blocks), dim3(256), 0, ctx->stream, packed, M, (const double*)src->d_values.p,
+                       (uint32_t*)d_best, (uint32_t*)d_bits);
+    hipLaunchKernelGGL(ss_cand_multi_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, packed, M, (const uint32_t*)d_bits,
+                       (uint32_t*)d_cnt, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    DSS(hipGetLastError());
+    size_t tb = 0;
+    DSS(rocprim::exclusive_scan(nullptr, tb, (const uint32_t*)d_cnt, (uint32_t*)d_off, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), ctx->stream));
+    DSS(dp_dev_malloc(&d_tmp, tb + 64));
+    DSS(rocprim::exclusive_scan(d_tmp, tb, (const uint32_t*)d_cnt, (uint32_t*)d_off, 0u, (size_t)nw + 1, rocprim::plus<uint32_t>(), ctx->stream));
+    uint32_t total = 0;
+    DSS(hipMemcpyAsync(&total, (const uint32_t*)d_off + nw, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DSS(dp_stream_sync(ctx));  // (the one wait of the chain besides the last: the candidates' total sizes their array)
+    DSS(dp_dev_malloc(&d_cand, (size_t)total * 4 + 64));
+    hipLaunchKernelGGL(ss_cand_multi_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, packed, M, (const uint32_t*)d_bits,
+                       (uint32_t*)nullptr, (const uint32_t*)d_off, (uint32_t*)d_cand);
+    DSS(hipGetLastError());
+    // [win_off n_reads + 1 | best nw | off nw + 1 | cand total] in ordinary host memory of the context, as dp_single_seed_candidates
+    ctx->ss_host.resize(headWords + (size_t)2 * nw + 1 + total + 16);
+    uint32_t* h = ctx->ss_host.data();
+    memcpy(h, winOff.data(), headWords * 4);
+    uint32_t* hb = h + headWords;
+    DSS(hipMemcpyAsync(hb, d_best, (size_t)nw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DSS(hipMemcpyAsync(hb + nw, d_off, ((size_t)nw + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (total) DSS(hipMemcpyAsync(hb + 2 * (size_t)nw + 1, d_cand, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DSS(dp_stream_sync(ctx));
+#undef DSS
+    cleanup();
+    out->n_windows = nw;
+    out->n_reads = n_reads;
+    out->best = hb;
+    out->cand_off = hb + nw;
+    out->cand = hb + 2 * (size_t)nw + 1;
+    out->win_off = h;
+    return DP_OK;
+}
+
 int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_off, const uint32_t* w_len, uint32_t nw, int k,
                         dp_chain_batch* out, int phase, int32_t* thr_io) {
     if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_map_windows before dp_round_begin");

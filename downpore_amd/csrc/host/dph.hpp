@@ -757,6 +757,7 @@ struct MapParams {  // flag table commands/map.go:19-20
     i64 querySize = 1000, minLength = 500, chunkSize = 10000, seedRate = 40;
     int numWorkers = 4;
     int indexLayout = 0;  // reference index: 0 = auto (sparse when the dense one would not fit the device), 1 = dense, 2 = sparse
+    bool allSequences = false;  // map against every sequence of the reference file, not the first one only
 };
 struct MapStats {
     uint64_t n_chunks = 0, n_seeds = 0, n_windows = 0, n_chains = 0, n_batches = 0;
@@ -769,8 +770,8 @@ struct MapStats {
     int64_t index_layout = 0, index_bytes = 0, dense_estimate = 0, device_total = 0, hits = 0, index_builds = 0;
     int64_t regimes[4] = {0, 0, 0, 0};
 };
-// Runs the whole command on HIP device `device`: reference = first sequence of refSet (top-level, cache=false), reads
-// top-level.  paf receives the PAF lines (read order), errText the reference's stderr lines.
+// Runs the whole command on HIP device `device`: reference = first sequence of refSet (top-level, cache=false; every sequence of it
+// with p.allSequences), reads top-level.  paf receives the PAF lines (read order), errText the reference's stderr lines.
 size_t releaseMapStaging();  // dph_release_caches: the staging block kept for the process's next map command
 int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
            MapStats* stats, std::string& error);

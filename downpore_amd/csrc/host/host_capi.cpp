@@ -910,7 +910,7 @@ extern "C" const char* dph_finalcheck(void* readsH, int k, int64_t overlapSize, 
 }
 
 // ---- `downpore map` ------------------------------------------------------------------------------------------------
-// params: circular,k,querySize,minLength,chunkSize,seedRate[,index layout].  Returns a handle holding paf/err text, or NULL.
+// params: circular,k,querySize,minLength,chunkSize,seedRate[,index layout[,all sequences]].  Returns a handle holding paf/err text, or NULL.
 namespace {
 struct MapH {
     std::string paf, err;
@@ -918,17 +918,22 @@ struct MapH {
 };
 }  // namespace
 extern "C" void* dph_map_run_ex(void* refH, void* readsH, const int64_t* params, int n_params, int device) {
-    if (!refH || !readsH || !params || (n_params != 6 && n_params != 7)) {
-        g_err = "dph_map_run_ex: bad arguments (6 or 7 parameters)";
+    if (!refH || !readsH || !params || n_params < 6 || n_params > 8) {
+        g_err = "dph_map_run_ex: bad arguments (6, 7 or 8 parameters)";
         return nullptr;
     }
-    if (n_params == 7 && (params[6] < 0 || params[6] > 2)) {  // (refused before any device call)
+    if (n_params >= 7 && (params[6] < 0 || params[6] > 2)) {  // (refused before any device call)
         g_err = "dph_map_run_ex: index layout " + std::to_string((long long)params[6]) + " (0 = auto, 1 = dense, 2 = sparse)";
+        return nullptr;
+    }
+    if (n_params == 8 && params[7] != 0 && params[7] != 1) {
+        g_err = "dph_map_run_ex: all sequences " + std::to_string((long long)params[7]) + " (0 = the first sequence of the reference, 1 = all of them)";
         return nullptr;
     }
     MapH* h = new MapH();
     MapParams p;
-    p.indexLayout = n_params == 7 ? (int)params[6] : 0;
+    p.indexLayout = n_params >= 7 ? (int)params[6] : 0;
+    p.allSequences = n_params == 8 && params[7] == 1;
     p.circular = params[0] != 0;
     p.k = (int)params[1];
     p.querySize = params[2];

@@ -171,12 +171,13 @@ int main(int argc, char** argv) {
              "Maximum number of queries per batch (if max seeds not reached)", "Minimum proportion of seeds that must match each query",
              "Number of worker threads to spawn", "Fasta/fastq input file", "File containing values to use during seed selection.",
              "Whether to cache all reads in memory"});
-    mp.make({"input", "reference", "circular", "k", "query_size", "min_length", "chunk_size", "seed_rate", "num_workers"},
-            {"", "", "true", "11", "1000", "500", "10000", "40", "4"},
+    mp.make({"input", "reference", "circular", "k", "query_size", "min_length", "chunk_size", "seed_rate", "num_workers", "all_sequences"},
+            {"", "", "true", "11", "1000", "500", "10000", "40", "4", "false"},
             {"Fasta/fastq input file", "A fasta file containing a reference sequence to align against",
              "Whether the reference genome is circular", "Length of seeds in bases", "The number of bases to query at a time",
              "The minimum sequence size to generate queries from", "The number of bases for reference index chunks",
-             "The maximum number of bases between seeds in the reference", "The number of worker process to use for mapping"});
+             "The maximum number of bases between seeds in the reference", "The number of worker process to use for mapping",
+             "Whether to map against every sequence of the reference file, not only the first"});
     tr.make({"input", "k", "chunk_size", "middle_threshold", "discard_middle", "check_reads", "adapter_threshold", "extra_end_trim",
              "extra_middle_trim", "tag_adapters", "verbosity", "front_adapters", "back_adapters", "num_workers", "himem", "demultiplex",
              "require_pairs", "determine_adapters"},
@@ -229,6 +230,7 @@ int main(int argc, char** argv) {
         p.querySize = parseInt(mp.args["query_size"], ok);
         p.chunkSize = parseInt(mp.args["chunk_size"], ok);
         p.seedRate = parseInt(mp.args["seed_rate"], ok);
+        p.allSequences = parseBool(mp.args["all_sequences"]);
         if (!ok) return 1;
         ReadSet ref, reads;
         if (!ReadSet::fromFile(mp.args["reference"], 0, false, ref, err) || !ReadSet::fromFile(mp.args["input"], p.minLength, false, reads, err)) {

@@ -28,6 +28,7 @@ struct Mapping {  // mapping/mapping.go:11-20
     i64 Start = 0, End = 0, QueryOffset = 0, QueryInset = 0;
     bool RC = false;
     i64 ids = 0;
+    int ref = 0;  // the reference sequence of the chunk the chain was found in (`-all_sequences`; 0 otherwise)
 };
 
 // Go sort.Sort stand-in (DESIGN.md canonical semantics): insertion sort <= 12 elements, stable sort above.
@@ -44,7 +45,8 @@ void goSort(std::vector<T>& v, Less less) {
 struct Chunk {  // an indexed reference chunk (seeds.SeedSequence of a reference.SubSequence)
     const int32_t* seg = nullptr;
     int n = 0;
-    i64 offset = 0, inset = 0;
+    i64 offset = 0, inset = 0;  // within its reference sequence
+    int ref = 0;                // which reference sequence it was cut from
 };
 
 struct WindowReq {
@@ -71,8 +73,8 @@ struct MapperImpl {
     int k = 11;
     i64 edgeSize = 1000;
     bool circular = true;
-    i64 refLen = 0;
-    std::string refName;
+    std::vector<i64> refLens;  // the reference sequences mapped against: the first of the file, or all of them in file order
+    std::vector<std::string> refNames;
     std::vector<Chunk> chunks;
     std::vector<int32_t> chunkSegs;  // host copy of the chunk scan
     Sched* sched = nullptr;
@@ -120,10 +122,11 @@ void coroTrampoline(void* arg) {
 
 // ---- mapping.go:131-160
 bool MapperImpl::isConsistent(const Mapping* left, const Mapping* right) const {
+    if (left->ref != right->ref) return false;  // positions on two reference sequences have no distance
     if (left->RC != right->RC) return false;
     const i64 expectedDistance = right->QueryOffset - left->queryLen + left->QueryInset;
     i64 distance = !left->RC ? right->Start - left->End : left->Start - right->End;
-    if (circular && distance < -50) distance += refLen;
+    if (circular && distance < -50) distance += refLens[(size_t)left->ref];
     if (distance < 50 && expectedDistance < 50 && distance > -50) return true;
     if (distance < 500) return (expectedDistance < (distance * 3) / 2 && expectedDistance > (distance * 2) / 3);
     if (distance > 5000) return (expectedDistance < (distance * 10) / 9 && expectedDistance > (distance * 9) / 10);
@@ -194,6 +197,7 @@ void MapperImpl::matchPairs(std::vector<Mapping*>& openA, std::vector<Mapping*>&
                 c->QueryInset = qInset;
                 c->RC = ra->RC;
                 c->ids = ra->ids + rb->ids;
+                c->ref = ra->ref;
                 matchedNil = false;
                 matched.push_back(c);
                 openA[(size_t)i] = openA.back();
@@ -441,6 +445,7 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
         const i64 sqOffset = s == 0 ? vOffset : vInset, sqInset = s == 0 ? vInset : vOffset;
         for (const auto& ch : R.chains[s]) {
             const Chunk& c = chunks[ch.target];
+            const i64 refLen = refLens[(size_t)c.ref];
             i64 start = c.offset + segSeedOffset(c.seg, ch.b[0], k);
             const i64 end = refLen - c.inset - segSeedOffsetFromEnd(c.seg, c.n, ch.b.back(), k);
             if (circular && start > refLen) start -= refLen;
@@ -460,16 +465,17 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
             mp->End = end;
             mp->RC = s == 1;
             mp->ids = basesCoveredB(c.seg, ch.b, k);
+            mp->ref = c.ref;
             results.push_back(mp);
         }
     }
     (void)qlen;
     if (results.size() > 1) {  // :590-608
-        goSort(results, [](Mapping* x, Mapping* y) { return x->Start < y->Start; });
+        goSort(results, [](Mapping* x, Mapping* y) { return x->ref != y->ref ? x->ref < y->ref : x->Start < y->Start; });
         for (i64 i = (i64)results.size() - 1; i > 0; i--) {
             Mapping* ra = results[(size_t)(i - 1)];
             Mapping* rb = results[(size_t)i];
-            if (ra->RC == rb->RC && rb->Start < ra->End) {
+            if (ra->ref == rb->ref && ra->RC == rb->RC && rb->Start < ra->End) {
                 if (ra->End - ra->Start > rb->End - rb->Start) {
                     results[(size_t)i] = results.back();
                     results.pop_back();
@@ -486,12 +492,13 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
 
 // ---- AsString mapping.go:112-122
 std::string MapperImpl::asString(const Mapping& m, const std::string& qname, i64 qlen) const {
+    const i64 refLen = refLens[(size_t)m.ref];
     i64 mappedLength = m.End - m.Start;
     if (circular && mappedLength < 0) mappedLength = refLen - m.Start + m.End;
     char buf[512];
     snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%s\t", (long long)qlen, (long long)m.QueryOffset, (long long)(qlen - m.QueryInset),
              m.RC ? "-" : "+");
-    std::string s = qname + buf + refName;
+    std::string s = qname + buf + refNames[(size_t)m.ref];
     snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld\t%lld\t255", (long long)refLen, (long long)m.Start, (long long)m.End,
              (long long)m.ids, (long long)mappedLength);
     return s + buf;
@@ -505,7 +512,7 @@ std::string MapperImpl::asString(const Mapping& m, const std::string& qname, i64
 bool handIsConsistent(const i64* l, const i64* r, bool circular, i64 refLen) {
     MapperImpl m;
     m.circular = circular;
-    m.refLen = refLen;
+    m.refLens.assign(1, refLen);
     Mapping L, R;
     L.RC = l[0] != 0;
     L.queryLen = l[1];
@@ -588,26 +595,68 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         return -1;
     }
     const int k = p.k;
-    const i64 refLen = refSet.length(0);
-    const char* ref = refSet.seq(0);
+    // the sequences mapped against: the first of the reference file (commands/map.go:34-36) or, with -all_sequences, every top-level
+    // sequence of it in file order (one seed index, chunk ids running on from sequence to sequence)
+    const size_t T = p.allSequences ? refSet.size() : 1;
+    std::vector<i64> refLens(T);
+    for (size_t c = 0; c < T; c++) refLens[c] = refSet.length(c);
     // positions in the reference travel as 32-bit signed ints (chunk offsets, the reverse strand, the PAF's target fields): a longer
     // sequence is refused before anything is packed or allocated on the device
-    if (refLen > (i64)0x7fffffff) {
-        error = "map: the reference sequence is " + std::to_string((long long)refLen) + " bases long; at most 2147483647 are supported";
-        return DP_ERR_ARG;
+    for (size_t c = 0; c < T; c++)
+        if (refLens[c] > (i64)0x7fffffff) {
+            error = p.allSequences ? "map: the reference sequence " + refSet.names[c] + " is " + std::to_string((long long)refLens[c]) +
+                                         " bases long; at most 2147483647 are supported"
+                                   : "map: the reference sequence is " + std::to_string((long long)refLens[c]) +
+                                         " bases long; at most 2147483647 are supported";
+            return DP_ERR_ARG;
+        }
+    if (p.seedRate > 0 && p.chunkSize * 10 > p.querySize) {  // seed windows and chunks are numbered in 32 bits
+        const i64 step = p.chunkSize * 10 - p.querySize;
+        unsigned long long nWin = 0, nChk = 0;
+        for (size_t c = 0; c < T; c++) {
+            const i64 L = refLens[c];
+            if (L > p.seedRate) nWin += (unsigned long long)((L - 1) / p.seedRate);
+            for (i64 j = 0; j < 10; j++)
+                if (j * p.chunkSize < L - p.chunkSize / 2) nChk += (unsigned long long)((L - p.chunkSize / 2 - j * p.chunkSize + step - 1) / step);
+            nChk += p.circular ? 1 : 0;
+        }
+        if (nWin > 0xffffffffull || nChk > 0xffffffffull) {
+            error = "map: the reference has " + std::to_string(nWin) + " seed windows and " + std::to_string(nChk) +
+                    " chunks; fewer than 4294967296 of each are supported";
+            return DP_ERR_ARG;
+        }
     }
     if (p.indexLayout < 0 || p.indexLayout > 2) {
         error = "map: reference index layout " + std::to_string(p.indexLayout) + " (0 = auto, 1 = dense, 2 = sparse)";
         return DP_ERR_ARG;
     }
-    // ---- device read set: [0] reference, [1] circular join chunk, then (forward, reverse complement) of every read.  Its host
+    // ---- device read set: [0] reference, [1] circular join chunk, then (forward, reverse complement) of every read; with
+    // -all_sequences [0 .. T) the reference sequences, then the join chunk of every sequence that has one, then the reads.  Its host
     // staging copy is made by a thread of its own while the device computes the reference's k-mer table
     std::vector<i64> off(1, 0);
-    std::string join;
-    if (p.circular) join = std::string(ref + (refLen - p.querySize), (size_t)p.querySize) + std::string(ref, (size_t)p.querySize);
+    std::vector<std::string> joins;
+    std::vector<int> joinOf(T, -1);  // a sequence's join chunk among `joins`
+    std::string joinNotes;
+    for (size_t c = 0; c < T; c++) {
+        const char* ref = refSet.seq(c);
+        const i64 refLen = refLens[c];
+        if (!p.allSequences) {  // (a slot of its own even when it is empty)
+            joinOf[c] = 0;
+            joins.push_back(p.circular ? std::string(ref + (refLen - p.querySize), (size_t)p.querySize) + std::string(ref, (size_t)p.querySize) : std::string());
+        } else if (p.circular && refLen >= p.querySize) {
+            joinOf[c] = (int)joins.size();
+            joins.push_back(std::string(ref + (refLen - p.querySize), (size_t)p.querySize) + std::string(ref, (size_t)p.querySize));
+        } else if (p.circular) {  // (the reference would slice out of range, mapping.go:93-95)
+            joinNotes += "Sequence " + refSet.names[c] + " (" + std::to_string((long long)refLen) + " bases) is shorter than query_size " +
+                         std::to_string((long long)p.querySize) + ": no circular join chunk\n";
+        }
+    }
+    const uint32_t firstPaired = (uint32_t)(T + joins.size());  // device reads before the (forward, reverse complement) pairs
     // one staging buffer [reference | join chunk | all reads]; the reads are one contiguous block of the read set, copied
     // (and its pages first touched) by the worker pool in 4 MiB pieces
-    const size_t head = (size_t)refLen + join.size();
+    size_t head = 0;
+    for (size_t c = 0; c < T; c++) head += (size_t)refLens[c];
+    for (const std::string& j : joins) head += j.size();
     const size_t readBytes = reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
     // Round 6: the reads cross PCIe the way the reference holds them - 2 bits per base (sequence.packedSequence) - packed here by
     // the worker pool straight into a pinned block in the device's own layout (every read on a 16-byte boundary) and put in place by
@@ -626,12 +675,12 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         }
     } pinnedBack{pinned};
     if (packedUpload) {
-        const size_t n = 2 + reads.size();
+        const size_t n = firstPaired + reads.size();
         plens.resize(n);
         poff.assign(n + 1, 0);
-        plens[0] = (uint32_t)refLen;
-        plens[1] = (uint32_t)join.size();
-        for (size_t r = 0; r < reads.size(); r++) plens[2 + r] = (uint32_t)reads.length(r);
+        for (size_t c = 0; c < T; c++) plens[c] = (uint32_t)refLens[c];
+        for (size_t j = 0; j < joins.size(); j++) plens[T + j] = (uint32_t)joins[j].size();
+        for (size_t r = 0; r < reads.size(); r++) plens[firstPaired + r] = (uint32_t)reads.length(r);
         for (size_t r = 0; r < n; r++) poff[r + 1] = poff[r] + ((((uint64_t)plens[r] + 3) / 4 + 15) & ~(uint64_t)15);
         pinned = (uint8_t*)dp_host_alloc((size_t)poff[n] + 64);
         if (!pinned) {
@@ -643,8 +692,8 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     std::unique_ptr<char[]> staging = packedUpload ? std::unique_ptr<char[]>() : stagingTake(head + readBytes + 1, &stagingCap);
     std::thread concatThread([&] {
         if (packedUpload) {
-            packBases(ref, (size_t)refLen, pinned + poff[0], packScalar);
-            packBases(join.data(), join.size(), pinned + poff[1], packScalar);
+            for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned + poff[c], packScalar);
+            for (size_t j = 0; j < joins.size(); j++) packBases(joins[j].data(), joins[j].size(), pinned + poff[T + j], packScalar);
             // pieces of about 2 M bases: whole reads
             std::vector<size_t> cut(1, 0);
             i64 acc = 0;
@@ -657,14 +706,18 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             }
             if (cut.back() != reads.size()) cut.push_back(reads.size());
             parallelFor(cut.size() - 1, [&](size_t i) {
-                for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(reads.seq(r), (size_t)reads.length(r), pinned + poff[2 + r], packScalar);
+                for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(reads.seq(r), (size_t)reads.length(r), pinned + poff[firstPaired + r], packScalar);
             });
             return;
         }
-        memcpy(staging.get(), ref, (size_t)refLen);
-        memcpy(staging.get() + refLen, join.data(), join.size());
-        off.push_back((i64)refLen);
-        off.push_back((i64)head);
+        for (size_t c = 0; c < T; c++) {
+            memcpy(staging.get() + off.back(), refSet.seq(c), (size_t)refLens[c]);
+            off.push_back(off.back() + refLens[c]);
+        }
+        for (const std::string& j : joins) {
+            memcpy(staging.get() + off.back(), j.data(), j.size());
+            off.push_back(off.back() + (i64)j.size());
+        }
         const char* src = reads.size() ? reads.seq(0) : nullptr;
         const size_t piece = (size_t)4 << 20, nPieces = (readBytes + piece - 1) / piece;
         char* dst = staging.get() + head;
@@ -700,6 +753,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     if (rc) return fail(rc);
     mark("reference upload + value table");
     errText += "K-mer counting complete. Preparing to start indexing and querying...\n";
+    errText += joinNotes;
 
     // ---- AddSingleSeeds seeds/seeds.go:160-200 on the (top-level) reference, host, sequential - on a thread of its own while
     // this one concatenates the reads and the device uploads and packs them (neither needs the seeds)
@@ -709,16 +763,26 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     // (dp_single_seed_candidates: the reference and the value table are resident right now); the thread below then walks the
     // windows in order and probes five or six candidates per window instead of seed_rate k-mers (3.9 s -> 0.1 s per 375 Mb of
     // reference).  DP_MAP_SEEDS_HOST=1: the whole walk on the host as before.
+    // -all_sequences: AddSingleSeeds for one sequence after the other on the ONE index; the device numbers the windows of all sequences
+    // in sequence order and "best of any window" is over all of them (dp_single_seed_candidates_multi), so the walk below is the same.
     dp_single_seed_batch ssb;
     memset(&ssb, 0, sizeof ssb);
     bool deviceSeeds = false;
-    {
-        if (!dph_tune("map_seeds_host", 0) && refLen < ((i64)1 << 32)) {  // (tests: AddSingleSeeds walked on the host)
+    if (!dph_tune("map_seeds_host", 0)) {  // (tests: AddSingleSeeds walked on the host)
+        if (p.allSequences) {
+            dp_single_seed_multi_batch mb;
+            rc = dp_single_seed_candidates_multi(ctx, 0, (uint32_t)T, k, p.seedRate, &mb);
+            if (rc) return fail(rc);
+            ssb.n_windows = mb.n_windows;
+            ssb.best = mb.best;
+            ssb.cand_off = mb.cand_off;
+            ssb.cand = mb.cand;
+        } else {
             rc = dp_single_seed_candidates(ctx, 0, k, p.seedRate, &ssb);
             if (rc) return fail(rc);
-            deviceSeeds = true;
-            mark("single-seed candidates (device)");
         }
+        deviceSeeds = true;
+        mark("single-seed candidates (device)");
     }
     std::thread seedThread([&] {
         if (deviceSeeds) {
@@ -735,49 +799,53 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             return;
         }
         const uint32_t mask = (uint32_t)(((uint64_t)1 << (2 * k)) - 1);
-        const int finalLen = (int)(refLen % 4);  // top-level sequence: 0 when len%4 == 0 (sequence.go:70,88)
-        const i64 skipBack = 4 - finalLen;
-        auto code = [&](i64 pos) -> uint32_t { return pos < refLen ? baseCode((unsigned char)ref[pos]) : 0u; };  // zero padding
-        auto kmerAt = [&](i64 pos) {
-            uint32_t v = 0;
-            for (int j = 0; j < k; j++) v = (v << 2) | code(pos + j);
-            return v;
-        };
-        for (i64 i = 0; i < refLen - p.seedRate; i += p.seedRate) {
-            // CountKmersBetween(i, i+seedRate, 1, ...) == 0 ?  (sequence.go:332-337 + asm:81-203: whole bytes only,
-            // parent's skipBack, do-while group loop)
-            const i64 startB = (i + 3) / 4, endB = (i + p.seedRate) / 4;
-            const i64 nb = endB - startB;
-            const i64 nk = 4 * (nb - 1) - skipBack - k + 1;
-            i64 groups = (nk & ~(i64)3) / 4;
-            if (groups < 1) groups = 1;
-            const i64 P = 4 + 4 * groups + (nk & 3);
-            bool any = false;
-            {
-                const i64 p0 = startB * 4;
-                uint32_t km = kmerAt(p0);
-                for (i64 j = 0; j < P; j++) {
-                    if (j) km = ((km << 2) | code(p0 + j + k - 1)) & mask;
-                    if (index.isSeed(km)) {
-                        any = true;
-                        break;
+        for (size_t sq = 0; sq < T; sq++) {  // (one sequence after the other on the one index)
+            const char* ref = refSet.seq(sq);
+            const i64 refLen = refLens[sq];
+            const int finalLen = (int)(refLen % 4);  // top-level sequence: 0 when len%4 == 0 (sequence.go:70,88)
+            const i64 skipBack = 4 - finalLen;
+            auto code = [&](i64 pos) -> uint32_t { return pos < refLen ? baseCode((unsigned char)ref[pos]) : 0u; };  // zero padding
+            auto kmerAt = [&](i64 pos) {
+                uint32_t v = 0;
+                for (int j = 0; j < k; j++) v = (v << 2) | code(pos + j);
+                return v;
+            };
+            for (i64 i = 0; i < refLen - p.seedRate; i += p.seedRate) {
+                // CountKmersBetween(i, i+seedRate, 1, ...) == 0 ?  (sequence.go:332-337 + asm:81-203: whole bytes only,
+                // parent's skipBack, do-while group loop)
+                const i64 startB = (i + 3) / 4, endB = (i + p.seedRate) / 4;
+                const i64 nb = endB - startB;
+                const i64 nk = 4 * (nb - 1) - skipBack - k + 1;
+                i64 groups = (nk & ~(i64)3) / 4;
+                if (groups < 1) groups = 1;
+                const i64 P = 4 + 4 * groups + (nk & 3);
+                bool any = false;
+                {
+                    const i64 p0 = startB * 4;
+                    uint32_t km = kmerAt(p0);
+                    for (i64 j = 0; j < P; j++) {
+                        if (j) km = ((km << 2) | code(p0 + j + k - 1)) & mask;
+                        if (index.isSeed(km)) {
+                            any = true;
+                            break;
+                        }
                     }
                 }
-            }
-            if (!any) {
-                const i64 end = i + p.seedRate;
-                uint32_t km = kmerAt(i);
-                double bestValue = values[km];
-                uint32_t best = km;
-                for (i64 j = i + k; j < end; j++) {
-                    km = ((km << 2) | code(j)) & mask;
-                    const double v = values[km];
-                    if (v > bestValue) {
-                        bestValue = v;
-                        best = km;
+                if (!any) {
+                    const i64 end = i + p.seedRate;
+                    uint32_t km = kmerAt(i);
+                    double bestValue = values[km];
+                    uint32_t best = km;
+                    for (i64 j = i + k; j < end; j++) {
+                        km = ((km << 2) | code(j)) & mask;
+                        const double v = values[km];
+                        if (v > bestValue) {
+                            bestValue = v;
+                            best = km;
+                        }
                     }
+                    index.addSeedKmer(best);
                 }
-                index.addSeedKmer(best);
             }
         }
     });
@@ -808,54 +876,67 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             if (st) stagingPut(std::move(st), cap);
         }
     } stagingBack{ctx, staging, stagingCap};
-    rc = packedUpload  ? dp_reads_upload_packed_rc(ctx, pinned, plens.data(), (uint32_t)plens.size(), 2)
-         : asyncUpload ? dp_reads_upload_rc_begin(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), 2, 2)
-                       : dp_reads_upload_rc(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), 2);
+    rc = packedUpload  ? dp_reads_upload_packed_rc(ctx, pinned, plens.data(), (uint32_t)plens.size(), firstPaired)
+         : asyncUpload ? dp_reads_upload_rc_begin(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired, firstPaired)
+                       : dp_reads_upload_rc(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired);
     if (rc) return fail(rc);
     mark(packedUpload ? "packed upload + reverse strands" : asyncUpload ? "upload begun (reference packed)" : "upload + pack (both strands)");
     seedThread.join();
     mark("AddSingleSeeds (waited for)");
-    rc = dp_round_begin(ctx, k, index.seedMap.data(), (uint32_t)index.seedMap.size());
-    if (rc) return fail(rc);
-
-    // ---- chunk schedule mapping.go:79-96, canonical generation order
+    // ---- chunk schedule mapping.go:79-96, canonical generation order; sequence after sequence, the chunk ids running on
     MapperImpl M;
     M.ctx = ctx;
     M.k = k;
     M.edgeSize = p.querySize;
     M.circular = p.circular;
-    M.refLen = refLen;
-    M.refName = refSet.names[0];
+    M.refLens = refLens;
+    M.refNames.assign(refSet.names.begin(), refSet.names.begin() + (i64)T);
     std::vector<dp_scan_item> items;
     std::vector<std::pair<i64, i64>> meta;  // offset, inset per chunk
-    for (i64 j = 0; j < 10; j++) {
-        const i64 start = j * p.chunkSize, step = p.chunkSize * 10 - p.querySize;
-        for (i64 i = start; i < refLen - p.chunkSize / 2; i += step) {
-            i64 end = i + p.chunkSize;
-            if (i >= refLen) end = refLen;
-            if (end > refLen) end = refLen;  // SubSequence clamps
+    std::vector<int> chunkRef;              // its reference sequence
+    for (size_t sq = 0; sq < T; sq++) {
+        const i64 refLen = refLens[sq];
+        for (i64 j = 0; j < 10; j++) {
+            const i64 start = j * p.chunkSize, step = p.chunkSize * 10 - p.querySize;
+            for (i64 i = start; i < refLen - p.chunkSize / 2; i += step) {
+                i64 end = i + p.chunkSize;
+                if (i >= refLen) end = refLen;
+                if (end > refLen) end = refLen;  // SubSequence clamps
+                dp_scan_item it;
+                it.read = (uint32_t)sq;
+                it.start = (uint32_t)i;
+                it.n_kmers = (uint32_t)std::max<i64>(0, (end - i) - k + 1);
+                it.min_seeds = 0;
+                items.push_back(it);
+                meta.push_back({i, refLen - (end - 1)});  // SubSequence: offset+start, inset + length - (end-1)
+                chunkRef.push_back((int)sq);
+            }
+        }
+        if (p.circular && joinOf[sq] >= 0) {
+            // Append(...) is a fresh top-level sequence of 2*edge bases: len%4==0 loses its last 4 k-mers (asm:88-96)
+            const i64 jl = (i64)joins[(size_t)joinOf[sq]].size();
+            i64 nk = jl - k + 1;
+            if (jl % 4 == 0) nk -= 4;
             dp_scan_item it;
-            it.read = 0;
-            it.start = (uint32_t)i;
-            it.n_kmers = (uint32_t)std::max<i64>(0, (end - i) - k + 1);
+            it.read = (uint32_t)(T + (size_t)joinOf[sq]);
+            it.start = 0;
+            it.n_kmers = (uint32_t)std::max<i64>(0, nk);
             it.min_seeds = 0;
             items.push_back(it);
-            meta.push_back({i, refLen - (end - 1)});  // SubSequence: offset+start, inset + length - (end-1)
+            meta.push_back({refLen - p.querySize, refLen - (p.querySize - 1)});  // offset of the first part, inset of the second
+            chunkRef.push_back((int)sq);
         }
     }
-    if (p.circular) {
-        // Append(...) is a fresh top-level sequence of 2*edge bases: len%4==0 loses its last 4 k-mers (asm:88-96)
-        const i64 jl = (i64)join.size();
-        i64 nk = jl - k + 1;
-        if (jl % 4 == 0) nk -= 4;
-        dp_scan_item it;
-        it.read = 1;
-        it.start = 0;
-        it.n_kmers = (uint32_t)std::max<i64>(0, nk);
-        it.min_seeds = 0;
-        items.push_back(it);
-        meta.push_back({refLen - p.querySize, refLen - (p.querySize - 1)});  // offset of the first part, inset of the second
+    if (items.empty()) {  // no sequence is long enough for a chunk: an empty index matches nothing, every read is unmapped
+        if (stats) stats->n_seeds = index.seedMap.size(), stats->t_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tRun0;
+        char line[160];
+        snprintf(line, sizeof line, "Uniquely mapped: 0\nMultiple mappings: 0\ntotal: 0\nUnmapped: %lld\n", (long long)reads.size());
+        errText += line;
+        dp_ctx_destroy(ctx), ctx = nullptr;
+        return 0;
     }
+    rc = dp_round_begin(ctx, k, index.seedMap.data(), (uint32_t)index.seedMap.size());
+    if (rc) return fail(rc);
     dp_seedseq_batch sb;
     rc = dp_scan(ctx, items.data(), (uint32_t)items.size(), &sb);
     if (rc) return fail(rc);
@@ -870,6 +951,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         M.chunks[i].n = (int)(sb.seg_off[i + 1] - sb.seg_off[i]);
         M.chunks[i].offset = meta[i].first;
         M.chunks[i].inset = meta[i].second;
+        M.chunks[i].ref = chunkRef[i];
     }
     // ---- DP_MAP_SHARDS=N: the reference index spread over N contexts (DP_MAP_DEVICES=0,1,..: their GPUs, round robin;
     // default all on this one) - what BASELINE config 5 does with a 3 Gb reference on 8 GPUs.  Shard s holds the chunks
@@ -1108,7 +1190,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             const size_t nextRead = readOf(nextSeq);
             if (nextRead >= waitedBelow) {  // (the block may still be on its way to the device: dp_reads_upload_rc_begin)
                 const size_t upto = std::min(nReads, (nextRead / BL + 1) * BL);
-                rc = dp_reads_upload_wait(ownerCtx, (uint32_t)(2 + upto));  // (host reads 0 and 1: the reference and its join chunk)
+                rc = dp_reads_upload_wait(ownerCtx, (uint32_t)(firstPaired + upto));  // (the host reads before them: the reference and its join chunks)
                 if (rc) return fail(rc);
                 waitedBelow = upto;
             }
@@ -1149,7 +1231,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         for (auto& tp : live) {
             Task& t = *tp;
             const WindowReq& q = t.req;
-            const uint32_t fr = 2 + 2 * q.read, rr = fr + 1;
+            const uint32_t fr = firstPaired + 2 * q.read, rr = fr + 1;
             const i64 L = t.L, wl = q.b - q.a;
             dp_scan_item f, r;
             f.read = fr;

@@ -49,6 +49,16 @@ class ChainBatch(C.Structure):
                 ("kernel_ms", C.c_double), ("alg_bytes", C.c_double)]
 
 
+class SingleSeedBatch(C.Structure):  # dp_single_seed_batch
+    _fields_ = [("n_windows", C.c_uint32), ("best", C.POINTER(C.c_uint32)), ("cand_off", C.POINTER(C.c_uint32)),
+                ("cand", C.POINTER(C.c_uint32))]
+
+
+class SingleSeedMultiBatch(C.Structure):  # dp_single_seed_multi_batch
+    _fields_ = [("n_windows", C.c_uint32), ("n_reads", C.c_uint32), ("best", C.POINTER(C.c_uint32)),
+                ("cand_off", C.POINTER(C.c_uint32)), ("cand", C.POINTER(C.c_uint32)), ("win_off", C.POINTER(C.c_uint32))]
+
+
 class CandidateBatch(C.Structure):  # dp_candidate_batch
     _fields_ = [("n_queries", C.c_uint32), ("cand_off", C.POINTER(C.c_uint64)), ("cand", C.POINTER(C.c_uint32)),
                 ("meta", C.POINTER(C.c_uint32))]
@@ -64,7 +74,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_reads_count", "dp_reads_total_bases", "dp_kmer_histogram", "dp_kmer_values", "dp_round_begin", "dp_scan", "dp_scan_prepare", "dp_scan_reads", "dp_index_build",
            "dp_find_overlaps", "dp_query_prestage", "dp_map_windows", "dp_index_posting_row", "dp_index_seedset_row", "dp_scan_device_buffers",
            "dp_scan_import_segments", "dp_values_upload", "dp_select_seeds", "dp_reads_upload_rc", "dp_consensus_align", "dp_scan_release", "dp_consensus_paf", "dp_fetch_overlaps", "dp_select_windows", "dp_values_download",
-    "dp_values_download_codes", "dp_values_download_codes8", "dp_index_build_chunked", "dp_index_prechain", "dp_index_prechained", "dp_index_chunks", "dp_scan_fetch_mode", "dp_scan_fetch_segments", "dp_set_stream_wait", "dp_set_kernel_timing", "dp_index_meta", "dp_index_set_global", "dp_map_windows_shard", "dp_single_seed_candidates", "dp_comm_unique_id", "dp_comm_init", "dp_comm_init_local", "dp_quality_upload",
+    "dp_values_download_codes", "dp_values_download_codes8", "dp_index_build_chunked", "dp_index_prechain", "dp_index_prechained", "dp_index_chunks", "dp_scan_fetch_mode", "dp_scan_fetch_segments", "dp_set_stream_wait", "dp_set_kernel_timing", "dp_index_meta", "dp_index_set_global", "dp_map_windows_shard", "dp_single_seed_candidates", "dp_single_seed_candidates_multi", "dp_comm_unique_id", "dp_comm_init", "dp_comm_init_local", "dp_quality_upload",
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
@@ -211,6 +221,27 @@ class Context:
         out = np.zeros(4 ** k, dtype=np.float64)
         self._chk(self.L.dp_kmer_values(self.h, k, out.ctypes.data))
         return out
+
+    # ---- A18: the parallel part of AddSingleSeeds
+    def single_seed_candidates(self, read, k, seed_rate):
+        """dp_single_seed_candidates for one resident read (its value table resident): dict best, cand_off, cand"""
+        b = SingleSeedBatch()
+        self.L.dp_single_seed_candidates.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int64, C.POINTER(SingleSeedBatch)]
+        self._chk(self.L.dp_single_seed_candidates(self.h, read, k, seed_rate, C.byref(b)))
+        n = b.n_windows
+        off = _arr(b.cand_off, n + 1, np.uint32) if n else np.zeros(1, dtype=np.uint32)
+        return dict(best=_arr(b.best, n, np.uint32), cand_off=off, cand=_arr(b.cand, off[-1], np.uint32))
+
+    def single_seed_candidates_multi(self, first_read, n_reads, k, seed_rate):
+        """dp_single_seed_candidates_multi for a run of resident reads on one seed index: dict best, cand_off, cand, win_off"""
+        b = SingleSeedMultiBatch()
+        self.L.dp_single_seed_candidates_multi.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int64,
+                                                           C.POINTER(SingleSeedMultiBatch)]
+        self._chk(self.L.dp_single_seed_candidates_multi(self.h, first_read, n_reads, k, seed_rate, C.byref(b)))
+        n = b.n_windows
+        off = _arr(b.cand_off, n + 1, np.uint32) if n else np.zeros(1, dtype=np.uint32)
+        return dict(best=_arr(b.best, n, np.uint32), cand_off=off, cand=_arr(b.cand, off[-1], np.uint32),
+                    win_off=_arr(b.win_off, n_reads + 1, np.uint32))
 
     # ---- round
     def round_begin(self, k, seed_kmers):

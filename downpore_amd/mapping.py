@@ -24,10 +24,12 @@ def index_layout_code(index):
 
 
 def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
-              index="auto"):
+              index="auto", all_sequences=False):
     """ref / reads: downpore_amd.overlap.Reads (reference loaded with min_len=0, reads with min_len=min_length; both are
     treated as top-level sequences exactly like commands/map.go does).  index: the reference index's layout ("auto" takes the
-    sparse one when the dense one would not fit the device; both give the same PAF).  Returns (paf, stderr_text, stats);
+    sparse one when the dense one would not fit the device; both give the same PAF).  all_sequences: map against every sequence of
+    ref (one seed index and one chunk index over all of them; a PAF line names the sequence it lies on), not the first one only.
+    Returns (paf, stderr_text, stats);
     stats["index"] describes the index (MAP_INDEX_FIELDS, layout "dense" / "sparse")."""
     layout = index_layout_code(index)
     H = load_host()
@@ -40,7 +42,7 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     H.dph_map_stats.argtypes = [C.c_void_p, C.c_void_p]
     H.dph_map_index_info.restype = C.c_int
     H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout], dtype=np.int64)
+    p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout, 1 if all_sequences else 0], dtype=np.int64)
     h = H.dph_map_run_ex(ref.h, reads.h, p.ctypes.data, len(p), device)
     if not h:
         raise DpError("dph_map_run: " + H.dph_last_error(None).decode())

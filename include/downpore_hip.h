@@ -395,6 +395,23 @@ typedef struct {
     const uint32_t* cand;      /* candidate k-mers of every window's count region */
 } dp_single_seed_batch;
 DP_API int dp_single_seed_candidates(dp_ctx* ctx, uint32_t read, int k, int64_t seed_rate, dp_single_seed_batch* out);
+/* The same for a run of resident reads first_read .. first_read + n_reads - 1 (top-level sequences) that share ONE seed index
+ * (`map -all_sequences`: AddSingleSeeds called for one sequence after the other on the same index).  The windows of all sequences are
+ * numbered in sequence order: sequence c owns windows win_off[c] .. win_off[c + 1] - 1, each cut with that sequence's own length (a
+ * sequence no longer than seed_rate has none; bases beyond a sequence's end read as zero).  A window's candidates are the k-mers of
+ * its count region that are the best of ANY window of ANY of the sequences, so the caller's walk in window order is the sequential
+ * rule over the whole run.  One launch chain whatever n_reads; 2^32 or more windows are refused.  With n_reads = 1 the first three
+ * arrays are dp_single_seed_candidates'.  The arrays are the library's (the same memory as dp_single_seed_candidates' result). */
+typedef struct {
+    uint32_t n_windows;        /* windows of all sequences */
+    uint32_t n_reads;
+    const uint32_t* best;      /* [n_windows] */
+    const uint32_t* cand_off;  /* [n_windows + 1] offsets into cand */
+    const uint32_t* cand;
+    const uint32_t* win_off;   /* [n_reads + 1] first window of every sequence */
+} dp_single_seed_multi_batch;
+DP_API int dp_single_seed_candidates_multi(dp_ctx* ctx, uint32_t first_read, uint32_t n_reads, int k, int64_t seed_rate,
+                                           dp_single_seed_multi_batch* out);
 
 
 /* ---- A16 (part): seed-space multiple alignment of multiAligner.Consensus (seeds/alignment.go:52-247) ------------

@@ -133,11 +133,19 @@ DPH_API int dph_overlap_commit_blobs(void* h, const uint8_t* blobs, const uint64
  * kernel ms, seconds of set-up / window scans / dp_map_windows / host, algorithmic bytes of the map kernels (index query +
  * prefilter + chaining) and of the window scans (packed bases). */
 DPH_API void* dph_map_run(void* ref, void* reads, const int64_t* params, int device);
-/* dph_map_run with n_params = 6 (the same) or 7: params[6] = the reference index's layout, 0 = auto, 1 = dense, 2 = sparse
+/* dph_map_run with n_params = 6 (the same), 7 or 8: params[6] = the reference index's layout, 0 = auto, 1 = dense, 2 = sparse
  * (dp_index_build_sparse; mapper threads then borrow the one index).  Auto takes sparse when the dense estimate - S ceil(M/64) 8 +
  * M ceil(S/64) 8 bytes summed over the contexts / shards the run builds on a device - exceeds that device's free memory less an
  * eighth of its total.  Both layouts print the same PAF.  Another layout value is refused before any device call.  A reference
- * sequence longer than 2^31 - 1 bases is refused (with its length in the error) before anything is allocated. */
+ * sequence longer than 2^31 - 1 bases is refused (with its length in the error) before anything is allocated.
+ * params[7] (n_params = 8) = 1: map against EVERY sequence of `ref` in file order, 0 (the default): against the first one only;
+ * another value is refused before any device call.  The seeds are chosen for one sequence after the other on one index, the chunk
+ * ids run on from sequence to sequence (ten passes, then the circular join chunk of a sequence of at least query_size bases; a
+ * shorter one gets none and one stderr line says so), a chunk's positions are relative to its own sequence, mappings on two
+ * sequences are never joined or de-duplicated against each other, and columns 6 - 9 of a PAF line are its sequence's name, length
+ * and positions.  Both index layouts and DP_MAP_SHARDS work as they are (they cut by chunk id).  A sequence longer than 2^31 - 1
+ * bases (the error names it) and 2^32 or more seed windows or chunks in total are refused before anything is allocated; a
+ * reference without any chunk leaves every read unmapped.  With one sequence in `ref` the output is that of params[7] = 0. */
 DPH_API void* dph_map_run_ex(void* ref, void* reads, const int64_t* params, int n_params, int device);
 DPH_API void dph_map_free(void* m);
 DPH_API const char* dph_map_paf(void* m, int64_t* n);

@@ -20,9 +20,9 @@ type gpuMapCommand struct {
 
 func NewGPUMapCommand() Command {
 	args, alias, desc := MakeArgs(
-		[]string{"input", "reference", "circular", "k", "query_size", "min_length", "chunk_size", "seed_rate", "num_workers", "gpu"},
-		[]string{"", "", "true", "11", "1000", "500", "10000", "40", "4", "0"},
-		[]string{"Fasta/fastq input file", "A fasta file containing a reference sequence to align against", "Whether the reference genome is circular", "Length of seeds in bases", "The number of bases to query at a time", "The minimum sequence size to generate queries from", "The number of bases for reference index chunks", "The maximum number of bases between seeds in the reference", "The number of worker process to use for mapping", "HIP device to run on"})
+		[]string{"input", "reference", "circular", "k", "query_size", "min_length", "chunk_size", "seed_rate", "num_workers", "gpu", "all_sequences"},
+		[]string{"", "", "true", "11", "1000", "500", "10000", "40", "4", "0", "false"},
+		[]string{"Fasta/fastq input file", "A fasta file containing a reference sequence to align against", "Whether the reference genome is circular", "Length of seeds in bases", "The number of bases to query at a time", "The minimum sequence size to generate queries from", "The number of bases for reference index chunks", "The maximum number of bases between seeds in the reference", "The number of worker process to use for mapping", "HIP device to run on", "Whether to map against every sequence of the reference file, not only the first"})
 	cons := gpuMapCommand{args: args, alias: alias, desc: desc}
 	return &cons
 }
@@ -55,6 +55,7 @@ func (com *gpuMapCommand) Run(args map[string]string) {
 		MinLength: minLength,
 		ChunkSize: ParseInt(args["chunk_size"]),
 		SeedRate:  ParseInt(args["seed_rate"]),
+		AllSequences: ParseBool(args["all_sequences"]),
 	}
 	res, err := gpuhost.RunMap(ref, reads, p, ParseInt(args["gpu"]))
 	if err != nil {

@@ -634,6 +634,25 @@ func (c *Context) SingleSeedCandidates(read uint32, k int, seedRate int64) (best
 	return best, candOff, cand, nil
 }
 
+// SingleSeedCandidatesMulti is SingleSeedCandidates for the resident reads firstRead .. firstRead+nReads-1 on ONE seed index (`map
+// -all_sequences`): the windows of all sequences are numbered in sequence order, winOff[c] is the first window of sequence c, and a
+// window's candidates are the best k-mers of any window of any of the sequences (dp_single_seed_candidates_multi).
+func (c *Context) SingleSeedCandidatesMulti(firstRead, nReads uint32, k int, seedRate int64) (best []uint32, candOff []uint32, cand []uint32, winOff []uint32, err error) {
+	var b C.dp_single_seed_multi_batch
+	if rc := C.dp_single_seed_candidates_multi(c.h, C.uint32_t(firstRead), C.uint32_t(nReads), C.int(k), C.int64_t(seedRate), &b); rc != 0 {
+		return nil, nil, nil, nil, fail(c.h, "dp_single_seed_candidates_multi", rc)
+	}
+	winOff = append([]uint32(nil), unsafe.Slice((*uint32)(unsafe.Pointer(b.win_off)), int(nReads)+1)...)
+	n := int(b.n_windows)
+	if n == 0 {
+		return nil, []uint32{0}, nil, winOff, nil
+	}
+	best = append([]uint32(nil), unsafe.Slice((*uint32)(unsafe.Pointer(b.best)), n)...)
+	candOff = append([]uint32(nil), unsafe.Slice((*uint32)(unsafe.Pointer(b.cand_off)), n+1)...)
+	cand = append([]uint32(nil), unsafe.Slice((*uint32)(unsafe.Pointer(b.cand)), int(candOff[n]))...)
+	return best, candOff, cand, winOff, nil
+}
+
 // SelectWindows is the selection half of AddSeeds (seeds/seeds.go:62-129) for many query windows at once, assuming no
 // evaluated k-mer is a seed yet: top[w*numSeeds:] = the window's list (untouched slots hold k-mer 0), evaluated[w*stride:] =
 // every k-mer the walk evaluated (0xffffffff = unused): what the caller probes against its committed seeds to learn whether

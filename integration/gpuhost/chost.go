@@ -327,6 +327,7 @@ func (o *Overlap) RunRoundParallel(slots int, emit func(paf []byte)) error {
 type MapParams struct {
 	Circular                                           bool
 	K, QuerySize, MinLength, ChunkSize, SeedRate int
+	AllSequences                                       bool // map against every sequence of the reference file, not the first one only
 }
 
 // MapResult holds what the command prints: the PAF lines (read order) and the stderr summary.
@@ -335,17 +336,22 @@ type MapResult struct {
 	ErrText string
 }
 
-// RunMap runs the whole command on HIP device `device`: reference = first sequence of ref (opened with himem = false, minLen 0),
-// reads opened with minLen = -min_length.
+// RunMap runs the whole command on HIP device `device`: reference = first sequence of ref (opened with himem = false, minLen 0;
+// every sequence of it with p.AllSequences), reads opened with minLen = -min_length.
 func RunMap(ref, reads *Reads, p MapParams, device int) (*MapResult, error) {
 	circ := C.int64_t(0)
 	if p.Circular {
 		circ = 1
 	}
-	params := [6]C.int64_t{circ, C.int64_t(p.K), C.int64_t(p.QuerySize), C.int64_t(p.MinLength), C.int64_t(p.ChunkSize), C.int64_t(p.SeedRate)}
-	h := C.dph_map_run(ref.h, reads.h, &params[0], C.int(device))
+	all := C.int64_t(0)
+	if p.AllSequences {
+		all = 1
+	}
+	// params[6] = 0: the reference index's layout is chosen by the library
+	params := [8]C.int64_t{circ, C.int64_t(p.K), C.int64_t(p.QuerySize), C.int64_t(p.MinLength), C.int64_t(p.ChunkSize), C.int64_t(p.SeedRate), 0, all}
+	h := C.dph_map_run_ex(ref.h, reads.h, &params[0], 8, C.int(device))
 	if h == nil {
-		return nil, lastError(nil, "dph_map_run")
+		return nil, lastError(nil, "dph_map_run_ex")
 	}
 	defer C.dph_map_free(h)
 	var n C.int64_t

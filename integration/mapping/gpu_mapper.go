@@ -10,6 +10,12 @@
 // is handed to a batcher goroutine, which scans the windows of all reads currently waiting in ONE dp_scan and chains them in
 // ONE dp_map_windows, so the GPU sees thousands of windows per call while every Map goroutine still sees a blocking call.
 // Start as many MapWorker goroutines as reads should be in flight (a few thousand: they only park on a channel).
+//
+// NewGPUMapperAll (`map -all_sequences`, DESIGN.md 4.7) is the same mapper over EVERY sequence of the reference file: one seed index
+// (AddSingleSeeds for one sequence after the other), chunk ids running on from sequence to sequence, every chunk remembering its
+// sequence.  It needs four edits of mapping.go, all no-ops with one sequence: `Mapping` gains `Ref int`; isConsistent returns false
+// first when left.Ref != right.Ref and takes m.references[left.Ref].Len() for m.reference.Len(); matchPairs' combined mapping takes
+// ra.Ref; AsString prints m.references[mapping.Ref]'s name and length (`mapper` gains `references []sequence.Sequence`, set here).
 package mapping
 
 import (
@@ -30,7 +36,8 @@ type windowRequest struct {
 type gpuMapper struct {
 	*mapper                            // reference, index (CPU side: seeds + chunk SeedSequences), edgeSize, circular
 	ctx      *gpu.Context
-	readBase int                       // device read id of query read 0 (the reference is device read 0)
+	readBase int                       // device read id of query read 0 (the reference sequences are the device reads before it)
+	chunkRef []int                     // reference sequence of every indexed chunk
 	requests chan windowRequest
 	active   sync.WaitGroup
 	waiting  chan int                  // +1 a Map goroutine parked on a request, -1 it left (see batcher)
@@ -41,21 +48,35 @@ type gpuMapper struct {
 // query read (forward and, produced on the device, reverse complement) become resident in HBM; the reference chunks are
 // scanned and indexed on the device in the order NewMapper indexes them.
 func NewGPUMapper(reference sequence.Sequence, set sequence.SequenceSet, circular bool, k uint, kmerValues []float64, seedRate int, edgeSize int, chunkSize int, numWorkers int, device int) Mapper {
-	m := &mapper{index: seeds.NewSeedIndex(k), reference: reference, edgeSize: edgeSize, circular: circular}
-	m.index.AddSingleSeeds(reference, seedRate, kmerValues) // sequential by nature, one pass over the reference
+	return NewGPUMapperAll([]sequence.Sequence{reference}, set, circular, k, kmerValues, seedRate, edgeSize, chunkSize, numWorkers, device)
+}
+
+// NewGPUMapperAll maps against every sequence of `references` (the top-level sequences of the reference file, in file order).
+func NewGPUMapperAll(references []sequence.Sequence, set sequence.SequenceSet, circular bool, k uint, kmerValues []float64, seedRate int, edgeSize int, chunkSize int, numWorkers int, device int) Mapper {
+	m := &mapper{index: seeds.NewSeedIndex(k), reference: references[0], references: references, edgeSize: edgeSize, circular: circular}
+	for _, reference := range references {
+		m.index.AddSingleSeeds(reference, seedRate, kmerValues) // sequential by nature, one pass over every sequence on the one index
+	}
 	ctx, err := gpu.NewContext(device)
 	if err != nil {
 		log.Fatal(err)
 	}
-	g := &gpuMapper{mapper: m, ctx: ctx, readBase: 1, requests: make(chan windowRequest, 1<<16), waiting: make(chan int, 1<<16), workers: numWorkers}
+	g := &gpuMapper{mapper: m, ctx: ctx, readBase: len(references), requests: make(chan windowRequest, 1<<16), waiting: make(chan int, 1<<16), workers: numWorkers}
 	m.perform = g.performMapping
-	// device read 0 = the reference (with its first edgeSize bases appended when circular: the join chunk is then a plain view),
-	// device reads 1 + 2i / 2 + 2i = query read i forward / reverse complement
-	bases := []byte(reference.String())
-	if circular {
-		bases = append(bases, reference.SubSequence(0, edgeSize).String()...)
+	// device read c = reference sequence c (with its first edgeSize bases appended when it gets a join chunk, which is then a plain
+	// view), device reads T + 2i / T + 2i + 1 = query read i forward / reverse complement
+	joined := func(reference sequence.Sequence) bool { return circular && reference.Len() >= edgeSize }
+	var bases []byte
+	off := []int64{0}
+	for _, reference := range references {
+		bases = append(bases, reference.String()...)
+		if joined(reference) {
+			bases = append(bases, reference.SubSequence(0, edgeSize).String()...)
+		} else if circular {
+			log.Println("Sequence", reference.GetName(), "is shorter than query_size: no circular join chunk")
+		}
+		off = append(off, int64(len(bases)))
 	}
-	off := []int64{0, int64(len(bases))}
 	for s := range set.GetSequences() {
 		if s == nil {
 			continue
@@ -63,7 +84,7 @@ func NewGPUMapper(reference sequence.Sequence, set sequence.SequenceSet, circula
 		bases = append(bases, s.String()...)
 		off = append(off, int64(len(bases)))
 	}
-	if err := ctx.UploadReadsRC(bases, off, 1); err != nil {
+	if err := ctx.UploadReadsRC(bases, off, len(references)); err != nil {
 		log.Fatal(err)
 	}
 	if err := ctx.RoundBegin(int(k), m.index.SeedKmers()); err != nil {
@@ -73,28 +94,31 @@ func NewGPUMapper(reference sequence.Sequence, set sequence.SequenceSet, circula
 	var items []gpu.ScanItem
 	var views []sequence.Sequence
 	kk := int(k)
-	addChunk := func(start, end int) {
-		n := end - start - kk + 1
-		if n < 0 {
-			n = 0
-		}
-		items = append(items, gpu.ScanItem{Read: 0, Start: uint32(start), NKmers: uint32(n)})
-	}
-	for j := 0; j < 10; j++ {
-		start := j * chunkSize
-		step := chunkSize*10 - edgeSize
-		for i := start; i < reference.Len()-chunkSize/2; i += step {
-			end := i + chunkSize
-			if end > reference.Len() {
-				end = reference.Len()
+	for c, reference := range references {
+		addChunk := func(start, end int) {
+			n := end - start - kk + 1
+			if n < 0 {
+				n = 0
 			}
-			addChunk(i, end)
-			views = append(views, reference.SubSequence(i, end))
+			items = append(items, gpu.ScanItem{Read: uint32(c), Start: uint32(start), NKmers: uint32(n)})
+			g.chunkRef = append(g.chunkRef, c)
 		}
-	}
-	if circular {
-		addChunk(reference.Len()-edgeSize, reference.Len()+edgeSize)
-		views = append(views, reference.SubSequence(reference.Len()-edgeSize, reference.Len()).Append(0, reference.SubSequence(0, edgeSize), nil))
+		for j := 0; j < 10; j++ {
+			start := j * chunkSize
+			step := chunkSize*10 - edgeSize
+			for i := start; i < reference.Len()-chunkSize/2; i += step {
+				end := i + chunkSize
+				if end > reference.Len() {
+					end = reference.Len()
+				}
+				addChunk(i, end)
+				views = append(views, reference.SubSequence(i, end))
+			}
+		}
+		if joined(reference) {
+			addChunk(reference.Len()-edgeSize, reference.Len()+edgeSize)
+			views = append(views, reference.SubSequence(reference.Len()-edgeSize, reference.Len()).Append(0, reference.SubSequence(0, edgeSize), nil))
+		}
 	}
 	segs, segOff, err := ctx.Scan(items)
 	if err != nil {
@@ -194,29 +218,44 @@ func (g *gpuMapper) batcher() {
 func (g *gpuMapper) mappingFromChain(sq *seeds.SeedSequence, c gpu.Chain, k int) *Mapping {
 	match := g.index.GetSeedSequence(uint(c.Target))
 	sm := &seeds.SeedMatch{MatchA: c.MatchA, MatchB: c.MatchB, SeqA: sq, SeqB: match}
+	ref := g.chunkRef[c.Target]
+	refLen := g.references[ref].Len() // the chunk's own sequence
 	start := match.GetOffset() + match.GetSeedOffset(c.MatchB[0], k)
-	end := g.reference.Len() - match.GetInset() - match.GetSeedOffsetFromEnd(c.MatchB[len(c.MatchB)-1], k)
-	if g.circular && start > g.reference.Len() {
-		start -= g.reference.Len()
+	end := refLen - match.GetInset() - match.GetSeedOffsetFromEnd(c.MatchB[len(c.MatchB)-1], k)
+	if g.circular && start > refLen {
+		start -= refLen
 	}
 	_, ids := sm.GetBasesCovered(k)
 	if c.Window%2 == 0 {
 		qOffset := sq.GetSeedOffset(c.MatchA[0], k) + sq.GetOffset()
 		qInset := sq.GetSeedOffsetFromEnd(c.MatchA[len(c.MatchA)-1], k) + sq.GetInset()
-		return &Mapping{Start: start, End: end, QueryOffset: qOffset, QueryInset: qInset, RC: false, match: sm, ids: ids}
+		return &Mapping{Start: start, End: end, QueryOffset: qOffset, QueryInset: qInset, RC: false, match: sm, ids: ids, Ref: ref}
 	}
 	qInset := sq.GetSeedOffset(c.MatchA[0], k) + sq.GetOffset()
 	qOffset := sq.GetSeedOffsetFromEnd(c.MatchA[len(c.MatchA)-1], k) + sq.GetInset()
-	return &Mapping{Start: start, End: end, QueryOffset: qOffset, QueryInset: qInset, RC: true, match: sm, ids: ids}
+	return &Mapping{Start: start, End: end, QueryOffset: qOffset, QueryInset: qInset, RC: true, match: sm, ids: ids, Ref: ref}
 }
 
-// dedupMappings is the tail of performMapping (:590-608): sort by Start, of two overlapping same-strand neighbours keep the longer.
+// mappingsByRefPos orders by (reference sequence, Start): mappingsByPos (mapping.go) when there is one sequence.
+type mappingsByRefPos []*Mapping
+
+func (a mappingsByRefPos) Len() int      { return len(a) }
+func (a mappingsByRefPos) Swap(i, j int) { a[i], a[j] = a[j], a[i] }
+func (a mappingsByRefPos) Less(i, j int) bool {
+	if a[i].Ref != a[j].Ref {
+		return a[i].Ref < a[j].Ref
+	}
+	return a[i].Start < a[j].Start
+}
+
+// dedupMappings is the tail of performMapping (:590-608): sort by (sequence, Start), of two overlapping same-strand neighbours on
+// one sequence keep the longer.
 func dedupMappings(results []*Mapping) []*Mapping {
 	if len(results) > 1 {
-		sort.Sort(mappingsByPos(results))
+		sort.Sort(mappingsByRefPos(results))
 		for i := len(results) - 1; i > 0; i-- {
 			ra, rb := results[i-1], results[i]
-			if ra.RC == rb.RC && rb.Start < ra.End {
+			if ra.Ref == rb.Ref && ra.RC == rb.RC && rb.Start < ra.End {
 				if ra.End-ra.Start > rb.End-rb.Start {
 					results[i] = results[len(results)-1]
 					results = results[:len(results)-1]
