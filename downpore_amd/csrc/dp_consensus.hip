@@ -347,12 +347,16 @@ struct CFWaveT {
     typedef CFCfg<TIER> C;
     typedef typename C::elem_t elem_t;
     elem_t T[C::T];               // trimmed sequences of the group, [gap, seed, ..., gap] each
-    elem_t R[C::R];               // their Reduced() forms
-    uint16_t Rmap[C::R / 2];
-    union {
+    // Room of the Reduced() forms: every sequence gets its trimmed ints + 1 (as if every seed were kept, rounded to even), so 64
+    // sequences of T trimmed ints in all need T + 64, and the walk's look-ahead two more: whatever fits T fits here (128: the
+    // arrays behind stay 16-byte aligned)
+    enum { RROOM = C::R + 128 };
+    elem_t R[RROOM];              // their Reduced() forms
+    uint16_t Rmap[RROOM / 2];
+    union alignas(16) {
         uint32_t hash[C::HASH];  // (seed + 1) << 8 | shared << 7 | first sequence
         struct {
-            uint16_t cmA[C::R / 2], cmB[C::R / 2];  // consensus matches of sequence s at [rb[s]/2 .. ): consensus index, index in T_s
+            uint16_t cmA[RROOM / 2], cmB[RROOM / 2];  // consensus matches of sequence s at [rb[s]/2 .. ): consensus index, index in T_s
             int32_t cons[C::CONS + 2];
             int32_t front[C::CONS / 8 + 2], backc[C::CONS / 8 + 2];
         };
@@ -758,7 +762,7 @@ struct consensus_full_kernel {
             const int slot = mine ? 2 * nsT_ + 2 : 0;
             const int incl = wave_incl_sum_dpp(slot);
             const int totalR = __builtin_amdgcn_readlane(incl, 63);
-            if (totalR + 2 >= CF::R) CF_NOFIT(4u)
+            if (totalR + 2 >= LW::RROOM) CF_NOFIT(4u)  // (cannot happen within 64 sequences and T trimmed ints)
             if (mine) {
                 const int rb = incl - slot;
                 int prev = -1, r = 0, offset = nsT_ > 0 ? (int)L.T[tb_] : 0;
@@ -1302,6 +1306,7 @@ struct consensus_full_kernel {
         gm.n_lines = (uint32_t)(np - 1);
         gm.n_ignore = (uint32_t)__popcll(ignMask);
         gm.reserved = (uint32_t)wave_sum((int)algB) + 4u * (uint32_t)nA + 40u * gm.n_lines + 4u * gm.n_ignore + 32u;
+        gm.reserved = (gm.reserved & DP_GROUP_BYTES_MASK) | ((uint32_t)TIER << DP_GROUP_LAYOUT_SHIFT);  // (which layout did the window: tests)
         gm.bad_back = (uint32_t)__popcll(__ballot(badBack != 0));
         gm.empty_match = (uint32_t)__popcll(__ballot(line && panicPrev));
         if (lane == 0) A.gmeta[g] = gm;

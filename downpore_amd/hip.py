@@ -64,6 +64,25 @@ class CandidateBatch(C.Structure):  # dp_candidate_batch
                 ("meta", C.POINTER(C.c_uint32))]
 
 
+class ConsensusBatch(C.Structure):  # dp_consensus_batch
+    _fields_ = [("n_groups", C.c_uint32), ("cons", C.POINTER(C.c_int32)), ("cons_off", C.POINTER(C.c_uint64)),
+                ("cons_len", C.POINTER(C.c_uint32)), ("match_a", C.POINTER(C.c_int32)), ("match_b", C.POINTER(C.c_int32)),
+                ("match_len", C.POINTER(C.c_uint32)), ("flags", C.POINTER(C.c_uint32)), ("kernel_ms", C.c_double)]
+
+
+class PafBatch(C.Structure):  # dp_paf_batch
+    _fields_ = [("n_groups", C.c_uint32), ("groups", C.c_void_p), ("paf", C.c_void_p), ("ignore_ids", C.POINTER(C.c_uint32)),
+                ("kernel_ms", C.c_double), ("n_indexed", C.c_uint32), ("query_kernel_ms", C.c_double), ("chain_kernel_ms", C.c_double),
+                ("query_bytes", C.c_uint64), ("chain_bytes", C.c_uint64), ("index_kernel_ms", C.c_double)]
+
+
+SEQ_META = np.dtype([("read", np.uint32), ("length", np.int32), ("offset", np.int32), ("inset", np.int32)])  # dp_seq_meta
+PAF_REC = np.dtype([("q_read", np.uint32), ("t_read", np.uint32), ("q_len", np.int32), ("q_start", np.int32), ("q_end", np.int32),
+                    ("t_len", np.int32), ("t_start", np.int32), ("t_end", np.int32), ("ident", np.int32), ("minus", np.uint32)])  # dp_paf_rec
+GROUP_META = np.dtype([("slot", np.uint32), ("n_lines", np.uint32), ("n_ignore", np.uint32), ("bad_back", np.uint32),
+                       ("empty_match", np.uint32), ("flag", np.uint32), ("n_matches", np.uint32), ("reserved", np.uint32)])  # dp_group_meta
+
+
 class IndexInfo(C.Structure):  # dp_index_info_t
     _fields_ = [("layout", C.c_uint32), ("borrowed", C.c_uint32), ("n_seeds", C.c_uint32), ("n_seqs", C.c_uint32),
                 ("device_bytes", C.c_uint64), ("entries", C.c_uint64), ("queries", C.c_uint64 * 4)]
@@ -367,12 +386,20 @@ class Context:
         return words
 
     # ---- A14 .. A8
-    def find_overlaps(self, q_segs, q_off, hit_fraction, k, max_query_len, want_candidates=False):
+    def find_overlaps(self, q_segs, q_off, hit_fraction, k, max_query_len, want_candidates=False, on_device=False, pending=False):
+        """on_device (bit 1 of want_candidates): the matches stay on the device for consensus_paf, only times and byte counts come
+        back; pending (bit 2, with on_device): the stage is not even waited for - the next call must be consensus_paf."""
         qs = np.ascontiguousarray(q_segs, dtype=np.int32)
         qo = np.ascontiguousarray(q_off, dtype=np.uint64)
         b = MatchBatch()
+        if pending and not on_device:
+            raise ValueError("find_overlaps: pending needs on_device")
+        bits = (1 if want_candidates else 0) | (2 if on_device else 0) | (4 if pending else 0)
         self._chk(self.L.dp_find_overlaps(self.h, qs.ctypes.data, qo.ctypes.data, len(qo) - 1, float(hit_fraction), k,
-                                          max_query_len, 1 if want_candidates else 0, C.byref(b)))
+                                          max_query_len, bits, C.byref(b)))
+        if on_device:
+            return dict(query_kernel_ms=b.query_kernel_ms, chain_kernel_ms=b.chain_kernel_ms, query_bytes=b.query_bytes,
+                        chain_bytes=b.chain_bytes)
         nm = b.n_matches
         off = _arr(b.off, nm + 1, np.uint64)
         tot = int(off[-1]) if nm else 0
@@ -386,6 +413,52 @@ class Context:
             res["cand_off"] = co
             res["cand"] = _arr(b.cand, int(co[-1]), np.uint32)
         return res
+
+    # ---- A15 - A17
+    def consensus_paf(self, metas, rc_of, k, overlap_size):
+        """dp_consensus_paf for the round whose find_overlaps(on_device=True) ran last.  metas: SEQ_META [n_seqs] (read, Len(),
+        GetOffset(), GetInset() of every indexed sequence), rc_of: int32 [n_seeds].  Returns dict groups (GROUP_META [windows]), paf
+        (PAF_REC, a window's lines at groups.slot ..), ignore_ids (uint32, likewise), n_indexed."""
+        m = np.ascontiguousarray(metas, dtype=SEQ_META)
+        rc = np.ascontiguousarray(rc_of, dtype=np.int32)
+        b = PafBatch()
+        self.L.dp_consensus_paf.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(PafBatch)]
+        self._chk(self.L.dp_consensus_paf(self.h, m.ctypes.data, len(m), rc.ctypes.data, len(rc), k, overlap_size, C.byref(b)))
+        ng = b.n_groups
+        if ng == 0 or not b.groups:
+            return dict(groups=np.zeros(0, dtype=GROUP_META), paf=np.zeros(0, dtype=PAF_REC), ignore_ids=np.zeros(0, dtype=np.uint32),
+                        n_indexed=int(b.n_indexed))
+        groups = np.frombuffer(C.string_at(b.groups, ng * GROUP_META.itemsize), dtype=GROUP_META).copy()
+        # the slots of the arrays are the round's matched pairs; a window owns [slot, slot + its pairs): read up to the last one in use
+        ok = groups["flag"] == 0
+        n = int(max((groups["slot"][ok].astype(np.int64) + np.maximum(groups["n_lines"][ok], groups["n_ignore"][ok])).max(initial=0), 0))
+        paf = np.frombuffer(C.string_at(b.paf, n * PAF_REC.itemsize), dtype=PAF_REC).copy() if n else np.zeros(0, dtype=PAF_REC)
+        return dict(groups=groups, paf=paf, ignore_ids=_arr(b.ignore_ids, n, np.uint32), n_indexed=int(b.n_indexed))
+
+    def consensus_align(self, segs, seq_off, group_off, k):
+        """dp_consensus_align: group g = sequences group_off[g] .. group_off[g + 1], sequence s = segs[seq_off[s] .. seq_off[s + 1]) in its
+        Reduced() form.  Returns dict flags [groups], cons (list of int32 arrays), match_a / match_b (lists, one pair of arrays per
+        sequence; match_b indexes the reduced sequence)."""
+        sg = np.ascontiguousarray(segs, dtype=np.int32)
+        so = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        b = ConsensusBatch()
+        self.L.dp_consensus_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(ConsensusBatch)]
+        self._chk(self.L.dp_consensus_align(self.h, sg.ctypes.data, so.ctypes.data, go.ctypes.data, len(go) - 1, k, C.byref(b)))
+        ng, ns = len(go) - 1, int(go[-1])
+        flags = _arr(b.flags, ng, np.uint32)
+        coff, clen = _arr(b.cons_off, ng + 1, np.uint64), _arr(b.cons_len, ng, np.uint32)
+        call = _arr(b.cons, int(coff[-1]), np.int32)
+        mlen = _arr(b.match_len, ns, np.uint32)
+        ma, mb = _arr(b.match_a, int(so[-1]), np.int32), _arr(b.match_b, int(so[-1]), np.int32)
+        cons, la, lb = [], [], []
+        for g in range(ng):
+            cons.append(call[int(coff[g]):int(coff[g]) + int(clen[g])] if flags[g] == 0 else None)
+            for s in range(int(go[g]), int(go[g + 1])):
+                n = int(mlen[s]) if flags[g] == 0 else 0
+                la.append(ma[int(so[s]):int(so[s]) + n])
+                lb.append(mb[int(so[s]):int(so[s]) + n])
+        return dict(flags=flags, cons=cons, match_a=la, match_b=lb)
 
     def query_candidates(self, q_segs, q_off, hit_fraction):
         """dp_query_candidates: Matches() alone on either layout -> cand_off, cand (ascending ids per query, shard-local), meta

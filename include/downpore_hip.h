@@ -447,8 +447,13 @@ DP_API int dp_consensus_align(dp_ctx* ctx, const int32_t* segs, const uint64_t* 
  * (overlap.go:253-318); rc_of[s] = kmerMap[ReverseComplement(seedMap[s], k)] (seeds/sequence.go:125-159).
  * Per group the caller gets the lines of the contig's parts in order - everything `Fprintf` prints except the names -
  * and the reads finalCheckWorker passes to SetIgnore (:203-205, 217-223), in call order.  flag != 0: the group does not
- * fit the device layout (> 64 trimmed sequences, > 4096 ints, a value beyond 2^28, or a state in which the reference
- * itself would panic); the caller then runs the host path for that group on the matches of dp_fetch_overlaps. */
+ * fit the last device layout that ran - the huge one from the round after a context first left a window to the caller, the
+ * large one before that.  Either holds a window of up to 256 matches whose forward query has up to 256 seeds, with up to 64
+ * trimmed sequences that passed the GetBasesCovered filter, a consensus of up to 1024 ints, and 4096 (large) or 12288 (huge)
+ * ints of trimmed sequences; their Reduced() forms are never longer and always fit.  A value beyond 2^28 or a state in which
+ * the reference itself would panic flags the group too.  The caller then runs the host path for that group on the matches
+ * of dp_fetch_overlaps.  (A small layout in front of these - 128 matches, 128 query seeds, 2048 ints, a consensus of 256,
+ * 16-bit values, seed ids below 2^15 - hands what it cannot hold to the large one, never to the caller.) */
 typedef struct {
     uint32_t read;                   /* SeedSequence.id */
     int32_t length, offset, inset;   /* Len(), GetOffset(), GetInset() */
@@ -468,9 +473,12 @@ typedef struct {
     uint32_t flag;
     uint32_t n_matches;              /* hits of the two queries of the window (commands/overlap.go:158-173) */
     uint32_t reserved;               /* flag == 0: algorithmic bytes the window's consensus read and wrote (records, chains, anchors,
-                                      * trimmed segments, query segments in; PAF records, ignore ids, this record out);
-                                      * flag == 1: why the device left the window to the caller (diagnosis) */
+                                      * trimmed segments, query segments in; PAF records, ignore ids, this record out) in the low 30
+                                      * bits, and above them the layout that computed a window with lines (0 small, 1 large, 2 huge:
+                                      * test hook); flag == 1: why the device left the window to the caller (diagnosis) */
 } dp_group_meta;
+#define DP_GROUP_BYTES_MASK 0x3fffffffu
+#define DP_GROUP_LAYOUT_SHIFT 30
 typedef struct {
     uint32_t n_groups;
     const dp_group_meta* groups;

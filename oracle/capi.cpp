@@ -433,6 +433,10 @@ const char* dpo_overlap_err(void* h, int64_t* n) {
 // Trace fields.  Nested fields come as (flat, offsets) pairs: field f = flat data, f+100 = offsets.
 //  0 seedKmers | 1 queryIDs | 2 querySeqIDs | 3 indexedIds | 4 indexedLength | 5 indexedOffset | 6 indexedInset
 //  7 matchQueryIndex | 8 matchTarget | 9 newlyIgnored | 10 scalars {firstSequence,numQuerySeqs,hits,qHits}
+//  11 queryLength | 12 queryOffset | 13 queryInset
+//  14 pafWindow (per PAF line: its query window) | 15 ignoreCalls, 16 ignoreWindow (every SetIgnore call in order: id, window)
+//  17 windowStats (8 per window: matches, kept trimmed sequences, their Trimmed() ints, their Reduced() ints, consensus ints, contig
+//     parts, "Bad back" events, empty-match lines)
 //  20 querySegments | 21 indexedSegments | 22 candidates | 23 matchA | 24 matchB
 static void flat(const std::vector<std::vector<i64>>& v, std::vector<i64>& data, std::vector<i64>& off) {
     off.push_back(0);
@@ -468,6 +472,10 @@ const int64_t* dpo_overlap_trace(void* hh, int64_t round, int field, int64_t* n)
             case 12: d = t.queryOffset; break;
             case 13: d = t.queryInset; break;
             case 10: d = {t.firstSequence, t.numQuerySeqs, t.hits, t.qHits}; break;
+            case 14: d = t.pafWindow; break;
+            case 15: d = t.ignoreCalls; break;
+            case 16: d = t.ignoreWindow; break;
+            case 17: d = t.windowStats; break;
             case 20: flat(t.querySegments, d, o); break;
             case 21: flat(t.indexedSegments, d, o); break;
             case 22: {

@@ -194,8 +194,9 @@ std::vector<SeedMatch> ssMatch(Arena& a, SeedSequence* seq, SeedSequence* query,
                                const IntSet* seqSet, i64 minMatch, int k);
 
 // seeds/alignment.go:23-268
+// reducedInts (optional): the total ints of the Reduced() forms the alignment ran on (:48-57)
 SeedSequence* multiAlignerConsensus(Arena& a, std::vector<SeedSequence*>& seqs, int k,
-                                    std::vector<std::unique_ptr<SeedMatch>>& matchesOut);
+                                    std::vector<std::unique_ptr<SeedMatch>>& matchesOut, i64* reducedInts = nullptr);
 
 // ---------------------------------------------------------------------------------------------
 // sequence/seqio.go fastaSequenceSet (FASTA / FASTQ, one line per read)
@@ -263,7 +264,13 @@ struct SeedContig {
     std::vector<std::unique_ptr<SeedMatch>> owned;
 };
 // badBack counts the "Bad back:" events (combine.go:93-102) — see the canonical-semantics note above.
-std::unique_ptr<SeedContig> buildConsensus(SeedIndex& sg, std::vector<SeedMatch*>& overlaps, i64* badBack);
+// What BuildConsensus saw for one query window (the sizes a device layout has to hold): trimmed sequences that passed the
+// GetBasesCovered filter, the ints of their Trimmed() and Reduced() forms, the ints of the consensus ([dist, seed, ..., 0]; 0 when
+// fewer than two sequences were left) and the matches multiAligner.Consensus returned (the contig's parts).
+struct ConsensusStats {
+    i64 kept = 0, trimmedInts = 0, reducedInts = 0, consInts = 0, parts = 0;
+};
+std::unique_ptr<SeedContig> buildConsensus(SeedIndex& sg, std::vector<SeedMatch*>& overlaps, i64* badBack, ConsensusStats* stats = nullptr);
 
 // Per-round trace a test can compare stage by stage.
 struct RoundTrace {
@@ -280,6 +287,10 @@ struct RoundTrace {
     i64 hits = 0, qHits = 0;
     std::string paf;
     std::vector<i64> newlyIgnored;
+    // the round's output by query window (window g = queries 2g, 2g + 1 = QueryID g)
+    std::vector<i64> pafWindow;                    // per line of paf: the window that printed it
+    std::vector<i64> ignoreCalls, ignoreWindow;    // every SetIgnore call in call order: read id, window
+    std::vector<i64> windowStats;                  // 8 per window: matches, ConsensusStats' five, "Bad back" events, empty-match lines
 };
 struct OverlapResult {
     std::string paf;      // everything the reference would print to stdout

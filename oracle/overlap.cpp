@@ -517,7 +517,7 @@ static std::unique_ptr<SeedContig> newSeedContig(Arena& ar, std::vector<SeedMatc
 }
 
 // BuildConsensus :163-193
-std::unique_ptr<SeedContig> buildConsensus(SeedIndex& sg, std::vector<SeedMatch*>& overlaps, i64* badBack) {
+std::unique_ptr<SeedContig> buildConsensus(SeedIndex& sg, std::vector<SeedMatch*>& overlaps, i64* badBack, ConsensusStats* stats) {
     int k = sg.seedSize;
     Arena& ar = sg.arena;
     std::vector<SeedSequence*> seqs;
@@ -532,9 +532,18 @@ std::unique_ptr<SeedContig> buildConsensus(SeedIndex& sg, std::vector<SeedMatch*
                       overlaps[0]->SeqA->getSeedOffsetFromEnd(lap->MatchA.back(), k), lap->MatchB.back(), k, nullptr);
         seqs.push_back(s);
     }
+    if (stats) {
+        *stats = ConsensusStats();
+        stats->kept = (i64)seqs.size();
+        for (auto* s : seqs) stats->trimmedInts += (i64)s->n;
+    }
     if (seqs.size() > 1) {
         std::vector<std::unique_ptr<SeedMatch>> overlap;
-        multiAlignerConsensus(ar, seqs, k, overlap);
+        SeedSequence* cons = multiAlignerConsensus(ar, seqs, k, overlap, stats ? &stats->reducedInts : nullptr);
+        if (stats) {
+            stats->consInts = (i64)cons->n;
+            stats->parts = (i64)overlap.size();
+        }
         if (overlap.size() > 1) {
             std::vector<SeedMatch*> ms;
             for (auto& m : overlap) ms.push_back(m.get());
@@ -646,13 +655,25 @@ OverlapResult runOverlap(FastaSet& set, const OverlapParams& p, const double* va
         res.err += line;
         std::string roundPaf;
         std::vector<i64> newlyIgnored;
+        i64 window = 0;
         auto setIgnore = [&](i64 id) {
             if (!set.ignore[(size_t)id]) newlyIgnored.push_back(id);
             set.ignore[(size_t)id] = 1;
+            if (keepTraces) {
+                tr.ignoreCalls.push_back(id);
+                tr.ignoreWindow.push_back(window);
+            }
         };
+        if (keepTraces) tr.windowStats.assign(8 * queryResults.size(), 0);
         for (auto& results : queryResults) {  // finalCheckWorker :197-233
+            window = (i64)(&results - queryResults.data());
+            i64* ws = keepTraces ? &tr.windowStats[8 * (size_t)window] : nullptr;
+            if (ws) ws[0] = (i64)results.size();
             if (results.size() <= 1) continue;
-            std::unique_ptr<SeedContig> contig = buildConsensus(seedIndex, results, &res.badBack);
+            ConsensusStats cs;
+            const i64 badBack0 = res.badBack, empty0 = res.emptyMatchPanics;
+            std::unique_ptr<SeedContig> contig = buildConsensus(seedIndex, results, &res.badBack, &cs);
+            if (ws) ws[1] = cs.kept, ws[2] = cs.trimmedInts, ws[3] = cs.reducedInts, ws[4] = cs.consInts, ws[5] = cs.parts, ws[6] = res.badBack - badBack0;
             if (contig && contig->Parts.size() > 1) {
                 if (contig->SeqLengths[0] <= p.overlapSize * 2) setIgnore(contig->Parts[0]);
                 i64 queryStart = contig->Offsets[0];
@@ -679,8 +700,10 @@ OverlapResult runOverlap(FastaSet& set, const OverlapParams& p, const double* va
                                     std::to_string(start) + "\t" + std::to_string(end) + "\t" + std::to_string(ident) +
                                     "\t0\t255\n";
                     roundPaf += s;
+                    if (keepTraces) tr.pafWindow.push_back(window);
                 }
             }
+            if (ws) ws[7] = res.emptyMatchPanics - empty0;
         }
         res.paf += roundPaf;
         res.rounds = round + 1;

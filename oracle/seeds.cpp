@@ -836,7 +836,7 @@ std::vector<SeedMatch> ssMatch(Arena& a, SeedSequence* seq, SeedSequence* query,
 // seeds/alignment.go:23-268 — multiAligner.Consensus (a fresh aligner per call: overlap/combine.go:186)
 
 SeedSequence* multiAlignerConsensus(Arena& arena, std::vector<SeedSequence*>& seqs, int k,
-                                    std::vector<std::unique_ptr<SeedMatch>>& matchesOut) {
+                                    std::vector<std::unique_ptr<SeedMatch>>& matchesOut, i64* reducedInts) {
     const size_t ns = seqs.size();
     // :25-44
     i64 maxSeed = 100;
@@ -859,6 +859,11 @@ SeedSequence* multiAlignerConsensus(Arena& arena, std::vector<SeedSequence*>& se
     std::vector<std::vector<i64>> seedMap(ns);
     std::vector<SeedSequence*> reds(ns, nullptr);
     for (size_t i = 0; i < ns; i++) reds[i] = ssReduced(arena, seqs[i], useSeeds, k, 1, &seedMap[i]);
+    if (reducedInts) {
+        *reducedInts = 0;
+        for (auto* r : reds)
+            if (r) *reducedInts += (i64)r->n;
+    }
     auto segp = [&](size_t i) -> const i64* { return reds[i] ? reds[i]->seg() : nullptr; };
     auto segn = [&](size_t i) -> i64 { return reds[i] ? (i64)reds[i]->n : 0; };
 

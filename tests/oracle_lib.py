@@ -334,6 +334,34 @@ def match(seq_seg, q_seg, min_match, k):
     return _matches(lib().dpo_match, ptr(s, i64p), len(s), ptr(q, i64p), len(q), min_match, k)
 
 
+def hand_consensus(seqs, k):
+    """multiAligner.Consensus (dpo_hand_consensus) on raw [gap, seed, ..., gap] sequences (a sequence without seeds: one gap).
+    Returns (consensus int64 array, {sequence index: (MatchA, MatchB)} of the sequences that survive with three or more pairs, their
+    indices in the order the function returns them)."""
+    L = lib()
+    L.dpo_hand_consensus.restype = C.c_int
+    L.dpo_hand_consensus.argtypes = [i64p, i64p, C.c_int, C.c_int, i64p, C.c_int64, i64p, C.POINTER(C.c_int), i64p, i64p, i64p,
+                                     C.c_int64, i64p]
+    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    sg = np.array([x for s in seqs for x in s], dtype=np.int64)
+    total = int(off[-1])
+    cons, ncons = np.zeros(total + 8, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    kept = (C.c_int * max(1, len(seqs)))()
+    counts = np.zeros(max(1, len(seqs)), dtype=np.int64)
+    a, b, nm = np.zeros(total + 8, dtype=np.int64), np.zeros(total + 8, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    rc = L.dpo_hand_consensus(ptr(sg, i64p), ptr(off, i64p), len(seqs), k, ptr(cons, i64p), len(cons), ptr(ncons, i64p), kept,
+                              ptr(counts, i64p), ptr(a, i64p), ptr(b, i64p), len(a), ptr(nm, i64p))
+    if rc != 0:
+        raise RuntimeError(L.dpo_last_error().decode())
+    pairs, order, at = {}, [], 0
+    for x in range(int(nm[0])):
+        n = int(counts[x])
+        pairs[int(kept[x])] = (a[at:at + n].copy(), b[at:at + n].copy())
+        order.append(int(kept[x]))
+        at += n
+    return cons[:int(ncons[0])].copy(), pairs, order
+
+
 class ReadSet:
     def __init__(self, bases=None, off=None, min_len=0, himem=True, fasta=None, quals=None):
         """quals: raw FASTQ quality characters (uint8, same offsets as bases): the set then behaves like a FASTQ file's."""
@@ -382,7 +410,8 @@ def _bytes(fn, h, *a):
 
 class OverlapRun:
     FIELDS = dict(seedKmers=0, queryIDs=1, querySeqIDs=2, indexedIds=3, indexedLength=4, indexedOffset=5,
-                  indexedInset=6, matchQueryIndex=7, matchTarget=8, newlyIgnored=9, scalars=10, queryLength=11, queryOffset=12, queryInset=13, querySegments=20,
+                  indexedInset=6, matchQueryIndex=7, matchTarget=8, newlyIgnored=9, scalars=10, queryLength=11, queryOffset=12, queryInset=13,
+                  pafWindow=14, ignoreCalls=15, ignoreWindow=16, windowStats=17, querySegments=20,
                   indexedSegments=21, candidates=22, matchA=23, matchB=24)
 
     def __init__(self, reads, k=10, overlap_size=1000, num_seeds=15, seed_batch_size=10000, chunk_size=10000,
@@ -420,6 +449,23 @@ class OverlapRun:
 
     def trace_paf(self, rnd):
         return _bytes(lib().dpo_overlap_trace_paf, self.h, rnd).decode()
+
+    #: columns of trace_windows(): matches of the window's two queries, then what BuildConsensus saw - trimmed sequences that passed the
+    #: GetBasesCovered filter, total ints of their Trimmed() and of their Reduced() forms, ints of the consensus, contig parts - and the
+    #: "Bad back" events and empty-match lines of the window
+    WINDOW_COLS = ("matches", "kept", "trimmed_ints", "reduced_ints", "cons_ints", "parts", "bad_back", "empty_match")
+
+    def trace_windows(self, rnd):
+        """The round's output by query window g (queries 2g, 2g + 1): dict of stats int64 [windows, 8] (WINDOW_COLS), lines (the PAF
+        lines of every window, in order) and ignores (the ids of its SetIgnore calls, in call order)."""
+        stats = self.trace(rnd, "windowStats").reshape(-1, len(self.WINDOW_COLS))
+        lines = [[] for _ in range(len(stats))]
+        for w, ln in zip(self.trace(rnd, "pafWindow"), self.trace_paf(rnd).splitlines()):
+            lines[int(w)].append(ln)
+        ignores = [[] for _ in range(len(stats))]
+        for w, i in zip(self.trace(rnd, "ignoreWindow"), self.trace(rnd, "ignoreCalls")):
+            ignores[int(w)].append(int(i))
+        return dict(stats=stats, lines=lines, ignores=ignores)
 
 
 def map_run(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40):
