@@ -752,6 +752,39 @@ __global__ void pack_kernel(const uint8_t* __restrict__ ascii, const int64_t* __
     packed[d] = out;
 }
 
+// The same layout cut from reads that are already resident (dp_reads_respan): 2 bit -> 2 bit, one thread per output dword.  Output
+// read r is bases [start, start + len) of source read spans[r].read: the dword's 16 bases begin at source base p = start + base0, i.e.
+// (p % 16) bases into source dword p / 16, and end in the next one at most.  With each dword byte-swapped its first base sits in the
+// top bits, so the pair is one 64-bit funnel shifted left by 2 (p % 16) bits.  The second dword is loaded only when one of the bases
+// wanted lies in it - never past the source read's own padded end; bases past the span's end and the padding up to the next read's
+// 16-byte boundary are zero.
+__global__ void repack_spans_kernel(const uint32_t* __restrict__ src, const uint64_t* __restrict__ sboff, const dp_read_span* __restrict__ spans,
+                                    const uint64_t* __restrict__ boff, uint32_t n_reads, uint32_t* __restrict__ packed, uint64_t n_dwords) {
+    const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_dwords) return;
+    const uint64_t byte = d * 4;
+    uint32_t lo = 0, hi = n_reads;  // binary search: last read with boff[r] <= byte
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (boff[mid] <= byte) lo = mid;
+        else hi = mid;
+    }
+    const dp_read_span sp = spans[lo];
+    const uint64_t base0 = (byte - boff[lo]) * 4;
+    uint32_t out = 0;
+    if (base0 < sp.len) {
+        const uint32_t nb = (uint32_t)(sp.len - base0 < 16 ? sp.len - base0 : 16);  // bases of this dword
+        const uint32_t p = sp.start + (uint32_t)base0, sh = p & 15u;
+        const uint32_t* w = src + sboff[sp.read] / 4 + (p >> 4);
+        uint64_t v = (uint64_t)__builtin_bswap32(w[0]) << 32;
+        if (sh + nb > 16) v |= __builtin_bswap32(w[1]);
+        uint32_t be = (uint32_t)((v << (2 * sh)) >> 32);
+        if (nb < 16) be &= ~0u << (2 * (16 - nb));
+        out = __builtin_bswap32(be);
+    }
+    packed[d] = out;
+}
+
 // Shared body of dp_reads_upload / dp_reads_upload_rc.  With first_paired < n_reads every host read r >= first_paired
 // becomes TWO device reads: first_paired + 2*(r - first_paired) (forward) and the next id (its reverse complement,
 // produced by the pack kernel; nothing but the forward ASCII crosses PCIe).
@@ -991,6 +1024,95 @@ extern "C" int dp_reads_upload(dp_ctx* ctx, const uint8_t* bases, const int64_t*
 
 extern "C" int dp_reads_upload_rc(dp_ctx* ctx, const uint8_t* bases, const int64_t* off, uint32_t n_reads, uint32_t first_paired) {
     return reads_upload_impl(ctx, bases, off, n_reads, first_paired);
+}
+
+// The resident read set replaced by spans of itself (the trimmed reads of `overlap -trim true`).  Only between the upload and a job's
+// set-up: everything a job derives from the reads (round tables, k-mer index, value table) would be void, and contexts that borrow the
+// reads hold plain copies of the blocks' addresses.
+extern "C" int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out) {
+    if (!ctx || (n_out && !spans)) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan: bad arguments") : DP_ERR_ARG;
+    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan on a context that borrows its reads");
+    if (ctx->n_borrowers.load() > 0) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan while contexts borrowing these reads exist");
+    {
+        std::lock_guard<std::mutex> lk(ctx->upload_mu);
+        if (ctx->upload) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan while an upload of dp_reads_upload_rc_begin is pending");
+    }
+    if (ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan after dp_round_begin: a round has been made on these reads");
+    if (ctx->kidx || ctx->d_kcounts) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan after a k-mer index or histogram has been made of these reads");
+    if (ctx->d_values.p) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan after a value table has been made for these reads");
+    if (n_out > 0x7fffffffu) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan: too many reads");
+    std::vector<uint64_t> h_boff((size_t)n_out + 1, 0);
+    std::vector<uint32_t> h_len(n_out, 0);
+    uint64_t pos = 0, total = 0;
+    for (uint32_t r = 0; r < n_out; r++) {
+        const dp_read_span& sp = spans[r];
+        if (sp.read >= ctx->n_reads || (uint64_t)sp.start + sp.len > ctx->h_len[sp.read]) {
+            const std::string msg = "dp_reads_respan: span " + std::to_string(r) + " lies outside its read";
+            return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+        }
+        h_boff[r] = pos;
+        h_len[r] = sp.len;
+        pos += ((uint64_t)(sp.len + 3) / 4 + 15) & ~(uint64_t)15;
+        total += sp.len;
+    }
+    h_boff[n_out] = pos;
+    hipSetDevice(ctx->device);
+    // both sets side by side: the new blocks are made, filled from the old ones, and only then take their place
+    DevBuf nb[3];
+    const size_t need[3] = {(size_t)pos + 64, ((size_t)n_out + 1) * 8, (size_t)n_out * 4 + 4};
+    void* d_spans = nullptr;
+    auto drop = [&] {
+        hipStreamSynchronize(ctx->stream);
+        for (DevBuf& b : nb)
+            if (b.p) dp_dev_free(b.p);
+        if (d_spans) dp_dev_free(d_spans);
+    };
+#define RS_HIP(call)                                                   \
+    do {                                                               \
+        const hipError_t e_ = (call);                                  \
+        if (e_ != hipSuccess) {                                        \
+            drop();                                                    \
+            return dp_fail(ctx, DP_ERR_HIP, "dp_reads_respan: " #call, e_); \
+        }                                                              \
+    } while (0)
+    for (int i = 0; i < 3; i++) {
+        nb[i].cap = (need[i] + 255) & ~(size_t)255;
+        RS_HIP(dp_dev_malloc(&nb[i].p, nb[i].cap));
+    }
+    RS_HIP(hipMemcpyAsync(nb[1].p, h_boff.data(), ((size_t)n_out + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_out) RS_HIP(hipMemcpyAsync(nb[2].p, h_len.data(), (size_t)n_out * 4, hipMemcpyHostToDevice, ctx->stream));
+    RS_HIP(hipMemsetAsync((uint8_t*)nb[0].p + pos, 0, 64, ctx->stream));
+    if (pos) {
+        RS_HIP(dp_dev_malloc(&d_spans, (size_t)n_out * sizeof(dp_read_span)));
+        RS_HIP(hipMemcpyAsync(d_spans, spans, (size_t)n_out * sizeof(dp_read_span), hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t n_dwords = pos / 4;
+        hipLaunchKernelGGL(repack_spans_kernel, dim3((uint32_t)((n_dwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_packed.p,
+                           (const uint64_t*)ctx->d_boff.p, (const dp_read_span*)d_spans, (const uint64_t*)nb[1].p, n_out, (uint32_t*)nb[0].p, n_dwords);
+        RS_HIP(hipGetLastError());
+    }
+    RS_HIP(dp_stream_sync(ctx));
+#undef RS_HIP
+    if (d_spans) dp_dev_free(d_spans);
+    DevBuf* res[3] = {&ctx->d_packed, &ctx->d_boff, &ctx->d_len};
+    for (int i = 0; i < 3; i++) {
+        if (res[i]->p) dp_dev_free(res[i]->p);  // (back to the block cache)
+        *res[i] = nb[i];
+    }
+    for (DevBuf* qb : {&ctx->d_qual, &ctx->d_qualoff, &ctx->d_hasq})  // the old set's quality bytes are void
+        if (qb->p) {
+            dp_dev_free(qb->p);
+            qb->p = nullptr;
+            qb->cap = 0;
+        }
+    ctx->n_reads = n_out;
+    ctx->ignore_epoch = ~0ull;  // (cached per-read-set state of dp_scan_reads)
+    ctx->ignore_shadow_valid = false;
+    ctx->items_ptr = nullptr;
+    ctx->h_boff.swap(h_boff);
+    ctx->h_len.swap(h_len);
+    ctx->packed_bytes = pos;
+    ctx->total_bases = total;
+    return DP_OK;
 }
 
 // ---- reads that arrive packed (round 6).  The reference keeps a read as 2 bits per base from the moment it is read from its file

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64 * TR_WAVES) void trim_edge_kernel(
 // ---------------------------------------------------------------------------------------------------------------
 // the device buffers of a handle: the adapter index (set-up), the edge stage's batch, the middle stage's chunks, pairs and records
 enum TrBuf { TB_TABLE, TB_SEGS, TB_OFF, TB_LEN, TB_BAR, TB_SIZE, TB_ROWS, TB_ROWST, TB_COUNTS, TB_ENABLED, TB_POOL, TB_ERR, TB_ENDS, TB_RECS,
-             TB_CBASES, TB_COFF, TB_CCOUNT, TB_CSEGOFF, TB_PAIRS, TB_MRECS, TB_MOVER, TB_MCNT, TB_N };
+             TB_CBASES, TB_COFF, TB_CCOUNT, TB_CSEGOFF, TB_PAIRS, TB_MRECS, TB_MOVER, TB_MCNT, TB_SPANS, TB_N };
 struct dp_trim {
     int device = 0, k = 0;
     uint32_t n_front = 0, n_back = 0, n_seeds = 0, SW = 0, qcap = 0, waves = 0;
@@ -831,5 +831,229 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
     out->index_ms = tr_ms(t, 0);
     out->query_ms = tr_ms(t, 1);
     if (n_pairs) out->kernel_ms = tr_ms(t, 2);
+    return DP_OK;
+}
+
+
+// ---- both stages on reads a context holds resident (`overlap -trim true`) --------------------------------------------------------------
+// The ends buffer and the chunk bases the two scan kernels read are spelled on the device from the context's 2-bit reads, so that what
+// crosses the link is a table of read ids or spans.  unpack_spans_kernel: one thread per 16 bytes of the destination.  Span i is, with
+// `ends_reads`, end i & 1 of read ends_reads[i >> 1] at i * 150 (the dense layout trim_edge_kernel reads: its spans start unaligned);
+// else spans[i] at doff[i].  A 16-byte group inside one span takes its 32 bits from at most two source dwords - the second one only when
+// the group's last base lies in it, so never past the read's padded end - and is stored at once; a group that straddles spans, or the
+// buffer's tail, goes base by base.  Traffic per base: 0.25 bytes read, 1 written.
+__global__ __launch_bounds__(256) void unpack_spans_kernel(const uint32_t* __restrict__ packed, const uint64_t* __restrict__ boff, const uint32_t* __restrict__ rlen,
+                                                           const uint32_t* __restrict__ ends_reads, const dp_read_span* __restrict__ spans,
+                                                           const uint64_t* __restrict__ doff, uint32_t n_spans, uint64_t total, uint8_t* __restrict__ dst) {
+    const uint64_t pos0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (pos0 >= total) return;
+    const uint8_t* src;
+    uint64_t lo, hi;  // the span's bytes of dst
+    uint32_t start;
+    auto load = [&](uint32_t i) {
+        uint32_t r;
+        if (ends_reads) {
+            r = ends_reads[i >> 1];
+            start = (i & 1u) ? rlen[r] - TR_EDGE : 0u;
+            lo = (uint64_t)i * TR_EDGE;
+            hi = lo + TR_EDGE;
+        } else {
+            r = spans[i].read;
+            start = spans[i].start;
+            lo = doff[i];
+            hi = doff[i + 1];
+        }
+        src = (const uint8_t*)packed + boff[r];
+    };
+    uint32_t i;
+    if (ends_reads) {
+        i = (uint32_t)(pos0 / TR_EDGE);
+    } else {  // the last span with doff[i] <= pos0 (empty spans before it share its offset)
+        uint32_t a = 0, b = n_spans;
+        while (b - a > 1) {
+            const uint32_t mid = (a + b) >> 1;
+            if (doff[mid] <= pos0) a = mid;
+            else b = mid;
+        }
+        i = a;
+    }
+    load(i);
+    if (pos0 + 16 <= hi) {
+        const uint32_t p = start + (uint32_t)(pos0 - lo);
+        const uint32_t* w = (const uint32_t*)src + (p >> 4);
+        u64 v = w[0];
+        if (p & 15u) v |= (u64)w[1] << 32;
+        uint32_t o[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const uint32_t q = (p & 15u) + j;  // base q of the two dwords: byte q / 4, first base in the byte's top bits
+            const uint32_t c = (uint32_t)(v >> (8 * (q >> 2) + 6 - 2 * (q & 3u))) & 3u;
+            o[j >> 2] |= ((0x54474341u >> (8 * c)) & 0xffu) << (8 * (j & 3));  // "ACGT"[c]
+        }
+        *(uint4*)(dst + pos0) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        const uint64_t end = pos0 + 16 < total ? pos0 + 16 : total;
+        for (uint64_t pos = pos0; pos < end; pos++) {
+            while (pos >= hi) load(++i);  // (pos < total: a span that holds it follows)
+            const uint32_t p = start + (uint32_t)(pos - lo);
+            const uint32_t c = (src[p >> 2] >> (6 - 2 * (p & 3u))) & 3u;
+            dst[pos] = (uint8_t)((0x54474341u >> (8 * c)) & 0xffu);
+        }
+    }
+}
+
+// doff[0 .. n] = the prefix of the spans' lengths (TB_COFF as chunk_scan_kernel reads it), by one workgroup: a slice per thread
+__global__ __launch_bounds__(1024) void span_offsets_kernel(const dp_read_span* __restrict__ spans, uint32_t n, uint64_t* __restrict__ doff) {
+    __shared__ u64 part[1024];
+    const uint32_t tid = threadIdx.x, per = (n + 1023u) / 1024u;
+    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
+    u64 s = 0;
+    for (uint32_t i = lo; i < hi; i++) s += spans[i].len;
+    part[tid] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const u64 v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    u64 run = part[tid] - s;
+    for (uint32_t i = lo; i < hi; i++) {
+        doff[i] = run;
+        run += spans[i].len;
+    }
+    if (tid == 1023) doff[n] = part[1023];
+}
+
+// what both resident calls check first, and the order they set up: `st` - the stream the unpack kernel runs on - waits for what is
+// queued on the context's stream (its upload) through an event of the handle's
+static int tr_resident_begin(dp_trim* t, dp_ctx* ctx, hipStream_t st, const char* who) {
+    const bool own = false;
+    if (!ctx) return tr_fail(t, DP_ERR_ARG, std::string(who) + ": null context");
+    if (ctx->device != t->device) return tr_fail(t, DP_ERR_ARG, std::string(who) + ": the handle and the context are on different devices");
+    {
+        std::lock_guard<std::mutex> lk(ctx->upload_mu);
+        if (ctx->upload) return tr_fail(t, DP_ERR_STATE, std::string(who) + ": an upload of dp_reads_upload_rc_begin is pending on the context");
+    }
+    TR_HIP(hipSetDevice(t->device));
+    TR_HIP(hipEventRecord(t->ev[0], ctx->stream));
+    TR_HIP(hipStreamWaitEvent(st, t->ev[0], 0));
+    return DP_OK;
+}
+
+extern "C" int dp_trim_edges_resident(dp_trim* t, dp_ctx* ctx, const uint32_t* reads, uint32_t n_reads, int mode, int min_match, int threshold,
+                                      dp_trim_rec* recs, uint64_t* counts, uint8_t* enabled, double* times_ms) {
+    if (!t) return tr_fail(nullptr, DP_ERR_ARG, "dp_trim_edges_resident: null handle");
+    const bool own = false;
+    if ((mode != DP_TRIM_MODE_TRIM && mode != DP_TRIM_MODE_DETERMINE) || (n_reads && !reads) || (mode == DP_TRIM_MODE_TRIM && n_reads && !recs))
+        return tr_fail(t, DP_ERR_ARG, "dp_trim_edges_resident: bad arguments");
+    if (mode == DP_TRIM_MODE_TRIM && min_match < 1) return tr_fail(t, DP_ERR_ARG, "dp_trim_edges_resident: min_match < 1");
+    if (n_reads > 0x3fffffffu) return tr_fail(t, DP_ERR_ARG, "dp_trim_edges_resident: batch too large");
+    if (int rc = tr_resident_begin(t, ctx, t->stream, "dp_trim_edges_resident")) return rc;
+    for (uint32_t i = 0; i < n_reads; i++)
+        if (reads[i] >= ctx->n_reads || ctx->h_len[reads[i]] < 200u)
+            return tr_fail(t, DP_ERR_ARG, "dp_trim_edges_resident: read " + std::to_string(reads[i]) + " is not a resident read of 200 bases or more");
+    const uint32_t nA = t->n_front + t->n_back, n_ends = 2 * n_reads;
+    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0;
+    if (n_ends) {
+        const size_t cap = std::max<size_t>(n_ends, 1u << 16);  // read ends the batch buffers hold once they grow
+        TR_HIP(tr_reserve(t, TB_ENDS, (size_t)n_ends * TR_EDGE, cap * TR_EDGE));
+        TR_HIP(tr_reserve(t, TB_RECS, (size_t)n_ends * sizeof(dp_trim_rec), cap * sizeof(dp_trim_rec)));
+        TR_HIP(tr_reserve(t, TB_SPANS, (size_t)n_reads * 4, cap * 2));
+        TR_HIP(hipMemsetAsync(t->buf[TB_ERR].p, 0, 64, t->stream));
+        TR_HIP(hipEventRecord(t->ev[0], t->stream));
+        TR_HIP(hipMemcpyAsync(t->buf[TB_SPANS].p, reads, (size_t)n_reads * 4, hipMemcpyHostToDevice, t->stream));
+        const uint64_t total = (uint64_t)n_ends * TR_EDGE;
+        hipLaunchKernelGGL(unpack_spans_kernel, dim3((uint32_t)((total + 4095) / 4096)), dim3(256), 0, t->stream, (const uint32_t*)ctx->d_packed.p,
+                           (const uint64_t*)ctx->d_boff.p, (const uint32_t*)ctx->d_len.p, t->dev<const uint32_t>(TB_SPANS), (const dp_read_span*)nullptr,
+                           (const uint64_t*)nullptr, n_ends, total, t->dev<uint8_t>(TB_ENDS));
+        TR_HIP(hipGetLastError());
+        TR_HIP(hipEventRecord(t->ev[1], t->stream));
+        const uint32_t blocks = std::min<uint32_t>(t->waves / TR_WAVES, (n_ends + TR_WAVES - 1) / TR_WAVES);
+        const size_t poolElems = (size_t)t->waves * M_CHAINS * t->qcap;
+        uint16_t* poolA = t->dev<uint16_t>(TB_POOL);
+        hipLaunchKernelGGL(trim_edge_kernel, dim3(blocks), dim3(64 * TR_WAVES), t->lds_bytes, t->stream, t->dev<const uint8_t>(TB_ENDS), n_ends, t->G,
+                           t->dev<const uint16_t>(TB_TABLE), t->dev<const int32_t>(TB_SEGS), t->dev<const uint32_t>(TB_OFF), t->dev<const int32_t>(TB_LEN),
+                           t->dev<const uint8_t>(TB_BAR), t->dev<const int32_t>(TB_SIZE), t->dev<const u64>(TB_ROWS), t->dev<const u64>(TB_ROWST), mode, min_match,
+                           threshold, t->dev<dp_trim_rec>(TB_RECS), t->dev<unsigned long long>(TB_COUNTS), t->dev<uint32_t>(TB_ENABLED), poolA, poolA + poolElems,
+                           poolA + 2 * poolElems, t->dev<uint32_t>(TB_ERR));
+        TR_HIP(hipGetLastError());
+        TR_HIP(hipEventRecord(t->ev[2], t->stream));
+        uint32_t errbits = 0;
+        if (mode == DP_TRIM_MODE_TRIM) TR_HIP(hipMemcpyAsync(recs, t->buf[TB_RECS].p, (size_t)n_ends * sizeof(dp_trim_rec), hipMemcpyDeviceToHost, t->stream));
+        TR_HIP(hipMemcpyAsync(&errbits, t->buf[TB_ERR].p, 4, hipMemcpyDeviceToHost, t->stream));
+        TR_HIP(hipEventRecord(t->ev[3], t->stream));
+        TR_HIP(hipStreamSynchronize(t->stream));
+        if (times_ms)
+            for (int i = 0; i < 3; i++) times_ms[i] = tr_ms(t, i);
+        if (errbits) return tr_fail(t, DP_ERR_CAPACITY, "dp_trim_edges_resident: chaining exceeded a device capacity (bits " + std::to_string(errbits) +
+                                                            ": 1 reduced sequence, 2 chain pool, 4 good-chain list)");
+    }
+    if (counts) TR_HIP(hipMemcpy(counts, t->buf[TB_COUNTS].p, (size_t)nA * 8, hipMemcpyDeviceToHost));
+    if (enabled) {
+        std::vector<uint32_t> en(nA);
+        TR_HIP(hipMemcpy(en.data(), t->buf[TB_ENABLED].p, (size_t)nA * 4, hipMemcpyDeviceToHost));
+        for (uint32_t a = 0; a < nA; a++) enabled[a] = en[a] ? 1 : 0;
+    }
+    return DP_OK;
+}
+
+extern "C" int dp_trim_scan_chunks_resident(dp_trim* t, dp_ctx* ctx, const dp_read_span* spans, uint32_t n_chunks, uint32_t* n_seeds_out,
+                                            double* times_ms) {
+    if (!t) return tr_fail(nullptr, DP_ERR_ARG, "dp_trim_scan_chunks_resident: null handle");
+    const bool own = false;
+    if (n_chunks && !spans) return tr_fail(t, DP_ERR_ARG, "dp_trim_scan_chunks_resident: bad arguments");
+    if (int rc = tr_mid_ctx(t)) return rc;
+    hipStream_t st = t->ctx->stream;
+    if (int rc = tr_resident_begin(t, ctx, st, "dp_trim_scan_chunks_resident")) return rc;
+    uint64_t nb = 0;
+    for (uint32_t c = 0; c < n_chunks; c++) {
+        if (spans[c].read >= ctx->n_reads || (uint64_t)spans[c].start + spans[c].len > ctx->h_len[spans[c].read])
+            return tr_fail(t, DP_ERR_ARG, "dp_trim_scan_chunks_resident: span " + std::to_string(c) + " lies outside its read");
+        nb += spans[c].len;
+    }
+    if (times_ms) times_ms[0] = times_ms[1] = 0;
+    t->n_chunks = 0;
+    t->c_count.assign(n_chunks, 0);
+    t->c_segoff.assign((size_t)n_chunks + 1, 0);
+    t->ctx->n_segs = 0;
+    if (!n_chunks) return DP_OK;
+    TR_HIP(tr_reserve(t, TB_CBASES, nb, nb + nb / 4));
+    const size_t cap = (size_t)n_chunks + n_chunks / 4 + 1024;  // chunks the per-chunk arrays hold once they grow
+    TR_HIP(tr_reserve(t, TB_COFF, ((size_t)n_chunks + 1) * 8, (cap + 1) * 8));
+    TR_HIP(tr_reserve(t, TB_CCOUNT, (size_t)n_chunks * 4, cap * 4));
+    TR_HIP(tr_reserve(t, TB_CSEGOFF, ((size_t)n_chunks + 1) * 8, (cap + 1) * 8));
+    TR_HIP(tr_reserve(t, TB_SPANS, (size_t)n_chunks * sizeof(dp_read_span), cap * sizeof(dp_read_span)));
+    TR_HIP(hipEventRecord(t->ev[0], st));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_SPANS].p, spans, (size_t)n_chunks * sizeof(dp_read_span), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(span_offsets_kernel, dim3(1), dim3(1024), 0, st, t->dev<const dp_read_span>(TB_SPANS), n_chunks, t->dev<uint64_t>(TB_COFF));
+    TR_HIP(hipGetLastError());
+    if (nb) {
+        hipLaunchKernelGGL(unpack_spans_kernel, dim3((uint32_t)((nb + 4095) / 4096)), dim3(256), 0, st, (const uint32_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p,
+                           (const uint32_t*)ctx->d_len.p, (const uint32_t*)nullptr, t->dev<const dp_read_span>(TB_SPANS), t->dev<const uint64_t>(TB_COFF), n_chunks, nb,
+                           t->dev<uint8_t>(TB_CBASES));
+        TR_HIP(hipGetLastError());
+    }
+    TR_HIP(hipEventRecord(t->ev[1], st));
+    const uint32_t blocks = std::min<uint32_t>(4096, (n_chunks + 3) / 4);
+    hipLaunchKernelGGL(chunk_scan_kernel<false>, dim3(blocks), dim3(256), 0, st, t->dev<const uint8_t>(TB_CBASES), t->dev<const uint64_t>(TB_COFF), n_chunks, t->k,
+                       t->dev<const uint16_t>(TB_TABLE), t->dev<uint32_t>(TB_CCOUNT), (const uint64_t*)nullptr, (int32_t*)nullptr);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipMemcpyAsync(t->c_count.data(), t->buf[TB_CCOUNT].p, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, st));
+    TR_HIP(hipStreamSynchronize(st));
+    for (uint32_t c = 0; c < n_chunks; c++) t->c_segoff[c + 1] = t->c_segoff[c] + 2ull * t->c_count[c] + 1;
+    const uint64_t total = t->c_segoff[n_chunks];
+    if (dev_reserve(t->ctx, t->ctx->d_segs, (size_t)total * 4 + 64)) return tr_fail(t, DP_ERR_HIP, std::string("dp_trim_scan_chunks_resident: ") + dp_last_error(t->ctx));
+    TR_HIP(hipMemcpyAsync(t->buf[TB_CSEGOFF].p, t->c_segoff.data(), ((size_t)n_chunks + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(chunk_scan_kernel<true>, dim3(blocks), dim3(256), 0, st, t->dev<const uint8_t>(TB_CBASES), t->dev<const uint64_t>(TB_COFF), n_chunks, t->k,
+                       t->dev<const uint16_t>(TB_TABLE), t->dev<uint32_t>(TB_CCOUNT), t->dev<const uint64_t>(TB_CSEGOFF), (int32_t*)t->ctx->d_segs.p);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipEventRecord(t->ev[2], st));
+    TR_HIP(hipStreamSynchronize(st));
+    t->ctx->n_segs = total;
+    t->n_chunks = n_chunks;
+    if (times_ms)
+        for (int i = 0; i < 2; i++) times_ms[i] = tr_ms(t, i);
+    if (n_seeds_out) memcpy(n_seeds_out, t->c_count.data(), (size_t)n_chunks * 4);
     return DP_OK;
 }

@@ -823,6 +823,7 @@ struct TrimResult {
     std::vector<int32_t> plan;            // per planned chunk: read, start, end, remainder, seeds, indexed
     std::vector<int32_t> splits;          // per live entry of ids (trim.go:227-256): read, aEnd, bStart, kept halves (bit 0 left, bit 1 right)
     std::vector<std::string> extraNames, extraBases, extraQuals;  // AddSequence (seqio.go:396-399) in the order added; quals as written (phred + 33)
+    std::vector<dp_read_span> extraSpans;  // the same halves as spans of the reads the trim ran on (coordinates of the untrimmed read)
     std::vector<int32_t> applied;         // the records applied, in canonical order (six int32 each)
     i64 midChunks = 0, midSeeds = 0, midBatches = 0, midPairs = 0, midRecords = 0, midOverflowPairs = 0, midOutOfRange = 0;
     double mid_upload_ms = 0, mid_scan_ms = 0, mid_index_ms = 0, mid_query_ms = 0, mid_kernel_ms = 0;
@@ -833,7 +834,13 @@ void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int
                    std::vector<TrimMidRec>& out);
 bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error);
 // the whole edge stage on HIP device `device`; reads receives ignore / frontTrim / backTrim.  0, or < 0 with `error` (-2: no read of 200 bases)
-int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error);
+// resident: a context on `device` that holds `reads` as uploaded by dp_reads_upload - both stages then take their bases from it (read ids
+// and spans go up instead of bases) and nothing is written: res.out stays empty and the log has no "Writing" line (trimmedReadSet)
+int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error,
+            dp_ctx* resident = nullptr);
+// the read set `downpore trim`'s output gives when it is read back with minimum length minLen - without writing it - and the span of
+// `raw` (the reads the trim ran on) behind each of its records; pure host code
+void trimmedReadSet(const ReadSet& raw, const TrimResult& res, i64 minLen, bool himem, ReadSet& out, std::vector<dp_read_span>& spans);
 // the middle stage's matching results: seedCounts[planned chunks] and the matches, in any order
 struct TrimMidInput {
     const int32_t* seedCounts = nullptr;

@@ -21,6 +21,7 @@ struct OverlapH {
     dp_ctx* xctx = nullptr;           // round-parallel mode: the context (own stream) the result exchange runs on
     std::vector<dp_comm*> slotComms;  // scan-shard with executor slots: one communicator per slot
     ReadSet* reads = nullptr;
+    ReadsH* trimmed = nullptr;        // dph_overlap_open_trim: the trimmed read set the job runs on (owned; `reads` points into it)
     int textRoot = -1;                // dph_overlap_text_root: >= 0 = a superstep gathers the rounds' PAF text to that rank only
     bool keepText = true;             // dph_overlap_keep_text(0): gathered rounds of other ranks are committed without their PAF text
     double tCtx = 0, tUpload = 0, tInit = 0;
@@ -219,6 +220,7 @@ void dph_overlap_destroy(void* hh) {
     for (dp_comm* c : h->slotComms) dp_comm_destroy(c);
     if (h->xctx) dp_ctx_destroy(h->xctx);
     dp_ctx_destroy(h->ctx);
+    delete h->trimmed;
     delete h;
 }
 void dph_overlap_set_shard(void* hh, int64_t lo, int64_t hi) {
@@ -1120,6 +1122,75 @@ extern "C" int64_t dph_hand_trim_match(const int32_t* chunk_segs, int n_chunk, c
     return (int64_t)recs.size();
 }
 extern "C" void dph_trim_free(void* h) { delete (TrimH*)h; }
+// the read set the run's output gives when it is read back with minimum length min_len (ReadSet::addLine's rule), without the text: a
+// reads handle of the caller's (dph_reads_free).  Needs no device: works on the handles of dph_trim_apply / _apply_mid too.
+extern "C" void* dph_trim_reads(void* h, int64_t min_len, int himem) {
+    TrimH* t = (TrimH*)h;
+    if (!t || !t->reads) {
+        g_err = "dph_trim_reads: bad arguments";
+        return nullptr;
+    }
+    ReadsH* out = new ReadsH();
+    std::vector<dp_read_span> spans;
+    trimmedReadSet(*t->reads, t->res, min_len, himem != 0, out->set, spans);
+    return out;
+}
+// `overlap -trim true`: the reads go up once, both trim stages run on the resident copy, the trimmed read set (min_len: overlap_size) is cut
+// from it on the device and the handle that comes back runs the job on it.  *trim_out: the trim run's handle (log, table, stats).
+extern "C" void* dph_overlap_open_trim(void* reads, void* front, void* back, const int64_t* trim_params, int n_params, int64_t min_len, int device,
+                                       void** trim_out) {
+    if (trim_out) *trim_out = nullptr;
+    TrimParams p;
+    if (!reads || !front || !back || !trim_out || !trimParamsFrom(trim_params, n_params, p)) {
+        g_err = "dph_overlap_open_trim: bad arguments (8 trim parameters, or 14 with the middle stage's)";
+        return nullptr;
+    }
+    ReadSet& raw = ((ReadsH*)reads)->set;
+    OverlapH* h = new OverlapH();
+    TrimH* th = new TrimH();
+    th->reads = &raw;
+    auto fail = [&](const std::string& why) -> void* {
+        g_err = why;
+        if (h->ctx) dp_ctx_destroy(h->ctx);
+        delete h->trimmed;
+        delete h;
+        delete th;
+        return nullptr;
+    };
+    const double tc0 = now();
+    if (dp_ctx_create(device, &h->ctx) != 0) return fail(dp_last_error(nullptr));
+    const double tc1 = now();
+    if (dp_reads_upload(h->ctx, (const uint8_t*)raw.bases.data(), raw.off.data(), (uint32_t)raw.size()) != 0) return fail(dp_last_error(h->ctx));
+    const double tc2 = now();
+    std::string error;
+    if (runTrim(raw, ((ReadsH*)front)->set, ((ReadsH*)back)->set, p, device, th->res, error, h->ctx) != 0) return fail(error);
+    const double tc3 = now();
+    h->trimmed = new ReadsH();
+    std::vector<dp_read_span> spans;
+    trimmedReadSet(raw, th->res, min_len, raw.himem, h->trimmed->set, spans);
+    ReadSet& rs = h->trimmed->set;
+    const double tc4 = now();
+    int rc = dp_reads_respan(h->ctx, spans.data(), (uint32_t)spans.size());
+    if (rc == 0 && rs.isFastq && !rs.qual.empty()) {
+        rc = dp_quality_upload(h->ctx, (const uint8_t*)rs.qual.data(), rs.off.data(), rs.hasQual.data(), (uint32_t)rs.size());
+        if (rc == 0) h->run.qualityCtx = h->ctx;
+    }
+    if (rc != 0) return fail(dp_last_error(h->ctx));
+    h->reads = &rs;
+    h->tCtx = tc1 - tc0;
+    h->tUpload = (tc2 - tc1) + (now() - tc4);
+    if (g_prof.on)
+        fprintf(stderr, "[setup] context %.1f ms, upload + pack %.1f ms, trim on resident reads %.1f ms, trimmed read set %.1f ms, respan %.1f ms\n", 1e3 * h->tCtx,
+                1e3 * (tc2 - tc1), 1e3 * (tc3 - tc2), 1e3 * (tc4 - tc3), 1e3 * (now() - tc4));
+    *trim_out = th;
+    return h;
+}
+// the read set a handle's jobs run on: the caller's for dph_overlap_open, the handle's own trimmed one for dph_overlap_open_trim (valid
+// while the handle lives; not to be freed)
+extern "C" void* dph_overlap_reads(void* hh) {
+    OverlapH* h = (OverlapH*)hh;
+    return h->trimmed;
+}
 extern "C" const char* dph_trim_output(void* h, int64_t* n) {
     *n = (int64_t)((TrimH*)h)->res.out.size();
     return ((TrimH*)h)->res.out.data();

@@ -21,6 +21,16 @@ static i64 parseInt(const std::string& a, bool& ok) {
     return v;
 }
 
+static void printLog(const std::string& text);
+static bool trimMiddleFromEnv() {  // the middle stage is in force with DP_TRIM_MIDDLE=1
+    const char* midEnv = getenv("DP_TRIM_MIDDLE");
+    return midEnv && midEnv[0] && strcmp(midEnv, "0") != 0;
+}
+static const char* const kNoMiddleNotice =
+    "downpore trim: the search for adapters in the middle of reads is not part of this build; reads are end-trimmed only\n";
+static const char* const kNoAdapterLists =
+    "downpore trim: -front_adapters and -back_adapters are required (the adapter lists are not shipped with this build)\n";
+
 static int runOverlap(ArgTable& t) {
     bool ok = true;
     OverlapParams p;
@@ -38,7 +48,18 @@ static int runOverlap(ArgTable& t) {
         fprintf(stderr, "seed_values files are not supported by this build (out of scope, SURVEY #16)\n");
         return 1;
     }
-    ReadSet reads;
+    // -trim true: `downpore trim` with its default flags in front, on the reads the device holds anyway, instead of through a file
+    const bool trim = parseBool(t.args["trim"]);
+    TrimParams tp;
+    if (trim) {
+        if (t.args["front_adapters"].empty() || t.args["back_adapters"].empty()) {
+            fputs(kNoAdapterLists, stderr);
+            return 1;
+        }
+        tp.middle = trimMiddleFromEnv();
+        if (!tp.middle) fputs(kNoMiddleNotice, stderr);
+    }
+    ReadSet reads, raw, front, back;
     std::string err;
     const bool prof = getenv("DPH_PROFILE") != nullptr;
     double tm = now();
@@ -48,7 +69,9 @@ static int runOverlap(ArgTable& t) {
         fprintf(stderr, "[cli] %-24s %.1f ms\n", what, 1e3 * (tn - tm));
         tm = tn;
     };
-    if (!ReadSet::fromFile(t.args["input"], p.overlapSize, p.himem, reads, err)) {
+    if (trim ? !ReadSet::fromFile(t.args["front_adapters"], 0, false, front, err) || !ReadSet::fromFile(t.args["back_adapters"], 0, false, back, err) ||
+                   !ReadSet::fromFile(t.args["input"], 50, p.himem, raw, err)
+             : !ReadSet::fromFile(t.args["input"], p.overlapSize, p.himem, reads, err)) {
         fprintf(stderr, "%s\n", err.c_str());
         return 1;
     }
@@ -58,7 +81,26 @@ static int runOverlap(ArgTable& t) {
         fprintf(stderr, "downpore: %s\n", dp_last_error(nullptr));
         return 2;
     }
-    int rc = dp_reads_upload(ctx, (const uint8_t*)reads.bases.data(), reads.off.data(), (uint32_t)reads.size());
+    const ReadSet& up = trim ? raw : reads;
+    int rc = dp_reads_upload(ctx, (const uint8_t*)up.bases.data(), up.off.data(), (uint32_t)up.size());
+    if (trim && rc == 0) {
+        mark("upload + pack");
+        TrimResult res;
+        std::string error;
+        const int trc = runTrim(raw, front, back, tp, 0, res, error, ctx);
+        printLog(res.errText);
+        if (trc != 0) {
+            fprintf(stderr, "downpore: %s\n", error.c_str());
+            return 2;
+        }
+        mark("trim (resident reads)");
+        std::vector<dp_read_span> spans;
+        trimmedReadSet(raw, res, p.overlapSize, p.himem, reads, spans);
+        raw = ReadSet();
+        mark("trimmed read set");
+        rc = dp_reads_respan(ctx, spans.data(), (uint32_t)spans.size());
+        mark("respan");
+    }
     OverlapRun run;
     const char* ns = getenv("DP_EXEC_SLOTS");
     if (rc == 0) rc = run.init(ctx, &reads, p, nullptr, ns ? atoi(ns) : 8);
@@ -116,8 +158,7 @@ static int runTrimCommand(ArgTable& t) {  // commands/trim.go:32-50
     p.requirePairs = parseBool(t.args["require_pairs"]);
     p.determineAdapters = parseBool(t.args["determine_adapters"]);
     // the flags of the search for adapters in the middle of reads: in force with DP_TRIM_MIDDLE=1, else parsed and accepted
-    const char* midEnv = getenv("DP_TRIM_MIDDLE");
-    p.middle = midEnv && midEnv[0] && strcmp(midEnv, "0") != 0;
+    p.middle = trimMiddleFromEnv();
     p.chunkSize = parseInt(t.args["chunk_size"], ok);
     p.middleThreshold = (int)parseInt(t.args["middle_threshold"], ok);
     p.extraMiddleTrim = (int)parseInt(t.args["extra_middle_trim"], ok);
@@ -129,10 +170,10 @@ static int runTrimCommand(ArgTable& t) {  // commands/trim.go:32-50
         return 1;
     }
     if (t.args["front_adapters"].empty() || t.args["back_adapters"].empty()) {
-        fprintf(stderr, "downpore trim: -front_adapters and -back_adapters are required (the adapter lists are not shipped with this build)\n");
+        fputs(kNoAdapterLists, stderr);
         return 1;
     }
-    if (!p.middle) fprintf(stderr, "downpore trim: the search for adapters in the middle of reads is not part of this build; reads are end-trimmed only\n");
+    if (!p.middle) fputs(kNoMiddleNotice, stderr);
     ReadSet front, back, reads;
     std::string err;
     if (!ReadSet::fromFile(t.args["front_adapters"], 0, false, front, err) || !ReadSet::fromFile(t.args["back_adapters"], 0, false, back, err) ||
@@ -163,14 +204,15 @@ int main(int argc, char** argv) {
     setenv("GPU_MAX_HW_QUEUES", "8", 0);  // one hardware queue per executor slot's stream (the runtime's default is 4)
     ArgTable ov, mp, tr;
     ov.make({"overlap_size", "k", "num_seeds", "seed_batch_size", "chunk_size", "query_batch_size", "min_hits", "num_workers",
-             "input", "seed_values", "himem"},
-            {"1000", "10", "15", "10000", "10000", "20000", "0.25", "4", "", "", "true"},
+             "input", "seed_values", "himem", "trim", "front_adapters", "back_adapters"},
+            {"1000", "10", "15", "10000", "10000", "20000", "0.25", "4", "", "", "true", "false", "", ""},
             {"Size of overlap to search for in bases", "Number of bases in each seed",
              "Minimum number of seeds to generate for each overlap query", "Maximum total unique seeds to use in each query batch",
              "Size to chop long reads into for querying against, in bases",
              "Maximum number of queries per batch (if max seeds not reached)", "Minimum proportion of seeds that must match each query",
              "Number of worker threads to spawn", "Fasta/fastq input file", "File containing values to use during seed selection.",
-             "Whether to cache all reads in memory"});
+             "Whether to cache all reads in memory", "Whether to trim adapters off the reads first, as the trim command does with its default flags",
+             "Fasta/fastq file containing front adapters (with -trim)", "Fasta/fastq file containing back adapters (with -trim)"});
     mp.make({"input", "reference", "circular", "k", "query_size", "min_length", "chunk_size", "seed_rate", "num_workers", "all_sequences"},
             {"", "", "true", "11", "1000", "500", "10000", "40", "4", "false"},
             {"Fasta/fastq input file", "A fasta file containing a reference sequence to align against",

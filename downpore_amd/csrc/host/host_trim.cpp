@@ -81,6 +81,23 @@ void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
     }
 }
 
+// One edge call over the reads [lo, hi): their ends extracted here and sent, or - with `resident`, a context that holds `reads` - spelled on
+// the device from the packed reads, the eligible reads' ids being all that goes up.  `up` receives the bytes sent.
+int edgeCall(dp_trim* h, dp_ctx* resident, const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b, int mode, int minMatch, int threshold, dp_trim_rec* recs,
+             uint64_t* counts, uint8_t* enabled, double* tms, double* up) {
+    if (resident) {
+        *up = 4.0 * (double)b.reads.size();
+        return dp_trim_edges_resident(h, resident, b.reads.data(), (uint32_t)b.reads.size(), mode, minMatch, threshold, recs, counts, enabled, tms);
+    }
+    *up = (double)b.ends.size();
+    return dp_trim_edges(h, b.ends.data(), (uint32_t)b.reads.size(), mode, minMatch, threshold, recs, counts, enabled, tms);
+}
+// the batch of reads [lo, hi): with `resident` only the list of the eligible ones
+void edgeBatch(const ReadSet& reads, size_t lo, size_t hi, bool resident, EdgeBatch& b) {
+    if (resident) eligibleReads(reads, lo, hi, b.reads);
+    else extractEnds(reads, lo, hi, b);
+}
+
 // trimWorker's arithmetic on the device's records (trim.go:464-510): frontTrim / backTrim / ignore of the reads, their names after
 // tagging, seen / none, the table's adapter columns, and the adapters with their counts
 bool applyEdgeRecords(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimIndex& ix, const TrimParams& p, const std::vector<uint32_t>& eligible,
@@ -163,7 +180,7 @@ void writeExtras(const ReadSet& reads, const TrimResult& res, const std::vector<
 }
 
 // PrintStats (trim.go:260-268) and Write (seqio.go:401-458)
-int reportAndWrite(const ReadSet& reads, const ReadSet& front, const ReadSet& back, TrimResult& res, std::string& error) {
+int reportAndWrite(const ReadSet& reads, const ReadSet& front, const ReadSet& back, TrimResult& res, std::string& error, bool write = true) {
     // PrintStats: with seenCount == 0 the reference divides by zero
     if (res.seen == 0) {
         logLine(res.errText, "no reads long enough to trim");
@@ -175,9 +192,10 @@ int reportAndWrite(const ReadSet& reads, const ReadSet& front, const ReadSet& ba
     for (size_t i = 0; i < back.size(); i++)
         logLine(res.errText, "Back adapter: " + back.names[i] + " \t " + std::to_string((i64)(res.counts[front.size() + i] * 100) / res.seen) + " %");
     logLine(res.errText, std::to_string((res.none * 100) / res.seen) + " % with no adapters found.");
+    res.out.clear();
+    if (!write) return 0;  // (the reads stay on the device: trimmedReadSet)
     logLine(res.errText, "Writing trimmed sequences...");  // commands/trim.go:44
     const double t1 = now();
-    res.out.clear();
     trimWrite(reads, res.names, nullptr, res.out);
     writeExtras(reads, res, res.extraNames, nullptr, res.out);
     res.t_write = now() - t1;
@@ -362,6 +380,7 @@ void midEmitHalves(ReadSet& reads, const TrimParams& p, const std::vector<MidSpl
                 res.extraNames.push_back(res.names[id] + "_(left)");
                 res.extraBases.push_back(bases(id, 0, e));
                 res.extraQuals.push_back(quals(id, 0, e));
+                res.extraSpans.push_back(dp_read_span{(uint32_t)id, (uint32_t)reads.frontTrim[id], (uint32_t)e});
                 report += ": 0 - " + std::to_string(split.aEnd) + " and ";
                 kept |= 1;
             } else {
@@ -376,6 +395,7 @@ void midEmitHalves(ReadSet& reads, const TrimParams& p, const std::vector<MidSpl
                     res.extraNames.push_back(res.names[id] + "_(right)");
                     res.extraBases.push_back(bases(id, split.bStart, len));
                     res.extraQuals.push_back(quals(id, split.bStart, len));
+                    res.extraSpans.push_back(dp_read_span{(uint32_t)id, (uint32_t)(reads.frontTrim[id] + split.bStart), (uint32_t)(len - split.bStart)});
                     report += std::to_string(split.bStart) + " - " + std::to_string(len);
                     kept |= 2;
                 }
@@ -572,7 +592,7 @@ TrimDev setupDevice(const TrimIndex& ix, int device, std::string& error) {
 
 // the middle stage's device half over the plan `mp`: scan every planned chunk for its seed count, cut the flush batches, then per batch
 // scan -> index -> candidates -> matching kernel, and the host's Match for the pairs the kernel listed
-bool midDevice(dp_trim* h, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, MidPlan& mp, std::vector<int32_t>& seedCounts,
+bool midDevice(dp_trim* h, dp_ctx* resident, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, MidPlan& mp, std::vector<int32_t>& seedCounts,
                std::vector<TrimMidRec>& recs, TrimResult& res, std::string& error) {
     const size_t nC = mp.plan.size();
     seedCounts.assign(nC, 0);
@@ -581,25 +601,37 @@ bool midDevice(dp_trim* h, const ReadSet& reads, const TrimIndex& ix, const Trim
     std::vector<uint8_t> bases;
     std::vector<uint64_t> off;
     std::vector<uint32_t> cnt;
+    std::vector<dp_read_span> spans;
     double tms[2];
-    // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device
+    // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device.  With `resident` the chunks
+    // are named as spans of the reads that context holds, in the coordinates of the uploaded read.
     auto scan = [&](size_t lo, size_t hi) -> bool {
-        off.assign(1, 0);
-        for (size_t c = lo; c < hi; c++) off.push_back(off.back() + (uint64_t)(mp.plan[c].end - mp.plan[c].start));
-        bases.resize((size_t)off.back() + 1);
-        for (size_t c = lo; c < hi; c++) {
-            const TrimChunk& ch = mp.plan[c];
-            memcpy(bases.data() + off[c - lo], reads.seq(ch.read) + reads.frontTrim[ch.read] + ch.start, (size_t)(ch.end - ch.start));
-        }
         cnt.assign(hi - lo, 0);
-        if (!devOk(dp_trim_scan_chunks(h, bases.data(), off.data(), (uint32_t)(hi - lo), cnt.data(), tms) == 0, h, error)) return false;
+        if (resident) {
+            spans.clear();
+            for (size_t c = lo; c < hi; c++) {
+                const TrimChunk& ch = mp.plan[c];
+                spans.push_back(dp_read_span{ch.read, (uint32_t)(reads.frontTrim[ch.read] + ch.start), (uint32_t)(ch.end - ch.start)});
+            }
+            if (!devOk(dp_trim_scan_chunks_resident(h, resident, spans.data(), (uint32_t)spans.size(), cnt.data(), tms) == 0, h, error)) return false;
+            res.bytes_up += (double)(spans.size() * sizeof(dp_read_span));
+        } else {
+            off.assign(1, 0);
+            for (size_t c = lo; c < hi; c++) off.push_back(off.back() + (uint64_t)(mp.plan[c].end - mp.plan[c].start));
+            bases.resize((size_t)off.back() + 1);
+            for (size_t c = lo; c < hi; c++) {
+                const TrimChunk& ch = mp.plan[c];
+                memcpy(bases.data() + off[c - lo], reads.seq(ch.read) + reads.frontTrim[ch.read] + ch.start, (size_t)(ch.end - ch.start));
+            }
+            if (!devOk(dp_trim_scan_chunks(h, bases.data(), off.data(), (uint32_t)(hi - lo), cnt.data(), tms) == 0, h, error)) return false;
+            res.bytes_up += (double)off.back();
+        }
         res.mid_upload_ms += tms[0];
         res.mid_scan_ms += tms[1];
-        res.bytes_up += (double)off.back();
         for (size_t c = lo; c < hi; c++) seedCounts[c] = (int32_t)cnt[c - lo];
         return true;
     };
-    const uint64_t groupBases = (uint64_t)1 << 28;
+    const uint64_t groupBases = (uint64_t)1 << 28;  // (bytes of chunk bases on the device per scan, whichever way they get there)
     size_t scannedLo = 0, scannedHi = 0;  // what the device holds segments of
     for (size_t lo = 0; lo < nC;) {
         size_t hi = lo;
@@ -857,7 +889,8 @@ int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const
     return reportAndWrite(reads, front, back, res, error);
 }
 
-int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, int device, TrimResult& res, std::string& error) {
+int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, int device, TrimResult& res, std::string& error,
+            dp_ctx* resident) {
     res = TrimResult();
     TrimIndex ix;
     if (!trimBuildIndex(front0, back0, p.k, ix, error)) return -1;
@@ -873,9 +906,10 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
             const TrimDev h = setupDevice(ix, device, error);
             if (!h) return -1;
             for (size_t lo = 0; lo < nCheck; lo += batchReads) {
-                extractEnds(reads, lo, std::min(nCheck, lo + batchReads), eb);
-                if (!devOk(dp_trim_edges(h.get(), eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr,
-                                         enabled.data(), tms) == 0,
+                const size_t hi = std::min(nCheck, lo + batchReads);
+                double up;
+                edgeBatch(reads, lo, hi, resident != nullptr, eb);
+                if (!devOk(edgeCall(h.get(), resident, reads, lo, hi, eb, DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr, enabled.data(), tms, &up) == 0,
                            h.get(), error))
                     return -1;
                 res.k_determine_ms += tms[1];
@@ -898,19 +932,20 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
     }
     for (size_t lo = 0; lo < reads.size(); lo += batchReads) {
         const double t0 = now();
-        extractEnds(reads, lo, std::min(reads.size(), lo + batchReads), eb);
+        const size_t hi = std::min(reads.size(), lo + batchReads);
+        edgeBatch(reads, lo, hi, resident != nullptr, eb);
         res.t_extract += now() - t0;
         const size_t at = eligible.size();
         eligible.insert(eligible.end(), eb.reads.begin(), eb.reads.end());
         recs.resize(2 * eligible.size(), dp_trim_rec{kEdgeSize, 0, 0, 0, 0, 0});  // (no adapters at all: what findMatches returns)
         if (h && !eb.reads.empty()) {
-            if (!devOk(dp_trim_edges(h.get(), eb.ends.data(), (uint32_t)eb.reads.size(), DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms) == 0,
-                       h.get(), error))
+            double up;
+            if (!devOk(edgeCall(h.get(), resident, reads, lo, hi, eb, DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms, &up) == 0, h.get(), error))
                 return -1;
             res.upload_ms += tms[0];
             res.kernel_ms += tms[1];
             res.download_ms += tms[2];
-            res.bytes_up += (double)eb.ends.size();
+            res.bytes_up += up;
             res.bytes_down += (double)(2 * eb.reads.size() * sizeof(dp_trim_rec));
         }
     }
@@ -920,7 +955,7 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         MidPlan mp;
         std::vector<int32_t> seedCounts;
         std::vector<TrimMidRec> midRecs;
-        if (!midBuildPlan(reads, p, mp, error) || !midDevice(h.get(), reads, ix, p, mp, seedCounts, midRecs, res, error)) return -1;
+        if (!midBuildPlan(reads, p, mp, error) || !midDevice(h.get(), resident, reads, ix, p, mp, seedCounts, midRecs, res, error)) return -1;
         TrimMidInput mid;
         mid.seedCounts = seedCounts.data();
         mid.nChunks = seedCounts.size();
@@ -931,7 +966,46 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
     fillTable(reads, res);
     res.t_apply = now() - t0;
     h.reset();
-    return reportAndWrite(reads, front, back, res, error);
+    return reportAndWrite(reads, front, back, res, error, resident == nullptr);
+}
+
+// The read set `trim`'s output would give when read back (rules 3 and 4 of DESIGN.md 4.8), without the text: the non-ignored reads in
+// file order under their names after tagging, bases [front trim, length - back trim), then the halves of split reads in the order
+// added; every record spelled "ACGT"[code] with its quality bytes as trimWrite / writeExtras print them, and kept as
+// ReadSet::addLine keeps a written line of n bases: iff n + 1 >= minLen (a record of no bases is dropped).  spans[i] names record i of
+// `out` in the coordinates of `raw`, the read set the trim ran on.
+void trimmedReadSet(const ReadSet& raw, const TrimResult& res, i64 minLen, bool himem, ReadSet& out, std::vector<dp_read_span>& spans) {
+    out = ReadSet();
+    out.himem = himem;
+    out.off.push_back(0);
+    spans.clear();
+    std::string line, ql;
+    auto add = [&](const std::string& name, const dp_read_span& sp) {
+        if (sp.len == 0) return;
+        out.isFastq = raw.isFastq;  // (the written file's first line would begin with '@')
+        const char* s = raw.seq(sp.read) + sp.start;
+        line.resize((size_t)sp.len + 1);
+        for (uint32_t j = 0; j < sp.len; j++) line[j] = "ACGT"[baseCode((unsigned char)s[j])];
+        line[sp.len] = '\n';
+        const uint8_t* q = raw.isFastq ? raw.quality(sp.read) : nullptr;
+        ql.clear();
+        if (q)
+            for (uint32_t j = 0; j < sp.len; j++) ql += (char)(uint8_t)(q[sp.start + j] + 33);
+        ql += '\n';
+        const size_t before = out.size();
+        out.addLine(name, line.data(), line.size(), minLen, raw.isFastq ? ql.data() : nullptr, raw.isFastq ? ql.size() : 0);
+        if (out.size() != before) spans.push_back(sp);
+    };
+    for (size_t r = 0; r < raw.size(); r++) {
+        const int32_t* row = res.table.data() + 5 * r;
+        if (row[2]) continue;
+        add(res.names[r], dp_read_span{(uint32_t)r, (uint32_t)row[0], (uint32_t)(raw.length(r) - row[0] - row[1])});
+    }
+    for (size_t e = 0; e < res.extraSpans.size(); e++) add(res.extraNames[e], res.extraSpans[e]);
+    if (out.isFastq) {
+        out.qual.resize(out.bases.size(), 0);
+        out.hasQual.resize(out.names.size(), 0);
+    }
 }
 
 }  // namespace dph

@@ -97,7 +97,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
-           "dp_trim_chunk_segments", "dp_trim_search"]
+           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan"]
 
 _lib = None
 
@@ -228,6 +228,14 @@ class Context:
         n = C.c_uint64(0)
         self._chk(self.L.dp_reads_packed(self.h, r, out.ctypes.data, nb, C.byref(n)))
         return out[:nb]
+
+    def respan(self, spans):
+        """dp_reads_respan: the resident read set replaced by spans of itself - uint32 [n, 3] = (read, start, len) per new read, any order,
+        a read any number of times.  Only between the upload and the first round / index / value table (DpError otherwise)."""
+        sp = np.ascontiguousarray(spans, dtype=np.uint32).reshape(-1, 3)
+        self.L.dp_reads_respan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._chk(self.L.dp_reads_respan(self.h, sp.ctypes.data if len(sp) else None, len(sp)))
+        self.read_len = sp[:, 2].astype(np.int64)
 
     # ---- A22
     def kmer_histogram(self, k):

@@ -56,6 +56,10 @@ def load_host():
     H.dph_overlap_destroy.argtypes = [vp]
     H.dph_overlap_open.restype = vp
     H.dph_overlap_open.argtypes = [vp, C.c_int]
+    H.dph_overlap_open_trim.restype = vp
+    H.dph_overlap_open_trim.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_int, C.POINTER(vp)]
+    H.dph_overlap_reads.restype = vp
+    H.dph_overlap_reads.argtypes = [vp]
     H.dph_overlap_init.argtypes = [vp, C.c_void_p, C.c_double, C.c_void_p]
     H.dph_overlap_reset.argtypes = [vp]
     H.dph_overlap_setup_times.restype = None
@@ -202,6 +206,13 @@ class Reads:
                 self.h = H.dph_reads_from_arrays(b.ctypes.data, o.ctypes.data, len(o) - 1, min_len, 1 if himem else 0)
         self.H = H
 
+    @classmethod
+    def _wrap(cls, h, keep=None):
+        """a reads handle the library made (keep: what must stay alive for as long as it is used)"""
+        r = cls.__new__(cls)
+        r.H, r.h, r._keep = load_host(), h, keep
+        return r
+
     def __len__(self):
         return self.H.dph_reads_count(self.h)
 
@@ -222,7 +233,7 @@ class OverlapPipeline:
 
     def __init__(self, reads, device=0, k=10, overlap_size=1000, num_seeds=15, seed_batch_size=10000, chunk_size=10000,
                  query_batch_size=20000, min_hits=0.25, himem=True, values=None, rank=0, world=1, torch_device=None,
-                 mode="round", slots=1, query_type=1, defer_init=False, comm=None):
+                 mode="round", slots=1, query_type=1, defer_init=False, comm=None, trim=None):
         """mode (world > 1): "round" = pipelined round-parallel (rank r's executor pipeline works on the rounds
         r, r+world, ...; per superstep every rank contributes its next round, results are all-gathered and committed in
         order with the speculation check); "round-batch" = the same exchange with batch-synchronous supersteps (every rank
@@ -236,7 +247,11 @@ class OverlapPipeline:
         this state, so whole jobs can be run - and timed - repeatedly on resident reads.
         comm (scan-shard): "rccl" = the survivor exchange runs inside the library over an RCCL communicator (dp_comm_init; the
         128-byte id travels through torch.distributed once); "local" = in-process peers wired with link_local(); None = the
-        exchange is done here with torch.distributed on host copies (gloo tests)."""
+        exchange is done here with torch.distributed on host copies (gloo tests).
+        trim: dict(front=Reads, back=Reads, **keyword arguments of trim_reads) = `downpore trim` first, on the reads the device holds
+        anyway: `reads` (loaded with min_len=50) go up once, both trim stages run on the resident copy and the job runs on the
+        trimmed read set, cut from it on the device, as if `trim`'s output had been read back with min_len=overlap_size.  Afterwards
+        `self.trim` is the TrimResult (no output text) and `self.reads` the trimmed Reads."""
         self.H = load_host()
         if mode == "scan-shard" and world > 1 and comm is None:
             slots = 1  # (the host-side exchange of the gloo tests is one round at a time)
@@ -246,9 +261,23 @@ class OverlapPipeline:
         self.slots = slots
         self._values_keepalive = values
         self._params, self._min_hits = p, float(min_hits)
-        self.h = self.H.dph_overlap_open(reads.h, device)
-        if not self.h:
-            raise DpError("dph_overlap_open: " + self.H.dph_last_error(None).decode())
+        self.trim = None
+        if trim is not None:
+            from . import trim as T
+            kw = dict(trim)
+            front, back = kw.pop("front"), kw.pop("back")
+            tp = T.trim_params(**kw)
+            th = C.c_void_p()
+            self.h = self.H.dph_overlap_open_trim(reads.h, front.h, back.h, tp.ctypes.data, len(tp), overlap_size, device, C.byref(th))
+            if not self.h:
+                raise DpError("dph_overlap_open_trim: " + self.H.dph_last_error(None).decode())
+            self.raw_reads = reads  # (the TrimResult's stats read it)
+            self.trim = T.TrimResult(T._host(), th)
+            reads = Reads._wrap(self.H.dph_overlap_reads(self.h), keep=self)
+        else:
+            self.h = self.H.dph_overlap_open(reads.h, device)
+            if not self.h:
+                raise DpError("dph_overlap_open: " + self.H.dph_last_error(None).decode())
         self.reads = reads
         self.rank, self.world = rank, world
         self.torch_device = torch_device

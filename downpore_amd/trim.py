@@ -49,6 +49,8 @@ def _host():
     H.dph_trim_extras.restype = C.POINTER(C.c_char)
     H.dph_trim_extras.argtypes = [vp, C.POINTER(C.c_int64)]
     H.dph_trim_mid_stats.argtypes = [vp, vp]
+    H.dph_trim_reads.restype = vp
+    H.dph_trim_reads.argtypes = [vp, C.c_int64, C.c_int]
     return H
 
 
@@ -96,6 +98,16 @@ class TrimResult:
         """output, stderr, table, stats = trim_reads(...)"""
         return iter((self.output, self.stderr, self.table, self.stats))
 
+    def reads(self, min_len, himem=True):
+        """The read set `output` gives when it is read back with Reads(fasta=..., min_len=min_len) - the non-ignored reads trimmed, then
+        the halves of split reads - without the text (dph_trim_reads; no device needed).  This is how a consumer such as map_reads
+        gets trimmed reads without a file.  Keep the reads the trim ran on alive while calling it."""
+        from .overlap import Reads
+        h = self._H.dph_trim_reads(self._h, min_len, 1 if himem else 0)
+        if not h:
+            raise DpError("dph_trim_reads: " + self._H.dph_last_error(None).decode())
+        return Reads._wrap(h)
+
     def demultiplex(self, path):
         """Demultiplex (sequence/seqio.go:460-523) into directory `path`; returns the number of files written."""
         rc = self._H.dph_trim_demultiplex(self._h, str(path).encode())
@@ -115,6 +127,13 @@ class TrimResult:
             pass
 
 
+def trim_params(k=6, check_reads=10000, adapter_threshold=90, extra_end_trim=5, tag_adapters=True, require_pairs=False, determine_adapters=True,
+                verbosity=1, middle=False, chunk_size=5000, middle_threshold=85, extra_middle_trim=100, discard_middle=False, flush_seeds=300_000_000):
+    """trim_reads' keyword arguments as the int64 parameter block dph_trim_run / dph_overlap_open_trim take"""
+    p = _params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity)
+    return _mid_params(p, chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds) if middle else p
+
+
 def trim_reads(reads, front, back, k=6, check_reads=10000, adapter_threshold=90, extra_end_trim=5, tag_adapters=True,
                require_pairs=False, determine_adapters=True, device=0, verbosity=1, middle=False, chunk_size=5000, middle_threshold=85,
                extra_middle_trim=100, discard_middle=False, flush_seeds=300_000_000):
@@ -125,9 +144,8 @@ def trim_reads(reads, front, back, k=6, check_reads=10000, adapter_threshold=90,
     halves of split reads follow the file's reads as <name>_(left) / <name>_(right) (TrimResult.splits / .extras; needs k >= 4).
     middle=False is the edge stage alone."""
     H = _host()
-    p = _params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity)
-    if middle:
-        p = _mid_params(p, chunk_size, middle_threshold, extra_middle_trim, discard_middle, flush_seeds)
+    p = trim_params(k, check_reads, adapter_threshold, extra_end_trim, tag_adapters, require_pairs, determine_adapters, verbosity, middle, chunk_size,
+                    middle_threshold, extra_middle_trim, discard_middle, flush_seeds)
     h = H.dph_trim_run(reads.h, front.h, back.h, p.ctypes.data, len(p), device)
     if not h:
         raise DpError("dph_trim_run: " + H.dph_last_error(None).decode())
@@ -223,6 +241,8 @@ class TrimDevice:
         L.dp_trim_scan_chunks.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
         L.dp_trim_chunk_segments.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.dp_trim_search.argtypes = [vp, vp, C.c_uint32, C.c_int, C.POINTER(MidBatch)]
+        L.dp_trim_edges_resident.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.dp_trim_scan_chunks_resident.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
         self.L = L
         self.n_adapters = index["n_front"] + index["n_back"]
         ix = {key: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for key, v in index.items()}
@@ -249,6 +269,29 @@ class TrimDevice:
                                   enabled.ctypes.data, times.ctypes.data)
         self._check(rc, "dp_trim_edges")
         return (recs, counts, times) if mode == MODE_TRIM else (enabled, times)
+
+    def edges_resident(self, ctx, read_ids, mode=MODE_TRIM, min_match=3, threshold=90):
+        """edges() for reads the Context `ctx` holds resident (dp_trim_edges_resident): read_ids = the reads, each of 200 bases or more;
+        their ends are spelled on the device and only the ids go up.  Returns what edges() returns."""
+        ids = np.ascontiguousarray(read_ids, dtype=np.uint32)
+        recs = np.zeros((2 * len(ids), 6), dtype=np.int32)
+        counts = np.zeros(self.n_adapters, dtype=np.uint64)
+        enabled = np.zeros(self.n_adapters, dtype=np.uint8)
+        times = np.zeros(3, dtype=np.float64)
+        rc = self.L.dp_trim_edges_resident(self.h, ctx.h, ids.ctypes.data, len(ids), mode, min_match, threshold, recs.ctypes.data, counts.ctypes.data,
+                                           enabled.ctypes.data, times.ctypes.data)
+        self._check(rc, "dp_trim_edges_resident")
+        return (recs, counts, times) if mode == MODE_TRIM else (enabled, times)
+
+    def scan_chunks_resident(self, ctx, spans):
+        """scan_chunks() with chunk c = bases [start, start + len) of resident read `read` of the Context `ctx`: spans uint32 [n, 3] =
+        (read, start, len).  Returns what scan_chunks() returns; chunk_segments / search follow as usual."""
+        sp = np.ascontiguousarray(spans, dtype=np.uint32).reshape(-1, 3)
+        counts = np.zeros(len(sp), dtype=np.uint32)
+        times = np.zeros(2, dtype=np.float64)
+        rc = self.L.dp_trim_scan_chunks_resident(self.h, ctx.h, sp.ctypes.data, len(sp), counts.ctypes.data, times.ctypes.data)
+        self._check(rc, "dp_trim_scan_chunks_resident")
+        return counts, times
 
     def scan_chunks(self, chunks):
         """dp_trim_scan_chunks: chunks = a list of ASCII base strings (or bytes) -> (seeds per chunk uint32, times_ms [upload, scan]).

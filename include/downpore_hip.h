@@ -648,6 +648,30 @@ DP_API int dp_trim_scan_chunks(dp_trim* t, const uint8_t* bases, const uint64_t*
 DP_API int dp_trim_chunk_segments(dp_trim* t, uint32_t chunk, int32_t* out, uint64_t cap, uint64_t* n);
 DP_API int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, int mid_threshold, dp_trim_mid_batch* out);
 DP_API const char* dp_trim_error(const dp_trim* t);
+/* ---- `trim` on reads a context already holds (`overlap -trim true`) ---------------------------------------------------------------
+ * The reads go up once (dp_reads_upload, 2 bit per base); both trim stages take their bases from that copy and the trimmed read set is
+ * cut from it on the device, so the bases never cross the link again.  t and ctx must be on one device (DP_ERR_ARG otherwise); the
+ * handle's stream waits for what is queued on the context's stream through an event.  An upload of dp_reads_upload_rc_begin that is
+ * still pending is refused (DP_ERR_STATE).
+ * dp_trim_edges_resident: dp_trim_edges for the resident reads reads[0 .. n_reads), each of at least 200 bases (DP_ERR_ARG): the
+ * first and the last 150 bases of each, spelled "ACGT"[code], are written into the handle's ends buffer on the device; what goes up is
+ * the 4 bytes per read of the id list.  times_ms[0] is that copy and the kernel that spells the ends.
+ * dp_trim_scan_chunks_resident: dp_trim_scan_chunks with chunk c = spans[c]; 12 bytes per chunk go up.  dp_trim_chunk_segments and
+ * dp_trim_search follow it as they follow dp_trim_scan_chunks.
+ * dp_reads_respan: replaces the context's read set by the n_out spans of it (any order, a read any number of times, n_out = 0
+ * allowed), repacked 2 bit -> 2 bit on the device; both sets exist side by side for the length of the call, then the old blocks go
+ * back to the block cache.  Quality bytes of the old set are dropped (dp_quality_upload the new ones).  Allowed only between the
+ * upload and a job's set-up: a span outside its read (DP_ERR_ARG), a context that borrows its reads or lends them, one with an
+ * upload of dp_reads_upload_rc_begin pending, and one on which a round, a k-mer index or a value table has been made (DP_ERR_STATE)
+ * are refused with a message that names the reason. */
+typedef struct {
+    uint32_t read, start, len; /* bases [start, start + len) of resident read `read` */
+} dp_read_span;
+DP_API int dp_trim_edges_resident(dp_trim* t, dp_ctx* ctx, const uint32_t* reads, uint32_t n_reads, int mode, int min_match, int threshold,
+                                  dp_trim_rec* recs, uint64_t* counts, uint8_t* enabled, double* times_ms);
+DP_API int dp_trim_scan_chunks_resident(dp_trim* t, dp_ctx* ctx, const dp_read_span* spans, uint32_t n_chunks, uint32_t* n_seeds_out,
+                                        double* times_ms);
+DP_API int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out);
 
 #ifdef __cplusplus
 }

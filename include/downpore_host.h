@@ -60,6 +60,15 @@ DPH_API void dph_reads_reset_ignore(void* reads);
  * dph_overlap_reset  ends the job, keeps the handle, the resident reads and the executor contexts: dph_overlap_init starts the
  *                    next job (other k, other parameters).  dph_overlap_create = open + init. */
 DPH_API void* dph_overlap_open(void* reads, int device);
+/* dph_overlap_open_trim   `overlap -trim true`: dph_overlap_open of the read set `downpore trim` would write for `reads` (loaded with
+ *                    min_len 50), without the file: the reads go up once, the trim (params as dph_trim_run takes them) runs on the resident
+ *                    copy, the trimmed read set - kept as a written record of n bases is kept by a reader with minimum length min_len:
+ *                    n + 1 >= min_len - is cut from it on the device (dp_reads_respan) and its qualities follow.  The handle owns
+ *                    that read set (dph_overlap_reads: a reads handle valid while the overlap handle lives, NULL for a handle of
+ *                    dph_overlap_open); *trim_out receives the trim run's handle (log, table, stats; no output text; dph_trim_free). */
+DPH_API void* dph_overlap_open_trim(void* reads, void* front, void* back, const int64_t* trim_params, int n_params, int64_t min_len, int device,
+                                    void** trim_out);
+DPH_API void* dph_overlap_reads(void* h);
 DPH_API int dph_overlap_init(void* h, const int64_t* params, double min_hits, const double* values);
 DPH_API int dph_overlap_reset(void* h);
 DPH_API void* dph_overlap_create(void* reads, int device, const int64_t* params, double min_hits, const double* values);
@@ -179,6 +188,8 @@ DPH_API void* dph_trim_run(void* reads, void* front, void* back, const int64_t* 
 DPH_API void* dph_trim_apply(void* reads, void* front, void* back, const int64_t* params, int n_params, const uint8_t* enabled,
                              const int32_t* recs, int64_t n_rec_reads, const uint64_t* counts);
 DPH_API void dph_trim_free(void* t);
+/* the read set the run's output gives when read back with minimum length min_len, without the text (a new reads handle; no device needed) */
+DPH_API void* dph_trim_reads(void* t, int64_t min_len, int himem);
 DPH_API const char* dph_trim_output(void* t, int64_t* n);
 DPH_API const char* dph_trim_errtext(void* t, int64_t* n);
 DPH_API int64_t dph_trim_table(void* t, int32_t* out, int64_t cap_reads);
