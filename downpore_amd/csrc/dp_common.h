@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "downpore_hip.h"
+#include "dp_env.h"  // every run-time setting: the table, dp_tune / dp_debug, and when each is read
 
 // make COPYLOG=1: every hipMemcpyAsync of the library is counted per call site (file:line, direction, calls, bytes) and the table is
 // printed when the process ends - the tool that names the call sites behind the runtime's copy kernels in a profile
@@ -64,6 +65,11 @@ struct dp_ctx {
     hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [8], [9]: around the index build's kernels
     bool index_marked = false;  // marks 8 / 9 were recorded for the round's index build (dp_consensus_paf reads them)
     hipEvent_t ev_sync = nullptr;  // blocking-sync event: waiting host threads sleep instead of polling
+    // settings read when the context is created (dp_env.h, CREATE): what its rounds consult many times
+    dp_wait_mode wait;
+    struct {
+        bool kx = false, kx_bins = false, kx_oneshot = false, cons = false, cons_why = false, chain_prof = false, map_prof = false;
+    } dbg;
     bool stream_priority_set = false;  // (dp_ctx_set_priority: such a stream is destroyed with its context instead of being parked)
     std::string err;
     bool borrowed_reads = false;  // d_packed/d_boff/d_len belong to another context
@@ -266,10 +272,6 @@ int dp_kindex_ensure(dp_ctx* ctx, int k);
 struct dp_comm;
 int dp_comm_allgather_ranges(dp_comm* c, dp_ctx* ctx, void* dst, size_t elem, const uint64_t* first, const void* src);  // dp_comm.hip
 bool dp_comm_is_rccl(const dp_comm* c);  // dp_comm.hip
-// DP_DEBUG=a,b,c: diagnosis output of the named parts (no change of behaviour).  DP_TUNE=key=value,...: the numbers experiments vary
-// (grids, pools, polls; the defaults are what the measurements chose).  Both are read once per process.  (dp_scan.hip)
-bool dp_debug(const char* what);
-long dp_tune(const char* key, long dflt);
 // A rank's share of a k-mer position index built by several ranks (round 5): filled by dp_kindex_build_sorted from the first-digit
 // counts every rank computes alike - rank q sorts the k-mers [digit_first[q] << kmer_shift, digit_first[q + 1] << kmer_shift), which are
 // the entries [entry_first[q], entry_first[q + 1]) of the whole index; the offsets it writes are relative to its own first entry.

@@ -419,8 +419,8 @@ struct ConsFullArgs {
     dp_paf_rec* paf;           // [pairs]: lines of group g start at slot pbase[2g]
     uint32_t* ignore_ids;      // [pairs]: likewise
     dp_group_meta* gmeta;      // [n_groups]
-    unsigned long long* dbg;   // DP_CONS_DEBUG: per group 8 time stamps (wall_clock64, 100 MHz)
-    uint32_t flag_every;       // DP_CONS_FLAG_EVERY=n (test hook): every n-th window is left to the host path
+    unsigned long long* dbg;   // DP_DEBUG=cons: per group 8 time stamps (wall_clock64, 100 MHz)
+    uint32_t flag_every;       // DP_TUNE=cons_flag_every=n (test hook): every n-th window is left to the host path
     uint32_t out_cap;          // slots of paf / ignore_ids (a bound when the chaining stage's pair count is not known yet)
     uint32_t rec_cap;          // records the chaining stage's buffers hold (its pair count may exceed them: the stage is then repeated)
     const uint32_t* nseq_src;  // chunk count + overflow flag of dp_index_build_chunked (device), or null
@@ -428,7 +428,7 @@ struct ConsFullArgs {
     const uint32_t *in_count, *in_list;  // windows this launch works through: how many, their numbers (null: every window)
     uint32_t *out_count, *out_list;      // windows this layout cannot hold are listed here for the next one (null: flagged for the host
                                          // path); the counters are zeroed by the anchors launch
-    uint32_t spin_ticks;       // DP_CONS_SPIN=us (experiment): every window sleeps this long before it ends
+    uint32_t spin_ticks;       // (an experiment that is gone: every window slept this long before it ended; always 0)
     bool copy_nseq;            // this launch hands the chunk count of dp_index_build_chunked on to the host's block (the first one)
 };
 
@@ -459,7 +459,7 @@ struct consensus_full_kernel {
             }                                                                        \
         } else {                                                                     \
             gm.flag = 1;                                                             \
-            gm.reserved = (why_); /* (diagnosis: DP_CONS_WHY=1 prints a histogram) */ \
+            gm.reserved = (why_); /* (diagnosis: DP_DEBUG=cons_why prints a histogram) */ \
             if (lane == 0) A.gmeta[g] = gm;                                          \
         }                                                                            \
         continue;                                                                    \
@@ -810,7 +810,7 @@ struct consensus_full_kernel {
         int pos = -1, offs = 0, gaps = 50, supported = 0, dist = 0, mlen = 0, clen = 0;
         const int kLim = 1 << 28;
         const int ns = nseq;
-        unsigned dbgUni = 0, dbgGen = 0, dbgProp = 0;  // (DP_CONS_DEBUG: uniform steps, general steps, proposers looked at)
+        unsigned dbgUni = 0, dbgGen = 0, dbgProp = 0;  // (DP_DEBUG=cons: uniform steps, general steps, proposers looked at)
         unsigned long long dbgT[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (general steps: ticks before the scan, in it, in the selection, in the update; scan runs, walk trips of the scan, of the update)
         unsigned long long dbgT0 = 0;
 #define CF_T(i_) if (A.dbg) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long n_ = wall_clock64(); dbgT[i_] += n_ - dbgT0; dbgT0 = n_; }
@@ -1370,23 +1370,17 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
     A.refs = (const dp_seq_ref*)ctx->d_seqrefs.p;
     A.segs = (const int32_t*)ctx->d_segs.p;
     A.smeta = metas ? (const dp_seq_meta*)ctx->d_cin.p : (const dp_seq_meta*)ctx->d_chunk_meta.p;
-    {
-        static const uint32_t flag_every = (uint32_t)dp_tune("cons_flag_every", 0);  // (test hook: every n-th window goes to the host path)
-        A.flag_every = flag_every;
-        static const uint32_t spin = 0u;
-        A.spin_ticks = spin;
-    }
+    A.flag_every = (uint32_t)dp_tune("cons_flag_every", 0);  // (test hook: every n-th window goes to the host path)
+    A.spin_ticks = 0u;
     A.rc_of = (const int32_t*)((const uint8_t*)ctx->d_cin.p + b_meta);
     // small LDS layout first (int16: needs every seed id below 2^15), the large one for what it lists; DP_CONS_LAYOUTS=nosmall: large only.
     // The huge layout follows the large one from the round after the first in which a window did not fit the large one
     // (ctx->cons_huge; DP_CONS_LAYOUTS=huge / nohuge: always / never) - the sparse regime never pays its launch.
-    // DP_CONS_LAYOUTS (tests; read per call: they switch it between jobs of one process): "nosmall" = the large layout for every window,
+    // DP_CONS_LAYOUTS (tests): "nosmall" = the large layout for every window,
     // "eager" = the large layout launched behind the small one in every round, "huge" / "nohuge" = the huge layout always / never
-    const char* lay_env = getenv("DP_CONS_LAYOUTS");
-    const std::string lay = lay_env ? lay_env : "";
-    const bool small_off = lay.find("nosmall") != std::string::npos;
+    const bool small_off = dp_env_has_word("DP_CONS_LAYOUTS", "nosmall");
     const bool use_small = !small_off && n_seeds <= 32767;
-    const bool use_huge = lay.find("nohuge") != std::string::npos ? false : lay.find("huge") != std::string::npos ? true : ctx->cons_huge;
+    const bool use_huge = dp_env_has_word("DP_CONS_LAYOUTS", "nohuge") ? false : dp_env_has_word("DP_CONS_LAYOUTS", "huge") ? true : ctx->cons_huge;
     // lists: [count of list 1 | count of list 2 | list 1: ng entries | list 2: ng entries] (both counts zeroed by the anchors launch)
     uint32_t* lists = nullptr;
     if (use_small || use_huge) {
@@ -1407,7 +1401,7 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
     A.ignore_ids = (uint32_t*)(dout + b_gm + b_paf);
     A.out_cap = np;
     A.rec_cap = pending ? dp_find_pair_cap(ctx) : ctx->n_pairs;
-    static const bool cons_debug = dp_debug("cons");
+    const bool cons_debug = ctx->dbg.cons;
     A.dbg = nullptr;
     if (cons_debug) {
         DP_HIP(dp_dev_malloc((void**)&A.dbg, (size_t)ng * 128));
@@ -1419,7 +1413,7 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
     A.nseq_src = ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : nullptr;
     A.nseq_dst = h_nseq;
     bool lazy_large = false;
-    const bool lazy_off = lay.find("eager") != std::string::npos;
+    const bool lazy_off = dp_env_has_word("DP_CONS_LAYOUTS", "eager");
     DP_HIP(dp_mark(ctx, 0));
     {
         // small -> large -> huge: each layout works through what its predecessor listed and lists what it cannot hold for its
@@ -1573,8 +1567,7 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
     }
     const uint8_t* h = (const uint8_t*)ctx->h_cout.p;
     {
-        static const bool why = dp_debug("cons_why");
-        if (why) {
+        if (ctx->dbg.cons_why) {
             const dp_group_meta* gms = (const dp_group_meta*)h;
             uint32_t hist[16] = {0}, nf = 0;
             for (uint32_t g = 0; g < ng; g++)

@@ -490,7 +490,7 @@ int dp_kindex_build_sorted(dp_ctx* ctx, dp_ctx* ow, int k, uint32_t* d_counts, u
         while (((uint64_t)1 << G.pbits) <= max_len) G.pbits++;
         G.rbits = 1;
         while (((uint64_t)1 << G.rbits) < ow->n_reads) G.rbits++;
-        if (const char* e = getenv("DP_KB_MIN_PBITS")) G.pbits = std::max(G.pbits, std::min(32, atoi(e)));  // (test hook: small inputs reach the wider entry formats)
+        G.pbits = std::max(G.pbits, (int)dp_env_long("DP_KB_MIN_PBITS", 0, LONG_MIN, 32));  // (test hook: small inputs reach the wider entry formats)
         if (2 * k + G.pbits + G.rbits > 64) return 1;  // (the entry has no room for read and position: atomic scatter build)
     }
     const int pay = G.pbits + G.rbits;
@@ -517,7 +517,7 @@ int dp_kindex_build_sorted(dp_ctx* ctx, dp_ctx* ow, int k, uint32_t* d_counts, u
     G.dhi = (uint32_t)nb1;
     const uint32_t n_sub = (uint32_t)nb1 * (uint32_t)nb2;
     // how the entries are stored after each pass (DP_KINDEX_WIDE=1: eight bytes throughout, the index as read << 32 | position)
-    const bool wide = getenv("DP_KINDEX_WIDE") != nullptr;
+    const bool wide = dp_env_str("DP_KINDEX_WIDE") != nullptr;
     const int hb1 = 8, hb2 = 8;  // (bytes per entry of the two intermediate arrays)
     (void)wide;
     const int fmt = (wide || pay > 40) ? 8 : pay > 32 ? 5 : 4;

@@ -157,7 +157,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
     // DP_KINDEX_SHARD=0: every rank builds everything, as until round 4.
     // (DP_KINDEX_SHARD=force: also with a communicator of ONE rank - the test hook that takes the RCCL flavour of the gather, grouped
     // ncclBroadcasts between device buffers, through a real librccl on a one-GPU box)
-    const char* se = getenv("DP_KINDEX_SHARD");
+    const char* se = dp_env_str("DP_KINDEX_SHARD");
     // Over an RCCL communicator the shares are OPT-IN (DP_KINDEX_SHARD=1): their exchange - grouped ncclBroadcasts with several roots -
     // has run between in-process ranks (peer copies) and through a one-rank librccl, never yet between two GPUs (no multi-GPU node has
     // been available to this repository); until a run with two ranks has shown the index digests equal, every rank of a multi-process
@@ -178,8 +178,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
         // (the sorted build holds a second 8 B per base while it runs; when that does not fit, the atomic scatter path is
         // what is left and needs only the index itself)
         const uint64_t need = ow->total_bases * 8 + (uint64_t)nk * 16 + ((uint64_t)4 << 30);
-        int max_k = 14;
-        if (const char* e = getenv("DP_KINDEX_MAX_K")) max_k = std::min(14, atoi(e));
+        const int max_k = (int)dp_env_long("DP_KINDEX_MAX_K", 14, LONG_MIN, 14);
         mem_ok = !(k > max_k || need > free_b + ix->pos.cap + ix->off.cap);
         if (!mem_ok && !sharded) {
             ix->unavailable = true;
@@ -187,7 +186,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
         }
     }
     // Preferred: the radix-sort build (dp_kbuild.hip) - every pass streams HBM with coalesced traffic, and the k-mer
-    // histogram falls out of its last pass (kept for dp_kmer_values).  DP_KINDEX_ATOMIC=1 or an unsupported k: the
+    // histogram falls out of its last pass (kept for dp_kmer_values).  DP_TUNE=kindex_atomic=1 or an unsupported k: the
     // count -> offsets -> atomic scatter below.
     {
         void* d_cnt = nullptr;
@@ -539,7 +538,7 @@ struct kidx_walk {
                                                  int32_t* __restrict__ segs, unsigned long long* __restrict__ n_hits, uint32_t lps,
                                                  unsigned long long* __restrict__ dbg, const KxRec R) {
     const int lane = dp_lane();
-    // DP_KX_DEBUG: when a wave started, had its bucket bounds, its entries, its items, and was done (100 MHz ticks since dbg[15],
+    // DP_DEBUG=kx: when a wave started, had its bucket bounds, its entries, its items, and was done (100 MHz ticks since dbg[15],
     // sums over waves in dbg[0..4], maxima in dbg[5..9], waves in dbg[10])
 #define KX_TICK(i_)                                                                                     \
     if (KX_PROFILING && dbg) {                                                                          \
@@ -1698,9 +1697,9 @@ static uint32_t kidx_walk_blocks(const dp_kindex* ix, int k, uint32_t S) {
     return (waves + 3) / 4;
 }
 
-// workgroups of the count walk's launch: all of its work at once (default), or DP_KX_WALK_BLOCKS of them striding over it
+// workgroups of the count walk's launch: all of its work at once (default), or DP_TUNE=kx_walk_blocks of them striding over it
 static uint32_t kidx_walk_grid(const dp_kindex* ix, int k, uint32_t S) {
-    static const uint32_t lim = (uint32_t)std::max(0L, dp_tune("kx_walk_blocks", 0));
+    const uint32_t lim = (uint32_t)std::max(0L, dp_tune("kx_walk_blocks", 0));
     const uint32_t all = kidx_walk_blocks(ix, k, S);
     return lim ? std::min(lim, all) : all;
 }
@@ -1773,19 +1772,18 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     // round 4).  Bins of 512 .. 16 k reads, at most 256 of them while that keeps a bin inside the LDS; the bins share the record
     // buffer of the shards (1.5 x the previous round's hits + 4096 each), the extra items' list lives in the group table's place.
     KxBins B{};
-    const char* bins_env = getenv("DP_KX_BINS");  // (read per call: tests switch it between jobs of one process)
-    const bool bins_on = !(bins_env && bins_env[0] == '0');
+    const bool bins_on = dp_env_tristate("DP_KX_BINS") != 0;
     // round 6, the dense regime (this context's previous round had 16 and more hits per read - k = 10: ~100): small bins whose
     // workgroup fills AND sorts in LDS (kidx_bin_sort_dense), eight trips of a walk workgroup per bin reservation, the count as a launch
     // of its own (one workgroup per bin instead of one per 4 096 reads inside kidx_offsets).  DP_KX_DENSE=0: off (A/B runs)
-    const char* dense_env = getenv("DP_KX_DENSE");  // (read per call: tests switch it between jobs of one process)
+    const int dense_env = dp_env_tristate("DP_KX_DENSE");
     bool dense = false;
     if (one && R.rec && bins_on && n_read_items && S < (1u << KXB_SEED_BITS)) {
         uint32_t bshift = 9;
         while (((n_read_items + (1u << bshift) - 1) >> bshift) > 256 && bshift < KXB_RIB_BITS) bshift++;
         // (DP_KX_DENSE=1, tests: whatever the hit density - small inputs reach the dense kernels through it)
-        dense = one->sort_cap <= 1024 && (dense_env && dense_env[0] == '1' ? true
-                                          : !(dense_env && dense_env[0] == '0') && lps == 64 && one->hits_guess >= 16ull * n_read_items &&
+        dense = one->sort_cap <= 1024 && (dense_env == 1 ? true
+                                          : dense_env != 0 && lps == 64 && one->hits_guess >= 16ull * n_read_items &&
                                             one->hits_guess >= (1ull << 20));
         if (dense) {
             bshift = 6;
@@ -1803,7 +1801,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         // consecutive reads that contain every seed of the round by construction: + 2 S (measured at config 2: mean 2.3 k records per
         // bin, 7.4 k in the query reads' bin)
         uint64_t cap = total / n_bins + std::min<uint64_t>(2 * (uint64_t)S, dense ? ((uint64_t)128 << bshift) : ~0ull) + 1024;
-        if (const char* e = getenv("DP_KX_BINS_CAP")) cap = (uint64_t)std::max(16, atoi(e));  // (test hook: bins that overflow)
+        cap = (uint64_t)dp_env_long("DP_KX_BINS_CAP", (long)cap, 16);  // (test hook: bins that overflow)
         if (n_bins <= KX_MAXBINS && cap < 0x7fffffffu) {
             if (dev_reserve(ctx, ctx->d_kx_tmp, std::max((size_t)n_groups * 8, (size_t)xcap * 16) + 64)) return DP_ERR_HIP;
             if (dev_reserve(ctx, ctx->d_kx_keys, (size_t)cap * n_bins * 8 + 64)) return DP_ERR_HIP;
@@ -1825,7 +1823,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             dense = false;
         }
     }
-    static const bool kx_debug = dp_debug("kx");
+    const bool kx_debug = ctx->dbg.kx;
     unsigned long long* dbg = nullptr;
     const size_t n_dbg_waves = (size_t)kidx_walk_blocks(ix, k, S) * 4;
     if (kx_debug) {
@@ -1835,7 +1833,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     bool count_in_offsets = false;
     if (S && B.rec) {
         const uint32_t n_waves = kidx_walk_blocks(ix, k, S) * 4;
-        static const int bin_waves = (int)dp_tune("kx_bin_waves", 8);
+        const int bin_waves = (int)dp_tune("kx_bin_waves", 8);
 #define KX_WALK_BIN(W_)                                                                                                                            \
     dp_launch<kidx_walk_bin<W_>>(ctx, dim3((n_waves + W_ - 1) / W_), dim3(64 * W_), dp_seeds_ptr(ctx), S, (const uint64_t*)ix->off.p, ix->view(), \
                                  d_items, lo, hi, n_read_items, (const uint32_t*)head, (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves)
@@ -1853,8 +1851,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
 #undef KX_WALK_BIN
         // bins no larger than a tile of kidx_offsets are counted by that kernel (one launch less per round; DP_KX_FUSE=0: as before.
         // Fill + sort in one launch for the sparse regime - DP_KX_FUSE=2 in round 5 - was slower and is gone: profiles/r05/ab12_fusions.txt)
-        const char* fuse_env = getenv("DP_KX_FUSE");  // (read per call, like DP_KX_BINS: tests switch it between jobs of one process)
-        const bool fuse_off = fuse_env && fuse_env[0] == '0';
+        const bool fuse_off = dp_env_tristate("DP_KX_FUSE") == 0;
         count_in_offsets = !fuse_off && !dense && (1u << B.bshift) <= KX_TILE * KX_IPT;
         if (count_in_offsets) {
         } else if (B.bshift <= 9)
@@ -1863,8 +1860,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             dp_launch<kidx_bin_count<4096>>(ctx, dim3(B.n_bins), dim3(512), B, d_counts, n_read_items, lo);
         else
             dp_launch<kidx_bin_count<16384>>(ctx, dim3(B.n_bins), dim3(512), B, d_counts, n_read_items, lo);
-        static const bool bins_debug = dp_debug("kx_bins");
-        if (bins_debug) {  // (diagnosis: waits for the stream) how full the bins and the extra list are
+        if (ctx->dbg.kx_bins) {  // (diagnosis: waits for the stream) how full the bins and the extra list are
             std::vector<uint32_t> cur((size_t)KX_MAXBINS + 2);
             uint64_t fl = 0;
             hipStreamSynchronize(ctx->stream);

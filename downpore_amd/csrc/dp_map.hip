@@ -135,7 +135,7 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
     // algorithmic bytes of this wave's windows: posting words the index query gathered for them, 2 x 8 x SW per
     // prefiltered candidate + 4 per candidate out, 8 per seed of both sides of every pair that is chained, 8 per chain link out
     unsigned long long algb = 0;
-    // profiling build (make PROF=1, DP_MAP_PROF=1 prints them): ticks of 10 ns per phase, summed per wave, added to cursor[16 ..] at the end
+    // profiling build (make PROF=1, DP_DEBUG=map_prof prints them): ticks of 10 ns per phase, summed per wave, added to cursor[16 ..] at the end
 #ifdef DP_PROF_BUILD
     unsigned long long mp[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mlast = wall_clock64();
     const unsigned long long mstart = mlast;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(64 * M_WAVES) void map_kernel(const int32_t* __rest
                         nQ = nT < 0 ? -1 : m_reduce_wave<uint16_t>(qSeg, qN, tset, k, minMatch, L.q, L.qIdx, L.qmax(), &err);
                     }
                     MP_TICK(2)  // Reduced() of the query window
-                    // dynamicMatch: the probes on 64 lanes, the walk's decisions on lane 0 (DP_MAP_ONE_LANE=1: all of it on lane 0 as
+                    // dynamicMatch: the probes on 64 lanes, the walk's decisions on lane 0 (DP_TUNE=map_one_lane=1: all of it on lane 0 as
                     // before round 4)
                     int nGoodW = 0;
                     if (nT >= 0 && nQ >= 0 && !one_lane) nGoodW = m_dynamic_match_wave(L, 2 * nQ + 1, 2 * nT + 1, minMatch, k, P, chainLen, &err);
@@ -703,10 +703,10 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     uint32_t int_cap = std::max<uint32_t>(1u << 21, (uint32_t)(ctx->d_ma.cap / 4));
     uint32_t cur[16];
     float total_ms = 0;
-    // profiling build + DP_MAP_PROF=1: per-phase sums of the launch's waves (map_kernel's MP_TICK), printed per call
+    // profiling build + DP_DEBUG=map_prof: per-phase sums of the launch's waves (map_kernel's MP_TICK), printed per call
     unsigned long long* d_mprof = nullptr;
 #ifdef DP_PROF_BUILD
-    static const bool map_prof = dp_debug("map_prof");
+    const bool map_prof = ctx->dbg.map_prof;
     if (map_prof) {
         if (dev_reserve(ctx, ctx->d_sb, 16 * 8 + 64)) return DP_ERR_HIP;
         d_mprof = (unsigned long long*)ctx->d_sb.p;

@@ -538,9 +538,9 @@ static int index_chunked_launch(dp_ctx* ctx, int64_t chunk_size, int64_t overlap
     // (profiles/r04/ab_rows3.txt) - the 400 k atomics it removes cost less than the transpose it adds.
     // Where the matrices are large it wins: at k = 10 (100 k chunks x 20 k seeds: 250 MB each, 20 M atomics) a round's index build
     // and query stage take 1.22 ms instead of 1.67 (profiles/r04/dense_rows.txt) - the default from 4 M seed-set words (32 MB) up.
-    const char* ife = getenv("DP_INDEX_FILL_ROWS");  // (read per call: tests switch it between jobs of one process; 0 / 1 force)
+    const int ife = dp_env_tristate("DP_INDEX_FILL_ROWS");  // (0 / 1 force)
     const bool rows_fit = SW <= IFR_SW_MAX && S > 0;
-    const bool rows_mode = rows_fit && (ife ? ife[0] == '1' : (uint64_t)cap * SW >= ((uint64_t)4 << 20));
+    const bool rows_mode = rows_fit && (ife >= 0 ? ife == 1 : (uint64_t)cap * SW >= ((uint64_t)4 << 20));
     if (!n_survivors) {  // (no chunk_kernel launch to clear the matrices and to write the chunk count)
         const dp_zero_region z[3] = {{ctx->d_posting.p, zb_post}, {ctx->d_seedsets.p, zb_sets}, {ctx->d_nseqs.p, 8}};
         if (int rc = dp_zero_regions(ctx, z, 3)) return rc;
@@ -1022,7 +1022,7 @@ struct query_kernel {
                                uint32_t word_base, const uint32_t* __restrict__ n_seqs_dev, u64* __restrict__ qsets, uint32_t SW,
                                uint32_t dbg_flags, uint32_t split, u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws,
                                uint32_t big_stride) {
-        // (the pair-offset scan as the last act of this launch's last workgroup - round 5's DP_QUERY_SCAN - cost a release fence per
+        // (the pair-offset scan as the last act of this launch's last workgroup - an experiment of round 5 - cost a release fence per
         // workgroup, more than the launch it saved: profiles/r05/ab12_query_scan.txt; removed in round 6)
         if (blockIdx.x < nq * split)
             body(qsegs, qoff, nq, posting, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt, word_base, n_seqs_dev, qsets, SW, dbg_flags, split, own_zero,
@@ -1051,7 +1051,7 @@ struct query_kernel {
     __shared__ unsigned long long sh_gathered;
     const int lane = dp_lane();
     const int wave = threadIdx.x >> 6;
-    // `split` workgroups per query can share its word range (64-word pieces dealt round robin; DP_QUERY_SPLIT).  Measured on the
+    // `split` workgroups per query can share its word range (64-word pieces dealt round robin; DP_TUNE=query_split).  Measured on the
     // dense regime (W ~ 1.5 k words, 25 sets per query, 668 queries): 1 -> 62.8 us, 2 -> 63.3, 3 -> 64.6, 4 -> 66.0, 8 -> 106: the
     // kernel is not held back by the 668 workgroups' fit on 256 CUs, so one workgroup per query stays the default
     const uint32_t q = blockIdx.x / split, part = blockIdx.x % split;
@@ -1242,7 +1242,7 @@ struct query_kernel {
     const int minCount = (int)sh_u[4];
     const int64_t i_last = sh_ilast;
     if (n < 5 || status || n >= mc_n) return;  // cand row stays zero
-    if (dbg_flags & 1u) return;  // DP_QUERY_DEBUG=1 (timing experiments): the set-up alone, no posting word is read
+    if (dbg_flags & 1u) return;  // DP_TUNE=query_debug=1 (timing experiments): the set-up alone, no posting word is read
     if constexpr (SPARSE) {
         u64 gathered = 0;  // (ids read)
         int nCand = 0;
@@ -1424,7 +1424,7 @@ struct window_list_kernel {
 // ---------------------------------------------------------------------------------------------------------------
 // A6 + A7 + A8: matchWorker body
 
-// Profiling build (make PROF=1): per-wave phase timers of the chaining kernels (DP_CHAIN_PROF=1 prints them).  In the normal
+// Profiling build (make PROF=1): per-wave phase timers of the chaining kernels (DP_DEBUG=chain_prof prints them).  In the normal
 // build the timers are compiled out - their sums live in a per-thread array that ends up in scratch memory.
 #ifdef DP_PROF_BUILD
 #define DP_PROFILING 1
@@ -2535,7 +2535,7 @@ struct ChainArgs {
     uint32_t n_refs;      // entries of refs[] (indexed sequences, or their upper bound)
     uint32_t prof_walk_slot;   // first per-wave slot of walk(0) in prof[] (behind the passes')
     uint32_t prof_stride;      // per-wave slots of one pass
-    unsigned long long* prof;  // DP_CHAIN_PROF=1: [0] pairs looked at, [1] chained, [2..6] wall-clock ticks (100 MHz) per phase of chain_spec_kernel
+    unsigned long long* prof;  // DP_DEBUG=chain_prof: [0] pairs looked at, [1] chained, [2..6] wall-clock ticks (100 MHz) per phase of chain_spec_kernel
 };
 
 // per-query candidate counts -> pair / scratch offsets (one workgroup; a round has a few hundred to a few ten thousand queries)
@@ -2582,7 +2582,7 @@ __device__ __forceinline__ int chain_prefilter(const u64* __restrict__ tset, con
 // The same count - CountIntersectionTo(seedSet, matchSet), overlap.go:362: distinct seeds of the query that the target holds -
 // from the query's side: its seeds are staged (L.aSegL), a few dozen of them, so one probe of the target's set per seed (one
 // round of loads, 8 B each) replaces a pass over both sets' rows (157 words each at 10 k seeds: three rounds of two loads, the
-// largest single share of a pair's time in chain_spec_kernel: DP_CHAIN_PROF).  Lanes 0 .. nSeeds-1 (nSeeds <= 64) own one seed
+// largest single share of a pair's time in chain_spec_kernel: DP_DEBUG=chain_prof).  Lanes 0 .. nSeeds-1 (nSeeds <= 64) own one seed
 // each; a seed counts at its first occurrence in the query.  *inMask = membership of every seed (what chain_pair's aFlag holds).
 template <class LW>
 __device__ __forceinline__ int chain_prefilter_seeds(const LW& L, const u64* __restrict__ tset, int nSeeds, u64* inMask) {
@@ -2920,7 +2920,7 @@ struct chain_spec_kernel {
     // (a query that did not fit the buffers left its pairs' pq / clist unwritten: the host repeats the stage with larger ones)
     if (A.cursor[3] != 0 || A.cursor[8 + A.pass] == 0) return;  // ... or no query is open any more
     const uint32_t total = (uint32_t)min(totals[0], (u64)A.pair_cap);
-    // DP_CHAIN_PROF: every wave keeps its own sums (ticks of 10 ns) and stores them into its own slot of the pass - no shared
+    // DP_DEBUG=chain_prof: every wave keeps its own sums (ticks of 10 ns) and stores them into its own slot of the pass - no shared
     // counters (ten thousand atomics on one word take longer than the kernel)
     ChainProf pf = {};
     unsigned long long tprev = 0;
@@ -3117,11 +3117,6 @@ struct chain_resolve_kernel {
 }
 };
 
-static uint32_t query_dbg_flags() {
-    static const uint32_t f = (uint32_t)dp_tune("query_debug", 0);
-    return f;
-}
-
 // What the host sends for the query stage - query offsets, query segments, the minCount table - as one block in the context's
 // pinned staging area, laid out as it will lie on the device.  Returns the block's size (0: nothing to send).
 static size_t query_block_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t* mc_n_out,
@@ -3261,13 +3256,13 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
     uint32_t* d_qcnt = (uint32_t*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 24);
     const int32_t* d_mc = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off + up_segs);
     if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
-    // workgroups per query (DP_QUERY_SPLIT, experiments: see query_kernel)
-    static const int split_env = (int)dp_tune("query_split", 0);
+    // workgroups per query (DP_TUNE=query_split, experiments: see query_kernel)
+    const int split_env = (int)dp_tune("query_split", 0);
+    const uint32_t query_dbg = (uint32_t)dp_tune("query_debug", 0);
     const uint32_t q_split = split_env > 0 ? (uint32_t)std::min(split_env, 16) : 1u;
-    static const bool own_rows_env = true;
     // (short rows only - the sparse regime: a few hundred words per query; the dense regime's rows - W ~ 3 k words - are cleared
     // faster by the launch over all of them, and its index query is the kernel the bandwidth figure is quoted on)
-    const bool own_rows = own_rows_env && q_split == 1 && (size_t)W + SW <= 1024;
+    const bool own_rows = q_split == 1 && (size_t)W + SW <= 1024;
     {   // (the chaining stage's cursor block rides along: it is zero when the first attempt starts; and the same launch fetches
         // the upload block from its pinned staging - no copy is handed to the runtime)
         // (with one workgroup per query - the default - the light query kernel clears its query's rows itself and this launch only
@@ -3283,14 +3278,14 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
                        (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
                        (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
                        ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)ctx->d_qsets.p, SW,
-                       query_dbg_flags(), q_split, own_rows ? (u64*)ctx->d_cursor.p : (u64*)nullptr, (uint32_t*)nullptr, 0u);
+                       query_dbg, q_split, own_rows ? (u64*)ctx->d_cursor.p : (u64*)nullptr, (uint32_t*)nullptr, 0u);
     // the 16-ladder / exact-count regimes start at minCount 13: only a batch with a query of that many seeds needs the heavy variant
     if (mcLast >= 13) dp_launch<query_kernel<true>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
                        ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
                        (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
                        (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
                        ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)ctx->d_qsets.p, SW,
-                       query_dbg_flags(), q_split, (u64*)nullptr, (uint32_t*)nullptr, 0u);
+                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)nullptr, 0u);
     if (maxSeeds > Q_MAXSETS) {
         // a query may hold more sets than the kernel's LDS lists (round 6): the BIG variants, lists in global memory, for those queries
         const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
@@ -3300,13 +3295,13 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
                        (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
                        (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
                        ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW,
-                       query_dbg_flags(), q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
         if (mcLast >= 13) dp_launch<query_kernel<true, true>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
                        ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
                        (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
                        (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
                        ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW,
-                       query_dbg_flags(), q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
     }
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 5));
@@ -3413,11 +3408,9 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
     {
         // a stage whose consumers are on the device (it stays pending for dp_consensus_paf) leaves the chains in their scratch
         // columns: no cursor atomics, no copies in the walk and resolve kernels (DP_CHAIN_PACK=1: always pack)
-        const char* pk = getenv("DP_CHAIN_PACK");  // (read per call: tests switch it between jobs of one process)
-        const bool always_pack = pk && pk[0] == '1';
+        const bool always_pack = dp_env_tristate("DP_CHAIN_PACK") == 1;
         A.pack = (st.defer_fetch && !always_pack && st.sint_cap < 0xfffffff0ull) ? 0 : 1;
-        const char* pe = getenv("DP_CHAIN_PERFECT");  // (read per call: tests switch it between jobs of one process)
-        A.walk_always = pe && pe[0] == '0' ? 1 : 0;
+        A.walk_always = dp_env_tristate("DP_CHAIN_PERFECT") == 0 ? 1 : 0;
         ctx->chains_packed = A.pack != 0;
     }
     A.pair_cap = st.pair_cap;
@@ -3430,8 +3423,7 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
     A.prof = nullptr;
     A.prof_walk_slot = 0;
     A.prof_stride = 0;
-    static const bool chain_prof = dp_debug("chain_prof");
-    if (chain_prof) {
+    if (ctx->dbg.chain_prof) {
         const size_t pb = ((size_t)st.passes * st.spec_blocks * S_WAVES + (size_t)A.walk0_blocks * S_WAVES) * 128;
         if (dev_reserve(ctx, ctx->d_sched, pb + 128)) return DP_ERR_HIP;
         A.prof = (unsigned long long*)ctx->d_sched.p;
@@ -3508,8 +3500,7 @@ static int chain_check(dp_ctx* ctx, FindState& st, bool* grow) {
 // a checked attempt without overflow: the stage's errors, totals and statistics
 static int chain_finish(dp_ctx* ctx, FindState& st) {
     st.pending = false;
-    static const bool chain_prof = dp_debug("chain_prof");
-    if (chain_prof && ctx->d_sched.p) {
+    if (ctx->dbg.chain_prof && ctx->d_sched.p) {
         const size_t waves = (size_t)st.spec_blocks * S_WAVES;
         const size_t wwaves = (size_t)std::max<uint32_t>(1, std::min<uint32_t>(1024, (st.nq + S_WAVES - 1) / S_WAVES)) * S_WAVES;
         std::vector<unsigned long long> h(((size_t)st.passes * waves + wwaves) * 16);
@@ -3550,7 +3541,7 @@ static int chain_finish(dp_ctx* ctx, FindState& st) {
             }
         }
     }
-    if (chain_prof) fprintf(stderr, "[chain prof] final walk: %u pairs chained, %u of them marked for the full layout; open ahead of pass 1 / 2: %u / %u, passes %d\n",
+    if (ctx->dbg.chain_prof) fprintf(stderr, "[chain prof] final walk: %u pairs chained, %u of them marked for the full layout; open ahead of pass 1 / 2: %u / %u, passes %d\n",
                             st.cur[20], st.cur[21], st.cur[24] + st.cur[25], st.cur[26] + st.cur[27], st.passes);
     st.query_ms = dp_elapsed(ctx, 4, 5);
     st.chain_bytes = st.alg_bytes;
@@ -3642,14 +3633,13 @@ int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_
     if (dev_reserve(ctx, ctx->d_pbase, ((size_t)nq + 1) * 4 + ((size_t)nq + 1) * 8 + (size_t)nq * sizeof(QState) + (size_t)nq * 4 + 128)) return DP_ERR_HIP;
     if (int rc = dp_query_stage(ctx, q_segs, q_off, nq, hf, &st.d_qmeta, &d_words, &d_mc, &st.mc_n, &st.d_qcnt)) return rc;
     st.d_mc = d_mc;
-    const char* tier_env = getenv("DP_CHAIN_TIER");  // tests: 2 = lds tier, 3 = one-lane tier for every pair
-    st.chain_tier = tier_env ? atoi(tier_env) : 0;
-    const char* pass_env = getenv("DP_CHAIN_PASSES");  // proposal passes (0 = the serial walk alone: the round-1 behaviour)
-    st.passes = pass_env ? std::max(0, std::min(6, atoi(pass_env))) : 3;
+    st.chain_tier = (int)dp_env_long("DP_CHAIN_TIER", 0);  // tests: 2 = lds tier, 3 = one-lane tier for every pair
+    const long pass_env = dp_env_long("DP_CHAIN_PASSES", -1, 0, 6);  // proposal passes (0 = the serial walk alone: the round-1 behaviour)
+    st.passes = pass_env >= 0 ? (int)pass_env : 3;
     // (round 6) the third pass is left out only when this context's previous stage left it next to nothing.  A threshold of 24 pairs - "at
     // k = 13 it sees ~18 short pairs, which the final walk chains as well" - saved two launches a round and cost more than it saved: the
     // final walk, one wave per QUERY, went from 13 to 53 us a launch under five slots (profiles/r06/k13_against_round5.txt).
-    if (!pass_env && ctx->chain_open_ahead[1] < 2u) st.passes = 2;
+    if (pass_env < 0 && ctx->chain_open_ahead[1] < 2u) st.passes = 2;
     st.walk_blocks = std::min<uint32_t>(256, (nq + C_WAVES - 1) / C_WAVES);
     st.spec_blocks = 1024;  // 4096 persistent waves, 16 per CU: what CSlim's 8.5 KB per wave lets a CU hold
     st.spec_blocks = (uint32_t)std::max(1L, dp_tune("spec_blocks", st.spec_blocks));

@@ -65,13 +65,11 @@ static ScanGate g_scan_mu;
 //         wake-up is 50-70 us late, but a waiting thread costs nothing - what a process needs when it has fewer cores than
 //         waiting threads (round 1: five slots, 17 core-ms of host work per round on a 16-core quota).
 // dp_set_stream_wait() chooses (the host pipeline does, from its CPU budget and its number of slots); DP_SPIN_SYNC=0/1 in the
-// environment overrides it.  sync_poll_us=0: blocking hipEventSynchronize instead of the poll loop.
+// environment overrides it.  sync_poll_us=0: blocking hipEventSynchronize instead of the poll loop.  Both are read by
+// dp_ctx_create into the context (ctx->wait): a round waits five to seven times.
 static std::atomic<int> g_wait_spin{0};
 extern "C" void dp_set_stream_wait(int spin) { g_wait_spin.store(spin ? 1 : 0); }
-static std::atomic<long> g_timing_every{[] {
-    const char* e = getenv("DP_KERNEL_TIMING");
-    return e ? atol(e) : 8L;
-}()};
+static std::atomic<long> g_timing_every{dp_env_long("DP_KERNEL_TIMING", 8)};
 extern "C" void dp_set_kernel_timing(int every) { g_timing_every.store(every < 0 ? 0 : every); }
 
 #ifdef DP_COPY_LOG
@@ -117,62 +115,11 @@ const void* dp_stage(dp_ctx* ctx, const void* src, size_t bytes) {
 
 hipStream_t dp_ctx_stream(const dp_ctx* ctx) { return ctx->stream; }
 
-static std::map<std::string, std::string> env_tokens(const char* name) {
-    std::map<std::string, std::string> m;
-    const char* e = getenv(name);
-    if (!e) return m;
-    std::string s(e);
-    size_t at = 0;
-    while (at <= s.size()) {
-        size_t end = s.find(',', at);
-        if (end == std::string::npos) end = s.size();
-        const std::string tok = s.substr(at, end - at);
-        const size_t eq = tok.find('=');
-        if (!tok.empty()) m[eq == std::string::npos ? tok : tok.substr(0, eq)] = eq == std::string::npos ? "1" : tok.substr(eq + 1);
-        at = end + 1;
-    }
-    return m;
-}
-// (parsed again whenever the variable's text has changed: tests set it between jobs of one process)
-struct EnvTokens {
-    const char* name;
-    std::mutex mu;
-    std::string text;
-    bool parsed = false;
-    std::map<std::string, std::string> m;
-    const std::map<std::string, std::string>& get() {  // (call with mu held)
-        const char* e = getenv(name);
-        if (!e) e = "";
-        if (!parsed || text != e) {
-            text = e;
-            m = env_tokens(name);
-            parsed = true;
-        }
-        return m;
-    }
-};
-bool dp_debug(const char* what) {
-    static EnvTokens t{"DP_DEBUG"};
-    std::lock_guard<std::mutex> lk(t.mu);
-    return t.get().count(what) != 0;
-}
-long dp_tune(const char* key, long dflt) {
-    static EnvTokens t{"DP_TUNE"};
-    std::lock_guard<std::mutex> lk(t.mu);
-    const auto& m = t.get();
-    const auto it = m.find(key);
-    return it == m.end() ? dflt : atol(it->second.c_str());
-}
-
+static bool wait_spins(const dp_ctx* ctx) { return ctx->wait.spin >= 0 ? ctx->wait.spin == 1 : g_wait_spin.load(std::memory_order_relaxed) != 0; }
 hipError_t dp_stream_sync(dp_ctx* ctx) {
     ctx->stage_used = 0;  // (everything queued so far, copies out of the staging block included, is done when this returns)
-    static const int env_spin = [] {
-        const char* e = getenv("DP_SPIN_SYNC");
-        return e ? (e[0] == '1' ? 1 : 0) : -1;
-    }();
-    static const long poll_ns = dp_tune("sync_poll_us", 20) * 1000L;
-    const bool spin = env_spin >= 0 ? env_spin == 1 : g_wait_spin.load(std::memory_order_relaxed) != 0;
-    if (spin || !ctx->ev_sync) return hipStreamSynchronize(ctx->stream);
+    const long poll_ns = ctx->wait.poll_ns;
+    if (wait_spins(ctx) || !ctx->ev_sync) return hipStreamSynchronize(ctx->stream);
     hipError_t e = hipEventRecord(ctx->ev_sync, ctx->stream);
     if (e != hipSuccess) return e;
     if (poll_ns <= 0) return hipEventSynchronize(ctx->ev_sync);
@@ -204,11 +151,7 @@ int dp_fail(dp_ctx* ctx, int code, const char* what, hipError_t e) {
 // and the outgrown buffer is NOT freed here - hipFree / hipHostFree wait for the whole device, i.e. for every other
 // executor slot's kernels, which showed up as 20-30 ms stalls a few times per hundred rounds.  Old buffers go to the
 // context's retired list and are released with the context (their total is below the live size: geometric growth).
-// DP_ALLOC_TRACE=1: one stderr line per growth (what, bytes, how long the allocation call took)
-static bool alloc_trace() {
-    static const bool on = dp_debug("alloc");
-    return on;
-}
+// DP_DEBUG=alloc: one stderr line per growth (what, bytes, how long the allocation call took)
 static double alloc_now() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -217,7 +160,8 @@ static double alloc_now() {
 
 int dev_reserve(dp_ctx* ctx, DevBuf& b, size_t bytes, bool keep) {
     if (bytes <= b.cap) return 0;
-    const double t0 = alloc_trace() ? alloc_now() : 0;
+    const bool trace = dp_debug("alloc");
+    const double t0 = trace ? alloc_now() : 0;
     // (per-round buffers get head room; the big resident ones - packed reads, k-mer index - are sized exactly)
     size_t ncap = bytes > ((size_t)256 << 20) ? bytes : std::max(bytes + bytes / 2, b.cap * 2);
     ncap = (ncap + 255) & ~(size_t)255;
@@ -227,7 +171,7 @@ int dev_reserve(dp_ctx* ctx, DevBuf& b, size_t bytes, bool keep) {
         if (keep) DP_HIP(hipMemcpyAsync(np, b.p, b.cap, hipMemcpyDeviceToDevice, ctx->stream));
         ctx->retired_dev.push_back(b.p);  // (work already queued on the stream may still read it)
     }
-    if (alloc_trace()) fprintf(stderr, "[alloc] device %zu -> %zu bytes, %.3f ms\n", b.cap, ncap, 1e3 * (alloc_now() - t0));
+    if (trace) fprintf(stderr, "[alloc] device %zu -> %zu bytes, %.3f ms\n", b.cap, ncap, 1e3 * (alloc_now() - t0));
     b.p = np;
     b.cap = ncap;
     return 0;
@@ -237,9 +181,10 @@ int pin_reserve(dp_ctx* ctx, PinBuf& b, size_t bytes) {
     size_t ncap = bytes > ((size_t)256 << 20) ? bytes : std::max(bytes + bytes / 2, b.cap * 2);
     ncap = (ncap + 4095) & ~(size_t)4095;
     void* np = nullptr;
-    const double t0 = alloc_trace() ? alloc_now() : 0;
+    const bool trace = dp_debug("alloc");
+    const double t0 = trace ? alloc_now() : 0;
     DP_HIP(dp_pin_malloc(&np, ncap));
-    if (alloc_trace()) fprintf(stderr, "[alloc] pinned %zu -> %zu bytes, %.3f ms\n", b.cap, ncap, 1e3 * (alloc_now() - t0));
+    if (trace) fprintf(stderr, "[alloc] pinned %zu -> %zu bytes, %.3f ms\n", b.cap, ncap, 1e3 * (alloc_now() - t0));
     if (b.p) ctx->retired_pin.push_back(b.p);
     b.p = np;
     b.cap = ncap;
@@ -293,10 +238,7 @@ BigCache& pin_cache() {
 }
 constexpr size_t kBig = (size_t)4 << 10;
 constexpr size_t kPinMin = (size_t)4 << 10;
-size_t cache_cap(const char* env, size_t dflt_mb) {
-    const char* e = getenv(env);
-    return (size_t)(e ? std::max(0, atoi(e)) : (int)dflt_mb) << 20;
-}
+size_t cache_cap(const char* env, long dflt_mb) { return (size_t)dp_env_long(env, dflt_mb, 0) << 20; }  // (read once, where the cache is first trimmed)
 struct DeviceGuard {  // makes `device` current for the scope, then restores the caller's
     int prev = -1;
     explicit DeviceGuard(int device) {
@@ -393,14 +335,15 @@ hipError_t dp_dev_malloc(void** p, size_t bytes) {
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
     BigCache& c = big_cache();
     if ((*p = cache_take(c, dev, bytes)) != nullptr) return hipSuccess;
-    const double t0 = alloc_trace() ? alloc_now() : 0;
+    const bool trace = dp_debug("alloc");
+    const double t0 = trace ? alloc_now() : 0;
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) {  // out of memory with blocks parked in the cache: give them back and try again
         (void)hipGetLastError();
         dp_dev_trim();
         e = hipMalloc(p, bytes);
     }
-    if (alloc_trace() && bytes >= ((size_t)1 << 20)) fprintf(stderr, "[alloc] device block %zu bytes on device %d from the driver, %.3f ms (parked now: %zu bytes)\n", bytes, dev, 1e3 * (alloc_now() - t0), dp_dev_cached_bytes());
+    if (trace && bytes >= ((size_t)1 << 20)) fprintf(stderr, "[alloc] device block %zu bytes on device %d from the driver, %.3f ms (parked now: %zu bytes)\n", bytes, dev, 1e3 * (alloc_now() - t0), dp_dev_cached_bytes());
     if (e == hipSuccess) {
         std::lock_guard<std::mutex> lk(c.mu);
         c.live[*p] = BigBlock{bytes, dev};
@@ -595,6 +538,14 @@ extern "C" int dp_ctx_create(int device, dp_ctx** out) {
     if (device < 0 || device >= n) return dp_fail(nullptr, DP_ERR_ARG, "device index out of range");
     dp_ctx* ctx = new dp_ctx();
     ctx->device = device;
+    ctx->wait = dp_wait_mode_read();
+    ctx->dbg.kx = dp_debug("kx");
+    ctx->dbg.kx_bins = dp_debug("kx_bins");
+    ctx->dbg.kx_oneshot = dp_debug("kx_oneshot");
+    ctx->dbg.cons = dp_debug("cons");
+    ctx->dbg.cons_why = dp_debug("cons_why");
+    ctx->dbg.chain_prof = dp_debug("chain_prof");
+    ctx->dbg.map_prof = dp_debug("map_prof");
     if ((e = hipSetDevice(device)) != hipSuccess) {
         dp_fail(nullptr, DP_ERR_HIP, "hipSetDevice", e);
         delete ctx;
@@ -791,7 +742,7 @@ __global__ void repack_spans_kernel(const uint32_t* __restrict__ src, const uint
 // The ASCII bases of a read set on their way to the device.  From pageable memory a gigabyte travels at 13-18 GB/s (the runtime
 // stages it piece by piece on one thread: 55-75 ms for config 2's reads); here a few helper threads copy 4 MiB pieces into a ring of
 // pinned blocks and every piece is sent on as soon as it is complete (pinned to device: ~40 GB/s), so the host copies, not the
-// link, set the pace.  Small inputs go the plain way.  DP_UPLOAD_THREADS (default 4; 0 = plain copy; measured at config 2: 54 ms plain, 33-35 ms with 4, 6 or 8 helpers).
+// link, set the pace.  Small inputs go the plain way.  DP_TUNE=upload_threads (default 4; 0 = plain copy; measured at config 2: 54 ms plain, 33-35 ms with 4, 6 or 8 helpers).
 namespace {
 std::mutex g_ring_mu;  // held by whoever uses the ring, for as long as it does
 uint8_t* g_ring = nullptr;
@@ -811,7 +762,7 @@ uint8_t* ring_get(size_t bytes) {  // (caller holds g_ring_mu) null: no pinned m
     return g_ring;
 }
 int upload_threads() {
-    static const int n_thr = (int)std::max(0L, std::min(16L, dp_tune("upload_threads", 4)));
+    static const int n_thr = (int)std::max(0L, std::min(16L, dp_tune("upload_threads", 4)));  // (the ring they fill is the process's)
     return n_thr;
 }
 }  // namespace
@@ -1892,7 +1843,7 @@ __global__ __launch_bounds__(SCAN_THREADS, FILTER >= 2 ? 8 : 4) void scan_kernel
                 if (g <= g1) {
                     uint32_t m = (FILTER == 1 ? ProbeLoop<0>::run(w, bloom, pshift) : FILTER == 3 ? PairLoop<0, true>::run(w, bloom) : PairLoop<0>::run(w, bloom));
                     if (g == g0 || g == g1) m &= valid_mask(g, a0, a1);  // only the item's first / last group is partial
-                    if (dbg & 1) {  // timing experiments only (DP_SCAN_DEBUG): drop the candidate loop
+                    if (dbg & 1) {  // timing experiments only (DP_TUNE=scan_debug): drop the candidate loop
                         cnt += __builtin_popcount(m);
                         m = 0;
                     }
@@ -2195,9 +2146,9 @@ __global__ __launch_bounds__(OFF_TILE) void compact_write(const dp_scan_item* __
 
 // does dp_scan_reads answer from the resident k-mer position index (when that can be built) rather than by scanning?
 static bool scan_wants_index(const dp_ctx* ctx) {
-    bool use_index = ctx->total_bases >= 1000000000ull || (ctx->owner && ctx->owner->total_bases >= 1000000000ull);
-    if (const char* e = getenv("DP_SCAN_INDEX")) use_index = e[0] == '1';
-    return use_index;
+    const bool use_index = ctx->total_bases >= 1000000000ull || (ctx->owner && ctx->owner->total_bases >= 1000000000ull);
+    const int forced = dp_env_tristate("DP_SCAN_INDEX");
+    return forced < 0 ? use_index : forced == 1;
 }
 
 extern "C" int dp_scan_prepare(dp_ctx* ctx, int k) {
@@ -2233,12 +2184,8 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
 // complete - not for the stream, which may already carry the chunk stage (dp_index_prechain).  Spins or polls as dp_stream_sync
 // does; a flag that does not arrive within two seconds (a kernel that faulted) is left to the stream's own wait and its error.
 static hipError_t kx_wait_done(dp_ctx* ctx, const uint32_t* flag, uint32_t seq) {
-    static const int env_spin = [] {
-        const char* e = getenv("DP_SPIN_SYNC");
-        return e ? (e[0] == '1' ? 1 : 0) : -1;
-    }();
-    static const long poll_ns = dp_tune("sync_poll_us", 20) * 1000L;
-    const bool spin = env_spin >= 0 ? env_spin == 1 : g_wait_spin.load(std::memory_order_relaxed) != 0;
+    const long poll_ns = ctx->wait.poll_ns;
+    const bool spin = wait_spins(ctx);
     timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     for (unsigned it = 1;; it++) {
@@ -2418,8 +2365,8 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     const bool v2 = k >= 9;
     // persistent workgroups per CU: 2 fill every wave slot and all LDS of the CU (fastest scan in isolation) - and keep every
-    // other slot's kernels out until the scan is done; DP_SCAN_WG_PER_CU=1 leaves half of each CU to them
-    static const int wg_per_cu = (int)std::max(1L, std::min(2L, dp_tune("scan_wg_per_cu", 2)));
+    // other slot's kernels out until the scan is done; DP_TUNE=scan_wg_per_cu=1 leaves half of each CU to them
+    const int wg_per_cu = (int)std::max(1L, std::min(2L, dp_tune("scan_wg_per_cu", 2)));
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)dev_cus * (v2 ? wg_per_cu : 1), ((uint64_t)n_items + 15) / 16);
     uint64_t* totals = (uint64_t*)ctx->d_total.p;  // [0] n_segs, [1] n_survivors
     uint64_t* tilesA = totals + 4;
@@ -2446,8 +2393,7 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     // before the one wait, into buffers sized from this context's previous index-mode round (twice its segments, 1.5 x its hits, the
     // sort tier of 1.25 x its largest survivor); the rare round that outgrows a guess repeats fill + sort the old way after the
     // wait.  DP_KX_ONESHOT=0: count, wait, size, fill, sort, wait - as before.
-    const char* ose = getenv("DP_KX_ONESHOT");  // (read per call: tests switch it between jobs of one process)
-    const bool oneshot_env = !(ose && ose[0] == '0');
+    const bool oneshot_env = dp_env_tristate("DP_KX_ONESHOT") != 0;
     bool oneshot = false;
     dp_kindex_oneshot one;
     memset(&one, 0, sizeof one);
@@ -2484,10 +2430,9 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     if (use_index) {
         // counts, segment offsets, survivor list and totals in three launches, no sort and no host round trip (dp_kindex.hip)
         // (views served whole - top_level == 0 - have a k-mer at every indexed position: the walk tests the ignore byte instead of
-        // reading the read's item, and looks for extra items only on the round's query reads; DP_KX_FAST=0: off)
+        // reading the read's item, and looks for extra items only on the round's query reads)
         dp_kindex_fast fastArgs = {nullptr, 0u, 0u};
-        static const bool fast_off = false;
-        if (!top_level && !fast_off && ctx->d_ignore.p) {
+        if (!top_level && ctx->d_ignore.p) {
             uint32_t qmin = 0xffffffffu, qmax = 0;
             for (uint32_t i = 0; i < n_extra; i++) {
                 qmin = std::min(qmin, extra[i].read);
@@ -2545,13 +2490,6 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     }
     if (wait_flag) DP_HIP(kx_wait_done(ctx, one.done_flag, one.done_seq));
     else DP_HIP(dp_stream_sync(ctx));
-    {
-        // DP_SCAN_RELEASE_EARLY=1 opens the gate here, after the count pass, so that the short write pass overlaps the
-        // next slot's count pass.  Measured: it does not - the count pass is a persistent grid that owns every CU's LDS, so
-        // the write pass queues behind it (0.08 -> 0.2 ms) and the slot only gets slower.  Off by default.
-        static const bool early = false;
-        if (early && scan_lock.owns_lock()) scan_lock.unlock();
-    }
     const uint64_t n_segs = ((uint64_t*)ctx->h_total.p)[0];
     const uint64_t n_surv_all = ((uint64_t*)ctx->h_total.p)[1];  // surviving reads + all extra items
     if (use_index) {
@@ -2570,8 +2508,7 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
         ctx->kx_prev_segs = n_segs;
         ctx->kx_prev_max = kx_max_count;
         ctx->kx_prev_surv = (uint32_t)n_surv_all;
-        static const bool dbg1 = dp_debug("kx_oneshot");
-        if (dbg1 && !oneshot_done)
+        if (ctx->dbg.kx_oneshot && !oneshot_done)
             fprintf(stderr, "[kx] one-go step repeated: segs %llu / cap %llu, records %s, largest survivor %u / sort %u (%llu of %llu rounds)\n",
                     (unsigned long long)n_segs, (unsigned long long)one.seg_cap, rec_full ? "full" : "ok", kx_max_count, one.sort_cap,
                     (unsigned long long)ctx->kx_oneshot_redone, (unsigned long long)ctx->kx_oneshot_rounds);

@@ -22,7 +22,7 @@
 #define TR_WAVES 4
 #define TR_EDGE 150                  // edgeSize (trim.go:432,453)
 #define TR_TCAP 152                  // seeds of an end: <= 150 - k + 1
-#define TR_MAX_ADAPTER 512           // bases of the longest adapter the LDS working set is sized for (DP_TRIM_MAX_ADAPTER)
+#define TR_MAX_ADAPTER 512           // bases of the longest adapter the LDS working set is sized for
 #define TR_MAX_SEEDS 16384           // distinct seeds of the adapter index (256 set words per end)
 #define TR_NONE 0xffffu
 
@@ -779,8 +779,7 @@ extern "C" int dp_trim_search(dp_trim* t, const uint32_t* sel, uint32_t n_sel, i
         const size_t lds = (size_t)TR_WAVES * G.wave_words * 4;
         TR_HIP(hipFuncSetAttribute((const void*)trim_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         // the record buffer is sized from a guess - nearly every pair emits nothing - and the launch repeated when it was too small
-        size_t rec_cap = std::max<size_t>(1024, n_pairs / 64);
-        if (const char* e = getenv("DP_TRIM_MID_REC_CAP")) rec_cap = std::max<long>(1, atol(e));
+        size_t rec_cap = (size_t)dp_env_long("DP_TRIM_MID_REC_CAP", (long)std::max<size_t>(1024, n_pairs / 64), 1);
         const uint32_t blocks = std::min<uint32_t>(t->waves / TR_WAVES, (n_pairs + TR_WAVES - 1) / TR_WAVES);
         const size_t poolElems = (size_t)t->waves * M_CHAINS * t->qcap;
         uint16_t* poolA = t->dev<uint16_t>(TB_POOL);

@@ -443,7 +443,7 @@ class Overlapper {
 unsigned hostThreads();  // DP_HOST_THREADS or hardware_concurrency (<= 96): size of the shared worker pool
 void setHostThreadShare(unsigned concurrentUsers);
 void profilePrint();  // DPH_PROFILE counters to stderr
-void sampleProfStart();  // DPH_SAMPLE_PROF=1: CPU-time sampling by HIP API entry (host_pool.cpp), between start and stop
+void sampleProfStart();  // DP_DEBUG=sample_prof: CPU-time sampling by HIP API entry (host_pool.cpp), between start and stop
 void sampleProfStop();
 void sampleProfRegister(const char* role);  // a pipeline thread announces itself to the sampler
 void sampleProfUnregister();
@@ -652,7 +652,7 @@ struct OverlapRun {
     std::string paf;      // PAF text of the last committed round(s)
     int adaptRounds_ = 0;           // step(): rounds since the planner's lanes were last looked at
     double adaptT_ = 0;
-    double initEnd_ = 0;  // when init() returned (DPH_START_TRACE prints a job's first rounds against it)
+    double initEnd_ = 0;  // when init() returned (DP_DEBUG=start prints a job's first rounds against it)
     long long adaptWait_ = 0;
     std::atomic<long long> planWaitUs_{0};  // microseconds this handle's slots waited for plans (executeRoundOnImpl)
     int adaptLanes_ = 0;            // lanes the last job grew to (0: none yet)
@@ -708,9 +708,14 @@ struct OverlapRun {
     // scan-shard with per-slot communicators: the query windows of a round are dealt to the ranks as well ("queries
     // are partitioned by QueryID") - every rank builds the whole index from the gathered survivors but queries, chains and
     // builds the consensus for its own contiguous share of the windows only; the ranks' PAF text, SetIgnore ids and counters are
-    // all-gathered (dp_allgather_blobs on the slot's communicator) and joined in rank order = query order.  DPH_SHARD_QUERIES=0:
+    // all-gathered (dp_allgather_blobs on the slot's communicator) and joined in rank order = query order.  DP_TUNE=no_shard_queries=1:
     // every rank does every window (round 2's behaviour).
     bool shardQueries = true;
+    // settings read by init(), when the job starts (dp_env.h, CREATE): its rounds consult them
+    struct {
+        bool planner = false, start = false, exchange = false, slow = false;  // DP_DEBUG tokens
+    } dbg_;
+    i64 issueWindow_ = 10;  // DP_TUNE=issue_window: rounds issued beyond the slots' own
     void abortComms();
     // ---- round-parallel mode: execute round `r` speculatively against the current flags, commit gathered results
     int executeRound(i64 r, RoundResult& out);

@@ -739,7 +739,7 @@ void dph_overlap_text_root(void* hh, int root) { ((OverlapH*)hh)->textRoot = roo
 }  // extern "C"
 
 // ---- host-logic test hook (no GPU needed): ignore flags that arrive while the planner thread holds a finished plan in
-// its hands (set DPH_TEST_PLAN_DELAY_US).  A commit flags one read below the next plan's firstIn and one of that plan's own
+// its hands (set DP_TUNE=plan_delay_us).  A commit flags one read below the next plan's firstIn and one of that plan's own
 // query reads; the plan must be thrown away and recomputed.  Returns 0 = the plan handed out is current, 1 = stale plan,
 // <0 = the scenario could not be set up.
 extern "C" int dph_selftest_planner_flags(void* readsH, int k, int64_t seedBatchSize, const double* values) {
@@ -750,7 +750,7 @@ extern "C" int dph_selftest_planner_flags(void* readsH, int k, int64_t seedBatch
     Planner pl(reads, p, values, true, nullptr);
     std::shared_ptr<const RoundPlan> p0 = pl.get(0);  // the thread goes on with plan 1 (prefetch depth)
     if (!p0 || p0->empty || p0->firstOut <= 1 || p0->firstOut >= (i64)reads.size()) return -1;
-    const long delay = dph::dph_tune("plan_delay_us", 0);
+    const long delay = dp_tune("plan_delay_us", 0);
     if (delay <= 0) return -2;
     usleep((useconds_t)(delay / 2));  // plan 1 is computed by now and sits in the hook's sleep
     const int small = 0, big = (int)p0->firstOut;  // big = first query read of plan 1

@@ -23,7 +23,7 @@ static i64 parseInt(const std::string& a, bool& ok) {
 
 static void printLog(const std::string& text);
 static bool trimMiddleFromEnv() {  // the middle stage is in force with DP_TRIM_MIDDLE=1
-    const char* midEnv = getenv("DP_TRIM_MIDDLE");
+    const char* midEnv = dp_env_str("DP_TRIM_MIDDLE");
     return midEnv && midEnv[0] && strcmp(midEnv, "0") != 0;
 }
 static const char* const kNoMiddleNotice =
@@ -61,7 +61,7 @@ static int runOverlap(ArgTable& t) {
     }
     ReadSet reads, raw, front, back;
     std::string err;
-    const bool prof = getenv("DPH_PROFILE") != nullptr;
+    const bool prof = dp_profile_on();
     double tm = now();
     auto mark = [&](const char* what) {
         if (!prof) return;
@@ -102,8 +102,7 @@ static int runOverlap(ArgTable& t) {
         mark("respan");
     }
     OverlapRun run;
-    const char* ns = getenv("DP_EXEC_SLOTS");
-    if (rc == 0) rc = run.init(ctx, &reads, p, nullptr, ns ? atoi(ns) : 8);
+    if (rc == 0) rc = run.init(ctx, &reads, p, nullptr, (int)dp_env_long("DP_EXEC_SLOTS", 8));
     if (rc != 0) {
         fprintf(stderr, "downpore: %s\n", run.error.empty() ? dp_last_error(ctx) : run.error.c_str());
         return 2;

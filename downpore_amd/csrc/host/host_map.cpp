@@ -582,7 +582,7 @@ size_t releaseMapStaging() {
 int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
            MapStats* stats, std::string& error) {
     const double tRun0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    const bool prof = getenv("DPH_PROFILE") != nullptr;
+    const bool prof = dp_profile_on();
     double tMark = tRun0;
     auto mark = [&](const char* what) {
         if (!prof) return;
@@ -662,9 +662,9 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     // the worker pool straight into a pinned block in the device's own layout (every read on a 16-byte boundary) and put in place by
     // dp_reads_upload_packed_rc, which also makes the reverse strands: 100 MB instead of 400 at config 3, one copy instead of three
     // (staging, pinned ring, link).  DP_TUNE=map_ascii_upload=1: the ASCII path below, as before (it is what map_async_upload uses).
-    const bool asyncUpload = dph_tune("map_async_upload", 0) != 0;
-    const bool packedUpload = !asyncUpload && !dph_tune("map_ascii_upload", 0);
-    const bool packScalar = dph_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
+    const bool asyncUpload = dp_tune("map_async_upload", 0) != 0;
+    const bool packedUpload = !asyncUpload && !dp_tune("map_ascii_upload", 0);
+    const bool packScalar = dp_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
     std::vector<uint32_t> plens;
     std::vector<uint64_t> poff;
     uint8_t* pinned = nullptr;
@@ -762,13 +762,13 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     // its count region are the best of ANY window (only those can ever be seeds) - comes from the device for all windows at once
     // (dp_single_seed_candidates: the reference and the value table are resident right now); the thread below then walks the
     // windows in order and probes five or six candidates per window instead of seed_rate k-mers (3.9 s -> 0.1 s per 375 Mb of
-    // reference).  DP_MAP_SEEDS_HOST=1: the whole walk on the host as before.
+    // reference).  DP_TUNE=map_seeds_host=1: the whole walk on the host as before.
     // -all_sequences: AddSingleSeeds for one sequence after the other on the ONE index; the device numbers the windows of all sequences
     // in sequence order and "best of any window" is over all of them (dp_single_seed_candidates_multi), so the walk below is the same.
     dp_single_seed_batch ssb;
     memset(&ssb, 0, sizeof ssb);
     bool deviceSeeds = false;
-    if (!dph_tune("map_seeds_host", 0)) {  // (tests: AddSingleSeeds walked on the host)
+    if (!dp_tune("map_seeds_host", 0)) {  // (tests: AddSingleSeeds walked on the host)
         if (p.allSequences) {
             dp_single_seed_multi_batch mb;
             rc = dp_single_seed_candidates_multi(ctx, 0, (uint32_t)T, k, p.seedRate, &mb);
@@ -859,7 +859,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     // on the device
     concatThread.join();
     mark("concatenate reads (waited for)");
-    // Round 5, DP_MAP_ASYNC_UPLOAD=1: the reads travel while they are mapped (dp_reads_upload_rc_begin: this call returns when the
+    // Round 5, DP_TUNE=map_async_upload=1: the reads travel while they are mapped (dp_reads_upload_rc_begin: this call returns when the
     // reference and the join chunk are packed; the mapper threads wait for "reads below n are packed" block by block).  Built, parity
     // tested and left OFF: set-up 14.5 -> 8 ms and the best run 56.0 -> 54.4 ms, but the runs of a process spread 55 - 107 ms where
     // they were 56 - 65 (means of 12 runs 69 / 77 against 62 / 69 ms, profiles/r05/map_threads_and_reads_in_flight.txt): the upload's
@@ -969,10 +969,9 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
                 if (sh.ctx) dp_ctx_destroy(sh.ctx);
         }
     } shardGuard{shards};
-    int nShards = 1;
-    if (const char* e = getenv("DP_MAP_SHARDS")) nShards = std::max(1, atoi(e));
+    const int nShards = (int)dp_env_long("DP_MAP_SHARDS", 1, 1, INT_MAX);
     std::vector<int> devs;
-    if (const char* e = getenv("DP_MAP_DEVICES")) {
+    if (const char* e = dp_env_str("DP_MAP_DEVICES")) {
         for (const char* q = e; *q;) {
             devs.push_back(atoi(q));
             while (*q && *q != ',') q++;
@@ -984,10 +983,9 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     const uint32_t perShard = ((nChunksAll + (uint32_t)nShards - 1) / (uint32_t)nShards + 63) / 64 * 64;  // whole 64-chunk words
     // mapper threads (each with a context of its own) when the index is not sharded
     auto plannedThreads = [&]() -> size_t {
-        const char* e = getenv("DP_MAP_THREADS");
-        size_t n = (size_t)std::max(1, e ? atoi(e) : (hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3));
-        size_t perThread = 2048;  // (fewer reads than that per thread are not worth a context; DP_MAP_MIN_READS_PER_THREAD: test hook)
-        perThread = (size_t)std::max(1L, dph_tune("map_min_reads_per_thread", (long)perThread));
+        const size_t n = (size_t)dp_env_long("DP_MAP_THREADS", hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3, 1);
+        // (fewer reads than that per thread are not worth a context; the key is a test hook)
+        const size_t perThread = (size_t)std::max(1L, dp_tune("map_min_reads_per_thread", 2048));
         return std::min(n, std::max<size_t>(1, reads.size() / perThread));
     };
     // ---- the reference index's layout.  Dense: S x ceil(M/64) + M x ceil(S/64) words per context or shard; the estimate D sums them
@@ -1159,7 +1157,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     // round 6, once a context no longer costs a thread 4 ms: 8 x 2 048 runs 46 - 47 ms where 6 x 2 730 runs 50 - 51 (three alternations on
     // one box, profiles/r06/map_threads_sweep.txt)
     size_t inflight = nThreadsPlanned >= 8 ? 2048 : std::max<size_t>(2730, 10922 / nThreadsPlanned);
-    if (const char* e = getenv("DP_MAP_INFLIGHT")) inflight = (size_t)std::max(64, atoi(e));
+    inflight = (size_t)dp_env_long("DP_MAP_INFLIGHT", (long)inflight, 64);
     const size_t stackBytes = 256 * 1024;
     std::vector<std::unique_ptr<Task>> live;
     // coroutine stacks: allocated once (never zero-filled) and recycled — 50 k reads x 256 KiB of fresh zeroed vectors

@@ -404,7 +404,7 @@ int Overlapper::IndexSurvivors(const Survivors& all, RoundStats& st) {
         const double tq0 = now();
         buildQueries(st);
         assembleQueries();
-        const bool prestage = !dph_tune("no_query_prestage", 0) && !dp_index_prechained(ctx_);  // (tests: dp_find_overlaps uploads them itself)  // (chunk stage launched already: nothing to ride on)
+        const bool prestage = !dp_tune("no_query_prestage", 0) && !dp_index_prechained(ctx_);  // (tests: dp_find_overlaps uploads them itself)  // (chunk stage launched already: nothing to ride on)
         if (prestage && !queries.empty()) {
             int prc = dp_query_prestage(ctx_, querySegs_.data(), queryOff_.data(), (uint32_t)queries.size(), hitFraction_);
             if (prc != 0) {
@@ -648,22 +648,15 @@ int Overlapper::FindOverlapsAndFinalCheck(std::vector<SeedMatch>& pool, i64 over
     dp_match_batch mb;
     const double tq0 = now();
     // want_candidates 6: the matches stay on the device and the stage is left pending - dp_consensus_paf below evaluates it in the
-    // wait it needs anyway (DP_FIND_PENDING=0: wait here, as every other caller of dp_find_overlaps does)
-    static const bool pendingFind = true;
+    // wait it needs anyway (every other caller of dp_find_overlaps waits there)
     int rc = dp_find_overlaps(ctx_, querySegs_.data(), queryOff_.data(), (uint32_t)queries.size(), hitFraction_, index_.k,
-                              (uint32_t)(overlap_ / 2), pendingFind ? 6 : 2, &mb);
+                              (uint32_t)(overlap_ / 2), 6, &mb);
     if (rc != 0) {
         err = dp_last_error(ctx_);
         return rc;
     }
     const double tq1 = now();
     g_prof.add(9, tq1 - tq0);
-    if (!pendingFind) {
-        st.k_query_ms += mb.query_kernel_ms;
-        st.k_chain_ms += mb.chain_kernel_ms;
-        st.query_bytes += mb.query_bytes;
-        st.chain_bytes += mb.chain_bytes;
-    }
     if ((!chunksOnDevice_ && index_.sequences.empty()) || (chunksOnDevice_ && nIndexedCap_ == 0) || queries.empty())
         return 0;  // nothing indexed: no candidate, no line
     if (index_.rcOf.size() != index_.seedMap.size()) index_.buildRcTable();
@@ -692,12 +685,10 @@ int Overlapper::FindOverlapsAndFinalCheck(std::vector<SeedMatch>& pool, i64 over
         nIndexedExact_ = pb.n_indexed;
         st.n_indexed = pb.n_indexed;
     }
-    if (pendingFind) {
-        st.k_query_ms += pb.query_kernel_ms;
-        st.k_chain_ms += pb.chain_kernel_ms;
-        st.query_bytes += pb.query_bytes;
-        st.chain_bytes += pb.chain_bytes;
-    }
+    st.k_query_ms += pb.query_kernel_ms;  // (of the pending stage the call finished)
+    st.k_chain_ms += pb.chain_kernel_ms;
+    st.query_bytes += pb.query_bytes;
+    st.chain_bytes += pb.chain_bytes;
     st.k_cons_ms += pb.kernel_ms;
     st.k_index_ms += pb.index_kernel_ms;
     const double tq2 = now();
@@ -849,8 +840,8 @@ void TextJobBuffers::giveTexts(std::vector<std::string>& v) {
     // capped by bytes, not by entries: a long-lived embedder keeps at most that much until dph_release_caches().  512 MB: the text
     // of a config-2 job is 235 MB in 599 strings whose capacities add up to a little more - with a cap of 256 MB a tenth of the
     // rounds of every job allocated (and page-faulted) fresh strings on the committing thread, which a 20-job run showed as 0.15 ->
-    // 0.18 ms per round (DPH_TEXT_POOL_MB: another cap)
-    static const size_t CAP_BYTES = (size_t)std::max(1L, dph_tune("text_pool_mb", 512)) << 20;
+    // 0.18 ms per round (DP_TUNE=text_pool_mb: another cap, read when the pool first takes strings back)
+    static const size_t CAP_BYTES = (size_t)std::max(1L, dp_tune("text_pool_mb", 512)) << 20;
     for (std::string& s : v)
         if (s.capacity() >= 65536 && g_txt_bytes + s.capacity() <= CAP_BYTES) {
             g_txt_bytes += s.capacity();
@@ -1078,9 +1069,8 @@ int finalCheck(Arena& arena, const SeedIndex& index, ReadSet& reads, const std::
     // DP_DEVICE_CONSENSUS=1: run the seed-space alignment in the middle of BuildConsensus on the device
     // (dp_consensus_align).  Off by default: measured on config 2 it takes 1.7 core-ms per round off the host (of 13.6)
     // but adds a 0.22 ms kernel and a second fork/join to every round, a net loss (5.6 M -> 4.6 M overlaps/s) until the
-    // trimming before it and trimToBestSeed after it move to the device too.  Read per call so tests can toggle it.
-    const char* devCons = getenv("DP_DEVICE_CONSENSUS");
-    if (ctx && jobs && devCons && devCons[0] == '1' && nw > 0) {
+    // trimming before it and trimToBestSeed after it move to the device too.
+    if (ctx && jobs && dp_env_tristate("DP_DEVICE_CONSENSUS") == 1 && nw > 0) {
         // ---- phase 1 (pool): trim the matched targets and reduce them, per query window
         if (jobs->size() < nw) jobs->resize(nw);
         parallelFor(nw, [&](size_t w) {

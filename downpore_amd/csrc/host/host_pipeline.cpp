@@ -281,7 +281,11 @@ struct Planner::Impl {
     uint64_t epoch = 0;       // bumped whenever an ignore flag is set
     bool stop = false;
     bool fromCache = false;   // plans come from the window cache (QueryEdges with the cache's numSeeds)
-    long testDelayUs = 0;     // DPH_TEST_PLAN_DELAY_US: sleep before every compute (tests/test_planner_epoch.py)
+    long testDelayUs = 0;     // DP_TUNE=plan_delay_us: sleep after every compute (tests/test_planner_epoch.py)
+    // plans computed beyond the highest round anybody asked for (DP_TUNE=plan_depth): the slots ask in bursts - a commit that was
+    // holding the issue window releases several rounds at once - and a lane needs 0.3 ms per plan
+    i64 depth = 6;
+    bool dbg = false;         // DP_DEBUG=planner
     struct Lane {
         std::thread th;
         SeedIndex index;
@@ -313,7 +317,9 @@ Planner::Planner(ReadSet& reads, const OverlapParams& p, ValueView values, bool 
     // remember the epoch of the flags they hold, and a new job's epoch n must not look like the old job's epoch n
     static std::atomic<uint64_t> serial{0};
     d->epoch = (serial.fetch_add(1) + 1) << 32;
-    d->testDelayUs = dph_tune("plan_delay_us", 0);  // (test hook)
+    d->testDelayUs = dp_tune("plan_delay_us", 0);  // (test hook)
+    d->depth = std::max(1L, dp_tune("plan_depth", 6));
+    d->dbg = dp_debug("planner");
     d->fromCache = cache && (p.queryType & 1) && !(p.queryType & 8) && p.numSeeds == cache->numSeeds;
     if (threaded) setLanes(1);
 }
@@ -321,7 +327,7 @@ Planner::Planner(ReadSet& reads, const OverlapParams& p, ValueView values, bool 
 // Lanes for a run of `world` ranks (in the round-parallel mode every rank's planner walks the whole chain while its GPU
 // executes one round in `world`, so the chain has to be `world` times faster than a GPU) next to `slots` executor threads.
 int Planner::lanesFor(int world, int slots) {
-    if (const char* e = getenv("DPH_PLAN_LANES")) return std::max(1, std::min(8, atoi(e)));
+    if (const long fixed = dp_env_long("DPH_PLAN_LANES", 0, 1, 8)) return (int)fixed;
     const int spare = (int)hostThreads() - std::max(1, slots) - 4;  // slots, window cache, formatter, commit
     // (ownership mode - setOwnership - leaves a rank's planner 1 / world of the chain: three lanes as on one GPU; without it the
     // whole chain has to be walked `world` times faster than a GPU executes)
@@ -334,7 +340,7 @@ int Planner::lanesFor(int world, int slots) {
 // a plan takes 0.45 ms instead of 0.33, three lanes are 84 % busy and the slots waited 18 ms each per job; on the fast ones three are
 // enough and more threads are only more contention.
 int Planner::lanesMax(int world, int slots) {
-    if (getenv("DPH_PLAN_LANES")) return lanesFor(world, slots);
+    if (dp_env_str("DPH_PLAN_LANES")) return lanesFor(world, slots);
     const int spare = (int)hostThreads() - std::max(1, slots) - 4;
     return std::max(lanesFor(world, slots), std::min(6, spare));
 }
@@ -587,7 +593,7 @@ void Planner::laneMain(size_t li) {
         me.maxFlagged = -1;
         const uint64_t e0 = d->epoch;
         lk.unlock();
-        static const bool dbg = dph_debug("planner");
+        const bool dbg = d->dbg;
         if (dbg) fprintf(stderr, "[planner %zu] computing plan %lld (firstIn %lld, wantUpTo %lld, base %lld)\n", li, (long long)m, (long long)firstIn, (long long)d->wantUpTo, (long long)d->base);
         std::shared_ptr<RoundPlan> plan = compute(m, firstIn, me.index);
         if (d->testDelayUs > 0) usleep((useconds_t)d->testDelayUs);  // test hook: flags arrive after this plan has read them
@@ -634,9 +640,7 @@ std::shared_ptr<const RoundPlan> Planner::get(i64 round) {
             d->cache[m] = plan;
         }
     }
-    // plans computed beyond the highest round anybody asked for (DPH_PLAN_DEPTH): the slots ask in bursts - a commit that was
-    // holding the issue window releases several rounds at once - and a lane needs 0.3 ms per plan
-    static const i64 depth = std::max(1L, dph_tune("plan_depth", 6));
+    const i64 depth = d->depth;
     if (d->ownWorld > 1 && round % d->ownWorld != d->ownRank) {
         // somebody asks for a round this rank does not own (not the round-parallel workers): the whole chain from here on
         d->ownWorld = 1;
@@ -844,6 +848,12 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
     numQuerySeqs = 0;
     last = RoundStats();
     total = RoundStats();
+    g_prof.on = dp_profile_on();
+    dbg_.planner = dp_debug("planner");
+    dbg_.start = dp_debug("start");
+    dbg_.exchange = dp_debug("exchange");
+    dbg_.slow = dp_debug("slow");
+    issueWindow_ = std::max(0L, dp_tune("issue_window", 10));
     char line[160];
     snprintf(line, sizeof line, "Counting all %d-mers in the input...\n", p.k);
     errText += line;
@@ -867,7 +877,7 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
     }
     if (valuesOrNull) {
         values.assign(valuesOrNull, (size_t)1 << (2 * p.k));
-    } else if (dph_tune("host_values", 0)) {  // (tests) histogram on the GPU, table on the host
+    } else if (dp_tune("host_values", 0)) {  // (tests) histogram on the GPU, table on the host
         std::vector<uint64_t> counts((size_t)1 << (2 * p.k));
         int rc = dp_kmer_histogram(ctx, p.k, counts.data());
         if (rc != 0) {
@@ -944,7 +954,7 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
     }
     errText += "Counting complete. Starting indexing and querying...";
     {
-        if (!dph_tune("host_select", 0) && p.numSeeds <= 64 && !valuesOnDevice) {  // value table resident for dp_select_seeds
+        if (!dp_tune("host_select", 0) && p.numSeeds <= 64 && !valuesOnDevice) {  // value table resident for dp_select_seeds
             int rc = dp_values_upload(ctx, values.data(), values.size());
             if (rc != 0) {
                 error = dp_last_error(ctx);
@@ -965,9 +975,7 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
         // formatter threads (DPH_TEXT_THREADS): a round's text is ~0.26 ms of one thread, so two of them cap a run at 7.7 rounds per ms -
         // which is where the rounds arrived in round 5 (0.135 ms each): three where the host has the threads for it (commit's wait for
         // its round's text 46 -> 40 ms per job, 0.141 - 0.152 -> 0.133 - 0.141 ms per round; four and six: the same as three)
-        int nText = hostThreads() >= 12 ? 3 : 2;
-        if (const char* te = getenv("DPH_TEXT_THREADS")) nText = std::max(1, std::min(16, atoi(te)));
-        textPool.reset(new TextPool(nText));
+        textPool.reset(new TextPool((int)dp_env_long("DPH_TEXT_THREADS", hostThreads() >= 12 ? 3 : 2, 1, 16)));
     }
     setHostThreadShare((unsigned)std::max(1, nSlots));
     // every executor slot's thread waits for its stream five to seven times per round: busy waits when this process has the
@@ -997,8 +1005,8 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
     }
     mark("executor slots");
     // (tests: DP_TUNE=no_planner_thread=1 plans on the calling thread, host_select=1 keeps the speculative seed selection on host threads)
-    const bool nothread = dph_tune("no_planner_thread", 0) != 0;
-    const bool wantPlannerCtx = !dph_tune("host_select", 0) && p.numSeeds <= 64;
+    const bool nothread = dp_tune("no_planner_thread", 0) != 0;
+    const bool wantPlannerCtx = !dp_tune("host_select", 0) && p.numSeeds <= 64;
     if (plannerCtx && !wantPlannerCtx) {
         dp_ctx_destroy(plannerCtx);
         plannerCtx = nullptr;
@@ -1019,8 +1027,7 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
         // QueryEdges without WeightEdges (the overlap command): the windows' speculative selection and evaluated k-mers come
         // from a producer thread that runs ahead of the plan chain on the planner's context.  DP_WINDOW_CACHE=0: per-plan
         // dp_select_seeds calls and base-by-base speculation checks (the round-1 path).
-        const char* wc = getenv("DP_WINDOW_CACHE");
-        if (plannerCtx && p.queryType == 1 && !(wc && wc[0] == '0'))
+        if (plannerCtx && p.queryType == 1 && dp_env_tristate("DP_WINDOW_CACHE") != 0)
             winCache.reset(new WindowCache(plannerCtx, *reads, p.overlapSize, p.k, p.numSeeds));
     }
     if (dl.joinable()) {
@@ -1064,9 +1071,9 @@ int OverlapRun::init(dp_ctx* c, ReadSet* r, const OverlapParams& params, const d
 int OverlapRun::beginRound(ExecSlot& sl, const RoundPlan& plan) {
     const double tb0 = now();
     if (dp_comm* cm = sl.comm ? sl.comm : comm)
-        if (const long fr = dph_tune("fail_begin_rank", -1); fr >= 0)  // test hook: this rank's round fails before it reaches any exchange
+        if (const long fr = dp_tune("fail_begin_rank", -1); fr >= 0)  // test hook: this rank's round fails before it reaches any exchange
             if (fr == dp_comm_rank(cm)) {
-                sl.error = "injected failure before the exchange (DPH_FAIL_BEGIN_RANK)";
+                sl.error = "injected failure before the exchange (DP_TUNE=fail_begin_rank)";
                 return -1;
             }
     // seeds.NewSeedIndex(k) per round (:125): the plan's seed list and reverse-complement table, as the planner left them
@@ -1091,18 +1098,13 @@ int OverlapRun::beginRound(ExecSlot& sl, const RoundPlan& plan) {
     sl.lap->setTextPool(textPool.get());
     {
         // chunkWorker on the device (dp_index_build_chunked) wherever the consensus runs there too; DP_DEVICE_CHUNK=0: host chunks
-        static const bool deviceChunk = [] {
-            const char* e = getenv("DP_DEVICE_CHUNK");
-            const char* c = getenv("DP_DEVICE_CONSENSUS");
-            return !(e && e[0] == '0') && !(c && c[0] == '0');
-        }();
+        const bool deviceChunk = dp_env_tristate("DP_DEVICE_CHUNK") != 0 && dp_device_consensus_on();
         sl.lap->setDeviceChunking(deviceChunk);  // (scan-shard mode too: the gathered survivors are chunked where the exchange put them)
         // dp_index_prechain (the chunk stage launched behind the un-waited scan) shortens a round's chain of waits: 0.460 -> 0.440 ms
         // per round with one slot, 0.194 -> 0.186 with three - and nothing with five or six (0.154 / 0.158: the GPU is the limit there,
         // and the guess-sized bit matrices cost what the wait saved; profiles/r04/ab_prechain_s*.txt).  Default: up to three slots.
-        const char* pce = getenv("DPH_PRECHAIN");  // (read per round: tests switch it between jobs of one process)
-        const int prechainEnv = pce ? (pce[0] == '0' ? 0 : 1) : -1;
-        const bool prechain = prechainEnv >= 0 ? prechainEnv == 1 : slots.size() <= 3;
+        const int prechainEnv = dp_env_tristate("DPH_PRECHAIN");
+        const bool prechain = prechainEnv >= 0 ? prechainEnv != 0 : slots.size() <= 3;
         sl.lap->setPrechain(prechain && deviceChunk && sl.comm == nullptr && comm == nullptr);
     }
     sl.lap->setIgnoreView(reads->ignore.data(), planner->ignoreEpoch());
@@ -1134,12 +1136,8 @@ int OverlapRun::finishRound(ExecSlot& sl, const Survivors& all, RoundResult& out
     st.t_index = t1 - t0;
     // DP_DEVICE_CONSENSUS=0: matches come back to the host, BuildConsensus / finalCheckWorker run on the worker pool (the
     // round-1 path, still what a window the device flags falls back to)
-    static const bool deviceConsensus = [] {
-        const char* e = getenv("DP_DEVICE_CONSENSUS");
-        return !(e && e[0] == '0');
-    }();
     double t2;
-    if (deviceConsensus && (sl.lap->queries.size() % 2) == 0) {
+    if (dp_device_consensus_on() && (sl.lap->queries.size() % 2) == 0) {
         rc = sl.lap->FindOverlapsAndFinalCheck(sl.matchPool, p.overlapSize, out.paf, out.fs, &out.ignores, st, &out.text);
         if (rc != 0) {
             sl.error = sl.lap->err;
@@ -1211,11 +1209,10 @@ int OverlapRun::executeRoundOnImpl(ExecSlot& sl, i64 r, RoundResult& out) {
             pass(run->resultTurn_);
         }
     } exchangeTurn{this, sl.slotNo, sl.comm != nullptr && exchangeOrdered_};
-    static const bool dbgExec = dph_debug("planner");
+    const bool dbgExec = dbg_.planner, startTrace = dbg_.start, dbgX = dbg_.exchange, slowTrace = dbg_.slow;
     if (dbgExec) fprintf(stderr, "[exec] round %lld waiting for its plan\n", (long long)r);
     std::shared_ptr<const RoundPlan> plan = planner->get(r);
     if (dbgExec) fprintf(stderr, "[exec] round %lld got plan\n", (long long)r);
-    static const bool startTrace = dph_debug("start");  // a job's first rounds, in ms since the end of its set-up
     const double tPlan = now();
     {
         const long long waitedUs = (long long)((now() - t0) * 1e6);
@@ -1245,7 +1242,6 @@ int OverlapRun::executeRoundOnImpl(ExecSlot& sl, i64 r, RoundResult& out) {
     out.st.t_prepare = t1 - t0;
     const bool sharded = sl.comm != nullptr;  // scan-shard: this rank scans its reads, the survivors of all ranks are exchanged
     rc = sl.lap->ScanLocal(sharded ? shardLo : 0, sharded ? shardHi : reads->size(), sl.local, out.st);
-    static const bool dbgX = dph_debug("exchange");
     if (dbgX) fprintf(stderr, "[x %p] slot %d round %lld scanned rc %d, waiting for turn (turn %d)\n", (void*)this, sl.slotNo, (long long)r, rc, exchangeTurn_);
     if (sharded && exchangeOrdered_) {  // this slot's turn among the batch's exchanges (taken also by a slot whose scan failed)
         std::unique_lock<std::mutex> lk(exchangeMu_);
@@ -1327,7 +1323,6 @@ int OverlapRun::executeRoundOnImpl(ExecSlot& sl, i64 r, RoundResult& out) {
     }
     if (dbgExec) fprintf(stderr, "[exec] round %lld finished rc %d\n", (long long)r, rc);
     const double t2 = now();
-    static const bool slowTrace = dph_debug("slow");  // rounds that took a slot more than 3 ms, with where the time went
     if (slowTrace && t2 - t0 > 3e-3)
         fprintf(stderr, "[slow] round %lld slot %d at %.1f ms of its job: %.2f ms = plan wait %.2f + prepare %.2f + scan / count %.2f + index %.2f + query / chain / consensus %.2f + rest %.2f\n",
                 (long long)r, sl.slotNo, 1e3 * (t0 - initEnd_), 1e3 * (t2 - t0), 1e3 * (tPlan - t0), 1e3 * (out.st.t_prepare - (tPlan - t0)), 1e3 * out.st.t_scan,
@@ -1479,8 +1474,8 @@ void OverlapRun::workerMain(size_t si) {
     } reg;
     ExecSlot& sl = *slots[si];
     // rounds issued ahead of the commit point (owned ones only): commits are in order, so a round that takes longer than its
-    // neighbours holds the window; DPH_ISSUE_WINDOW = rounds beyond the slot count (config 2, six slots: +2 0.370, +6 0.344, +12 0.338, +24 0.343 ms per round)
-    static const i64 extra = std::max(0L, dph_tune("issue_window", 10));
+    // neighbours holds the window; DP_TUNE=issue_window = rounds beyond the slot count (config 2, six slots: +2 0.370, +6 0.344, +12 0.338, +24 0.343 ms per round)
+    const i64 extra = issueWindow_;
     const i64 window = ((i64)slots.size() + extra) * world_;
     std::unique_lock<std::mutex> lk(pmu_);
     for (;;) {
@@ -1764,9 +1759,7 @@ int OverlapRun::roundSharded() {
 
 int OverlapRun::roundsShardedBatch() {
     if (done) return 0;
-    {
-        shardQueries = !dph_tune("no_shard_queries", 0);
-    }
+    shardQueries = !dp_tune("no_shard_queries", 0);
     if (slotComms.size() < slots.size()) {
         error = "roundsShardedBatch: fewer communicators than executor slots";
         return -1;

@@ -26,7 +26,7 @@ namespace dph {
 // per-round objects).  With glibc's defaults every other free hands memory back to the kernel (heap trim, munmap of large
 // chunks) and the next round faults it in again; those calls take the process-wide mmap lock for writing and stall every
 // thread's page faults - measured as 12 % of the whole job (two processes with four slots each on one GPU ran 19 % faster
-// than one process with eight).  Keep freed memory in the allocator instead.  DPH_MALLOC_DEFAULTS=1 leaves glibc alone.
+// than one process with eight).  Keep freed memory in the allocator instead.
 static const bool g_malloc_tuned = [] {
     mallopt(M_MMAP_THRESHOLD, 32 << 20);      // (the largest value glibc accepts; fixes the threshold)
     mallopt(M_TRIM_THRESHOLD, 1 << 30);
@@ -35,7 +35,7 @@ static const bool g_malloc_tuned = [] {
 }();
 
 
-// DPH_SEGV_TRACE=1: a crashing host thread prints its frames (module + offset: addr2line on the in-tree build) before dying
+// DP_DEBUG=segv: a crashing host thread prints its frames (module + offset: addr2line on the in-tree build) before dying
 static void segvTrace(int sig) {
     void* frames[48];
     const int n = backtrace(frames, 48);
@@ -46,7 +46,7 @@ static void segvTrace(int sig) {
     raise(sig);
 }
 static const bool g_segv_trace = [] {
-    if (dph::dph_debug("segv")) {
+    if (dp_debug("segv")) {
         signal(SIGSEGV, segvTrace);
         signal(SIGBUS, segvTrace);
         signal(SIGABRT, segvTrace);
@@ -55,7 +55,7 @@ static const bool g_segv_trace = [] {
     return false;
 }();
 
-// DPH_SAMPLE_PROF=1: wall-clock sampling of the pipeline's threads (executor slots, planner lanes, window cache, formatters):
+// DP_DEBUG=sample_prof: wall-clock sampling of the pipeline's threads (executor slots, planner lanes, window cache, formatters):
 // a sampler thread signals each registered thread every 0.2 ms, the thread records its frames.  A sample is attributed to
 // the innermost frame inside our own libraries - the call site of the HIP API call (or host code) the thread is in, as
 // module+offset (tools/sample_resolve.py turns them into file:line with addr2line on the in-tree build; the runtime
@@ -123,7 +123,7 @@ void profReport() {
     }
 }
 const bool g_profOn = [] {
-    if (!dph::dph_debug("sample_prof")) return false;
+    if (!dp_debug("sample_prof")) return false;
     g_profSamples = new ProfSample[kProfMax];
     void* warm[4];
     backtrace(warm, 4);  // (loads the unwinder now, not inside the first signal)
@@ -214,8 +214,8 @@ static unsigned cpuBudget() {
 }
 
 unsigned hostThreads() {
-    static unsigned n = [] {
-        const char* e = getenv("DP_HOST_THREADS");
+    static const unsigned n = [] {  // (the worker pool's size, and what every other thread count is derived from: the process's)
+        const char* e = dp_env_str("DP_HOST_THREADS");
         unsigned v = e ? (unsigned)atoi(e) : cpuBudget();
         if (v == 0) v = 1;
         return std::min(v, 96u);
@@ -269,9 +269,9 @@ class WorkPool {
         const unsigned n = hostThreads();
         // Workers sleep between jobs and are woken together by the submitting thread; the scheduler tends to leave such
         // short bursts stacked on the waker's CPU.  Each worker is therefore pinned to its own CPU of the allowed set
-        // (spread evenly) when DP_PIN_WORKERS=1.
+        // (spread evenly) when DP_TUNE=pin_workers=1.
         std::vector<int> cpus;
-        const long pinMode = dph::dph_tune("pin_workers", 0);
+        const long pinMode = dp_tune("pin_workers", 0);
         const char pinBuf[2] = {(char)('0' + (pinMode & 7)), 0};
         const char* pin = pinBuf;
         if (pin[0] != '0') {  // 1: one worker per physical core, spread over all cores; 2: the same within NUMA node 0

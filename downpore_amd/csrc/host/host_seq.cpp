@@ -369,7 +369,7 @@ __attribute__((target("avx512f"))) bool touchAvx512(const SeedIndex& ix, const u
 }
 
 TouchFn pickTouch() {
-    if (const long want = dph_tune("touch_isa", -1); want >= 0) {  // tests: 0 scalar, 1 AVX2, 2 AVX-512 (only what the CPU has)
+    if (const long want = dp_tune("touch_isa", -1); want >= 0) {  // tests: 0 scalar, 1 AVX2, 2 AVX-512 (only what the CPU has)
         if (want >= 2 && __builtin_cpu_supports("avx512f")) return touchAvx512;
         if (want >= 1 && __builtin_cpu_supports("avx2")) return touchAvx2;
         return touchScalar;

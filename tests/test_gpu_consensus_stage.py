@@ -16,7 +16,7 @@ from tests import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
 
-#: DP_CONS_LAYOUTS settings (None: unset) - read per call
+#: DP_CONS_LAYOUTS settings (None: unset)
 SETTINGS = [None, "nosmall,nohuge", "nosmall,huge", "huge", "eager,nohuge"]
 LAYOUT_ID = {"small": 0, "large": 1, "huge": 2}
 
@@ -65,8 +65,8 @@ def _records(out, g):
     return np.stack([r[f].astype(np.int64) for f in CC.PAF_FIELDS], axis=1) if len(r) else np.zeros((0, 10), dtype=np.int64)
 
 
-def _check(c, out, layouts):
-    """Every window of one call against the oracle; returns the windows left to the host."""
+def _check(c, out, layouts, forced=()):
+    """Every window of one call against the oracle; returns the windows left to the host (forced: windows a test hook sends there)."""
     gms = out["groups"]
     assert len(gms) == c.n_windows
     assert set(np.unique(gms["flag"]).tolist()) <= {0, 1}
@@ -77,7 +77,7 @@ def _check(c, out, layouts):
     for g in sorted(left):
         # (the oracle ran this round to the end: none of its windows is a state the reference would panic in)
         assert int(gms["reserved"][g]) in CC.CAPACITY_REASONS, (c.name, last, g, int(gms["reserved"][g]), c.stats[g].tolist())
-    want_left = {g for g, why in enumerate(beyond) if why}
+    want_left = {g for g, why in enumerate(beyond) if why} | set(forced)
     assert left == want_left, (c.name, last, "left without a capacity exceeded:", [(g, c.stats[g].tolist(), int(c.query_seeds[g])) for g in sorted(left - want_left)][:5],
                                "computed beyond a capacity:", [(g, beyond[g]) for g in sorted(want_left - left)][:5])
     assert np.array_equal(gms["n_matches"], c.stats[:, 0])
@@ -162,6 +162,35 @@ def test_ordinary_round_leaves_no_window_to_the_host(ctx, monkeypatch):
     out, layouts = _round(ctx, c, monkeypatch, "huge")
     assert layouts[-1] == "huge" and not (out["groups"]["flag"] != 0).any()
     assert int(out["groups"]["n_lines"].sum()) == sum(len(ls) for ls in c.lines) == 5674
+
+
+def test_cons_flag_every_is_read_by_every_call(ctx, monkeypatch):
+    """DP_TUNE=cons_flag_every between three calls of one process, on the module's context, under one layout setting, on the case with
+    the fewest reads.  Unset: the windows left to the host are the ones the oracle's numbers say the last layout cannot hold.  =2: every
+    window with g % 2 == 0 that builds a consensus at all is left to the host as well (consensus_full_kernel: the hook sits behind the
+    exit of the windows with fewer than two matches, which no path builds a consensus for), the odd windows are left exactly as before,
+    and every window that is not left still equals the oracle.  Unset again: the first call's output."""
+    c = CC.oracle_case("deep")
+    assert c.n_windows >= 4
+    _load(ctx, c)
+    monkeypatch.delenv("DP_TUNE", raising=False)
+    first, layouts = _round(ctx, c, monkeypatch, "huge")
+    left = _check(c, first, layouts)
+    assert left == {g for g, why in enumerate(CC.beyond(c, "huge")) if why}
+    forced = {g for g in range(0, c.n_windows, 2) if c.stats[g, 0] >= 2}
+    assert len(forced - left) >= 2 and any(g % 2 == 1 and g not in left and c.stats[g, 0] >= 2 for g in range(c.n_windows))
+    monkeypatch.setenv("DP_TUNE", "cons_flag_every=2")
+    second, layouts2 = _round(ctx, c, monkeypatch, "huge")
+    assert layouts2 == layouts
+    left2 = _check(c, second, layouts2, forced)
+    assert left2 == left | forced and forced <= left2
+    assert {g for g in left2 if g % 2} == {g for g in left if g % 2}
+    monkeypatch.delenv("DP_TUNE")
+    third, layouts3 = _round(ctx, c, monkeypatch, "huge")
+    assert layouts3 == layouts and _check(c, third, layouts3) == left
+    assert np.array_equal(third["groups"], first["groups"])
+    for g in range(c.n_windows):
+        assert np.array_equal(_records(third, g), _records(first, g)), g
 
 
 def test_huge_layout_follows_the_first_window_left_to_the_host(monkeypatch):

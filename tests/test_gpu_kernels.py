@@ -495,6 +495,36 @@ def test_matches_reference_test2sharedids_vectors(ctx):
         assert out["cand"].tolist() == want, (min_count,)
 
 
+@pytest.mark.parametrize("M", [500, 2 * 64 * 64 + 100])
+def test_query_split_is_read_by_every_query_stage(ctx, monkeypatch, M):
+    """DP_TUNE=query_split between three dp_query_candidates calls of one process, on the 20 sets over 500 ids of the test above (eight
+    candidate words) and on as many sets over 8292 ids (130 words).  What the values select (dp_query_stage, query_kernel):
+      unset (0) and 1  one workgroup per query; the rows are short (W + SW <= 1024 words), so the query kernel clears its query's
+                       candidate and set rows itself and the launch in front of it only fetches the upload block;
+      2                two workgroups per query, the query's words dealt to them in 64-word pieces round robin (500 ids: the second
+                       workgroup has no piece; 8292 ids: pieces 0 and 2 against piece 1), no workgroup clears its own rows: the
+                       launch in front clears all four regions.
+    minCount 16 of 20 sets: the light kernel and the 16-ladder's heavy variant both run.  The candidates are those of the unset call
+    every time, and the known answer."""
+    k = 10
+    ctx.upload_reads(np.frombuffer(b"ACGT" * 30, dtype=np.uint8), np.array([0, 120], dtype=np.int64))
+    counts = np.array([16 if i % 7 == 0 else 8 if i % 5 == 0 else 4 if i % 3 == 0 else 2 if i % 2 == 0 else 0 for i in range(M)])
+    _index_from_sets(ctx, k, [[j < counts[i] for i in range(M)] for j in range(20)])
+    qs, qo = _all_seed_query(20)
+    outs = []
+    for tune in (None, "query_split=1", "query_split=2"):
+        if tune is None:
+            monkeypatch.delenv("DP_TUNE", raising=False)
+        else:
+            monkeypatch.setenv("DP_TUNE", tune)
+        outs.append(ctx.query_candidates(qs, qo, 0.8))
+    assert outs[0]["cand"].tolist() == [i for i in range(M) if counts[i] >= 16]
+    assert outs[0]["meta"][0, :2].tolist() == [20, 16]
+    for out in outs[1:]:
+        for f in ("cand_off", "cand", "meta"):
+            assert np.array_equal(out[f], outs[0][f]), f
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_matches_all_ladder_regimes_vs_oracle(ctx, seed):
     """Matches -> GetSharedIDs(fast=true) for every threshold regime (<=1, 2-8 exact, 9-12 -> 8, 13-16 exact incl. the
