@@ -107,6 +107,7 @@ inline constexpr Setting kSettings[] = {
     {DEBUG, "cons", CREATE, "per-window records of the consensus kernel"},
     {DEBUG, "cons_why", CREATE, "why a window was left to the host path"},
     {DEBUG, "chain_prof", CREATE, "the chaining stage's per-wave phase timers (make PROF=1)"},
+    {DEBUG, "chain_paths", CALL, "the chaining stage records which kernel and which path made every pair final (tests: dp_debug_chain_paths)"},
     {DEBUG, "map_prof", CREATE, "the map kernel's phase timers (make PROF=1)"},
     {DEBUG, "planner", CREATE, "plans as they are computed and fetched"},
     {DEBUG, "start", CREATE, "a job's first twelve rounds, in ms since the end of its set-up"},

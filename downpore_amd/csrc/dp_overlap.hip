@@ -1550,8 +1550,25 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
     int32_t* const aRed = spill ? spill : L.aRed;
     int32_t* const aMap = spill ? spill + maxLength + 2 : L.aMap;
     const int redCap = spill ? maxLength + 2 : 512;
-    int nNodes = 0;
+    // Chain links: a chain owns its links (an extension replaces the chain's head, a new chain starts a list of its own), so the links
+    // of a chain the reference hands back to its pool (removeOpenState, a chain shorter than minMatches) go to a free list and are
+    // used again.  The links in use are then never more than the reference's live states, and a target of 65 535 seeds that opens
+    // and drops a chain at every event - 66 032 links made - needs no more of the pool than its 500 open chains.
+    int nNodes = 0, freeNode = -1;
     int live = 0;
+#define NODE_ALLOC(idx_)                                                           \
+    {                                                                              \
+        if (freeNode >= 0) {                                                       \
+            idx_ = freeNode;                                                       \
+            freeNode = node_get(L, nodes, freeNode).prev;                          \
+        } else {                                                                   \
+            if (nNodes >= (int)C_NODES) {                                          \
+                *err |= 8;                                                         \
+                return 0;                                                          \
+            }                                                                      \
+            idx_ = nNodes++;                                                       \
+        }                                                                          \
+    }
     // prepareInitial :341-388
     int maxAIndex = aN - minMatches * 2 + 1;
     int aLen = 0, offset = -k, startSize = 0, prevSeedA = -1;
@@ -1622,6 +1639,15 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
             resultsSize++;                                                         \
         } else {                                                                   \
             live -= sl_;                                                           \
+            int tail_ = sn_;                                                       \
+            CNode tn_ = node_get(L, nodes, tail_);                                 \
+            while (tn_.prev >= 0) {                                                \
+                tail_ = tn_.prev;                                                  \
+                tn_ = node_get(L, nodes, tail_);                                   \
+            }                                                                      \
+            tn_.prev = freeNode;                                                   \
+            node_put(L, nodes, tail_, tn_);                                        \
+            freeNode = sn_;                                                        \
         }                                                                          \
     }
 
@@ -1667,19 +1693,17 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
                 for (int j = aGapIndex; j < aRedLen && g <= maxGap; j += 2) {
                     if (aRed[j] == bSeed) {
                         found = j;
-                        if (nNodes >= (int)C_NODES) {
-                            *err |= 8;
-                            return 0;
-                        }
                         if (++live > C_POOLSTATES) {
                             *err |= 2;
                             return 0;
                         }
+                        int ni;
+                        NODE_ALLOC(ni)
                         CNode nd;
                         nd.a = (uint16_t)aMap[j / 2];
                         nd.b = (uint16_t)(bIndex / 2);
                         nd.prev = L.o_node[i];
-                        node_put(L, nodes, nNodes, nd);
+                        node_put(L, nodes, ni, nd);
                         const int nl = L.o_len[i] + 1;
                         L.o_aPos[i] = j;
                         L.o_bPos[i] = bIndex;
@@ -1687,7 +1711,7 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
                         L.o_aGap[i] = aRed[j + 1];
                         L.o_bGap[i] = bSeg[bIndex + 1];
                         L.o_len[i] = nl;
-                        L.o_node[i] = nNodes++;
+                        L.o_node[i] = ni;
                         if ((nl * 2) / 3 > minMatches) {
                             minMatches = (nl * 2) / 3;
                             maxBIndex = bN - minMatches * 2 + 1;
@@ -1719,26 +1743,24 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
                         }
                     }
                     if (found == aPos || openSize >= C_OPEN) continue;
-                    if (nNodes >= (int)C_NODES) {
-                        *err |= 8;
-                        return 0;
-                    }
                     if (++live > C_POOLSTATES) {
                         *err |= 2;
                         return 0;
                     }
+                    int ni;
+                    NODE_ALLOC(ni)
                     CNode nd;
                     nd.a = (uint16_t)aMap[i];
                     nd.b = (uint16_t)(bIndex / 2);
                     nd.prev = -1;
-                    node_put(L, nodes, nNodes, nd);
+                    node_put(L, nodes, ni, nd);
                     L.o_aPos[openSize] = aPos;
                     L.o_bPos[openSize] = bIndex;
                     L.o_aGapIndex[openSize] = aPos + 2;
                     L.o_aGap[openSize] = aRed[aPos + 1];
                     L.o_bGap[openSize] = bSeg[bIndex + 1];
                     L.o_len[openSize] = 1;
-                    L.o_node[openSize] = nNodes++;
+                    L.o_node[openSize] = ni;
                     openSize++;
                 }
             }
@@ -1758,6 +1780,7 @@ __device__ int pairwise_align(const int32_t* aSeg, int aN, const int32_t* bSeg, 
         }
     }
 #undef REMOVE_OPEN
+#undef NODE_ALLOC
     *resNode = firstNode;
     return resultsSize ? firstLen : 0;
 }
@@ -2488,8 +2511,14 @@ struct PSpec {
     int32_t c;    // CountIntersectionTo result of the pair (-1: not computed yet)
     int32_t mm;   // minMatches the proposal below was chained with (-1: none)
     int32_t len;  // its chain length (pairs in the pair's scratch column)
-    uint32_t pad;
+    uint32_t pad; // DP_DEBUG=chain_paths (tests): how the pair became final, the CPATH_ bits below; 0 otherwise
 };
+// PSpec.pad under DP_DEBUG=chain_paths (dp_debug_chain_paths hands it out; include/downpore_hip.h documents the same bits)
+#define CPATH_TIER 3u       // chain_pair's usedTier: 0 one lane from global memory (prep == 2), 1 reg, 2 lds, 3 one lane (not staged)
+#define CPATH_SLIM 4u       // chained on the slim layout
+#define CPATH_CHAINED 8u    // the pair's final result came out of chain_pair (c >= minMatches); the two fields above are its
+#define CPATH_MARKED 16u    // an earlier slim pass had marked the pair for the full layout (mm == -2)
+#define CPATH_KERNEL(x_) ((uint32_t)(x_) << 8)  // who made it final: 1 walk 0, 2 + n resolve after pass n, 15 the final walk
 struct QState {
     int32_t mm;      // minMatches in force for the query's next candidate
     uint32_t next;   // rank of the first candidate that is not final yet
@@ -2527,6 +2556,7 @@ struct ChainArgs {
     uint32_t int_cap;
     uint32_t* cursor;    // [0] packed ints used, [2] error bits, [3] overflow flag, [8 + pass] "a query is open" flags, [16..19] totals, [24 + 2 * pass + (q & 1)], pass 0 / 1: pairs left open by the pass's resolve step, [32 ..] 64 shards of the algorithmic bytes (u64)
     int walk_always;      // DP_CHAIN_PERFECT=0 (tests): no pair takes the perfect-chain shortcut of wave_chain_reg
+    int paths;            // DP_DEBUG=chain_paths (tests): PSpec.pad of every pair says how it became final (CPATH_)
     int pack;             // 1: final chains are copied into ma/mb, densely (what a host fetch wants); 0: they stay where they were
                           // chained - the pair's scratch column - and the record's offset points there (ma = sa, mb = sb for the
                           // device consumers; dp_fetch_overlaps packs them then, should a host consumer turn up)
@@ -2603,7 +2633,7 @@ template <class LW>
 __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, const int32_t* __restrict__ aSeg, int aN, bool aStaged,
                           const u64* qs, const u64* __restrict__ qset, uint32_t t, int minMatches, int32_t* __restrict__ ca,
                           int32_t* __restrict__ cb, bool haveAMask = false, u64 aMask = 0, const dp_seq_ref* rPre = nullptr,
-                          ChainProf* cp = nullptr) {
+                          ChainProf* cp = nullptr, uint32_t* tierOut = nullptr) {
     const int lane = dp_lane();
     // (profiling build: ticks of: b staged + flags, initial positions, b events + chain walk, result out)
 #define CP_TICK(f_)                                                  \
@@ -2690,6 +2720,7 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
         }
     }
     CP_TICK(walk)
+    if (tierOut) *tierOut = (uint32_t)usedTier;
     if (lane == 0 && err) atomicOr(&A.cursor[2], err);
     if (err) resLen = 0;
     if (resLen > 0) {
@@ -2816,6 +2847,7 @@ struct chain_walk_kernel {
             const int spmm = RFL(sp.mm);
             int len;
             bool chained = false;
+            uint32_t tier = 0;
             bool haveMask = false;
             u64 aMask = 0;
             if (c < 0) {
@@ -2839,7 +2871,7 @@ struct chain_walk_kernel {
                     atomicAdd(&A.cursor[20], 1u);
                     if (spmm == -2) atomicAdd(&A.cursor[21], 1u);
                 }
-                len = chain_pair(L, nodes, A, aSeg, aN, aStaged, qs, qset, t, mm, ca, cb, haveMask, aMask, nullptr, wprof ? &pf : (ChainProf*)nullptr);
+                len = chain_pair(L, nodes, A, aSeg, aN, aStaged, qs, qset, t, mm, ca, cb, haveMask, aMask, nullptr, wprof ? &pf : (ChainProf*)nullptr, &tier);
                 if (SLIM && len < 0) {  // needs the full layout: the query stays open at this pair (marked: slim passes skip it)
                     if (lane == 0) {
                         PSpec o = {c, -2, 0, 0};
@@ -2851,6 +2883,9 @@ struct chain_walk_kernel {
                 pf.chained++;
                 WK_TICK(pair)
             }
+            if (A.paths && lane == 0)  // (a proposal that is taken keeps what the pass that made it wrote)
+                A.pspec[p].pad = (chained ? CPATH_CHAINED | (SLIM ? CPATH_SLIM : 0u) | tier : c >= mm ? sp.pad : 0u) | (spmm == -2 ? CPATH_MARKED : 0u) |
+                                 CPATH_KERNEL(mode == 0 ? 1 : 15);
             algBytes += 16ull * A.SW;
             if (c >= mm) algBytes += 4ull * (u64)(aN + (int)(2 * A.refs[t].n_seeds + 1));
             uint32_t off = 0;
@@ -2975,10 +3010,11 @@ struct chain_spec_kernel {
         }
         SP_TICK(pre)  // prefilter
         int len = 0, pmm = mm;
+        uint32_t tier = 0;
         if (c >= mm) {
             pf.chained++;
             len = chain_pair(L, (CNode*)nullptr, A, aSeg, aN, aStaged, qs, qset, t, mm, A.sa + ib + (u64)i * nSeeds, A.sb + ib + (u64)i * nSeeds,
-                             haveMask, aMask, &rT, (DP_PROFILING && A.prof) ? &pf : (ChainProf*)nullptr);
+                             haveMask, aMask, &rT, (DP_PROFILING && A.prof) ? &pf : (ChainProf*)nullptr, &tier);
             if (len < 0) {  // does not fit the slim layout: no proposal (-2: no slim pass tries again), the final walk chains it
                 len = 0;
                 pmm = -2;
@@ -2986,7 +3022,7 @@ struct chain_spec_kernel {
         }
         SP_TICK(pair)  // chain_pair
         if (lane == 0) {
-            PSpec o = {c, pmm, len, 0};
+            PSpec o = {c, pmm, len, (A.paths && c >= mm && pmm != -2) ? (CPATH_CHAINED | CPATH_SLIM | tier) : 0u};
             A.pspec[p] = o;
         }
         __builtin_amdgcn_wave_barrier();
@@ -3086,6 +3122,7 @@ __device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane) {
             }
             MRec rec = {q, t, hit && room ? myOff : 0u, (uint32_t)wlen};
             A.recs[pb + i] = rec;
+            if (A.paths) A.pspec[pb + i].pad = (((chainedMask >> lane) & 1ull) ? sp.pad : 0u) | CPATH_KERNEL(2 + A.pass);
             algBytes += 16ull * A.SW + 8ull * (u64)wlen;
             if ((chainedMask >> lane) & 1ull) algBytes += 4ull * (u64)(aN + (int)(2 * A.refs[t].n_seeds + 1));
         }
@@ -3332,6 +3369,7 @@ struct FindState {
     uint32_t pair_cap = 0, int_cap = 0;
     uint64_t sint_cap = 0;
     int attempt = 0;
+    bool paths = false;  // DP_DEBUG=chain_paths was set for this stage (dp_debug_chain_paths)
     float chain_ms = 0;
     bool pending = false;
     bool defer_fetch = false;  // the first attempt's read-back rides in the anchors launch of the consensus call (a pending stage)
@@ -3411,6 +3449,8 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
         const bool always_pack = dp_env_tristate("DP_CHAIN_PACK") == 1;
         A.pack = (st.defer_fetch && !always_pack && st.sint_cap < 0xfffffff0ull) ? 0 : 1;
         A.walk_always = dp_env_tristate("DP_CHAIN_PERFECT") == 0 ? 1 : 0;
+        A.paths = dp_debug("chain_paths") ? 1 : 0;
+        st.paths = A.paths != 0;
         ctx->chains_packed = A.pack != 0;
     }
     A.pair_cap = st.pair_cap;
@@ -3589,6 +3629,39 @@ int dp_find_complete(dp_ctx* ctx, bool* reran) {
     }
     return chain_finish(ctx, *st);
 }
+// Test hook (DP_DEBUG=chain_paths): how the context's last dp_find_overlaps dealt with every (query, candidate) pair - see
+// include/downpore_hip.h.  Waits for the context's stream.
+extern "C" int dp_debug_chain_paths(dp_ctx* ctx, uint32_t* out3, uint32_t cap, uint32_t* n_pairs, uint32_t* info4) {
+    if (!ctx || !n_pairs || !info4 || (cap && !out3)) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_debug_chain_paths: bad arguments") : DP_ERR_ARG;
+    const FindState* st = ctx->find_state;
+    if (!st || st->pending) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: no finished dp_find_overlaps on this context");
+    if (!st->paths) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: the stage ran without DP_DEBUG=chain_paths");
+    hipSetDevice(ctx->device);
+    uint64_t tp = 0;
+    memcpy(&tp, &st->cur[16], 8);
+    info4[0] = (uint32_t)st->attempt;
+    info4[1] = (uint32_t)st->passes;
+    info4[2] = st->cur[2];
+    info4[3] = st->pair_cap;
+    *n_pairs = (uint32_t)tp;
+    if (tp > st->pair_cap) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: the last attempt did not fit its buffers");
+    if (tp > cap) return DP_OK;  // (the caller sizes its array by *n_pairs and asks again)
+    DP_HIP(dp_stream_sync(ctx));
+    std::vector<uint32_t> pq(tp), cl(tp);
+    std::vector<PSpec> sp(tp);
+    if (tp) {
+        DP_HIP(hipMemcpy(cl.data(), ctx->d_clist.p, tp * 4, hipMemcpyDeviceToHost));
+        DP_HIP(hipMemcpy(pq.data(), (const uint32_t*)ctx->d_clist.p + st->pair_cap, tp * 4, hipMemcpyDeviceToHost));
+        DP_HIP(hipMemcpy(sp.data(), ctx->d_pspec.p, tp * sizeof(PSpec), hipMemcpyDeviceToHost));
+    }
+    for (uint64_t p = 0; p < tp; p++) {
+        out3[3 * p] = pq[p];
+        out3[3 * p + 1] = cl[p];
+        out3[3 * p + 2] = sp[p].pad;
+    }
+    return DP_OK;
+}
+
 void dp_find_stats(const dp_ctx* ctx, double* query_ms, double* chain_ms, uint64_t* query_bytes, uint64_t* chain_bytes) {
     const FindState* st = ctx->find_state;
     *query_ms = st ? st->query_ms : 0;

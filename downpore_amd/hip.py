@@ -97,7 +97,8 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
-           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan"]
+           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan",
+           "dp_debug_chain_paths"]
 
 _lib = None
 
@@ -408,6 +409,17 @@ class Context:
         if on_device:
             return dict(query_kernel_ms=b.query_kernel_ms, chain_kernel_ms=b.chain_kernel_ms, query_bytes=b.query_bytes,
                         chain_bytes=b.chain_bytes)
+        return self._match_lists(b, want_candidates)
+
+    def fetch_overlaps(self):
+        """dp_fetch_overlaps: the match lists of the last find_overlaps (what that call returns itself unless on_device)"""
+        b = MatchBatch()
+        self.L.dp_fetch_overlaps.argtypes = [C.c_void_p, C.POINTER(MatchBatch)]
+        self._chk(self.L.dp_fetch_overlaps(self.h, C.byref(b)))
+        return self._match_lists(b, False)
+
+    @staticmethod
+    def _match_lists(b, want_candidates):
         nm = b.n_matches
         off = _arr(b.off, nm + 1, np.uint64)
         tot = int(off[-1]) if nm else 0
@@ -421,6 +433,19 @@ class Context:
             res["cand_off"] = co
             res["cand"] = _arr(b.cand, int(co[-1]), np.uint32)
         return res
+
+    def chain_paths(self):
+        """dp_debug_chain_paths (test hook) for the last find_overlaps, which must have run under DP_DEBUG=chain_paths: dict of query,
+        target, path (uint32 per pair, the header's bits), attempts, passes, error_bits, pair_cap."""
+        self.L.dp_debug_chain_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+        n = C.c_uint32(0)
+        info = np.zeros(4, dtype=np.uint32)
+        self._chk(self.L.dp_debug_chain_paths(self.h, None, 0, C.byref(n), info.ctypes.data))
+        out = np.zeros((max(1, n.value), 3), dtype=np.uint32)
+        self._chk(self.L.dp_debug_chain_paths(self.h, out.ctypes.data, n.value, C.byref(n), info.ctypes.data))
+        out = out[:n.value]
+        return dict(query=out[:, 0].copy(), target=out[:, 1].copy(), path=out[:, 2].copy(), attempts=int(info[0]), passes=int(info[1]),
+                    error_bits=int(info[2]), pair_cap=int(info[3]))
 
     # ---- A15 - A17
     def consensus_paf(self, metas, rc_of, k, overlap_size):

@@ -319,6 +319,19 @@ typedef struct {
 DP_API int dp_find_overlaps(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t n_queries,
                      double hit_fraction, int k, uint32_t max_query_len, int want_candidates, dp_match_batch* out);
 
+/* Test hook: which way every (query, candidate) pair of the context's last dp_find_overlaps went.  That call must have run with the
+ * token chain_paths in DP_DEBUG (read per call) and must not be pending.  *n_pairs = the stage's pairs; when cap >= *n_pairs,
+ * out3[3 p ..] = {query, candidate (indexed-sequence index), path} in the stage's pair order (queries ascending, candidates
+ * ascending within a query).  path: bits 0-1 the tier that chained the pair (0 one lane from global memory, 1 reg, 2 lds, 3 one
+ * lane, operands not staged), bit 2 chained on the slim layout, bit 3 the pair's final result came out of a chaining (it passed
+ * the CountIntersectionTo prefilter; bits 0-2 mean nothing without it), bit 4 an earlier pass on the slim layout had marked the
+ * pair for the full one, bits 8-11 the kernel that made the pair final: 1 the first walk, 2 + n the resolve step after proposal
+ * pass n, 15 the final walk, 0 none (the stage ended with an error first).  info4 = {attempts the stage took (more than one: a
+ * buffer was too small and the stage was repeated with larger ones), proposal passes, the stage's error bits (1 reduced buffer,
+ * 2 state pool, 4 results, 8 nodes), pairs the pair buffers held}.  Also valid after a dp_find_overlaps that returned
+ * DP_ERR_CAPACITY. */
+DP_API int dp_debug_chain_paths(dp_ctx* ctx, uint32_t* out3, uint32_t cap, uint32_t* n_pairs, uint32_t* info4);
+
 /* Optional: announces the queries of the round's coming dp_find_overlaps before the index is built (matchWorker's queries are
  * known as soon as the scan is: overlap/overlap.go:200-214 builds them from the scan's output).  The library stages them now
  * and the index build's first launch (dp_index_build_chunked) carries them to the device, so that the query stage starts with

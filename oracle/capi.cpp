@@ -593,4 +593,103 @@ const char* dpo_map_err(void* h, int64_t* n) {
     return ((MapH*)h)->res.err.data();
 }
 
+// ---- the chaining stage on crafted segments (tests/chain_cases.py) ----------------------------------------------------------
+// dpo_pairwise that also fills prof[PairProfile::FIELDS] (aLen, initialSize, bEvents, peakOpen, longestChain, peakLive, popped,
+// resultsSize, minMatches at the end, limit).  A call that hits a reference limit returns -1 with prof filled up to there.
+int dpo_pairwise_profile(const int64_t* aSeg, int64_t aN, const int64_t* bSeg, int64_t bN, int64_t minMatches, int k,
+                         int64_t maxLength, int64_t* outCounts, int64_t* outA, int64_t* outB, int64_t cap, int64_t* nMatches,
+                         int64_t* prof) {
+    PairProfile pp;
+    *nMatches = 0;
+    int rc = guard([&] {
+        Arena ar;
+        SeedSequence* a = mkSeq(ar, aSeg, aN);
+        SeedSequence* b = mkSeq(ar, bSeg, bN);
+        IntSet aSet;
+        for (i64 i = 0; i < a->numSeeds(); i++) aSet.add((u64)a->getSeed(i));
+        IntSet bSet = seedSetLikeIndex(b);
+        SeedAligner al(maxLength);
+        std::vector<SeedMatch> ms = al.pairwiseAlignments(a, b, aSet, bSet, minMatches, k, &pp);
+        flatten(ms, outCounts, outA, outB, cap, nMatches);
+    });
+    pp.store(prof);
+    return rc;
+}
+
+// Overlapper.FindOverlaps (overlap/overlap.go:320-387) over an index of exactly the given sequences: sequence i =
+// idxSegs[idxOff[i] .. idxOff[i + 1]), query j likewise, seeds are seed ids < nSeedIds.  The index is the oracle's SeedIndex filled
+// the way AddSequence + indexSequences fill it; its k-mer tables are not needed (nothing is scanned), so it is made for k = 1 and told k.
+// Fields (dpo_find_segments_field): 0 scalars {limit, limitQuery, limitRank}; 1 candOff, 2 cand; 3 the pair table, PAIR_COLS values per
+// (query, candidate) pair in the loop's order: query, rank, target, c, minMatches, chained, kept, then PairProfile's fields;
+// 4 matchQuery, 5 matchTarget, 6 matchOff, 7 matchA, 8 matchB.
+struct FindSegH {
+    std::vector<std::vector<i64>> f;
+};
+void* dpo_find_overlaps_segments(const int64_t* idxSegs, const int64_t* idxOff, int64_t nIdx, const int64_t* qSegs, const int64_t* qOff,
+                                 int64_t nQ, int64_t nSeedIds, double hitFraction, int k, int64_t maxLength) {
+    FindSegH* h = new FindSegH();
+    int rc = guard([&] {
+        SeedIndex ix(1);
+        ix.seedSize = k;
+        ix.size = nSeedIds;
+        ix.sequenceSets.resize((size_t)nSeedIds);
+        auto checked = [&](const int64_t* seg, int64_t n) {
+            if (n < 1 || (n & 1) == 0) throw std::runtime_error("dpo_find_overlaps_segments: a sequence is [gap, seed, ..., gap]");
+            for (int64_t i = 1; i < n; i += 2)
+                if (seg[i] < 0 || seg[i] >= nSeedIds) throw std::runtime_error("dpo_find_overlaps_segments: seed id out of range");
+            return mkSeq(ix.arena, seg, n);
+        };
+        for (int64_t i = 0; i < nIdx; i++) ix.addSequence(checked(idxSegs + idxOff[i], idxOff[i + 1] - idxOff[i]));
+        ix.indexSequences();
+        std::vector<SeedQuery> queries((size_t)nQ);
+        for (int64_t j = 0; j < nQ; j++) {
+            queries[(size_t)j].ID = j;
+            queries[(size_t)j].Query = checked(qSegs + qOff[j], qOff[j + 1] - qOff[j]);
+        }
+        Overlapper lap(ix, 0, maxLength * 2, 0, hitFraction);  // (the aligner's maxLength is overlap / 2, overlap.go:349)
+        FindTrace tr;
+        std::vector<std::unique_ptr<SeedMatch>> ms = lap.findOverlaps(queries, &tr);
+        h->f.assign(9, {});
+        h->f[0] = {tr.limit, tr.limitQuery, tr.limitRank};
+        h->f[1].push_back(0);
+        for (auto& c : tr.candidates) {
+            for (u64 x : c) h->f[2].push_back((i64)x);
+            h->f[1].push_back((i64)h->f[2].size());
+        }
+        for (auto& p : tr.pairs) {
+            const i64 head[7] = {p.query, p.rank, p.target, p.c, p.minMatches, p.chained ? 1 : 0, p.kept};
+            h->f[3].insert(h->f[3].end(), head, head + 7);
+            i64 pf[PairProfile::FIELDS];
+            p.profile.store(pf);
+            h->f[3].insert(h->f[3].end(), pf, pf + PairProfile::FIELDS);
+        }
+        h->f[6].push_back(0);
+        for (auto& m : ms) {
+            h->f[4].push_back(m->QueryID);
+            i64 target = -1;
+            for (size_t i = 0; i < ix.sequences.size(); i++)
+                if (ix.sequences[i] == m->SeqB) target = (i64)i;
+            h->f[5].push_back(target);
+            h->f[7].insert(h->f[7].end(), m->MatchA.begin(), m->MatchA.end());
+            h->f[8].insert(h->f[8].end(), m->MatchB.begin(), m->MatchB.end());
+            h->f[6].push_back((i64)h->f[7].size());
+        }
+    });
+    if (rc) {
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+const int64_t* dpo_find_segments_field(void* h, int field, int64_t* n) {
+    FindSegH* f = (FindSegH*)h;
+    if (field < 0 || field >= (int)f->f.size()) {
+        *n = -1;
+        return nullptr;
+    }
+    *n = (int64_t)f->f[(size_t)field].size();
+    return f->f[(size_t)field].data();
+}
+void dpo_find_segments_free(void* h) { delete (FindSegH*)h; }
+
 }  // extern "C"

@@ -179,13 +179,34 @@ void smReverseComplement(SeedMatch& m, int k, SeedIndex& index);               /
 bool smGetBasesCovered(const SeedMatch& m, int k, i64* a, i64* b);             // :830-858; false = reference panics
 void smGetBaseIndex(const SeedMatch& m, i64 aIndex, int k, i64* index, i64* bases, i64* distance);  // :1190-1237
 
+// What one PairwiseAlignments call went through (tests: which capacity of a device layout the pair needs).  Counters only.
+struct PairProfile {
+    enum { NONE = 0, REDUCED_BUFFER = 1, STATE_POOL = 2, RESULTS = 4 };  // the limit that made the call throw
+    i64 aLen = 0;          // kept seeds of a (ints of the reduced a = 2 * aLen + 1)
+    i64 initialSize = 0;   // initial positions left after the trim by maxAIndex
+    i64 bEvents = 0;       // b seeds that reach searchMatch
+    i64 peakOpen = 0;      // largest openSize
+    i64 longestChain = 0;  // largest length any state reached
+    i64 peakLive = 0;      // most states out of the pool at once
+    i64 popped = 0;        // states popped after prepareInitial: one per chain link
+    i64 resultsSize = 0;
+    i64 minMatches = 0;    // its value at the end
+    i64 limit = NONE;
+    bool inWalk = false;
+    enum { FIELDS = 10 };
+    void store(i64* out) const {
+        const i64 v[FIELDS] = {aLen, initialSize, bEvents, peakOpen, longestChain, peakLive, popped, resultsSize, minMatches, limit};
+        for (int i = 0; i < FIELDS; i++) out[i] = v[i];
+    }
+};
+
 // seeds/alignment.go:274-616
 struct SeedAligner {
     i64 maxLength;
     explicit SeedAligner(i64 maxLen) : maxLength(maxLen) {}
     // returns matches in the reference's (reversed) order; empty == nil
     std::vector<SeedMatch> pairwiseAlignments(SeedSequence* a, SeedSequence* b, const IntSet& aSet,
-                                              const IntSet& bSet, i64 minMatches, int k);
+                                              const IntSet& bSet, i64 minMatches, int k, PairProfile* prof = nullptr);
 };
 void gapRange(i64 gap, int k, i64* minGap, i64* maxGap);                       // alignment.go:411-424
 
@@ -238,6 +259,21 @@ struct OverlapParams {
     bool himem = true;
     int queryType = 1;  // overlap.QueryEdges (overlap.go:18-21): 1 edges, 2 centre, 4 all, +8 weight edges
 };
+// What findOverlaps did pair by pair (tests).  With a trace, a PairwiseAlignments call that hits a reference limit ends the loop
+// there - limit / limitQuery / limitRank say where - and the matches made before it are returned.
+struct FindTrace {
+    struct Pair {
+        i64 query = 0, rank = 0, target = 0;
+        i64 c = 0;          // CountIntersectionTo(seedSet, minMatches) as returned
+        i64 minMatches = 0; // in force at this pair's turn
+        bool chained = false;
+        i64 kept = 0;       // length of the chain matchWorker kept (0: none)
+        PairProfile profile;
+    };
+    std::vector<std::vector<u64>> candidates;  // per query: Matches()
+    std::vector<Pair> pairs;
+    i64 limit = 0, limitQuery = -1, limitRank = -1;
+};
 struct Overlapper {
     SeedIndex& index;
     i64 chunkSize, overlap, minSeeds;
@@ -248,7 +284,7 @@ struct Overlapper {
                                           const std::vector<PackedSeq>& seqs, int queryType = 1);   // :157
     void chunkAndAdd(SeedSequence* s);                                          // chunkWorker :253-318
     void addSequences(const std::vector<PackedSeq>& seqs);                      // :217
-    std::vector<std::unique_ptr<SeedMatch>> findOverlaps(const std::vector<SeedQuery>& queries);  // :320 + matchWorker :346
+    std::vector<std::unique_ptr<SeedMatch>> findOverlaps(const std::vector<SeedQuery>& queries, FindTrace* trace = nullptr);  // :320 + matchWorker :346
 };
 
 // pieces of overlap.go / combine.go / mapping.go that tests/test_hand_known_answers.py calls on bare numbers (capi.cpp: dpo_hand_*)

@@ -359,21 +359,49 @@ void Overlapper::addSequences(const std::vector<PackedSeq>& seqs) {
 }
 
 // FindOverlaps :320-340 + matchWorker :346-387
-std::vector<std::unique_ptr<SeedMatch>> Overlapper::findOverlaps(const std::vector<SeedQuery>& queries) {
+std::vector<std::unique_ptr<SeedMatch>> Overlapper::findOverlaps(const std::vector<SeedQuery>& queries, FindTrace* trace) {
     std::vector<std::unique_ptr<SeedMatch>> output;
     int k = index.seedSize;
     IntSet seedSet;
     SeedAligner aligner(overlap / 2);
-    for (const auto& q : queries) {
+    for (size_t qi = 0; qi < queries.size(); qi++) {
+        const SeedQuery& q = queries[qi];
         seedSet.clear();
         for (i64 i = 0; i < q.Query->numSeeds(); i++) seedSet.add((u64)q.Query->getSeed(i));
         std::vector<u64> matches = index.matches(q.Query, hitFraction);
         i64 minMatches = (i64)(hitFraction * (double)q.Query->numSeeds() + 0.5);
-        for (u64 match : matches) {
+        if (trace) trace->candidates.push_back(matches);
+        for (size_t rank = 0; rank < matches.size(); rank++) {
+            const u64 match = matches[rank];
             const IntSet& matchSet = index.seedSets[(size_t)match];
-            if (matchSet.countIntersectionTo(seedSet, minMatches) < (u64)minMatches) continue;
+            const u64 shared = matchSet.countIntersectionTo(seedSet, minMatches);
+            FindTrace::Pair* tp = nullptr;
+            if (trace) {
+                trace->pairs.emplace_back();
+                tp = &trace->pairs.back();
+                tp->query = (i64)qi;
+                tp->rank = (i64)rank;
+                tp->target = (i64)match;
+                tp->c = (i64)shared;
+                tp->minMatches = minMatches;
+            }
+            if (shared < (u64)minMatches) continue;
             SeedSequence* m = index.sequences[(size_t)match];
-            std::vector<SeedMatch> sMatches = aligner.pairwiseAlignments(q.Query, m, seedSet, matchSet, minMatches, k);
+            std::vector<SeedMatch> sMatches;
+            if (tp) {
+                tp->chained = true;
+                try {
+                    sMatches = aligner.pairwiseAlignments(q.Query, m, seedSet, matchSet, minMatches, k, &tp->profile);
+                } catch (const std::runtime_error&) {
+                    if (!tp->profile.limit) throw;
+                    trace->limit = tp->profile.limit;
+                    trace->limitQuery = (i64)qi;
+                    trace->limitRank = (i64)rank;
+                    return output;
+                }
+            } else {
+                sMatches = aligner.pairwiseAlignments(q.Query, m, seedSet, matchSet, minMatches, k);
+            }
             if (!sMatches.empty()) {
                 SeedMatch* best = nullptr;
                 i64 bestCount = 0;  // never updated in the reference (:369-375)
@@ -387,6 +415,7 @@ std::vector<std::unique_ptr<SeedMatch>> Overlapper::findOverlaps(const std::vect
                 best->ReverseComplementQuery = q.ReverseComplement;
                 output.emplace_back(new SeedMatch(std::move(*best)));
                 i64 blen = (i64)output.back()->MatchA.size();
+                if (tp) tp->kept = blen;
                 if (blen * 2 > minMatches * 3) minMatches = (blen * 2) / 3;
             }
         }

@@ -470,8 +470,13 @@ struct PairState {  // :286-295
 };
 }  // namespace
 
+// prof (tests): counters of this call, written as it goes - they are observers only, no branch reads them - so a call that throws
+// leaves what it had reached and which limit ended it
 std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequence* b, const IntSet& aSet,
-                                                       const IntSet& bSet, i64 minMatches, int k) {
+                                                       const IntSet& bSet, i64 minMatches, int k, PairProfile* prof) {
+    PairProfile unused;
+    PairProfile& P = prof ? *prof : unused;
+    P = PairProfile();
     const i64* aSegments = a->seg();
     const i64 aN = (i64)a->n;
     const i64* bSegments = b->seg();
@@ -482,9 +487,14 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
     std::vector<std::unique_ptr<PairState>> pool;
     size_t live = 0;
     auto popState = [&]() -> PairState* {
-        if (live >= POOL) throw std::runtime_error("oracle: seedAligner state pool exhausted (reference would panic)");
+        if (live >= POOL) {
+            P.limit = PairProfile::STATE_POOL;
+            throw std::runtime_error("oracle: seedAligner state pool exhausted (reference would panic)");
+        }
         pool.emplace_back(new PairState());
         live++;
+        if ((i64)live > P.peakLive) P.peakLive = (i64)live;
+        if (P.inWalk) P.popped++;
         return pool.back().get();
     };
     auto pushState = [&](PairState*) { live--; };
@@ -509,8 +519,10 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
         }
         prevSeedA = aSeed;
         offset += aSegments[i - 1] + k;
-        if ((size_t)(aLen * 2 + 1) >= redCap || (size_t)aLen >= mapCap)
+        if ((size_t)(aLen * 2 + 1) >= redCap || (size_t)aLen >= mapCap) {
+            P.limit = PairProfile::REDUCED_BUFFER;
             throw std::runtime_error("oracle: seedAligner reduced buffer overflow (reference would panic)");
+        }
         aRedBuf[(size_t)(aLen * 2)] = offset;
         aRedBuf[(size_t)(aLen * 2 + 1)] = aSeed;
         aMapping[(size_t)aLen] = i / 2;
@@ -524,14 +536,21 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
             startSize++;
         }
         aLen++;
+        P.aLen = aLen;
     }
-    if ((size_t)(aLen * 2) >= redCap) throw std::runtime_error("oracle: seedAligner reduced buffer overflow (reference would panic)");
+    if ((size_t)(aLen * 2) >= redCap) {
+        P.limit = PairProfile::REDUCED_BUFFER;
+        throw std::runtime_error("oracle: seedAligner reduced buffer overflow (reference would panic)");
+    }
     aRedBuf[(size_t)(aLen * 2)] = 0;
     while (startSize > 0 && initials[(size_t)(startSize - 1)]->aPos > maxAIndex) {
         startSize--;
         pushState(initials[(size_t)startSize]);
     }
     const i64 initialSize = startSize;
+    P.initialSize = initialSize;
+    P.inWalk = true;
+    P.minMatches = minMatches;
     const i64* aRed = aRedBuf.data();
     const i64 aRedLen = aLen * 2 + 1;
 
@@ -544,8 +563,13 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
         openSize--;
         if (s->length >= minMatches) {
             if ((s->length * 2) / 3 > minMatches) minMatches = (s->length * 2) / 3;
-            if ((size_t)resultsSize >= RESULTS) throw std::runtime_error("oracle: seedAligner results overflow (reference would panic)");
+            P.minMatches = minMatches;
+            if ((size_t)resultsSize >= RESULTS) {
+                P.limit = PairProfile::RESULTS;
+                throw std::runtime_error("oracle: seedAligner results overflow (reference would panic)");
+            }
             results[(size_t)resultsSize++] = s;
+            P.resultsSize = resultsSize;
         } else {
             for (PairState* p = s; p != nullptr; p = p->prev) pushState(p);
         }
@@ -566,6 +590,7 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
             continue;
         }
         prevSeed = bSeed;
+        P.bEvents++;
         i64 found = -1;
         // searchMatch: :465-547 (the "dominated chain" block :499-514 is dead code: found is always -1 there)
         for (i64 i = openSize - 1; i >= 0; i--) {
@@ -599,9 +624,11 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
                         ns->bGap = bSegments[bIndex + 1];
                         ns->length = s->length + 1;
                         open[(size_t)i] = ns;
+                        if (ns->length > P.longestChain) P.longestChain = ns->length;
                         if ((ns->length * 2) / 3 > minMatches) {
                             minMatches = (ns->length * 2) / 3;
                             maxBIndex = bN - minMatches * 2 + 1;
+                            P.minMatches = minMatches;
                         }
                         extended = true;
                         break;
@@ -640,6 +667,8 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
                     ns->length = 1;
                     ns->prev = nullptr;
                     open[(size_t)openSize++] = ns;
+                    if (openSize > P.peakOpen) P.peakOpen = openSize;
+                    if (P.longestChain < 1) P.longestChain = 1;
                 }
             }
         }
@@ -647,8 +676,12 @@ std::vector<SeedMatch> SeedAligner::pairwiseAlignments(SeedSequence* a, SeedSequ
     for (i64 i = 0; i < openSize; i++) {  // :597-604
         PairState* s = open[(size_t)i];
         if (s->length >= minMatches) {
-            if ((size_t)resultsSize >= RESULTS) throw std::runtime_error("oracle: seedAligner results overflow (reference would panic)");
+            if ((size_t)resultsSize >= RESULTS) {
+                P.limit = PairProfile::RESULTS;
+                throw std::runtime_error("oracle: seedAligner results overflow (reference would panic)");
+            }
             results[(size_t)resultsSize++] = s;
+            P.resultsSize = resultsSize;
         }
     }
     std::vector<SeedMatch> out;

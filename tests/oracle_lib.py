@@ -304,13 +304,13 @@ def soft_union(which, words):
     return out
 
 
-def _matches(fn, *args):
+def _matches(fn, *args, tail=()):
     cap = 1 << 16
     counts = np.zeros(1024, dtype=np.int64)
     a = np.zeros(cap, dtype=np.int64)
     b = np.zeros(cap, dtype=np.int64)
     n = C.c_int64(0)
-    rc = fn(*args, ptr(counts, i64p), ptr(a, i64p), ptr(b, i64p), cap, C.byref(n))
+    rc = fn(*args, ptr(counts, i64p), ptr(a, i64p), ptr(b, i64p), cap, C.byref(n), *tail)
     if rc != 0:
         raise RuntimeError(lib().dpo_last_error().decode())
     out = []
@@ -326,6 +326,68 @@ def pairwise(a_seg, b_seg, min_matches, k, max_length=500):
     a = np.ascontiguousarray(a_seg, dtype=np.int64)
     b = np.ascontiguousarray(b_seg, dtype=np.int64)
     return _matches(lib().dpo_pairwise, ptr(a, i64p), len(a), ptr(b, i64p), len(b), min_matches, k, max_length)
+
+
+#: dpo_pairwise_profile's counters (oracle.hpp PairProfile); limit: 0 none, 1 reduced buffer, 2 state pool, 4 results
+PROFILE_FIELDS = ("aLen", "initialSize", "bEvents", "peakOpen", "longestChain", "peakLive", "popped", "resultsSize", "minMatches", "limit")
+
+
+def pairwise_profile(a_seg, b_seg, min_matches, k, max_length=500):
+    """-> (matches as pairwise() gives them, or None where the reference would panic; dict of PROFILE_FIELDS)"""
+    L = lib()
+    L.dpo_pairwise_profile.argtypes = [i64p, C.c_int64, i64p, C.c_int64, C.c_int64, C.c_int, C.c_int64, i64p, i64p, i64p, C.c_int64, i64p, i64p]
+    a = np.ascontiguousarray(a_seg, dtype=np.int64)
+    b = np.ascontiguousarray(b_seg, dtype=np.int64)
+    prof = np.zeros(len(PROFILE_FIELDS), dtype=np.int64)
+    try:
+        ms = _matches(L.dpo_pairwise_profile, ptr(a, i64p), len(a), ptr(b, i64p), len(b), min_matches, k, max_length, tail=(ptr(prof, i64p),))
+    except RuntimeError:
+        if not prof[-1]:
+            raise
+        ms = None
+    return ms, dict(zip(PROFILE_FIELDS, (int(x) for x in prof)))
+
+
+PAIR_COLS = ("query", "rank", "target", "c", "mm", "chained", "kept") + PROFILE_FIELDS
+
+
+def find_overlaps_segments(index_seqs, queries, n_seed_ids, hit_fraction, k, max_length):
+    """Overlapper.FindOverlaps over an index of exactly index_seqs (segment arrays [gap, seed id, ..., gap]) for the given queries.
+    -> dict: cand_off, cand (Matches() per query); pairs: int64 [n, len(PAIR_COLS)], one row per (query, candidate) pair the loop
+    reached (c = CountIntersectionTo's value, mm = minMatches in force, chained = PairwiseAlignments was called, kept = length of the
+    chain kept, then the call's profile); query, target, off, match_a, match_b: the matches in emission order; limit, limit_query,
+    limit_rank: the first reference limit hit (0: none) - the loop ends there, as the reference's process would."""
+    L = lib()
+    L.dpo_find_overlaps_segments.restype = C.c_void_p
+    L.dpo_find_overlaps_segments.argtypes = [i64p, i64p, C.c_int64, i64p, i64p, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int64]
+    L.dpo_find_segments_field.restype = i64p
+    L.dpo_find_segments_field.argtypes = [C.c_void_p, C.c_int, i64p]
+    L.dpo_find_segments_free.argtypes = [C.c_void_p]
+
+    def flat(seqs):
+        off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+        data = np.concatenate([np.asarray(s, dtype=np.int64) for s in seqs]) if len(seqs) else np.zeros(0, dtype=np.int64)
+        return np.ascontiguousarray(data), off
+
+    isg, iof = flat(index_seqs)
+    qsg, qof = flat(queries)
+    h = L.dpo_find_overlaps_segments(ptr(isg, i64p), ptr(iof, i64p), len(index_seqs), ptr(qsg, i64p), ptr(qof, i64p), len(queries),
+                                     n_seed_ids, float(hit_fraction), k, max_length)
+    if not h:
+        raise RuntimeError(L.dpo_last_error().decode())
+
+    def field(f):
+        n = C.c_int64(0)
+        p = L.dpo_find_segments_field(h, f, C.byref(n))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value > 0 else np.zeros(0, dtype=np.int64)
+
+    try:
+        sc = field(0)
+        return dict(limit=int(sc[0]), limit_query=int(sc[1]), limit_rank=int(sc[2]), cand_off=field(1), cand=field(2),
+                    pairs=field(3).reshape(-1, len(PAIR_COLS)), query=field(4), target=field(5), off=field(6), match_a=field(7),
+                    match_b=field(8))
+    finally:
+        L.dpo_find_segments_free(h)
 
 
 def match(seq_seg, q_seg, min_match, k):
