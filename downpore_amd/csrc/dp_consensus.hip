@@ -11,7 +11,6 @@
 #include "dp_common.h"
 #include <string>
 
-#include "dp_launch.h"
 
 #define CA_WAVES 4
 #define CA_CAP 6144  // ints of one group staged in LDS
@@ -433,9 +432,7 @@ struct ConsFullArgs {
 };
 
 template <int TIER>
-struct consensus_full_kernel {
-    enum { THREADS = 64 };
-    static __device__ void run(const ConsFullArgs A) {
+__device__ void consensus_full_body(const ConsFullArgs A) {
     constexpr bool SMALL = TIER == 0;
     typedef CFWaveT<TIER> LW;
     typedef typename LW::C CF;
@@ -1323,7 +1320,13 @@ struct consensus_full_kernel {
     }
 #undef CF_NOFIT
 }
-};
+// (the body is a function of its own on purpose: it takes its own copy of A, as it always has.  With the body in the kernel itself
+// the compiler allocated differently - 78 scalar registers spilled instead of 63 at TIER 0, 20 more VGPRs in every tier - and the
+// kernel measured 4.5 % slower: profiles/launch_wrapper_removed_resources.txt)
+template <int TIER>
+__global__ __launch_bounds__(64) void consensus_full_kernel(const ConsFullArgs A) {
+    consensus_full_body<TIER>(A);
+}
 
 // Device consensus of the round whose chaining stage (dp_find_overlaps) last ran on this context.
 int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs, const int32_t* rc_of, uint32_t n_seeds, int k,
@@ -1436,7 +1439,7 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
         };
         if (use_small) {
             stage(false);
-            dp_launch<consensus_full_kernel<0>>(ctx, dim3(std::min<uint32_t>(ng, 4096)), dim3(64), A);
+            hipLaunchKernelGGL((consensus_full_kernel<0>), dim3(std::min<uint32_t>(ng, 4096)), dim3(64), 0, ctx->stream, A);
         }
         // The large layout behind the small one nearly always finds its list empty (config 2: a window in a few hundred rounds) and
         // still was a launch of 4 us alone, 12 us under five slots, in every round: it is launched at once only while the context's
@@ -1444,11 +1447,13 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
         lazy_large = use_small && !use_huge && ctx->cons_large_rounds == 0 && !lazy_off;
         if (!lazy_large) {
             stage(!use_huge);
-            dp_launch<consensus_full_kernel<1>>(ctx, dim3(std::min<uint32_t>(ng, use_small ? 96u : 4096u)), dim3(64), A);
+            hipLaunchKernelGGL((consensus_full_kernel<1>), dim3(std::min<uint32_t>(ng, use_small ? 96u : 4096u)), dim3(64), 0, ctx->stream,
+                               A);
             if (use_huge) {
                 stage(true);
                 // (144 KB of LDS per wave: one per CU; behind the small + large layouts it mostly finds its list short or empty)
-                dp_launch<consensus_full_kernel<2>>(ctx, dim3(std::min<uint32_t>(ng, use_small ? 64u : 256u)), dim3(64), A);
+                hipLaunchKernelGGL((consensus_full_kernel<2>), dim3(std::min<uint32_t>(ng, use_small ? 64u : 256u)), dim3(64), 0,
+                                   ctx->stream, A);
             }
         }
     }
@@ -1466,7 +1471,7 @@ int dp_consensus_paf_impl(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_seqs
             A.copy_nseq = false;
             A.out_count = nullptr;
             A.out_list = nullptr;
-            dp_launch<consensus_full_kernel<1>>(ctx, dim3(std::min<uint32_t>(ng, 96u)), dim3(64), A);
+            hipLaunchKernelGGL((consensus_full_kernel<1>), dim3(std::min<uint32_t>(ng, 96u)), dim3(64), 0, ctx->stream, A);
             DP_HIP(hipGetLastError());
             DP_HIP(dp_stream_sync(ctx));
         }

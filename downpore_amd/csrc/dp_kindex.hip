@@ -13,7 +13,6 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "dp_common.h"
-#include "dp_launch.h"
 
 struct dp_kindex {
     std::mutex mu;
@@ -388,12 +387,10 @@ __global__ void kidx_link_extra(const dp_scan_item* __restrict__ items, uint32_t
 }
 // start of a round's counting step in one launch: the work area (fill cursors, tile status, ticket, hit slots), the item
 // counters and the totals go to zero, and the extra items are linked to their reads (head[] is all zero between calls)
-struct kidx_prepare {
-    enum { THREADS = 256 };
-    static __device__ void run(uint32_t* __restrict__ work, uint32_t n_work, uint32_t* __restrict__ counts, uint32_t n_counts,
-                             uint32_t* __restrict__ totals16, dp_scan_item* __restrict__ items, uint32_t n_read_items,
-                             uint32_t n_extra, uint32_t* __restrict__ head, uint32_t* __restrict__ next,
-                             const dp_scan_item* __restrict__ extra_src) {
+__global__ __launch_bounds__(256) void kidx_prepare(uint32_t* __restrict__ work, uint32_t n_work, uint32_t* __restrict__ counts,
+                                                    uint32_t n_counts, uint32_t* __restrict__ totals16, dp_scan_item* __restrict__ items,
+                                                    uint32_t n_read_items, uint32_t n_extra, uint32_t* __restrict__ head,
+                                                    uint32_t* __restrict__ next, const dp_scan_item* __restrict__ extra_src) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_work) work[i] = 0;
     if (i < n_counts) counts[i] = 0;
@@ -406,16 +403,12 @@ struct kidx_prepare {
         next[i] = atomicExch(&head[it.read], i + 1);
     }
 }
-};
-struct kidx_unlink_extra {
-    enum { THREADS = 256 };
-    static __device__ void run(const dp_scan_item* __restrict__ items, uint32_t n_read_items, uint32_t n_extra,
-                                  uint32_t* __restrict__ head) {
+__global__ __launch_bounds__(256) void kidx_unlink_extra(const dp_scan_item* __restrict__ items, uint32_t n_read_items, uint32_t n_extra,
+                                                         uint32_t* __restrict__ head) {
     const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_extra) return;
     head[items[n_read_items + e].read] = 0;
 }
-};
 
 #ifdef DP_PROF_BUILD
 #define KX_PROFILING 1
@@ -444,13 +437,12 @@ __device__ __forceinline__ unsigned long long kx_rec(bool x, bool v, uint32_t r,
 }
 
 // the fill pass from records: same thread layout as the count pass (a group's lanes over its stretch), no bucket walk
-struct kidx_fill_rec {
-    enum { THREADS = 256 };
-    static __device__ void run(const KxRec R, uint32_t n_groups, uint32_t lps, const dp_scan_item* __restrict__ items, uint32_t lo,
-                               uint32_t n_read_items, uint32_t min_seeds, const uint32_t* __restrict__ head,
-                               const uint32_t* __restrict__ next, const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
-                               const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs, const uint64_t* __restrict__ totals,
-                               uint64_t seg_cap) {
+__global__ __launch_bounds__(256) void kidx_fill_rec(const KxRec R, uint32_t n_groups, uint32_t lps, const dp_scan_item* __restrict__ items,
+                                                     uint32_t lo, uint32_t n_read_items, uint32_t min_seeds,
+                                                     const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
+                                                     const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
+                                                     const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
+                                                     const uint64_t* __restrict__ totals, uint64_t seg_cap) {
     if (R.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
     const int lane = dp_lane();
     const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -513,30 +505,13 @@ struct kidx_fill_rec {
         }
     }
 }
-};
 
 template <bool FILL>
-struct kidx_walk {
-    enum { THREADS = 256 };
-    // (round 4: a launch may be narrower than its work - `n_waves` wave-sized pieces, walked with the grid's stride: the count
-    // walk's 160 k lanes of dependent random loads and atomics are what slows every other round's kernels, HISTORY.md 5.7)
-    static __device__ void run(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
-                               const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
-                               uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
-                               uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff,
-                               int32_t* __restrict__ segs, unsigned long long* __restrict__ n_hits, uint32_t lps,
-                               unsigned long long* __restrict__ dbg, const KxRec R, uint32_t n_waves) {
-        const uint32_t stride = gridDim.x * (blockDim.x >> 6);
-        for (uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_waves; w += stride)
-            one(w, seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, fillc, segoff, segs, n_hits, lps, dbg, R);
-    }
-    static __device__ void one(const uint32_t w, const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
-                                                 const KxPos pos, const dp_scan_item* __restrict__ items,
-                                                 uint32_t lo, uint32_t hi, uint32_t n_read_items, const uint32_t* __restrict__ head,
-                                                 const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
-                                                 uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff,
-                                                 int32_t* __restrict__ segs, unsigned long long* __restrict__ n_hits, uint32_t lps,
-                                                 unsigned long long* __restrict__ dbg, const KxRec R) {
+__device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
+                              const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi, uint32_t n_read_items,
+                              const uint32_t* __restrict__ head, const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
+                              uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
+                              unsigned long long* __restrict__ n_hits, uint32_t lps, unsigned long long* __restrict__ dbg, const KxRec R) {
     const int lane = dp_lane();
     // DP_DEBUG=kx: when a wave started, had its bucket bounds, its entries, its items, and was done (100 MHz ticks since dbg[15],
     // sums over waves in dbg[0..4], maxima in dbg[5..9], waves in dbg[10])
@@ -685,7 +660,20 @@ struct kidx_walk {
     KX_TICK(4)
 #undef KX_TICK
 }
-};
+// (round 4: a launch may be narrower than its work - `n_waves` wave-sized pieces, walked with the grid's stride: the count
+// walk's 160 k lanes of dependent random loads and atomics are what slows every other round's kernels, HISTORY.md 5.7)
+template <bool FILL>
+__global__ __launch_bounds__(256) void kidx_walk(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
+                                                 const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
+                                                 uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
+                                                 uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
+                                                 const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
+                                                 unsigned long long* __restrict__ n_hits, uint32_t lps, unsigned long long* __restrict__ dbg,
+                                                 const KxRec R, uint32_t n_waves) {
+    const uint32_t stride = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_waves; w += stride)
+        kidx_walk_one<FILL>(w, seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, fillc, segoff, segs, n_hits, lps, dbg, R);
+}
 
 // ---- round 5: the counting step without scattered atomics - hits binned by read range, counted in LDS ---------------------------
 // The count walk of rounds 1 - 4 bumps a counter per hit: 450 k memory-side atomics per config-2 round (10 M in the dense regime),
@@ -726,519 +714,515 @@ __device__ __forceinline__ unsigned long long kxb_rec(uint32_t rib, uint32_t s, 
     return ((unsigned long long)rib << (KXB_SEED_BITS + 24)) | ((unsigned long long)s << 24) | (unsigned long long)(p & 0xffffffu);
 }
 
+// four consecutive bucket entries of one lane: counted (WRITE = false) or written as records (WRITE = true)
+template <bool WRITE>
+__device__ __forceinline__ void kxb_four(const uint64_t e[4], const bool v[4], uint32_t s, const dp_scan_item* __restrict__ items,
+                                         uint32_t lo, uint32_t hi, uint32_t n_read_items, const uint32_t* __restrict__ head,
+                                         const uint32_t* __restrict__ next, uint32_t* __restrict__ counts, const KxBins& B, uint32_t* hist,
+                                         const uint32_t* base, uint32_t* xs) {
+    bool valid[4];
+    uint32_t hd[4];
+    const uint32_t rmask = (1u << B.bshift) - 1u;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t r = (uint32_t)(e[u] >> 32), p = (uint32_t)e[u];
+        const bool in = v[u] && r >= lo && r < hi;
+        if (B.ign) {
+            // (the ignore byte is NOT looked at here: another slot's commit may flag the read between the two passes, and a record
+            // slot that was counted and not written would hold a stale word.  kidx_bin_count applies it, once per read)
+            valid[u] = in;
+            hd[u] = (v[u] && r - B.qlo < B.qspan) ? head[r] : 0u;
+        } else {
+            // (ignored reads carry n_kmers == 0; a top-level read with len % 4 == 0 four k-mers less)
+            valid[u] = in && p < items[in ? r - lo : 0u].n_kmers;
+            hd[u] = v[u] ? head[r] : 0u;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t r = (uint32_t)(e[u] >> 32), p = (uint32_t)e[u];
+        if (valid[u]) {
+            const uint32_t bin = (r - lo) >> B.bshift;
+            if (!WRITE) {
+                atomicAdd(&hist[bin], 1u);
+            } else {
+                const uint32_t b = base[bin];
+                if (b != 0xffffffffu) {
+                    const uint32_t rank = atomicAdd(&hist[bin], 1u);
+                    B.rec[(size_t)bin * B.cap + b + rank] = kxb_rec((r - lo) & rmask, s, p);
+                } else {
+                    atomicAdd(&counts[r - lo], 1u);  // (the bin is full: counted the old way, kidx_bin_count adds its own on top)
+                }
+            }
+        }
+        // the round's extra items on this read (query windows): counted in the first pass, kept as a list in the second - a stretch of
+        // the list per workgroup (xs[0] counts, then ranks; xs[1] = the stretch's start: ONE returning atomic per workgroup - a
+        // returning atomic per hit, 5 k per round on one address, was 40 us of this kernel)
+        for (uint32_t x = hd[u]; x; x = next[x - 1]) {
+            const uint32_t it = n_read_items + x - 1;
+            const dp_scan_item xi = items[it];
+            if (p - xi.start < xi.n_kmers && p >= xi.start) {
+                if (!WRITE) {
+                    atomicAdd(&counts[it], 1u);
+                    atomicAdd(&xs[0], 1u);
+                } else if (xs[1] != 0xffffffffu) {
+                    B.xrec[xs[1] + atomicAdd(&xs[0], 1u)] = make_uint4(it, p - xi.start, s, 0u);
+                }
+            }
+        }
+    }
+}
+// what lies behind a lane's first four entries.  Dense seeds (a wave per quarter bucket): the wave's stride, as ever.  Four seeds per
+// wave: a seed's 16 lanes cover 64 entries per trip - and the kernel is as long as its longest bucket (a repeat's k-mer with a few
+// thousand occurrences was 40+ dependent trips of ONE quarter wave, twice over with two passes): everything beyond a bucket's first
+// 64 entries is walked by the WHOLE wave, 256 entries per trip, one seed of the wave after the other
+template <bool WRITE>
+__device__ __forceinline__ void kxb_tail(uint32_t lps, int lane, uint32_t w, uint32_t s, uint64_t o, uint32_t i0, uint32_t i1,
+                                         uint32_t step, const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
+                                         uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
+                                         uint32_t* __restrict__ counts, const KxBins& B, uint32_t* hist, const uint32_t* base,
+                                         uint32_t* xs) {
+    if (lps == 64) {
+        for (uint32_t ib = i0 + 4 * step; ib < i1; ib += 4 * step) {
+            uint64_t e[4];
+            bool v[4];
+            kx_entry4(pos, o + ib, e);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                v[u] = ib + (uint32_t)u < i1;
+                e[u] = v[u] ? e[u] : 0ull;
+            }
+            kxb_four<WRITE>(e, v, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        }
+        return;
+    }
+    if (!__ballot(i1 > 64u)) return;  // (wave-uniform: no bucket of this wave goes beyond its first trip)
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const uint32_t ng = (uint32_t)__shfl((int)i1, 16 * g, 64);
+        if (ng <= 64u) continue;
+        const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)o, 16 * g, 64), hi32 = (uint32_t)__shfl((int)(uint32_t)(o >> 32), 16 * g, 64);
+        const uint64_t og = ((uint64_t)hi32 << 32) | lo32;
+        const uint32_t sg = w * 4 + (uint32_t)g;
+        for (uint32_t ib = 64u + 4u * (uint32_t)lane; ib < ng; ib += 256u) {
+            uint64_t e[4];
+            bool v[4];
+            kx_entry4(pos, og + ib, e);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                v[u] = ib + (uint32_t)u < ng;
+                e[u] = v[u] ? e[u] : 0ull;
+            }
+            kxb_four<WRITE>(e, v, sg, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        }
+    }
+}
+// One trip per workgroup and reservation - the sparse regime's form (workgroups of up to 8 waves), as it was before the dense regime's
+// trips, table and look-ahead were built into kidx_walk_bin below: those cost the k = 13 walk 20 us a launch (36 -> 56 us under five slots,
+// profiles/r06/k13_against_round5.txt) and buy it nothing - its reservations are one trip long.
+template <int WAVES>
+__device__ void kidx_walk_bin_one_trip(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
+                                       const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
+                                       uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
+                                       uint32_t* __restrict__ counts, unsigned long long* __restrict__ n_hits, uint32_t lps, const KxBins B,
+                                       uint32_t n_waves) {
+    enum { THREADS = 64 * WAVES };
+    __shared__ uint32_t hist[KX_MAXBINS], base[KX_MAXBINS];
+    __shared__ uint32_t xs[2];
+    __shared__ unsigned long long sh_hits;
+    const int lane = dp_lane();
+    const uint32_t stride = gridDim.x * WAVES;
+    // (every wave of a workgroup makes the same number of trips: the barriers below are the workgroup's)
+    for (uint32_t wb = blockIdx.x * WAVES; wb < n_waves; wb += stride) {
+        for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) hist[t] = 0u;
+        if (threadIdx.x == 0) {
+            sh_hits = 0ull;
+            xs[0] = xs[1] = 0u;
+        }
+        __syncthreads();
+        const uint32_t w = wb + (threadIdx.x >> 6);
+        // the groups of kidx_walk: KX_PARTS waves per seed (dense seeds), or four seeds per wave
+        uint32_t s = 0, i0 = 0, i1 = 0, step = 16, gfirst = 0;
+        uint64_t o = 0;
+        bool gleader = false;
+        if (w < n_waves) {
+            if (lps == 64) {
+                s = w / KX_PARTS;
+                if (s < n_seeds) {
+                    const uint32_t part = w % KX_PARTS;
+                    o = off[seeds[s]];
+                    const uint32_t n = (uint32_t)(off[(uint64_t)seeds[s] + 1] - o);
+                    const uint32_t per = (n + KX_PARTS - 1) / KX_PARTS;
+                    gfirst = min(n, part * per);
+                    i0 = part * per + 4u * (uint32_t)lane;
+                    i1 = min(n, part * per + per);
+                    step = 64;
+                    gleader = lane == 0;
+                }
+            } else {
+                s = w * 4 + ((uint32_t)lane >> 4);
+                if (s < n_seeds) {
+                    o = off[seeds[s]];
+                    i0 = 4u * ((uint32_t)lane & 15u);
+                    i1 = (uint32_t)(off[(uint64_t)seeds[s] + 1] - o);
+                    gleader = (lane & 15) == 0;
+                }
+            }
+        }
+        if (gleader && i1 > gfirst) atomicAdd(&sh_hits, (unsigned long long)(i1 - gfirst));
+        // the lane's first four entries stay in registers across the barriers (a seed of config 2 has 20 - 60 entries: for most groups
+        // the first trip is the only one, and the second pass reads nothing); later trips are read again (from the L2)
+        uint64_t e0[4] = {0, 0, 0, 0};
+        bool v0[4] = {false, false, false, false};
+        if (i0 < i1) {
+            kx_entry4(pos, o + i0, e0);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                v0[u] = i0 + (uint32_t)u < i1;
+                e0[u] = v0[u] ? e0[u] : 0ull;
+            }
+            kxb_four<false>(e0, v0, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        }
+        kxb_tail<false>(lps, lane, w, s, o, i0, i1, step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) {
+            const uint32_t c = hist[t];
+            uint32_t b = 0u;
+            if (c) {
+                b = atomicAdd(&B.cursor[t], c);
+                if (b + c > B.cap) {  // (its share of the bin does not fit: the whole share is counted the old way)
+                    // what it reserved below the bin's end stays unwritten: marked, so that kidx_bin_count skips it
+                    for (uint32_t j = b; j < B.cap; j++) B.rec[(size_t)t * B.cap + j] = ~0ull;
+                    b = 0xffffffffu;
+                    B.flags[0] = 1u;
+                }
+            }
+            base[t] = b;
+            hist[t] = 0u;
+        }
+        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
+        if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
+            const uint32_t c = xs[0];
+            uint32_t xb = 0u;
+            if (c) {
+                xb = atomicAdd(B.xcursor, c);
+                if (xb + c > B.xcap) {
+                    xb = 0xffffffffu;
+                    B.flags[0] = 1u;
+                }
+            }
+            xs[1] = xb;
+            xs[0] = 0u;
+        }
+        __syncthreads();
+        if (i0 < i1) kxb_four<true>(e0, v0, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        kxb_tail<true>(lps, lane, w, s, o, i0, i1, step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+        __syncthreads();
+    }
+}
 // WAVES waves per workgroup: more waves = fewer (workgroup, bin) reservations per hit, but a workgroup that is harder to place
 // beside the other rounds' kernels and whose waves all wait at its barriers for the slowest one
-template <int WAVES_>
-struct kidx_walk_bin {
-    enum { WAVES = WAVES_, THREADS = 64 * WAVES_ };
-    // four consecutive bucket entries of one lane: counted (WRITE = false) or written as records (WRITE = true)
-    template <bool WRITE>
-    static __device__ __forceinline__ void four(const uint64_t e[4], const bool v[4], uint32_t s, const dp_scan_item* __restrict__ items,
-                                                uint32_t lo, uint32_t hi, uint32_t n_read_items, const uint32_t* __restrict__ head,
-                                                const uint32_t* __restrict__ next, uint32_t* __restrict__ counts, const KxBins& B,
-                                                uint32_t* hist, const uint32_t* base, uint32_t* xs) {
-        bool valid[4];
-        uint32_t hd[4];
-        const uint32_t rmask = (1u << B.bshift) - 1u;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t r = (uint32_t)(e[u] >> 32), p = (uint32_t)e[u];
-            const bool in = v[u] && r >= lo && r < hi;
-            if (B.ign) {
-                // (the ignore byte is NOT looked at here: another slot's commit may flag the read between the two passes, and a record
-                // slot that was counted and not written would hold a stale word.  kidx_bin_count applies it, once per read)
-                valid[u] = in;
-                hd[u] = (v[u] && r - B.qlo < B.qspan) ? head[r] : 0u;
-            } else {
-                // (ignored reads carry n_kmers == 0; a top-level read with len % 4 == 0 four k-mers less)
-                valid[u] = in && p < items[in ? r - lo : 0u].n_kmers;
-                hd[u] = v[u] ? head[r] : 0u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t r = (uint32_t)(e[u] >> 32), p = (uint32_t)e[u];
-            if (valid[u]) {
-                const uint32_t bin = (r - lo) >> B.bshift;
-                if (!WRITE) {
-                    atomicAdd(&hist[bin], 1u);
-                } else {
-                    const uint32_t b = base[bin];
-                    if (b != 0xffffffffu) {
-                        const uint32_t rank = atomicAdd(&hist[bin], 1u);
-                        B.rec[(size_t)bin * B.cap + b + rank] = kxb_rec((r - lo) & rmask, s, p);
-                    } else {
-                        atomicAdd(&counts[r - lo], 1u);  // (the bin is full: counted the old way, kidx_bin_count adds its own on top)
-                    }
-                }
-            }
-            // the round's extra items on this read (query windows): counted in the first pass, kept as a list in the second - a stretch of
-            // the list per workgroup (xs[0] counts, then ranks; xs[1] = the stretch's start: ONE returning atomic per workgroup - a
-            // returning atomic per hit, 5 k per round on one address, was 40 us of this kernel)
-            for (uint32_t x = hd[u]; x; x = next[x - 1]) {
-                const uint32_t it = n_read_items + x - 1;
-                const dp_scan_item xi = items[it];
-                if (p - xi.start < xi.n_kmers && p >= xi.start) {
-                    if (!WRITE) {
-                        atomicAdd(&counts[it], 1u);
-                        atomicAdd(&xs[0], 1u);
-                    } else if (xs[1] != 0xffffffffu) {
-                        B.xrec[xs[1] + atomicAdd(&xs[0], 1u)] = make_uint4(it, p - xi.start, s, 0u);
-                    }
-                }
-            }
-        }
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void kidx_walk_bin(const uint32_t* __restrict__ seeds, uint32_t n_seeds,
+        const uint64_t* __restrict__ off, const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
+        uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
+        unsigned long long* __restrict__ n_hits, uint32_t lps, const KxBins B, uint32_t n_waves) {
+    if constexpr (WAVES != 16) {
+        kidx_walk_bin_one_trip<WAVES>(seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, n_hits, lps, B, n_waves);
+        return;
     }
-    // what lies behind a lane's first four entries.  Dense seeds (a wave per quarter bucket): the wave's stride, as ever.  Four seeds per
-    // wave: a seed's 16 lanes cover 64 entries per trip - and the kernel is as long as its longest bucket (a repeat's k-mer with a few
-    // thousand occurrences was 40+ dependent trips of ONE quarter wave, twice over with two passes): everything beyond a bucket's first
-    // 64 entries is walked by the WHOLE wave, 256 entries per trip, one seed of the wave after the other
-    template <bool WRITE>
-    static __device__ __forceinline__ void tail(uint32_t lps, int lane, uint32_t w, uint32_t s, uint64_t o, uint32_t i0, uint32_t i1, uint32_t step,
-                                                const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
-                                                uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
-                                                uint32_t* __restrict__ counts, const KxBins& B, uint32_t* hist, const uint32_t* base, uint32_t* xs) {
-        if (lps == 64) {
-            for (uint32_t ib = i0 + 4 * step; ib < i1; ib += 4 * step) {
-                uint64_t e[4];
-                bool v[4];
-                kx_entry4(pos, o + ib, e);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    v[u] = ib + (uint32_t)u < i1;
-                    e[u] = v[u] ? e[u] : 0ull;
-                }
-                four<WRITE>(e, v, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            }
-            return;
-        }
-        if (!__ballot(i1 > 64u)) return;  // (wave-uniform: no bucket of this wave goes beyond its first trip)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const uint32_t ng = (uint32_t)__shfl((int)i1, 16 * g, 64);
-            if (ng <= 64u) continue;
-            const uint32_t lo32 = (uint32_t)__shfl((int)(uint32_t)o, 16 * g, 64), hi32 = (uint32_t)__shfl((int)(uint32_t)(o >> 32), 16 * g, 64);
-            const uint64_t og = ((uint64_t)hi32 << 32) | lo32;
-            const uint32_t sg = w * 4 + (uint32_t)g;
-            for (uint32_t ib = 64u + 4u * (uint32_t)lane; ib < ng; ib += 256u) {
-                uint64_t e[4];
-                bool v[4];
-                kx_entry4(pos, og + ib, e);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    v[u] = ib + (uint32_t)u < ng;
-                    e[u] = v[u] ? e[u] : 0ull;
-                }
-                four<WRITE>(e, v, sg, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            }
-        }
-    }
-    // One trip per workgroup and reservation - the sparse regime's form (workgroups of up to 8 waves), as it was before the dense regime's
-    // trips, table and look-ahead were built into run() below: those cost the k = 13 walk 20 us a launch (36 -> 56 us under five slots,
-    // profiles/r06/k13_against_round5.txt) and buy it nothing - its reservations are one trip long.
-    static __device__ void run_one_trip(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off, const KxPos pos,
-                               const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi, uint32_t n_read_items,
-                               const uint32_t* __restrict__ head, const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
-                               unsigned long long* __restrict__ n_hits, uint32_t lps, const KxBins B, uint32_t n_waves) {
-        __shared__ uint32_t hist[KX_MAXBINS], base[KX_MAXBINS];
-        __shared__ uint32_t xs[2];
-        __shared__ unsigned long long sh_hits;
-        const int lane = dp_lane();
-        const uint32_t stride = gridDim.x * WAVES;
-        // (every wave of a workgroup makes the same number of trips: the barriers below are the workgroup's)
-        for (uint32_t wb = blockIdx.x * WAVES; wb < n_waves; wb += stride) {
-            for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) hist[t] = 0u;
-            if (threadIdx.x == 0) {
-                sh_hits = 0ull;
-                xs[0] = xs[1] = 0u;
-            }
-            __syncthreads();
-            const uint32_t w = wb + (threadIdx.x >> 6);
-            // the groups of kidx_walk: KX_PARTS waves per seed (dense seeds), or four seeds per wave
-            uint32_t s = 0, i0 = 0, i1 = 0, step = 16, gfirst = 0;
-            uint64_t o = 0;
-            bool gleader = false;
-            if (w < n_waves) {
-                if (lps == 64) {
-                    s = w / KX_PARTS;
-                    if (s < n_seeds) {
-                        const uint32_t part = w % KX_PARTS;
-                        o = off[seeds[s]];
-                        const uint32_t n = (uint32_t)(off[(uint64_t)seeds[s] + 1] - o);
-                        const uint32_t per = (n + KX_PARTS - 1) / KX_PARTS;
-                        gfirst = min(n, part * per);
-                        i0 = part * per + 4u * (uint32_t)lane;
-                        i1 = min(n, part * per + per);
-                        step = 64;
-                        gleader = lane == 0;
-                    }
-                } else {
-                    s = w * 4 + ((uint32_t)lane >> 4);
-                    if (s < n_seeds) {
-                        o = off[seeds[s]];
-                        i0 = 4u * ((uint32_t)lane & 15u);
-                        i1 = (uint32_t)(off[(uint64_t)seeds[s] + 1] - o);
-                        gleader = (lane & 15) == 0;
-                    }
-                }
-            }
-            if (gleader && i1 > gfirst) atomicAdd(&sh_hits, (unsigned long long)(i1 - gfirst));
-            // the lane's first four entries stay in registers across the barriers (a seed of config 2 has 20 - 60 entries: for most groups
-            // the first trip is the only one, and the second pass reads nothing); later trips are read again (from the L2)
-            uint64_t e0[4] = {0, 0, 0, 0};
-            bool v0[4] = {false, false, false, false};
-            if (i0 < i1) {
-                kx_entry4(pos, o + i0, e0);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    v0[u] = i0 + (uint32_t)u < i1;
-                    e0[u] = v0[u] ? e0[u] : 0ull;
-                }
-                four<false>(e0, v0, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            }
-            tail<false>(lps, lane, w, s, o, i0, i1, step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            __syncthreads();
-            for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) {
-                const uint32_t c = hist[t];
-                uint32_t b = 0u;
-                if (c) {
-                    b = atomicAdd(&B.cursor[t], c);
-                    if (b + c > B.cap) {  // (its share of the bin does not fit: the whole share is counted the old way)
-                        // what it reserved below the bin's end stays unwritten: marked, so that kidx_bin_count skips it
-                        for (uint32_t j = b; j < B.cap; j++) B.rec[(size_t)t * B.cap + j] = ~0ull;
-                        b = 0xffffffffu;
-                        B.flags[0] = 1u;
-                    }
-                }
-                base[t] = b;
-                hist[t] = 0u;
-            }
-            if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
-            if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
-                const uint32_t c = xs[0];
-                uint32_t xb = 0u;
-                if (c) {
-                    xb = atomicAdd(B.xcursor, c);
-                    if (xb + c > B.xcap) {
-                        xb = 0xffffffffu;
-                        B.flags[0] = 1u;
-                    }
-                }
-                xs[1] = xb;
-                xs[0] = 0u;
-            }
-            __syncthreads();
-            if (i0 < i1) four<true>(e0, v0, s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            tail<true>(lps, lane, w, s, o, i0, i1, step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-            __syncthreads();
-        }
-    }
-    static __device__ void run(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off, const KxPos pos,
-                               const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi, uint32_t n_read_items,
-                               const uint32_t* __restrict__ head, const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
-                               unsigned long long* __restrict__ n_hits, uint32_t lps, const KxBins B, uint32_t n_waves) {
-        if constexpr (WAVES != 16) {
-            run_one_trip(seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, n_hits, lps, B, n_waves);
-            return;
-        }
-        __shared__ uint32_t hist[KX_MAXBINS], base[KX_MAXBINS];
-        __shared__ uint32_t xs[2];
-        __shared__ unsigned long long sh_hits;
-        const int lane = dp_lane();
-        const uint32_t stride = gridDim.x * WAVES;
-        // B.batch trips of the workgroup share one reservation per bin (round 6, the dense regime: a seed's bucket holds a thousand
-        // entries, a workgroup trip 2 - 4 seeds - a few records per bin and trip, each stretch a returning atomic and a short run of
-        // stores; eight trips a reservation are eight times fewer atomics and runs eight times as long).  Trips behind the first read
-        // their entries again in the second pass (from the L2).
-        const uint32_t T = min(32u, max(1u, B.batch));  // (the table below holds 32 trips)
-        // the groups of kidx_walk: KX_PARTS waves per seed (dense seeds), or four seeds per wave
-        struct Grp {
-            uint32_t s, i0, i1, step, gfirst;
-            uint64_t o;
-            bool gleader;
-        };
-        // Round 6: where a seed's bucket starts and how long it is comes from an LDS table the whole workgroup fills at once, for
-        // every trip of the reservation (lps == 64: a wave per quarter bucket) - two dependent loads less in front of every trip's
-        // entries - and the entries of the next trip are asked for before the current trip's are worked on (below)
-        __shared__ unsigned long long t_o[WAVES * 32 / KX_PARTS + 2];
-        __shared__ uint32_t t_n[WAVES * 32 / KX_PARTS + 2];
-        uint32_t t_first = 0u;  // seed of the table's first row
-        auto group_of = [&](uint32_t w) {
-            Grp g = {0u, 0u, 0u, 16u, 0u, 0ull, false};
-            if (w < n_waves) {
-                if (lps == 64) {
-                    g.s = w / KX_PARTS;
-                    if (g.s < n_seeds) {
-                        const uint32_t part = w % KX_PARTS;
-                        g.o = t_o[g.s - t_first];
-                        const uint32_t n = t_n[g.s - t_first];
-                        const uint32_t per = (n + KX_PARTS - 1) / KX_PARTS;
-                        g.gfirst = min(n, part * per);
-                        g.i0 = part * per + 4u * (uint32_t)lane;
-                        g.i1 = min(n, part * per + per);
-                        g.step = 64;
-                        g.gleader = lane == 0;
-                    }
-                } else {
-                    g.s = w * 4 + ((uint32_t)lane >> 4);
-                    if (g.s < n_seeds) {
-                        g.o = off[seeds[g.s]];
-                        g.i0 = 4u * ((uint32_t)lane & 15u);
-                        g.i1 = (uint32_t)(off[(uint64_t)seeds[g.s] + 1] - g.o);
-                        g.gleader = (lane & 15) == 0;
-                    }
-                }
-            }
-            return g;
-        };
-        // (every wave of a workgroup makes the same number of trips: the barriers below are the workgroup's)
-        for (uint32_t wb = blockIdx.x * WAVES * T; wb < n_waves; wb += stride * T) {
-            for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) hist[t] = 0u;
-            if (threadIdx.x == 0) {
-                sh_hits = 0ull;
-                xs[0] = xs[1] = 0u;
-            }
+    enum { THREADS = 64 * WAVES };
+    __shared__ uint32_t hist[KX_MAXBINS], base[KX_MAXBINS];
+    __shared__ uint32_t xs[2];
+    __shared__ unsigned long long sh_hits;
+    const int lane = dp_lane();
+    const uint32_t stride = gridDim.x * WAVES;
+    // B.batch trips of the workgroup share one reservation per bin (round 6, the dense regime: a seed's bucket holds a thousand
+    // entries, a workgroup trip 2 - 4 seeds - a few records per bin and trip, each stretch a returning atomic and a short run of
+    // stores; eight trips a reservation are eight times fewer atomics and runs eight times as long).  Trips behind the first read
+    // their entries again in the second pass (from the L2).
+    const uint32_t T = min(32u, max(1u, B.batch));  // (the table below holds 32 trips)
+    // the groups of kidx_walk: KX_PARTS waves per seed (dense seeds), or four seeds per wave
+    struct Grp {
+        uint32_t s, i0, i1, step, gfirst;
+        uint64_t o;
+        bool gleader;
+    };
+    // Round 6: where a seed's bucket starts and how long it is comes from an LDS table the whole workgroup fills at once, for
+    // every trip of the reservation (lps == 64: a wave per quarter bucket) - two dependent loads less in front of every trip's
+    // entries - and the entries of the next trip are asked for before the current trip's are worked on (below)
+    __shared__ unsigned long long t_o[WAVES * 32 / KX_PARTS + 2];
+    __shared__ uint32_t t_n[WAVES * 32 / KX_PARTS + 2];
+    uint32_t t_first = 0u;  // seed of the table's first row
+    auto group_of = [&](uint32_t w) {
+        Grp g = {0u, 0u, 0u, 16u, 0u, 0ull, false};
+        if (w < n_waves) {
             if (lps == 64) {
-                t_first = wb / KX_PARTS;
-                const uint32_t rows = (WAVES * min(T, 32u) + KX_PARTS - 1) / KX_PARTS + 1u;
-                for (uint32_t t = threadIdx.x; t < rows; t += THREADS) {
-                    const uint32_t sd = t_first + t;
-                    unsigned long long o = 0ull;
-                    uint32_t n = 0u;
-                    if (sd < n_seeds) {
-                        const uint32_t km = seeds[sd];
-                        o = off[km];
-                        n = (uint32_t)(off[(uint64_t)km + 1] - o);
-                    }
-                    t_o[t] = o;
-                    t_n[t] = n;
+                g.s = w / KX_PARTS;
+                if (g.s < n_seeds) {
+                    const uint32_t part = w % KX_PARTS;
+                    g.o = t_o[g.s - t_first];
+                    const uint32_t n = t_n[g.s - t_first];
+                    const uint32_t per = (n + KX_PARTS - 1) / KX_PARTS;
+                    g.gfirst = min(n, part * per);
+                    g.i0 = part * per + 4u * (uint32_t)lane;
+                    g.i1 = min(n, part * per + per);
+                    g.step = 64;
+                    g.gleader = lane == 0;
+                }
+            } else {
+                g.s = w * 4 + ((uint32_t)lane >> 4);
+                if (g.s < n_seeds) {
+                    g.o = off[seeds[g.s]];
+                    g.i0 = 4u * ((uint32_t)lane & 15u);
+                    g.i1 = (uint32_t)(off[(uint64_t)seeds[g.s] + 1] - g.o);
+                    g.gleader = (lane & 15) == 0;
                 }
             }
-            __syncthreads();
-            // the lane's first four entries of the FIRST trip stay in registers across the barriers (a seed of config 2 has 20 - 60
-            // entries: for most groups the first trip is the only one, and the second pass reads nothing)
-            uint64_t e0[4] = {0, 0, 0, 0};
-            bool v0[4] = {false, false, false, false};
-            {
-                Grp g = group_of(wb + (threadIdx.x >> 6));
-                uint64_t e[4] = {0, 0, 0, 0};
-                if (g.i0 < g.i1) kx_entry4(pos, g.o + g.i0, e);
-                for (uint32_t tr = 0; tr < T; tr++) {
-                    const uint32_t w = wb + tr * WAVES + (threadIdx.x >> 6);
-                    // the next trip's entries are on their way while this trip's are counted
-                    Grp gn = g;
-                    uint64_t en[4] = {0, 0, 0, 0};
-                    if (tr + 1 < T) {
-                        gn = group_of(w + WAVES);
-                        if (gn.i0 < gn.i1) kx_entry4(pos, gn.o + gn.i0, en);
+        }
+        return g;
+    };
+    // (every wave of a workgroup makes the same number of trips: the barriers below are the workgroup's)
+    for (uint32_t wb = blockIdx.x * WAVES * T; wb < n_waves; wb += stride * T) {
+        for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) hist[t] = 0u;
+        if (threadIdx.x == 0) {
+            sh_hits = 0ull;
+            xs[0] = xs[1] = 0u;
+        }
+        if (lps == 64) {
+            t_first = wb / KX_PARTS;
+            const uint32_t rows = (WAVES * min(T, 32u) + KX_PARTS - 1) / KX_PARTS + 1u;
+            for (uint32_t t = threadIdx.x; t < rows; t += THREADS) {
+                const uint32_t sd = t_first + t;
+                unsigned long long o = 0ull;
+                uint32_t n = 0u;
+                if (sd < n_seeds) {
+                    const uint32_t km = seeds[sd];
+                    o = off[km];
+                    n = (uint32_t)(off[(uint64_t)km + 1] - o);
+                }
+                t_o[t] = o;
+                t_n[t] = n;
+            }
+        }
+        __syncthreads();
+        // the lane's first four entries of the FIRST trip stay in registers across the barriers (a seed of config 2 has 20 - 60
+        // entries: for most groups the first trip is the only one, and the second pass reads nothing)
+        uint64_t e0[4] = {0, 0, 0, 0};
+        bool v0[4] = {false, false, false, false};
+        {
+            Grp g = group_of(wb + (threadIdx.x >> 6));
+            uint64_t e[4] = {0, 0, 0, 0};
+            if (g.i0 < g.i1) kx_entry4(pos, g.o + g.i0, e);
+            for (uint32_t tr = 0; tr < T; tr++) {
+                const uint32_t w = wb + tr * WAVES + (threadIdx.x >> 6);
+                // the next trip's entries are on their way while this trip's are counted
+                Grp gn = g;
+                uint64_t en[4] = {0, 0, 0, 0};
+                if (tr + 1 < T) {
+                    gn = group_of(w + WAVES);
+                    if (gn.i0 < gn.i1) kx_entry4(pos, gn.o + gn.i0, en);
+                }
+                if (g.gleader && g.i1 > g.gfirst) atomicAdd(&sh_hits, (unsigned long long)(g.i1 - g.gfirst));
+                bool v[4] = {false, false, false, false};
+                if (g.i0 < g.i1) {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        v[u] = g.i0 + (uint32_t)u < g.i1;
+                        e[u] = v[u] ? e[u] : 0ull;
                     }
-                    if (g.gleader && g.i1 > g.gfirst) atomicAdd(&sh_hits, (unsigned long long)(g.i1 - g.gfirst));
-                    bool v[4] = {false, false, false, false};
-                    if (g.i0 < g.i1) {
+                    kxb_four<false>(e, v, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) e[u] = 0ull;
+                }
+                if (tr == 0) {
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        e0[u] = e[u];
+                        v0[u] = v[u];
+                    }
+                }
+                kxb_tail<false>(lps, lane, w, g.s, g.o, g.i0, g.i1, g.step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+                g = gn;
+#pragma unroll
+                for (int u = 0; u < 4; u++) e[u] = en[u];
+            }
+        }
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) {
+            const uint32_t c = hist[t];
+            uint32_t b = 0u;
+            if (c) {
+                b = atomicAdd(&B.cursor[t], c);
+                if (b + c > B.cap) {  // (its share of the bin does not fit: the whole share is counted the old way)
+                    // what it reserved below the bin's end stays unwritten: marked, so that kidx_bin_count skips it
+                    for (uint32_t j = b; j < B.cap; j++) B.rec[(size_t)t * B.cap + j] = ~0ull;
+                    b = 0xffffffffu;
+                    B.flags[0] = 1u;
+                }
+            }
+            base[t] = b;
+            hist[t] = 0u;
+        }
+        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
+        if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
+            const uint32_t c = xs[0];
+            uint32_t xb = 0u;
+            if (c) {
+                xb = atomicAdd(B.xcursor, c);
+                if (xb + c > B.xcap) {
+                    xb = 0xffffffffu;
+                    B.flags[0] = 1u;
+                }
+            }
+            xs[1] = xb;
+            xs[0] = 0u;
+        }
+        __syncthreads();
+        {
+            Grp g = group_of(wb + (threadIdx.x >> 6));
+            uint64_t e[4] = {0, 0, 0, 0};
+            for (uint32_t tr = 0; tr < T; tr++) {
+                const uint32_t w = wb + tr * WAVES + (threadIdx.x >> 6);
+                Grp gn = g;
+                uint64_t en[4] = {0, 0, 0, 0};
+                if (tr + 1 < T) {  // (the first trip's entries waited in registers; every later trip's are read again - from the L2 - a trip ahead)
+                    gn = group_of(w + WAVES);
+                    if (gn.i0 < gn.i1) kx_entry4(pos, gn.o + gn.i0, en);
+                }
+                if (g.i0 < g.i1) {
+                    if (tr == 0) {
+                        kxb_four<true>(e0, v0, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+                    } else {
+                        bool v[4];
 #pragma unroll
                         for (int u = 0; u < 4; u++) {
                             v[u] = g.i0 + (uint32_t)u < g.i1;
                             e[u] = v[u] ? e[u] : 0ull;
                         }
-                        four<false>(e, v, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; u++) e[u] = 0ull;
-                    }
-                    if (tr == 0) {
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            e0[u] = e[u];
-                            v0[u] = v[u];
-                        }
-                    }
-                    tail<false>(lps, lane, w, g.s, g.o, g.i0, g.i1, g.step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-                    g = gn;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) e[u] = en[u];
-                }
-            }
-            __syncthreads();
-            for (uint32_t t = threadIdx.x; t < B.n_bins; t += THREADS) {
-                const uint32_t c = hist[t];
-                uint32_t b = 0u;
-                if (c) {
-                    b = atomicAdd(&B.cursor[t], c);
-                    if (b + c > B.cap) {  // (its share of the bin does not fit: the whole share is counted the old way)
-                        // what it reserved below the bin's end stays unwritten: marked, so that kidx_bin_count skips it
-                        for (uint32_t j = b; j < B.cap; j++) B.rec[(size_t)t * B.cap + j] = ~0ull;
-                        b = 0xffffffffu;
-                        B.flags[0] = 1u;
+                        kxb_four<true>(e, v, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
                     }
                 }
-                base[t] = b;
-                hist[t] = 0u;
-            }
-            if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
-            if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
-                const uint32_t c = xs[0];
-                uint32_t xb = 0u;
-                if (c) {
-                    xb = atomicAdd(B.xcursor, c);
-                    if (xb + c > B.xcap) {
-                        xb = 0xffffffffu;
-                        B.flags[0] = 1u;
-                    }
-                }
-                xs[1] = xb;
-                xs[0] = 0u;
-            }
-            __syncthreads();
-            {
-                Grp g = group_of(wb + (threadIdx.x >> 6));
-                uint64_t e[4] = {0, 0, 0, 0};
-                for (uint32_t tr = 0; tr < T; tr++) {
-                    const uint32_t w = wb + tr * WAVES + (threadIdx.x >> 6);
-                    Grp gn = g;
-                    uint64_t en[4] = {0, 0, 0, 0};
-                    if (tr + 1 < T) {  // (the first trip's entries waited in registers; every later trip's are read again - from the L2 - a trip ahead)
-                        gn = group_of(w + WAVES);
-                        if (gn.i0 < gn.i1) kx_entry4(pos, gn.o + gn.i0, en);
-                    }
-                    if (g.i0 < g.i1) {
-                        if (tr == 0) {
-                            four<true>(e0, v0, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-                        } else {
-                            bool v[4];
+                kxb_tail<true>(lps, lane, w, g.s, g.o, g.i0, g.i1, g.step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
+                g = gn;
 #pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                v[u] = g.i0 + (uint32_t)u < g.i1;
-                                e[u] = v[u] ? e[u] : 0ull;
-                            }
-                            four<true>(e, v, g.s, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-                        }
-                    }
-                    tail<true>(lps, lane, w, g.s, g.o, g.i0, g.i1, g.step, pos, items, lo, hi, n_read_items, head, next, counts, B, hist, base, xs);
-                    g = gn;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) e[u] = en[u];
-                }
+                for (int u = 0; u < 4; u++) e[u] = en[u];
             }
-            __syncthreads();
         }
+        __syncthreads();
     }
-};
+}
 
 // RB = counters a workgroup's LDS holds (reads per bin <= RB)
 template <int RB>
-struct kidx_bin_count {
+__global__ __launch_bounds__(512) void kidx_bin_count(const KxBins B, uint32_t* __restrict__ counts, uint32_t n_read_items, uint32_t lo) {
     enum { THREADS = 512 };
-    static __device__ void run(const KxBins B, uint32_t* __restrict__ counts, uint32_t n_read_items, uint32_t lo) {
-        __shared__ uint32_t cnt[RB];
-        const uint32_t bin = blockIdx.x;
-        if (bin >= B.n_bins) return;
-        const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
-        const uint32_t n = min(B.cursor[bin], B.cap);
-        for (uint32_t i = threadIdx.x; i < rb; i += THREADS) cnt[i] = 0u;
-        __syncthreads();
-        const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
-        for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {  // (four consecutive records per thread and trip)
-            unsigned long long e[4];
+    __shared__ uint32_t cnt[RB];
+    const uint32_t bin = blockIdx.x;
+    const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
+    const uint32_t n = min(B.cursor[bin], B.cap);
+    for (uint32_t i = threadIdx.x; i < rb; i += THREADS) cnt[i] = 0u;
+    __syncthreads();
+    const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
+    for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {  // (four consecutive records per thread and trip)
+        unsigned long long e[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
+        for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
 #pragma unroll
-            for (int u = 0; u < 4; u++)
-                if (e[u] != ~0ull) atomicAdd(&cnt[(uint32_t)(e[u] >> (KXB_SEED_BITS + 24))], 1u);
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
-            const uint32_t it = first + i;
-            if (it < n_read_items) {
-                const uint32_t c = cnt[i];
-                // (zeroed by kidx_prepare; a full bin's overflow was counted there directly.  A read ignored by now counts nothing - the
-                // walk's short cut tested this byte per hit; the fill pass goes by the count written here)
-                if (B.ign && B.ign[lo + it]) counts[it] = 0u;
-                else if (c) counts[it] += c;
-            }
+        for (int u = 0; u < 4; u++)
+            if (e[u] != ~0ull) atomicAdd(&cnt[(uint32_t)(e[u] >> (KXB_SEED_BITS + 24))], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
+        const uint32_t it = first + i;
+        if (it < n_read_items) {
+            const uint32_t c = cnt[i];
+            // (zeroed by kidx_prepare; a full bin's overflow was counted there directly.  A read ignored by now counts nothing - the
+            // walk's short cut tested this byte per hit; the fill pass goes by the count written here)
+            if (B.ign && B.ign[lo + it]) counts[it] = 0u;
+            else if (c) counts[it] += c;
         }
     }
-};
+}
 
+// workgroups behind the bins' that place the extra items' hits from their list (kidx_bin_fill, kidx_bin_sort_dense)
+constexpr uint32_t KX_XBLOCKS = 8;
 template <int RB>
-struct kidx_bin_fill {
-    enum { THREADS = 512, XBLOCKS = 8 };
-    static __device__ void run(const KxBins B, const dp_scan_item* __restrict__ items, uint32_t n_read_items,
-                               const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff,
-                               int32_t* __restrict__ segs, const uint64_t* __restrict__ totals, uint64_t seg_cap) {
-        __shared__ uint32_t cnt[RB];
-        if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
-        if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
-            const uint32_t xb = blockIdx.x - B.n_bins;
-            if (xb >= XBLOCKS) return;
-            const uint32_t nx = min(*B.xcursor, B.xcap);
-            for (uint32_t j = xb * THREADS + threadIdx.x; j < nx; j += XBLOCKS * THREADS) {
-                const uint4 x = B.xrec[j];
-                if (counts[x.x] >= items[x.x].min_seeds) {
-                    const uint32_t slot = atomicAdd(&fillc[x.x], 1u);
-                    const uint64_t to = segoff[x.x] + 2ull * slot;
-                    segs[to] = (int32_t)x.y;
-                    segs[to + 1] = (int32_t)x.z;
-                }
+__global__ __launch_bounds__(512) void kidx_bin_fill(const KxBins B, const dp_scan_item* __restrict__ items, uint32_t n_read_items,
+                                                     const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
+                                                     const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
+                                                     const uint64_t* __restrict__ totals, uint64_t seg_cap) {
+    enum { THREADS = 512 };
+    __shared__ uint32_t cnt[RB];
+    if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
+    if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
+        const uint32_t xb = blockIdx.x - B.n_bins;
+        if (xb >= KX_XBLOCKS) return;
+        const uint32_t nx = min(*B.xcursor, B.xcap);
+        for (uint32_t j = xb * THREADS + threadIdx.x; j < nx; j += KX_XBLOCKS * THREADS) {
+            const uint4 x = B.xrec[j];
+            if (counts[x.x] >= items[x.x].min_seeds) {
+                const uint32_t slot = atomicAdd(&fillc[x.x], 1u);
+                const uint64_t to = segoff[x.x] + 2ull * slot;
+                segs[to] = (int32_t)x.y;
+                segs[to + 1] = (int32_t)x.z;
             }
-            return;
         }
-        const uint32_t bin = blockIdx.x;
-        const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
-        const uint32_t n = min(B.cursor[bin], B.cap);
-        // slot counters of the bin's survivors (top bit: the read does not survive - its own min_seeds, what kidx_offsets tested)
-        for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
-            const uint32_t it = first + i;
-            bool surv = false;
-            if (it < n_read_items) {
-                const uint32_t c = counts[it];
-                surv = c > 0u && c >= items[it].min_seeds;
-            }
-            cnt[i] = surv ? 0u : 0x80000000u;
+        return;
+    }
+    const uint32_t bin = blockIdx.x;
+    const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
+    const uint32_t n = min(B.cursor[bin], B.cap);
+    // slot counters of the bin's survivors (top bit: the read does not survive - its own min_seeds, what kidx_offsets tested)
+    for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
+        const uint32_t it = first + i;
+        bool surv = false;
+        if (it < n_read_items) {
+            const uint32_t c = counts[it];
+            surv = c > 0u && c >= items[it].min_seeds;
         }
-        __syncthreads();
-        const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
-        for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {
-            unsigned long long e[4];
+        cnt[i] = surv ? 0u : 0x80000000u;
+    }
+    __syncthreads();
+    const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
+    for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {
+        unsigned long long e[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
+        for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (e[u] == ~0ull) continue;
-                const uint32_t rib = (uint32_t)(e[u] >> (KXB_SEED_BITS + 24));
-                if (cnt[rib] & 0x80000000u) continue;
-                const uint32_t rank = atomicAdd(&cnt[rib], 1u);
-                const uint64_t to = segoff[first + rib] + 2ull * rank;
-                segs[to] = (int32_t)((uint32_t)e[u] & 0xffffffu);
-                segs[to + 1] = (int32_t)((uint32_t)(e[u] >> 24) & ((1u << KXB_SEED_BITS) - 1u));
-            }
+        for (int u = 0; u < 4; u++) {
+            if (e[u] == ~0ull) continue;
+            const uint32_t rib = (uint32_t)(e[u] >> (KXB_SEED_BITS + 24));
+            if (cnt[rib] & 0x80000000u) continue;
+            const uint32_t rank = atomicAdd(&cnt[rib], 1u);
+            const uint64_t to = segoff[first + rib] + 2ull * rank;
+            segs[to] = (int32_t)((uint32_t)e[u] & 0xffffffu);
+            segs[to + 1] = (int32_t)((uint32_t)(e[u] >> 24) & ((1u << KXB_SEED_BITS) - 1u));
         }
     }
-};
+}
 
 // status word of a tile: flag << 62 | survivors << 38 | segment ints (flag 1 = the tile's own sums, 2 = inclusive prefix)
 #define KX_TILE 1024
 #ifndef KX_IPT
 #define KX_IPT 4
 #endif
-struct kidx_offsets {
+// B.rec != null (round 5, bins of at most a tile's 4 096 reads): the tile counts the records of its own bins in LDS first - what
+// kidx_bin_count does in a launch of its own (every launch of a round costs a five-slot round 1.5 - 1.9 us whatever it does:
+// profiles/r05/ab_extra_launches_five_slots.txt) - and stores the counts it then scans
+__global__ __launch_bounds__(KX_TILE) void kidx_offsets(const dp_scan_item* __restrict__ items, uint32_t* __restrict__ counts, uint32_t n,
+                                                        unsigned long long* __restrict__ status, uint32_t* __restrict__ ticket,
+                                                        uint64_t* __restrict__ segoff, uint32_t* __restrict__ s_item,
+                                                        uint32_t* __restrict__ s_count, uint64_t* __restrict__ s_off,
+                                                        uint4* __restrict__ s_pack, uint64_t* __restrict__ totals, uint32_t n_read_items,
+                                                        uint32_t* __restrict__ max_count, const unsigned long long* __restrict__ n_hits,
+                                                        unsigned long long* __restrict__ host_totals, const KxBins B, uint32_t lo) {
     enum { THREADS = KX_TILE };
-    // B.rec != null (round 5, bins of at most a tile's 4 096 reads): the tile counts the records of its own bins in LDS first - what
-    // kidx_bin_count does in a launch of its own (every launch of a round costs a five-slot round 1.5 - 1.9 us whatever it does:
-    // profiles/r05/ab_extra_launches_five_slots.txt) - and stores the counts it then scans
-    static __device__ void run(const dp_scan_item* __restrict__ items, uint32_t* __restrict__ counts,
-                                                       uint32_t n, unsigned long long* __restrict__ status, uint32_t* __restrict__ ticket,
-                                                       uint64_t* __restrict__ segoff, uint32_t* __restrict__ s_item,
-                                                       uint32_t* __restrict__ s_count, uint64_t* __restrict__ s_off,
-                                                       uint4* __restrict__ s_pack, uint64_t* __restrict__ totals,
-                                                       uint32_t n_read_items, uint32_t* __restrict__ max_count,
-                                                       const unsigned long long* __restrict__ n_hits,
-                                                       unsigned long long* __restrict__ host_totals, const KxBins B, uint32_t lo) {
     __shared__ uint32_t shA[16], shB[16];
     __shared__ uint32_t tile_s;
     __shared__ unsigned long long excl_s;
     __shared__ uint32_t tcnt[KX_TILE * KX_IPT];
-    // (a launch shared with other rounds has the largest round's grid: blocks beyond this round's own tiles take no ticket)
-    if (blockIdx.x >= (n + KX_TILE * KX_IPT - 1) / (KX_TILE * KX_IPT)) return;
     if (threadIdx.x == 0) tile_s = atomicAdd(ticket, 1u);  // tiles start in ticket order: a predecessor is always running or done
     __syncthreads();
     const uint32_t tile = tile_s;
@@ -1387,7 +1371,6 @@ struct kidx_offsets {
         }
     }
 }
-};
 
 // One survivor's slice: c unordered (position, seed) pairs at segs[out ..] -> sorted by position -> [gap, seed, ..., gap] in place (and in the
 // host mirror for an extra item).  Executed by ONE wave with `keys` (CAP words of LDS) to itself.  WG1: the wave is the whole workgroup
@@ -1486,9 +1469,7 @@ static_assert(KX_SORT_LDS <= (1 << 14), "kx_rec keeps the rank of a hit in 14 bi
 // CAP = keys the block's LDS holds (the launch picks the smallest that fits the round's largest survivor: a CU then holds
 // eight times as many waves for the usual few dozen hits per read as for the rare thousands)
 template <int CAP>
-struct kidx_sortwrite {
-    enum { THREADS = 64 };
-    static __device__ void run(const dp_scan_item* __restrict__ items, const uint32_t* __restrict__ sel,
+__global__ __launch_bounds__(64) void kidx_sortwrite(const dp_scan_item* __restrict__ items, const uint32_t* __restrict__ sel,
                                                      const uint32_t* __restrict__ n_sel_p, const uint32_t* __restrict__ counts,
                                                      const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs, int k,
                                                      uint32_t* __restrict__ overflow, uint32_t n_read_items, uint32_t n_extra,
@@ -1512,7 +1493,6 @@ struct kidx_sortwrite {
         kx_sort_one<CAP, true>(keys, lane, it, counts[it], segoff[it], (int)items[it].n_kmers, segs, k, overflow, n_read_items, host_segs);
     }
 }
-};
 
 // Round 6 - the dense regime (the command's default k = 10: every read holds ~100 seed occurrences, ten million hits a round).  There
 // kidx_bin_fill scattered 8-byte pairs into the reads' slices and kidx_sortwrite, a wave per read, read them back, sorted them and wrote
@@ -1524,168 +1504,165 @@ struct kidx_sortwrite {
 // bin's records per group - the bins of the round's query reads).  A read with more than MAXC hits raises the overflow word, as a
 // survivor beyond the sort pass's capacity always did (the host repeats fill + sort with the right tier).
 // The blocks behind the bins fill the extra items' slices from their list, as kidx_bin_fill's; kidx_sortwrite(extras_only) sorts those.
-template <int CAP>
-struct kidx_bin_sort_dense {
-    enum { THREADS = 512, WAVES = 8, RBMAX = 256, XBLOCKS = 8, MAXC = 1024, RPL = MAXC / 64 };
-    // c <= 64 R keys of one read, sorted in place by one wave: every key counts the keys below it (broadcast reads of the stretch), the
-    // ranks wait in registers until the wave has read everything, then the keys go to their ranks
-    // (a read's hits lie at distinct positions - one k-mer starts at a position - so the position, the key's upper word, ranks alone:
-    // 32-bit compares at full rate where the 64-bit ones took two issue slots each; the kernel is bound by exactly these - 65 M vector
-    // instructions a launch at k = 10, profiles/r06/pmc_k10.json)
-    template <int R>
-    static __device__ __forceinline__ void rank_in_place(unsigned long long* my, const uint32_t c, const int lane) {
-        unsigned long long key[R];
-        uint32_t kp[R], rk[R];
-        const uint32_t* pos = (const uint32_t*)my + 1;  // position of record l: pos[2 l]
+// c <= 64 R keys of one read, sorted in place by one wave: every key counts the keys below it (broadcast reads of the stretch), the
+// ranks wait in registers until the wave has read everything, then the keys go to their ranks
+// (a read's hits lie at distinct positions - one k-mer starts at a position - so the position, the key's upper word, ranks alone:
+// 32-bit compares at full rate where the 64-bit ones took two issue slots each; the kernel is bound by exactly these - 65 M vector
+// instructions a launch at k = 10, profiles/r06/pmc_k10.json)
+template <int R>
+__device__ __forceinline__ void kx_rank_in_place(unsigned long long* my, const uint32_t c, const int lane) {
+    unsigned long long key[R];
+    uint32_t kp[R], rk[R];
+    const uint32_t* pos = (const uint32_t*)my + 1;  // position of record l: pos[2 l]
 #pragma unroll
-        for (int u = 0; u < R; u++) {
-            const uint32_t j = (uint32_t)lane + 64u * (uint32_t)u;
-            key[u] = j < c ? my[j] : ~0ull;
-            kp[u] = (uint32_t)(key[u] >> 32);
-            rk[u] = 0u;
+    for (int u = 0; u < R; u++) {
+        const uint32_t j = (uint32_t)lane + 64u * (uint32_t)u;
+        key[u] = j < c ? my[j] : ~0ull;
+        kp[u] = (uint32_t)(key[u] >> 32);
+        rk[u] = 0u;
+    }
+    uint32_t l = 0;
+    for (; l + 8 <= c; l += 8) {  // (eight broadcast reads in flight: one read at a time is a trip through the LDS per key)
+        uint32_t o[8];
+#pragma unroll
+        for (int x = 0; x < 8; x++) o[x] = pos[2u * (l + (uint32_t)x)];
+#pragma unroll
+        for (int x = 0; x < 8; x++) {
+#pragma unroll
+            for (int u = 0; u < R; u++) rk[u] += o[x] < kp[u] ? 1u : 0u;
         }
-        uint32_t l = 0;
-        for (; l + 8 <= c; l += 8) {  // (eight broadcast reads in flight: one read at a time is a trip through the LDS per key)
-            uint32_t o[8];
+    }
+    for (; l < c; l++) {
+        const uint32_t o = pos[2u * l];
 #pragma unroll
-            for (int x = 0; x < 8; x++) o[x] = pos[2u * (l + (uint32_t)x)];
+        for (int u = 0; u < R; u++) rk[u] += o < kp[u] ? 1u : 0u;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int x = 0; x < 8; x++) {
-#pragma unroll
-                for (int u = 0; u < R; u++) rk[u] += o[x] < kp[u] ? 1u : 0u;
+    for (int u = 0; u < R; u++) {
+        const uint32_t j = (uint32_t)lane + 64u * (uint32_t)u;
+        if (j < c) my[rk[u]] = key[u];  // (positions are distinct: the ranks are a permutation)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+template <int CAP>
+__global__ __launch_bounds__(512) void kidx_bin_sort_dense(const KxBins B, const dp_scan_item* __restrict__ items, uint32_t n_read_items,
+        const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
+        const uint64_t* __restrict__ totals, uint64_t seg_cap, int k, uint32_t* __restrict__ overflow) {
+    enum { THREADS = 512, WAVES = 8, RBMAX = 256, MAXC = 1024, RPL = MAXC / 64 };
+    __shared__ unsigned long long recs[CAP];
+    __shared__ uint32_t cnt[RBMAX], offs[RBMAX + 1], cur[RBMAX], nks[RBMAX];
+    __shared__ unsigned long long sout[RBMAX];
+    __shared__ uint32_t g_hi_s;
+    if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
+    if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
+        const uint32_t xb = blockIdx.x - B.n_bins;
+        if (xb >= KX_XBLOCKS) return;
+        const uint32_t nx = min(*B.xcursor, B.xcap);
+        for (uint32_t j = xb * THREADS + threadIdx.x; j < nx; j += KX_XBLOCKS * THREADS) {
+            const uint4 x = B.xrec[j];
+            if (counts[x.x] >= items[x.x].min_seeds) {
+                const uint32_t slot = atomicAdd(&fillc[x.x], 1u);
+                const uint64_t to = segoff[x.x] + 2ull * slot;
+                segs[to] = (int32_t)x.y;
+                segs[to + 1] = (int32_t)x.z;
             }
         }
-        for (; l < c; l++) {
-            const uint32_t o = pos[2u * l];
-#pragma unroll
-            for (int u = 0; u < R; u++) rk[u] += o < kp[u] ? 1u : 0u;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int u = 0; u < R; u++) {
-            const uint32_t j = (uint32_t)lane + 64u * (uint32_t)u;
-            if (j < c) my[rk[u]] = key[u];  // (positions are distinct: the ranks are a permutation)
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        return;
     }
-    static __device__ void run(const KxBins B, const dp_scan_item* __restrict__ items, uint32_t n_read_items,
-                               const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff,
-                               int32_t* __restrict__ segs, const uint64_t* __restrict__ totals, uint64_t seg_cap, int k,
-                               uint32_t* __restrict__ overflow) {
-        __shared__ unsigned long long recs[CAP];
-        __shared__ uint32_t cnt[RBMAX], offs[RBMAX + 1], cur[RBMAX], nks[RBMAX];
-        __shared__ unsigned long long sout[RBMAX];
-        __shared__ uint32_t g_hi_s;
-        if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
-        if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
-            const uint32_t xb = blockIdx.x - B.n_bins;
-            if (xb >= XBLOCKS) return;
-            const uint32_t nx = min(*B.xcursor, B.xcap);
-            for (uint32_t j = xb * THREADS + threadIdx.x; j < nx; j += XBLOCKS * THREADS) {
-                const uint4 x = B.xrec[j];
-                if (counts[x.x] >= items[x.x].min_seeds) {
-                    const uint32_t slot = atomicAdd(&fillc[x.x], 1u);
-                    const uint64_t to = segoff[x.x] + 2ull * slot;
-                    segs[to] = (int32_t)x.y;
-                    segs[to + 1] = (int32_t)x.z;
+    const int lane = dp_lane(), wave = threadIdx.x >> 6;
+    const uint32_t bin = blockIdx.x;
+    const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
+    const uint32_t n = min(B.cursor[bin], B.cap);
+    for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
+        const uint32_t it = first + i;
+        uint32_t c = 0u;
+        if (it < n_read_items) {
+            // (everything a read's wave will want of memory, asked for at once: a wave sorts eight reads one after the other)
+            const dp_scan_item item = items[it];
+            const unsigned long long so = segoff[it];
+            c = counts[it];
+            if (c < item.min_seeds) c = 0u;
+            nks[i] = item.n_kmers;
+            sout[i] = so;
+        }
+        if (c > (uint32_t)MAXC || c > (uint32_t)CAP) {
+            atomicExch(overflow, 1u);
+            c = 0u;
+        }
+        cnt[i] = c;
+    }
+    __syncthreads();
+    const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
+    uint32_t g_lo = 0u;
+    while (g_lo < rb) {
+        // the group: reads g_lo .. g_hi - 1, as many as the array holds (every read fits by itself: c <= CAP)
+        if (wave == 0) {
+            uint32_t acc = 0u, i = g_lo;
+            for (;;) {
+                const uint32_t idx = i + (uint32_t)lane;
+                const uint32_t c = idx < rb ? cnt[idx] : 0u;
+                const uint32_t incl = (uint32_t)wave_incl_sum((int)c);
+                const bool fits = idx < rb && acc + incl <= (uint32_t)CAP;  // (a prefix of the lanes: the sums do not decrease)
+                const uint32_t nfit = (uint32_t)__popcll(__ballot(fits));
+                if (fits) offs[idx] = acc + incl - c;
+                if (nfit) acc += (uint32_t)__shfl((int)incl, (int)nfit - 1, 64);
+                i += nfit;
+                if (nfit < 64u) break;
+            }
+            if (lane == 0) {
+                offs[i] = acc;
+                g_hi_s = i;
+            }
+        }
+        for (uint32_t i = threadIdx.x; i < rb; i += THREADS) cur[i] = 0u;
+        __syncthreads();
+        const uint32_t g_hi = g_hi_s;
+        const uint32_t staged = offs[g_hi];
+        if (staged) {
+            for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {
+                unsigned long long e[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    if (e[u] == ~0ull) continue;
+                    const uint32_t rib = (uint32_t)(e[u] >> (KXB_SEED_BITS + 24));
+                    if (rib < g_lo || rib >= g_hi) continue;
+                    const uint32_t c = cnt[rib];
+                    if (!c) continue;
+                    const uint32_t rank = atomicAdd(&cur[rib], 1u);
+                    if (rank < c)  // key = position << 32 | seed: what kx_sort_one sorts
+                        recs[offs[rib] + rank] = ((unsigned long long)((uint32_t)e[u] & 0xffffffu) << 32) |
+                                                 (unsigned long long)((uint32_t)(e[u] >> 24) & ((1u << KXB_SEED_BITS) - 1u));
                 }
             }
-            return;
-        }
-        const int lane = dp_lane(), wave = threadIdx.x >> 6;
-        const uint32_t bin = blockIdx.x;
-        const uint32_t rb = 1u << B.bshift, first = bin << B.bshift;
-        const uint32_t n = min(B.cursor[bin], B.cap);
-        for (uint32_t i = threadIdx.x; i < rb; i += THREADS) {
-            const uint32_t it = first + i;
-            uint32_t c = 0u;
-            if (it < n_read_items) {
-                // (everything a read's wave will want of memory, asked for at once: a wave sorts eight reads one after the other)
-                const dp_scan_item item = items[it];
-                const unsigned long long so = segoff[it];
-                c = counts[it];
-                if (c < item.min_seeds) c = 0u;
-                nks[i] = item.n_kmers;
-                sout[i] = so;
-            }
-            if (c > (uint32_t)MAXC || c > (uint32_t)CAP) {
-                atomicExch(overflow, 1u);
-                c = 0u;
-            }
-            cnt[i] = c;
         }
         __syncthreads();
-        const unsigned long long* rec = B.rec + (size_t)bin * B.cap;
-        uint32_t g_lo = 0u;
-        while (g_lo < rb) {
-            // the group: reads g_lo .. g_hi - 1, as many as the array holds (every read fits by itself: c <= CAP)
-            if (wave == 0) {
-                uint32_t acc = 0u, i = g_lo;
-                for (;;) {
-                    const uint32_t idx = i + (uint32_t)lane;
-                    const uint32_t c = idx < rb ? cnt[idx] : 0u;
-                    const uint32_t incl = (uint32_t)wave_incl_sum((int)c);
-                    const bool fits = idx < rb && acc + incl <= (uint32_t)CAP;  // (a prefix of the lanes: the sums do not decrease)
-                    const uint32_t nfit = (uint32_t)__popcll(__ballot(fits));
-                    if (fits) offs[idx] = acc + incl - c;
-                    if (nfit) acc += (uint32_t)__shfl((int)incl, (int)nfit - 1, 64);
-                    i += nfit;
-                    if (nfit < 64u) break;
-                }
-                if (lane == 0) {
-                    offs[i] = acc;
-                    g_hi_s = i;
-                }
+        for (uint32_t i = g_lo + (uint32_t)wave; i < g_hi; i += WAVES) {
+            const uint32_t c = cnt[i];
+            if (!c) continue;
+            unsigned long long* my = recs + offs[i];
+            if (c <= 128u) kx_rank_in_place<2>(my, c, lane);
+            else if (c <= 256u) kx_rank_in_place<4>(my, c, lane);
+            else if (c <= 512u) kx_rank_in_place<8>(my, c, lane);
+            else kx_rank_in_place<RPL>(my, c, lane);
+            const uint64_t out = sout[i];
+            const int nk = (int)nks[i];
+            for (uint32_t j = lane; j < c; j += 64) {
+                const int p = (int)(my[j] >> 32);
+                const int prev = j ? (int)(my[j - 1] >> 32) : -k;  // "-k": the first gap is the hit's own index
+                segs[out + 2 * (uint64_t)j] = p - (prev + k);
+                segs[out + 2 * (uint64_t)j + 1] = (int32_t)(uint32_t)my[j];
             }
-            for (uint32_t i = threadIdx.x; i < rb; i += THREADS) cur[i] = 0u;
-            __syncthreads();
-            const uint32_t g_hi = g_hi_s;
-            const uint32_t staged = offs[g_hi];
-            if (staged) {
-                for (uint32_t jb = 4u * threadIdx.x; jb < n; jb += 4u * THREADS) {
-                    unsigned long long e[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) e[u] = jb + (uint32_t)u < n ? rec[jb + u] : ~0ull;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        if (e[u] == ~0ull) continue;
-                        const uint32_t rib = (uint32_t)(e[u] >> (KXB_SEED_BITS + 24));
-                        if (rib < g_lo || rib >= g_hi) continue;
-                        const uint32_t c = cnt[rib];
-                        if (!c) continue;
-                        const uint32_t rank = atomicAdd(&cur[rib], 1u);
-                        if (rank < c)  // key = position << 32 | seed: what kx_sort_one sorts
-                            recs[offs[rib] + rank] = ((unsigned long long)((uint32_t)e[u] & 0xffffffu) << 32) |
-                                                     (unsigned long long)((uint32_t)(e[u] >> 24) & ((1u << KXB_SEED_BITS) - 1u));
-                    }
-                }
-            }
-            __syncthreads();
-            for (uint32_t i = g_lo + (uint32_t)wave; i < g_hi; i += WAVES) {
-                const uint32_t c = cnt[i];
-                if (!c) continue;
-                unsigned long long* my = recs + offs[i];
-                if (c <= 128u) rank_in_place<2>(my, c, lane);
-                else if (c <= 256u) rank_in_place<4>(my, c, lane);
-                else if (c <= 512u) rank_in_place<8>(my, c, lane);
-                else rank_in_place<RPL>(my, c, lane);
-                const uint64_t out = sout[i];
-                const int nk = (int)nks[i];
-                for (uint32_t j = lane; j < c; j += 64) {
-                    const int p = (int)(my[j] >> 32);
-                    const int prev = j ? (int)(my[j - 1] >> 32) : -k;  // "-k": the first gap is the hit's own index
-                    segs[out + 2 * (uint64_t)j] = p - (prev + k);
-                    segs[out + 2 * (uint64_t)j + 1] = (int32_t)(uint32_t)my[j];
-                }
-                if (lane == 0) segs[out + 2 * (uint64_t)c] = nk - (int)(my[c - 1] >> 32) - 1;  // final gap (sequence/asm_amd64.s:387-392)
-            }
-            __syncthreads();
-            g_lo = g_hi;
+            if (lane == 0) segs[out + 2 * (uint64_t)c] = nk - (int)(my[c - 1] >> 32) - 1;  // final gap (sequence/asm_amd64.s:387-392)
         }
+        __syncthreads();
+        g_lo = g_hi;
     }
-};
+}
 
 // lanes per seed of kidx_walk: by the mean bucket size of the index (positions / 4^k)
 static uint32_t kidx_lps(const dp_kindex* ix, int k) {
@@ -1740,8 +1717,8 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     DP_HIP(dp_mark(ctx, 0));
     {
         const uint32_t n_thr = std::max(std::max(n_work, n_items), std::max(n_extra, 16u));
-        dp_launch<kidx_prepare>(ctx, dim3((n_thr + 255) / 256), dim3(256), (uint32_t*)ctx->d_kx_sz.p, n_work, d_counts, n_items,
-                           (uint32_t*)d_totals, const_cast<dp_scan_item*>(d_items), n_read_items, n_extra, head, next,
+        hipLaunchKernelGGL(kidx_prepare, dim3((n_thr + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t*)ctx->d_kx_sz.p, n_work, d_counts,
+                           n_items, (uint32_t*)d_totals, const_cast<dp_scan_item*>(d_items), n_read_items, n_extra, head, next,
                            ctx->extras_staged ? (const dp_scan_item*)ctx->h_extra.p : (const dp_scan_item*)nullptr);
         ctx->extras_staged = false;
     }
@@ -1834,17 +1811,19 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     if (S && B.rec) {
         const uint32_t n_waves = kidx_walk_blocks(ix, k, S) * 4;
         const int bin_waves = (int)dp_tune("kx_bin_waves", 8);
-#define KX_WALK_BIN(W_)                                                                                                                            \
-    dp_launch<kidx_walk_bin<W_>>(ctx, dim3((n_waves + W_ - 1) / W_), dim3(64 * W_), dp_seeds_ptr(ctx), S, (const uint64_t*)ix->off.p, ix->view(), \
-                                 d_items, lo, hi, n_read_items, (const uint32_t*)head, (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves)
+#define KX_WALK_BIN(W_)                                                                                                                \
+    hipLaunchKernelGGL((kidx_walk_bin<W_>), dim3((n_waves + W_ - 1) / W_), dim3(64 * W_), 0, ctx->stream, dp_seeds_ptr(ctx), S,        \
+                       (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head, (const uint32_t*)next, \
+                       d_counts, n_hits, lps, B, n_waves)
         // (dense: 16 waves - four seeds a trip; measured at k = 10, five slots: 0.582 against 0.606 s per job, profiles/r06/k10_knobs.txt)
         if (dense) {
             // (trips per reservation: as many as make ONE workgroup per CU cover the round's waves - a 16-wave workgroup with its 105 VGPRs
             // is alone on its CU, and 313 of them on 256 CUs were two rounds of workgroups for 1.2 rounds of work)
             B.batch = std::max<uint32_t>(1u, std::min<uint32_t>(32u, (n_waves + 16u * 256u - 1) / (16u * 256u)));
             const uint32_t per = 16u * B.batch;
-            dp_launch<kidx_walk_bin<16>>(ctx, dim3((n_waves + per - 1) / per), dim3(64 * 16), dp_seeds_ptr(ctx), S, (const uint64_t*)ix->off.p, ix->view(),
-                                         d_items, lo, hi, n_read_items, (const uint32_t*)head, (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves);
+            hipLaunchKernelGGL((kidx_walk_bin<16>), dim3((n_waves + per - 1) / per), dim3(64 * 16), 0, ctx->stream, dp_seeds_ptr(ctx), S,
+                               (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
+                               (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves);
         } else if (bin_waves <= 4) KX_WALK_BIN(4);
         else if (bin_waves <= 8) KX_WALK_BIN(8);
         else KX_WALK_BIN(16);
@@ -1855,11 +1834,11 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         count_in_offsets = !fuse_off && !dense && (1u << B.bshift) <= KX_TILE * KX_IPT;
         if (count_in_offsets) {
         } else if (B.bshift <= 9)
-            dp_launch<kidx_bin_count<512>>(ctx, dim3(B.n_bins), dim3(512), B, d_counts, n_read_items, lo);
+            hipLaunchKernelGGL((kidx_bin_count<512>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
         else if (B.bshift <= 12)
-            dp_launch<kidx_bin_count<4096>>(ctx, dim3(B.n_bins), dim3(512), B, d_counts, n_read_items, lo);
+            hipLaunchKernelGGL((kidx_bin_count<4096>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
         else
-            dp_launch<kidx_bin_count<16384>>(ctx, dim3(B.n_bins), dim3(512), B, d_counts, n_read_items, lo);
+            hipLaunchKernelGGL((kidx_bin_count<16384>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
         if (ctx->dbg.kx_bins) {  // (diagnosis: waits for the stream) how full the bins and the extra list are
             std::vector<uint32_t> cur((size_t)KX_MAXBINS + 2);
             uint64_t fl = 0;
@@ -1874,10 +1853,10 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
                     (unsigned long long)(one ? one->hits_guess : 0));
         }
     } else if (S)
-        dp_launch<kidx_walk<false>>(ctx, dim3(kidx_walk_grid(ix, k, S)), dim3(256), dp_seeds_ptr(ctx), S,
+        hipLaunchKernelGGL((kidx_walk<false>), dim3(kidx_walk_grid(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                            (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
-                           (const uint32_t*)next, d_counts, fillc, (const uint64_t*)nullptr, (int32_t*)nullptr, n_hits, kidx_lps(ix, k), dbg, R,
-                           kidx_walk_blocks(ix, k, S) * 4);
+                           (const uint32_t*)next, d_counts, fillc, (const uint64_t*)nullptr, (int32_t*)nullptr, n_hits, kidx_lps(ix, k),
+                           dbg, R, kidx_walk_blocks(ix, k, S) * 4);
     if (kx_debug) {
         std::vector<unsigned long long> h(n_dbg_waves * 8);
         hipStreamSynchronize(ctx->stream);
@@ -1907,8 +1886,8 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     {
         KxBins Bo = B;
         if (!count_in_offsets) Bo.rec = nullptr;
-        dp_launch<kidx_offsets>(ctx, dim3(n_tiles), dim3(KX_TILE), d_items, d_counts, n_items, status, ticket,
-                           d_segoff, s_item, s_count, s_off, s_pack, d_totals, n_read_items, (uint32_t*)(d_totals + 3),
+        hipLaunchKernelGGL(kidx_offsets, dim3(n_tiles), dim3(KX_TILE), 0, ctx->stream, d_items, d_counts, n_items, status, ticket, d_segoff,
+                           s_item, s_count, s_off, s_pack, d_totals, n_read_items, (uint32_t*)(d_totals + 3),
                            (const unsigned long long*)n_hits, host_totals, Bo, lo);
     }
     DP_HIP(hipGetLastError());
@@ -1916,24 +1895,24 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     if (one && R.rec) {
         DP_HIP(dp_mark(ctx, 2));
         if (B.rec && dense) {
-            dp_launch<kidx_bin_sort_dense<8192>>(ctx, dim3(B.n_bins + kidx_bin_sort_dense<8192>::XBLOCKS), dim3(512), B, d_items, n_read_items,
-                                                 (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals,
-                                                 one->seg_cap, k, (uint32_t*)(d_totals + 4));
+            hipLaunchKernelGGL((kidx_bin_sort_dense<8192>), dim3(B.n_bins + KX_XBLOCKS), dim3(512), 0, ctx->stream, B, d_items,
+                               n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff, one->d_segs,
+                               (const uint64_t*)d_totals, one->seg_cap, k, (uint32_t*)(d_totals + 4));
         } else if (B.rec) {
-            const dim3 fg(B.n_bins + kidx_bin_fill<512>::XBLOCKS), fb(512);
+            const dim3 fg(B.n_bins + KX_XBLOCKS), fb(512);
             if (B.bshift <= 9)
-                dp_launch<kidx_bin_fill<512>>(ctx, fg, fb, B, d_items, n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff,
-                                              one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
+                hipLaunchKernelGGL((kidx_bin_fill<512>), fg, fb, 0, ctx->stream, B, d_items, n_read_items, (const uint32_t*)d_counts, fillc,
+                                   (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
             else if (B.bshift <= 12)
-                dp_launch<kidx_bin_fill<4096>>(ctx, fg, fb, B, d_items, n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff,
-                                               one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
+                hipLaunchKernelGGL((kidx_bin_fill<4096>), fg, fb, 0, ctx->stream, B, d_items, n_read_items, (const uint32_t*)d_counts,
+                                   fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
             else
-                dp_launch<kidx_bin_fill<16384>>(ctx, fg, fb, B, d_items, n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff,
-                                                one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
+                hipLaunchKernelGGL((kidx_bin_fill<16384>), fg, fb, 0, ctx->stream, B, d_items, n_read_items, (const uint32_t*)d_counts,
+                                   fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
         } else
-        dp_launch<kidx_fill_rec>(ctx, dim3(kidx_walk_blocks(ix, k, S)), dim3(256), R, n_groups, lps, d_items, lo, n_read_items, one->min_seeds,
-                                 (const uint32_t*)head, (const uint32_t*)next, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff,
-                                 one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
+            hipLaunchKernelGGL(kidx_fill_rec, dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, R, n_groups, lps, d_items, lo,
+                               n_read_items, one->min_seeds, (const uint32_t*)head, (const uint32_t*)next, (const uint32_t*)d_counts,
+                               fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
         // (the survivor count is on the device only: the grid covers the most survivors a round of this context has had so far,
         // the kernel strides over the rest)
         const dim3 sg(dense ? std::max<uint32_t>(64u, std::min<uint32_t>(n_extra, 16384))
@@ -1941,17 +1920,17 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         uint32_t* ovf = (uint32_t*)(d_totals + 4);
         const uint32_t* nsp = (const uint32_t*)(d_totals + 1);
         if (one->sort_cap <= 256)
-            dp_launch<kidx_sortwrite<256>>(ctx, sg, sb, d_items, (const uint32_t*)s_item, nsp, (const uint32_t*)d_counts, (const uint64_t*)d_segoff,
-                                           one->d_segs, k, ovf, n_read_items, n_extra, head, one->host_segs, (const uint64_t*)d_totals, one->seg_cap,
-                                           dense ? 1u : 0u);
+            hipLaunchKernelGGL((kidx_sortwrite<256>), sg, sb, 0, ctx->stream, d_items, (const uint32_t*)s_item, nsp,
+                               (const uint32_t*)d_counts, (const uint64_t*)d_segoff, one->d_segs, k, ovf, n_read_items, n_extra, head,
+                               one->host_segs, (const uint64_t*)d_totals, one->seg_cap, dense ? 1u : 0u);
         else if (one->sort_cap <= 1024)
-            dp_launch<kidx_sortwrite<1024>>(ctx, sg, sb, d_items, (const uint32_t*)s_item, nsp, (const uint32_t*)d_counts, (const uint64_t*)d_segoff,
-                                            one->d_segs, k, ovf, n_read_items, n_extra, head, one->host_segs, (const uint64_t*)d_totals, one->seg_cap,
-                                            dense ? 1u : 0u);
+            hipLaunchKernelGGL((kidx_sortwrite<1024>), sg, sb, 0, ctx->stream, d_items, (const uint32_t*)s_item, nsp,
+                               (const uint32_t*)d_counts, (const uint64_t*)d_segoff, one->d_segs, k, ovf, n_read_items, n_extra, head,
+                               one->host_segs, (const uint64_t*)d_totals, one->seg_cap, dense ? 1u : 0u);
         else
-            dp_launch<kidx_sortwrite<KX_SORT_LDS>>(ctx, sg, sb, d_items, (const uint32_t*)s_item, nsp, (const uint32_t*)d_counts,
-                                                   (const uint64_t*)d_segoff, one->d_segs, k, ovf, n_read_items, n_extra, head, one->host_segs,
-                                                   (const uint64_t*)d_totals, one->seg_cap, 0u);
+            hipLaunchKernelGGL((kidx_sortwrite<KX_SORT_LDS>), sg, sb, 0, ctx->stream, d_items, (const uint32_t*)s_item, nsp,
+                               (const uint32_t*)d_counts, (const uint64_t*)d_segoff, one->d_segs, k, ovf, n_read_items, n_extra, head,
+                               one->host_segs, (const uint64_t*)d_totals, one->seg_cap, 0u);
         DP_HIP(hipGetLastError());
         DP_HIP(dp_mark(ctx, 3));
     }
@@ -1990,26 +1969,27 @@ int dp_kindex_write(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         rc = 1;
     } else if (n_sel) {
         if (S)
-            dp_launch<kidx_walk<true>>(ctx, dim3(kidx_walk_blocks(ix, k, S)), dim3(256), dp_seeds_ptr(ctx), S,
+            hipLaunchKernelGGL((kidx_walk<true>), dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                                (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
-                               (const uint32_t*)next, (uint32_t*)d_counts, fillc, d_segoff, d_segs, (unsigned long long*)nullptr, kidx_lps(ix, k),
-                               (unsigned long long*)nullptr, KxRec{nullptr, nullptr, nullptr, 0u, nullptr, 0u, 0u}, kidx_walk_blocks(ix, k, S) * 4);
+                               (const uint32_t*)next, (uint32_t*)d_counts, fillc, d_segoff, d_segs, (unsigned long long*)nullptr,
+                               kidx_lps(ix, k), (unsigned long long*)nullptr, KxRec{nullptr, nullptr, nullptr, 0u, nullptr, 0u, 0u},
+                               kidx_walk_blocks(ix, k, S) * 4);
         const dim3 sg(std::min<uint32_t>(n_sel, 16384)), sb(64);
         uint32_t* ovf = (uint32_t*)(d_totals + 4);
         const uint32_t* nsp = (const uint32_t*)(d_totals + 1);
         if (max_count <= 128)
-            dp_launch<kidx_sortwrite<256>>(ctx, sg, sb, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf, n_read_items,
-                               n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);
-        else if (max_count <= 512)
-            dp_launch<kidx_sortwrite<1024>>(ctx, sg, sb, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf, n_read_items,
-                               n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);
-        else
-            dp_launch<kidx_sortwrite<KX_SORT_LDS>>(ctx, sg, sb, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf,
+            hipLaunchKernelGGL((kidx_sortwrite<256>), sg, sb, 0, ctx->stream, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf,
                                n_read_items, n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);
+        else if (max_count <= 512)
+            hipLaunchKernelGGL((kidx_sortwrite<1024>), sg, sb, 0, ctx->stream, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf,
+                               n_read_items, n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);
+        else
+            hipLaunchKernelGGL((kidx_sortwrite<KX_SORT_LDS>), sg, sb, 0, ctx->stream, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k,
+                               ovf, n_read_items, n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);
         DP_HIP(hipGetLastError());
     }
     if (n_extra && (rc != DP_OK || !n_sel))  // (otherwise the sort kernel has put head[] back to zero)
-        dp_launch<kidx_unlink_extra>(ctx, dim3((n_extra + 255) / 256), dim3(256), d_items, n_read_items, n_extra, head);
+        hipLaunchKernelGGL(kidx_unlink_extra, dim3((n_extra + 255) / 256), dim3(256), 0, ctx->stream, d_items, n_read_items, n_extra, head);
     DP_HIP(hipGetLastError());
     return rc;
 }

@@ -14,7 +14,6 @@
 #include <cstring>
 
 #include "dp_common.h"
-#include "dp_launch.h"
 
 typedef uint64_t u64;
 
@@ -24,11 +23,10 @@ typedef uint64_t u64;
 // the chaining stage's cursor block: 32 words (cursor, flags, totals) + 64 shards of its algorithmic-byte count (one counter
 // would be a thousand same-address atomics per kernel: 12 ns each, in a row)
 #define C_CURSOR_BYTES 640
-struct index_fill_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const dp_seq_ref* __restrict__ refs, uint32_t n_seqs, const int32_t* __restrict__ segs,
-                                  u64* __restrict__ posting, u64* __restrict__ seedsets, uint32_t W, uint32_t SW,
-                                  const uint32_t* __restrict__ n_seqs_dev) {
+__global__ __launch_bounds__(256) void index_fill_kernel(const dp_seq_ref* __restrict__ refs, uint32_t n_seqs,
+                                                         const int32_t* __restrict__ segs, u64* __restrict__ posting,
+                                                         u64* __restrict__ seedsets, uint32_t W, uint32_t SW,
+                                                         const uint32_t* __restrict__ n_seqs_dev) {
     if (n_seqs_dev) n_seqs = *n_seqs_dev;  // (chunks made on the device: the launch was sized for an upper bound)
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
     const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -42,7 +40,6 @@ struct index_fill_kernel {
         }
     }
 }
-};
 
 // ---- round 4: the two bit matrices without atomics (sparse regime) ----------------------------------------------------------
 // A scattered device-scope atomic costs a five-slot job what it costs alone (HISTORY.md 5.7) and index_fill_kernel issued two per
@@ -50,94 +47,88 @@ struct index_fill_kernel {
 // to ONE wave: it is built in LDS (ds_or) and stored whole - rows need no clearing, rows beyond the chunk count are never read.
 // The posting matrix is the bit transpose of the seed sets: posting[s][w] bit b = seedsets[64 w + b][s / 64] bit (s % 64).
 #define IFR_SW_MAX 512  // seed-set words per row this path holds in LDS (32 768 seeds)
-struct index_fill_rows_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const dp_seq_ref* __restrict__ refs, const int32_t* __restrict__ segs, u64* __restrict__ seedsets,
-                               uint32_t SW, const uint32_t* __restrict__ n_seqs_dev) {
-        __shared__ u64 rows[4][IFR_SW_MAX];
-        u64* row = rows[threadIdx.x >> 6];
-        const uint32_t n_seqs = *n_seqs_dev;
-        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
-        const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        const int lane = dp_lane();
-        for (uint32_t idx = gw; idx < n_seqs; idx += waves) {
-            for (uint32_t x = lane; x < SW; x += 64) row[x] = 0ull;
-            __builtin_amdgcn_wave_barrier();
-            const dp_seq_ref r = refs[idx];
-            for (uint32_t i = lane; i < r.n_seeds; i += 64) {
-                const uint32_t seed = (uint32_t)segs[r.seg_off + 2 * (uint64_t)i + 1];
-                atomicOr(&row[seed >> 6], 1ull << (seed & 63));
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t x = lane; x < SW; x += 64) seedsets[(uint64_t)idx * SW + x] = row[x];
-            __builtin_amdgcn_wave_barrier();
+__global__ __launch_bounds__(256) void index_fill_rows_kernel(const dp_seq_ref* __restrict__ refs, const int32_t* __restrict__ segs,
+        u64* __restrict__ seedsets, uint32_t SW, const uint32_t* __restrict__ n_seqs_dev) {
+    __shared__ u64 rows[4][IFR_SW_MAX];
+    u64* row = rows[threadIdx.x >> 6];
+    const uint32_t n_seqs = *n_seqs_dev;
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = dp_lane();
+    for (uint32_t idx = gw; idx < n_seqs; idx += waves) {
+        for (uint32_t x = lane; x < SW; x += 64) row[x] = 0ull;
+        __builtin_amdgcn_wave_barrier();
+        const dp_seq_ref r = refs[idx];
+        for (uint32_t i = lane; i < r.n_seeds; i += 64) {
+            const uint32_t seed = (uint32_t)segs[r.seg_off + 2 * (uint64_t)i + 1];
+            atomicOr(&row[seed >> 6], 1ull << (seed & 63));
         }
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t x = lane; x < SW; x += 64) seedsets[(uint64_t)idx * SW + x] = row[x];
+        __builtin_amdgcn_wave_barrier();
     }
-};
+}
 // one wave per (eight words of posting rows, FOUR consecutive words of seed-set rows): thirty-two 64 x 64 bit transposes across the lanes;
 // lane j ends up with the eight words of seeds 64 (sw0 + i) + j, i = 0 .. 3 - four 64-byte stores.  (Round 6: one seed-set word per wave
 // and task made every lane's 8-byte load a sector of its own - 64 rows, 2.5 KB apart - of which an eighth was used: the launch
 // fetched 808 MB for a 240 MB matrix at k = 10, profiles/r05/pmc_dense.json.  Four words per lane are a lane's whole 32-byte sector,
 // and the four waves of a workgroup take the four quarters of the rows' 128-byte lines.)
-struct posting_transpose_kernel {
-    enum { THREADS = 256, SWPT = 4 };
-    static __device__ void run(const u64* __restrict__ seedsets, u64* __restrict__ posting, uint32_t n_seeds, uint32_t W, uint32_t SW,
-                               const uint32_t* __restrict__ n_seqs_dev) {
-        const uint32_t n_seqs = *n_seqs_dev;
-        const uint32_t wchunks = (W + 7) / 8;
-        const uint32_t swg = (SW + SWPT - 1) / SWPT;
-        const uint32_t tasks = wchunks * swg;
-        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
-        const int lane = dp_lane();
-        for (uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < tasks; t += waves) {
-            const uint32_t sw0 = (t % swg) * SWPT, w0 = (t / swg) * 8;
-            u64 x[8][SWPT];
+constexpr int PT_SWPT = 4;  // seed-set words of a wave's task
+__global__ __launch_bounds__(256) void posting_transpose_kernel(const u64* __restrict__ seedsets, u64* __restrict__ posting,
+        uint32_t n_seeds, uint32_t W, uint32_t SW, const uint32_t* __restrict__ n_seqs_dev) {
+    const uint32_t n_seqs = *n_seqs_dev;
+    const uint32_t wchunks = (W + 7) / 8;
+    const uint32_t swg = (SW + PT_SWPT - 1) / PT_SWPT;
+    const uint32_t tasks = wchunks * swg;
+    const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+    const int lane = dp_lane();
+    for (uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < tasks; t += waves) {
+        const uint32_t sw0 = (t % swg) * PT_SWPT, w0 = (t / swg) * 8;
+        u64 x[8][PT_SWPT];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const uint64_t rowi = (uint64_t)(w0 + u) * 64 + (uint32_t)lane;
+            const bool rv = w0 + u < W && rowi < n_seqs;
+            const u64* src = seedsets + rowi * SW + sw0;
+#pragma unroll
+            for (int i = 0; i < PT_SWPT; i++) x[u][i] = (rv && sw0 + i < SW) ? src[i] : 0ull;
+        }
+#pragma unroll
+        for (int i = 0; i < PT_SWPT; i++) {
+            // 64 x 64 bit transpose across the lanes (row r of the block in lane r): six exchange stages instead of 64 ballots
+            u64 out[8];
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-                const uint64_t rowi = (uint64_t)(w0 + u) * 64 + (uint32_t)lane;
-                const bool rv = w0 + u < W && rowi < n_seqs;
-                const u64* src = seedsets + rowi * SW + sw0;
-#pragma unroll
-                for (int i = 0; i < SWPT; i++) x[u][i] = (rv && sw0 + i < SW) ? src[i] : 0ull;
-            }
-#pragma unroll
-            for (int i = 0; i < SWPT; i++) {
-                // 64 x 64 bit transpose across the lanes (row r of the block in lane r): six exchange stages instead of 64 ballots
-                u64 out[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    u64 v = x[u][i];
-                    if (__ballot(v != 0) != 0) {  // (else: sixty-four chunks none of which holds any of these sixty-four seeds)
+                u64 v = x[u][i];
+                if (__ballot(v != 0) != 0) {  // (else: sixty-four chunks none of which holds any of these sixty-four seeds)
 #define PT_STAGE(j_, m_)                                                              \
     {                                                                                 \
         const u64 y_ = (u64)__shfl_xor((unsigned long long)v, (j_), 64);              \
         if ((lane & (j_)) == 0) v ^= ((((v >> (j_)) ^ y_) & (m_)) << (j_));           \
         else v ^= (((y_ >> (j_)) ^ v) & (m_));                                        \
     }
-                        PT_STAGE(32, 0x00000000FFFFFFFFull)
-                        PT_STAGE(16, 0x0000FFFF0000FFFFull)
-                        PT_STAGE(8, 0x00FF00FF00FF00FFull)
-                        PT_STAGE(4, 0x0F0F0F0F0F0F0F0Full)
-                        PT_STAGE(2, 0x3333333333333333ull)
-                        PT_STAGE(1, 0x5555555555555555ull)
+                    PT_STAGE(32, 0x00000000FFFFFFFFull)
+                    PT_STAGE(16, 0x0000FFFF0000FFFFull)
+                    PT_STAGE(8, 0x00FF00FF00FF00FFull)
+                    PT_STAGE(4, 0x0F0F0F0F0F0F0F0Full)
+                    PT_STAGE(2, 0x3333333333333333ull)
+                    PT_STAGE(1, 0x5555555555555555ull)
 #undef PT_STAGE
-                    }
-                    out[u] = v;
                 }
-                const uint32_t seed = (sw0 + (uint32_t)i) * 64 + (uint32_t)lane;
-                if (sw0 + (uint32_t)i < SW && seed < n_seeds) {
+                out[u] = v;
+            }
+            const uint32_t seed = (sw0 + (uint32_t)i) * 64 + (uint32_t)lane;
+            if (sw0 + (uint32_t)i < SW && seed < n_seeds) {
 #pragma unroll
-                    for (int u = 0; u < 8; u++)
-                        if (w0 + u < W) posting[(uint64_t)seed * W + w0 + u] = out[u];
-                }
+                for (int u = 0; u < 8; u++)
+                    if (w0 + u < W) posting[(uint64_t)seed * W + w0 + u] = out[u];
             }
         }
     }
-};
+}
 
-struct posting_meta_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const u64* __restrict__ posting, uint32_t n_seeds, uint32_t W, uint32_t* __restrict__ pmeta) {
+__global__ __launch_bounds__(256) void posting_meta_kernel(const u64* __restrict__ posting, uint32_t n_seeds, uint32_t W,
+                                                           uint32_t* __restrict__ pmeta) {
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
     const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = dp_lane();
@@ -170,7 +161,6 @@ struct posting_meta_kernel {
         }
     }
 }
-};
 
 int dp_index_build_impl(dp_ctx* ctx, const dp_seq_ref* seqs, uint32_t n_seqs) {
     if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_index_build before dp_round_begin");
@@ -203,13 +193,13 @@ int dp_index_build_impl(dp_ctx* ctx, const dp_seq_ref* seqs, uint32_t n_seqs) {
         DP_HIP(hipMemcpyAsync(ctx->d_seqrefs.p, dp_stage(ctx, seqs, (size_t)n_seqs * sizeof(dp_seq_ref)), (size_t)n_seqs * sizeof(dp_seq_ref),
                               hipMemcpyHostToDevice, ctx->stream));
         uint32_t blocks = std::min<uint32_t>(2048, (n_seqs + 3) / 4);
-        dp_launch<index_fill_kernel>(ctx, dim3(blocks), dim3(256), (const dp_seq_ref*)ctx->d_seqrefs.p, n_seqs,
+        hipLaunchKernelGGL(index_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const dp_seq_ref*)ctx->d_seqrefs.p, n_seqs,
                            (const int32_t*)ctx->d_segs.p, (u64*)ctx->d_posting.p, (u64*)ctx->d_seedsets.p, W, SW, (const uint32_t*)nullptr);
         DP_HIP(hipGetLastError());
     }
     if (S) {
         uint32_t blocks = std::min<uint32_t>(2048, (S + 3) / 4);
-        dp_launch<posting_meta_kernel>(ctx, dim3(blocks), dim3(256), (const u64*)ctx->d_posting.p, S, W,
+        hipLaunchKernelGGL(posting_meta_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const u64*)ctx->d_posting.p, S, W,
                            (uint32_t*)ctx->d_pmeta.p);
         DP_HIP(hipGetLastError());
     }
@@ -381,9 +371,9 @@ __device__ uint32_t chunk_one(const ChunkParams& P, uint32_t i, uint32_t at, Chu
 
 // status word of a tile of 1024 survivors: flag << 62 | chunks (flag 1 = the tile's own count, 2 = inclusive prefix); tiles take
 // their number from a ticket, so a predecessor is always running or done (the look-back cannot wait for a tile that has no CU)
-struct chunk_kernel {
+__global__ __launch_bounds__(1024) void chunk_kernel(const ChunkParams P, unsigned long long* __restrict__ status,
+                                                     uint32_t* __restrict__ ticket) {
     enum { THREADS = 1024 };
-    static __device__ void run(const ChunkParams P, unsigned long long* __restrict__ status, uint32_t* __restrict__ ticket) {
     __shared__ uint32_t wsum[16];
     __shared__ uint32_t tile_s, base_s;
     __shared__ ChunkCache cache[THREADS];
@@ -402,7 +392,8 @@ struct chunk_kernel {
             return;
         }
     }
-    // (a launch shared with other rounds has the largest round's grid: blocks beyond this round's own tiles take no ticket)
+    // (behind a guessed scan the grid holds P.grid_tiles tiles, the survivors may need fewer: the blocks beyond their tiles take no
+    // ticket - the first P.zero_blocks of them clear and fetch, the rest have nothing to do)
     const uint32_t n_tiles = (ns + 1023u) / 1024u;
     if (n_tiles == 0 && blockIdx.x == 0 && threadIdx.x == 0) {  // (no survivor: no tile writes the count)
         P.n_out[0] = 0u;
@@ -487,7 +478,6 @@ struct chunk_kernel {
         }
     }
 }
-};
 
 // upper bound of the chunks chunkWorker makes of a read with `numSeeds` hits: every chunk but the last holds >= minSeeds seeds
 // and the walk backs up at most 5 seeds (or overlap/2 bases) after each
@@ -585,21 +575,22 @@ static int index_chunked_launch(dp_ctx* ctx, int64_t chunk_size, int64_t overlap
             P.f_n16 = (ctx->q_pre_bytes + 15) / 16;
             ctx->q_pre_fetched = true;
         }
-        dp_launch<chunk_kernel>(ctx, dim3(n_tiles + P.zero_blocks), dim3(1024), P, (unsigned long long*)((uint8_t*)ctx->d_nseqs.p + 64),
-                           (uint32_t*)ctx->d_nseqs.p + 2);
+        hipLaunchKernelGGL(chunk_kernel, dim3(n_tiles + P.zero_blocks), dim3(1024), 0, ctx->stream, P,
+                           (unsigned long long*)((uint8_t*)ctx->d_nseqs.p + 64), (uint32_t*)ctx->d_nseqs.p + 2);
         DP_HIP(hipGetLastError());
         if (cap && rows_mode) {
             const uint32_t blocks = std::min<uint32_t>(2048, (cap + 3) / 4);
-            dp_launch<index_fill_rows_kernel>(ctx, dim3(blocks), dim3(256), (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p,
-                                              (u64*)ctx->d_seedsets.p, SW, (const uint32_t*)ctx->d_nseqs.p);
-            const uint32_t tasks = ((W + 7) / 8) * ((SW + posting_transpose_kernel::SWPT - 1) / posting_transpose_kernel::SWPT);
-            dp_launch<posting_transpose_kernel>(ctx, dim3(std::min<uint32_t>(4096, (tasks + 3) / 4)), dim3(256), (const u64*)ctx->d_seedsets.p,
-                                                    (u64*)ctx->d_posting.p, S, W, SW, (const uint32_t*)ctx->d_nseqs.p);
+            hipLaunchKernelGGL(index_fill_rows_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const dp_seq_ref*)ctx->d_seqrefs.p,
+                               (const int32_t*)ctx->d_segs.p, (u64*)ctx->d_seedsets.p, SW, (const uint32_t*)ctx->d_nseqs.p);
+            const uint32_t tasks = ((W + 7) / 8) * ((SW + PT_SWPT - 1) / PT_SWPT);
+            hipLaunchKernelGGL(posting_transpose_kernel, dim3(std::min<uint32_t>(4096, (tasks + 3) / 4)), dim3(256), 0, ctx->stream,
+                               (const u64*)ctx->d_seedsets.p, (u64*)ctx->d_posting.p, S, W, SW, (const uint32_t*)ctx->d_nseqs.p);
             DP_HIP(hipGetLastError());
         } else if (cap) {
             const uint32_t blocks = std::min<uint32_t>(2048, (cap + 3) / 4);
-            dp_launch<index_fill_kernel>(ctx, dim3(blocks), dim3(256), (const dp_seq_ref*)ctx->d_seqrefs.p, cap,
-                               (const int32_t*)ctx->d_segs.p, (u64*)ctx->d_posting.p, (u64*)ctx->d_seedsets.p, W, SW, (const uint32_t*)ctx->d_nseqs.p);
+            hipLaunchKernelGGL(index_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const dp_seq_ref*)ctx->d_seqrefs.p, cap,
+                               (const int32_t*)ctx->d_segs.p, (u64*)ctx->d_posting.p, (u64*)ctx->d_seedsets.p, W, SW,
+                               (const uint32_t*)ctx->d_nseqs.p);
             DP_HIP(hipGetLastError());
         }
     } else if (rows_mode && S) {
@@ -607,7 +598,8 @@ static int index_chunked_launch(dp_ctx* ctx, int64_t chunk_size, int64_t overlap
     }
     if (S) {
         const uint32_t blocks = std::min<uint32_t>(2048, (S + 3) / 4);
-        dp_launch<posting_meta_kernel>(ctx, dim3(blocks), dim3(256), (const u64*)ctx->d_posting.p, S, W, (uint32_t*)ctx->d_pmeta.p);
+        hipLaunchKernelGGL(posting_meta_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const u64*)ctx->d_posting.p, S, W,
+                           (uint32_t*)ctx->d_pmeta.p);
         DP_HIP(hipGetLastError());
     }
     DP_HIP(dp_mark(ctx, 9));
@@ -1012,35 +1004,17 @@ __device__ void q_sparse_ids(ST& S, uint32_t n, int minCount, int64_t w_lo, int6
 // (minCount >= 13: queries of fifty seeds and more), whose 17-level ladder and bit-sliced counter need twice the registers.  The
 // light kernel alone then runs at eight waves per SIMD instead of four; the heavy one is launched only when a query of the batch
 // can reach minCount 13 at all.
-template <bool HEAVY, bool BIG = false>
-struct query_kernel {
-    enum { THREADS = 64 * Q_WAVES };
+// SPARSE (query_sparse_kernel): `posting` is the sparse index's post_off, sp_ids its post_ids; the set list is prepared as in the
+// heavy variant (every regime: the gather order is recorded for the 16-ladder's queries) and the light variant's qmeta is written
+template <bool HEAVY, bool BIG, bool SPARSE = false>
+__device__ void query_body(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, const u64* __restrict__ posting,
+                           const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W, const int32_t* __restrict__ mc, uint32_t mc_n,
+                           u64* __restrict__ cand, uint32_t* __restrict__ qmeta, u64* __restrict__ words_read, uint32_t* __restrict__ qcnt,
+                           uint32_t word_base, const uint32_t* __restrict__ n_seqs_dev, u64* __restrict__ qsets, uint32_t SW,
+                           uint32_t dbg_flags, uint32_t split, u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws,
+                           uint32_t big_stride, const uint32_t* __restrict__ sp_ids = nullptr) {
     typedef typename std::conditional<BIG, QBig, QWave>::type ST;
-    static __device__ void run(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, const u64* __restrict__ posting,
-                               const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W, const int32_t* __restrict__ mc, uint32_t mc_n,
-                               u64* __restrict__ cand, uint32_t* __restrict__ qmeta, u64* __restrict__ words_read, uint32_t* __restrict__ qcnt,
-                               uint32_t word_base, const uint32_t* __restrict__ n_seqs_dev, u64* __restrict__ qsets, uint32_t SW,
-                               uint32_t dbg_flags, uint32_t split, u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws,
-                               uint32_t big_stride) {
-        // (the pair-offset scan as the last act of this launch's last workgroup - an experiment of round 5 - cost a release fence per
-        // workgroup, more than the launch it saved: profiles/r05/ab12_query_scan.txt; removed in round 6)
-        if (blockIdx.x < nq * split)
-            body(qsegs, qoff, nq, posting, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt, word_base, n_seqs_dev, qsets, SW, dbg_flags, split, own_zero,
-                 big_ws, big_stride);
-    }
-    // SPARSE (query_sparse_kernel): `posting` is the sparse index's post_off, sp_ids its post_ids; the set list is prepared as in the
-    // heavy variant (every regime: the gather order is recorded for the 16-ladder's queries) and the light variant's qmeta is written
-    template <bool SPARSE = false>
-    static __device__ void body(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff,
-                                                             uint32_t nq, const u64* __restrict__ posting,
-                                                             const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W,
-                                                             const int32_t* __restrict__ mc, uint32_t mc_n,
-                                                             u64* __restrict__ cand, uint32_t* __restrict__ qmeta,
-                                                             u64* __restrict__ words_read, uint32_t* __restrict__ qcnt,
-                                                             uint32_t word_base, const uint32_t* __restrict__ n_seqs_dev,
-                                                             u64* __restrict__ qsets, uint32_t SW, uint32_t dbg_flags, uint32_t split,
-                                                             u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws, uint32_t big_stride,
-                                                             const uint32_t* __restrict__ sp_ids = nullptr) {
+    enum { THREADS = 64 * Q_WAVES };
     if (n_seqs_dev) n_seqs = *n_seqs_dev;  // (chunks made on the device: the host only knows an upper bound)
     // word_base: a shard of a larger index (dp_index_set_global) holds the words [word_base, word_base + W) of every set; pmeta
     // and n_seqs then describe the WHOLE sets (global windows, counts), so the filter, the early-return cut and the gather
@@ -1373,53 +1347,57 @@ struct query_kernel {
         if (sh_u[5]) atomicAdd(&qcnt[q], sh_u[5]);
     }
 }
-};
+// (the pair-offset scan as the last act of this launch's last workgroup - an experiment of round 5 - cost a release fence per
+// workgroup, more than the launch it saved: profiles/r05/ab12_query_scan.txt; removed in round 6)
+template <bool HEAVY, bool BIG = false>
+__global__ __launch_bounds__(64 * Q_WAVES) void query_kernel(
+    const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, const u64* __restrict__ posting,
+    const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W, const int32_t* __restrict__ mc, uint32_t mc_n, u64* __restrict__ cand,
+    uint32_t* __restrict__ qmeta, u64* __restrict__ words_read, uint32_t* __restrict__ qcnt, uint32_t word_base,
+    const uint32_t* __restrict__ n_seqs_dev, u64* __restrict__ qsets, uint32_t SW, uint32_t dbg_flags, uint32_t split,
+    u64* __restrict__ own_zero, uint32_t* __restrict__ big_ws, uint32_t big_stride) {
+    query_body<HEAVY, BIG>(qsegs, qoff, nq, posting, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt, word_base, n_seqs_dev, qsets, SW,
+                           dbg_flags, split, own_zero, big_ws, big_stride);
+}
 
 // the index query on a sparse index: one workgroup per query, every regime in one launch (the BIG variant behind it for the queries
 // with more than Q_MAXSETS sets, as in the dense stage)
 template <bool BIG>
-struct query_sparse_kernel {
-    enum { THREADS = 64 * Q_WAVES };
-    static __device__ void run(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, const u64* __restrict__ post_off,
-                               const uint32_t* __restrict__ post_ids, const uint32_t* __restrict__ pmeta, uint32_t n_seqs, uint32_t W,
-                               const int32_t* __restrict__ mc, uint32_t mc_n, u64* __restrict__ cand, uint32_t* __restrict__ qmeta,
-                               u64* __restrict__ words_read, uint32_t* __restrict__ qcnt, uint32_t word_base, uint32_t* __restrict__ big_ws,
-                               uint32_t big_stride) {
-        if (blockIdx.x < nq)
-            query_kernel<true, BIG>::template body<true>(qsegs, qoff, nq, post_off, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt,
-                                                         word_base, (const uint32_t*)nullptr, (u64*)nullptr, 0u, 0u, 1u, (u64*)nullptr, big_ws,
-                                                         big_stride, post_ids);
-    }
-};
+__global__ __launch_bounds__(64 * Q_WAVES) void query_sparse_kernel(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff,
+        uint32_t nq, const u64* __restrict__ post_off, const uint32_t* __restrict__ post_ids, const uint32_t* __restrict__ pmeta,
+        uint32_t n_seqs, uint32_t W, const int32_t* __restrict__ mc, uint32_t mc_n, u64* __restrict__ cand, uint32_t* __restrict__ qmeta,
+        u64* __restrict__ words_read, uint32_t* __restrict__ qcnt, uint32_t word_base, uint32_t* __restrict__ big_ws, uint32_t big_stride) {
+    query_body<true, BIG, true>(qsegs, qoff, nq, post_off, pmeta, n_seqs, W, mc, mc_n, cand, qmeta, words_read, qcnt, word_base,
+                                (const uint32_t*)nullptr, (u64*)nullptr, 0u, 0u, 1u, (u64*)nullptr, big_ws, big_stride, post_ids);
+}
 
 // the windows' seeds in ascending order (repeats kept: the map kernel only asks "is x among them"), at wl + qoff[w] / 2 - a window
 // of n seeds has 2 n + 1 segment ints, so the lists do not overlap.  One workgroup per window: the rank of seed i is the number of
 // seeds below it plus the equal ones in front of it.
-struct window_list_kernel {
+__global__ __launch_bounds__(256) void window_list_kernel(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq,
+                                                          uint32_t* __restrict__ wl) {
     enum { THREADS = 256, LDS_SEEDS = 2048 };
-    static __device__ void run(const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff, uint32_t nq, uint32_t* __restrict__ wl) {
-        __shared__ uint32_t a[LDS_SEEDS];
-        for (uint32_t w = blockIdx.x; w < nq; w += gridDim.x) {
-            const int32_t* seg = qsegs + qoff[w];
-            const uint32_t ns = (uint32_t)((qoff[w + 1] - qoff[w]) / 2);
-            uint32_t* out = wl + qoff[w] / 2;
-            const bool inLds = ns <= LDS_SEEDS;
-            if (inLds)
-                for (uint32_t i = threadIdx.x; i < ns; i += THREADS) a[i] = (uint32_t)seg[2 * i + 1];
-            __syncthreads();
-            for (uint32_t i = threadIdx.x; i < ns; i += THREADS) {
-                const uint32_t v = inLds ? a[i] : (uint32_t)seg[2 * i + 1];
-                uint32_t r = 0;
-                for (uint32_t j = 0; j < ns; j++) {
-                    const uint32_t x = inLds ? a[j] : (uint32_t)seg[2 * j + 1];
-                    r += (x < v || (x == v && j < i)) ? 1u : 0u;
-                }
-                out[r] = v;
+    __shared__ uint32_t a[LDS_SEEDS];
+    for (uint32_t w = blockIdx.x; w < nq; w += gridDim.x) {
+        const int32_t* seg = qsegs + qoff[w];
+        const uint32_t ns = (uint32_t)((qoff[w + 1] - qoff[w]) / 2);
+        uint32_t* out = wl + qoff[w] / 2;
+        const bool inLds = ns <= LDS_SEEDS;
+        if (inLds)
+            for (uint32_t i = threadIdx.x; i < ns; i += THREADS) a[i] = (uint32_t)seg[2 * i + 1];
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < ns; i += THREADS) {
+            const uint32_t v = inLds ? a[i] : (uint32_t)seg[2 * i + 1];
+            uint32_t r = 0;
+            for (uint32_t j = 0; j < ns; j++) {
+                const uint32_t x = inLds ? a[j] : (uint32_t)seg[2 * j + 1];
+                r += (x < v || (x == v && j < i)) ? 1u : 0u;
             }
-            __syncthreads();
+            out[r] = v;
         }
+        __syncthreads();
     }
-};
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // A6 + A7 + A8: matchWorker body
@@ -1436,6 +1414,22 @@ struct ChainProf {  // ticks of 10 ns, summed per wave (profiling build)
     unsigned long long stageb, initial, walk, out, last;          // chain_pair's
     unsigned long long bev, nev, nperfect, why;  // why: 5 x 12-bit counts of why a pair was not a perfect chain          // wave_chain_reg's
 };
+// (profiling build) the ticks since `last_` go to prof_.field_; everything the wave has issued is waited for first
+#define CHAIN_TICK(enabled_, prof_, last_, field_)                   \
+    if (enabled_) {                                                  \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  \
+        const unsigned long long now_ = wall_clock64();              \
+        (prof_).field_ += now_ - (last_);                            \
+        (last_) = now_;                                              \
+    }
+// a wave's sums into its 16-word slot of the profile block (t0: when the wave entered its kernel)
+__device__ __forceinline__ void chain_prof_store(unsigned long long* slot, const ChainProf& pf, unsigned long long t0) {
+    slot[0] = pf.pairs, slot[1] = pf.chained, slot[2] = pf.rec, slot[3] = pf.stagea, slot[4] = pf.pre, slot[5] = pf.pair;
+    slot[6] = pf.stageb, slot[7] = pf.initial, slot[8] = pf.walk, slot[9] = pf.out;
+    slot[10] = t0;
+    slot[11] = wall_clock64();
+    slot[12] = pf.bev, slot[13] = pf.nev, slot[14] = pf.nperfect, slot[15] = pf.why;
+}
 #define C_WAVES 4
 #define S_WAVES 4  // waves per workgroup of the kernels on the slim layout
 #define C_OPEN 500       // len(align.open)          seeds/alignment.go:299
@@ -2406,14 +2400,13 @@ struct AnchorFetch {  // 8-byte words copied by the launch (either direction: pi
     const unsigned long long* src[3];
     unsigned long long n8[3];
 };
-struct match_anchor_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const MRec* __restrict__ recs, const uint32_t* __restrict__ n_pairs,
+__global__ __launch_bounds__(256) void match_anchor_kernel(const MRec* __restrict__ recs, const uint32_t* __restrict__ n_pairs,
                                                            uint32_t pair_cap, const int32_t* __restrict__ mb,
                                                            const dp_seq_ref* __restrict__ refs, const int32_t* __restrict__ segs, int k,
-                                                           int32_t* __restrict__ anchors, const AnchorFetch F, uint32_t* __restrict__ zero_word,
-                                                           const int32_t* __restrict__ ma, const int32_t* __restrict__ qsegs,
-                                                           const u64* __restrict__ qoff, int32_t* __restrict__ cover) {
+                                                           int32_t* __restrict__ anchors, const AnchorFetch F,
+                                                           uint32_t* __restrict__ zero_word, const int32_t* __restrict__ ma,
+                                                           const int32_t* __restrict__ qsegs, const u64* __restrict__ qoff,
+                                                           int32_t* __restrict__ cover) {
     const int lane = threadIdx.x & 63;
     if (zero_word && blockIdx.x == 0 && threadIdx.x < 2) zero_word[threadIdx.x] = 0;  // (the consensus stage's two list counters: next launches)
     // (the consensus kernel's input block - pinned host memory - is brought over by this launch, which runs just before it; a
@@ -2491,7 +2484,6 @@ struct match_anchor_kernel {
         }
     }
 }
-};
 
 // ---- the chaining stage: matchWorker's candidate loop (overlap/overlap.go:357-383) without its serial latency -------------
 // A query's candidates are chained in ascending order because of the ratchet: a chain longer than 3/2 minMatches raises
@@ -2560,8 +2552,6 @@ struct ChainArgs {
     int pack;             // 1: final chains are copied into ma/mb, densely (what a host fetch wants); 0: they stay where they were
                           // chained - the pair's scratch column - and the record's offset points there (ma = sa, mb = sb for the
                           // device consumers; dp_fetch_overlaps packs them then, should a host consumer turn up)
-    uint32_t walk_blocks; // grid of chain_walk_kernel for this round (its node pool is sized for it)
-    uint32_t walk0_blocks; // grid of its slim form (mode 0)
     uint32_t n_refs;      // entries of refs[] (indexed sequences, or their upper bound)
     uint32_t prof_walk_slot;   // first per-wave slot of walk(0) in prof[] (behind the passes')
     uint32_t prof_stride;      // per-wave slots of one pass
@@ -2569,14 +2559,11 @@ struct ChainArgs {
 };
 
 // per-query candidate counts -> pair / scratch offsets (one workgroup; a round has a few hundred to a few ten thousand queries)
-struct pair_scan_kernel {
-    enum { THREADS = 1024 };
-    static __device__ void run(const uint32_t* __restrict__ qcnt, const u64* __restrict__ qoff, uint32_t nq,
-                                                          uint32_t* __restrict__ pbase, u64* __restrict__ ibase, u64* __restrict__ totals) {
+__global__ __launch_bounds__(1024) void pair_scan_kernel(const uint32_t* __restrict__ qcnt, const u64* __restrict__ qoff, uint32_t nq,
+                                                         uint32_t* __restrict__ pbase, u64* __restrict__ ibase, u64* __restrict__ totals) {
     __shared__ u64 shp[1024], shi[1024];
     pair_scan_body<1024>(qcnt, qoff, nq, pbase, ibase, totals, shp, shi);
 }
-};
 
 // Load that goes to L2: for words another lane of this wave has just stored (a plain load may be served from a stale line of
 // the CU's vector L1).
@@ -2636,13 +2623,6 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
                           ChainProf* cp = nullptr, uint32_t* tierOut = nullptr) {
     const int lane = dp_lane();
     // (profiling build: ticks of: b staged + flags, initial positions, b events + chain walk, result out)
-#define CP_TICK(f_)                                                  \
-    if (DP_PROFILING && cp) {                                        \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  \
-        const unsigned long long n_ = wall_clock64();                \
-        cp->f_ += n_ - cp->last;                                     \
-        cp->last = n_;                                               \
-    }
     if (DP_PROFILING && cp) cp->last = wall_clock64();
     const u64* tset = A.seedsets + (uint64_t)t * A.SW;
     const dp_seq_ref r = rPre ? *rPre : A.refs[t];
@@ -2675,7 +2655,7 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
     }
     int resLen = 0, resNode = -1, usedTier = 3;
     uint32_t err = 0;
-    CP_TICK(stageb)
+    CHAIN_TICK(DP_PROFILING && cp, *cp, cp->last, stageb)
     if (staged) {
         const int mm = minMatches == 0 ? 1 : minMatches;
         int aLen = 0, startSize = 0;
@@ -2695,7 +2675,7 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
             }
             usedTier = 0;
         } else {
-            CP_TICK(initial)
+            CHAIN_TICK(DP_PROFILING && cp, *cp, cp->last, initial)
             resLen = -1;
             if (aLen <= 64 && (A.tier == 0 || LW::SLIM)) {
                 resLen = wave_chain_reg(aLen, startSize, bN, mm, k, L, &err, cp, A.walk_always != 0);
@@ -2719,7 +2699,7 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
             resNode = __shfl(resNode, 0, 64);
         }
     }
-    CP_TICK(walk)
+    CHAIN_TICK(DP_PROFILING && cp, *cp, cp->last, walk)
     if (tierOut) *tierOut = (uint32_t)usedTier;
     if (lane == 0 && err) atomicOr(&A.cursor[2], err);
     if (err) resLen = 0;
@@ -2742,31 +2722,25 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
             }
         }
     }
-    CP_TICK(out)
-#undef CP_TICK
+    CHAIN_TICK(DP_PROFILING && cp, *cp, cp->last, out)
     return resLen > 0 ? resLen : 0;
 }
 
 // mode 0: from the query's first candidate up to and including the first pair that is chained; 2 (last kernel of the stage):
 // whatever chain_resolve_kernel left open - proposals are taken where they fit, the rest is chained here, serially.
-// (mode 1 = mode 2 that stops instead of chaining: kept for experiments.)
 // SLIM (mode 0 only): the speculative kernel's 8.6 KB layout, one wave per query with sixteen of them on a CU instead of four
 // (a round's ~1 300 queries are then all resident at once: 45 -> 2x us); a pair that needs the full layout stops its query there
 // - it stays open, the proposal passes skip it and the final walk (full layout) chains it.
 // LY: 0 = the full layout (CWave), 1 = CSlim (mode 0 only)
 template <int LY>
-struct chain_walk_kernel {
+__global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk_kernel(const ChainArgs A, const int mode) {
     typedef typename std::conditional<LY == 0, CWave, CSlim>::type LW;
-    enum { SLIM = LY != 0, WAVES = SLIM ? S_WAVES : C_WAVES, THREADS = 64 * WAVES };
-    static __device__ void run(const ChainArgs A, const int mode) {
+    enum { SLIM = LY != 0, WAVES = SLIM ? S_WAVES : C_WAVES };
     __shared__ LW sh[WAVES];
     LW& L = sh[threadIdx.x >> 6];
     const int lane = dp_lane();
-    // (every wave owns a slice of the node pool, sized for THIS round's grid: in a launch shared with other rounds - the largest
-    // round's grid - the blocks beyond it have nothing to do)
-    const uint32_t nblocks = SLIM ? A.walk0_blocks : A.walk_blocks;
-    if (blockIdx.x >= nblocks) return;
-    const uint32_t waves = nblocks * WAVES;
+    // (every wave owns a slice of the node pool, which the host sizes for the largest grid it launches this kernel with)
+    const uint32_t waves = gridDim.x * WAVES;
     const uint32_t gw = blockIdx.x * WAVES + (threadIdx.x >> 6);
     CNode* nodes = SLIM ? (CNode*)nullptr : A.pool + (uint64_t)gw * A.pool_stride;  // (C_NODES links + the spill area of pairwise_align)
     if (mode != 0 && (A.cursor[3] != 0 || (A.pass > 0 && A.cursor[8 + A.pass] == 0))) return;  // overflow / every query closed already
@@ -2774,13 +2748,6 @@ struct chain_walk_kernel {
     const bool wprof = DP_PROFILING && A.prof && mode == 0;
     ChainProf pf = {};
     unsigned long long tprev = 0;
-#define WK_TICK(f_)                                                  \
-    if (wprof) {                                                     \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  \
-        const unsigned long long now_ = wall_clock64();              \
-        pf.f_ += now_ - tprev;                                       \
-        tprev = now_;                                                \
-    }
     const unsigned long long tkernel0 = wprof ? wall_clock64() : 0ull;
     for (uint32_t q = gw; q < A.nq; q += waves) {
         if (wprof) tprev = wall_clock64();
@@ -2825,12 +2792,12 @@ struct chain_walk_kernel {
             next = (uint32_t)RFL((int)st.next);
             if (next >= cnt) continue;
         }
-        WK_TICK(rec)  // the query's records and (mode 0) its candidate list
+        CHAIN_TICK(wprof, pf, tprev, rec)  // the query's records and (mode 0) its candidate list
         const int32_t* aSeg = A.qsegs + A.qoff[q];
         const u64* qset = A.qsets + (uint64_t)q * A.SW;
         const bool aStaged = aN <= (int)LW::ACAP && A.tier != 3;
         const u64* qs = chain_stage_a(L, aSeg, aN, qset, A.SW, aStaged);
-        WK_TICK(stagea)
+        CHAIN_TICK(wprof, pf, tprev, stagea)
         // algorithmic bytes of this query's share: two bitset rows per candidate (the exact-intersection
         // prefilter), both segment arrays per chained pair (4-byte ints here), the chain written out - counted once per
         // pair, when it becomes final
@@ -2859,13 +2826,11 @@ struct chain_walk_kernel {
                 }
             }
             pf.pairs++;
-            WK_TICK(pre)
+            CHAIN_TICK(wprof, pf, tprev, pre)
             if (c < mm) {
                 len = 0;
             } else if (spmm == mm) {
                 len = RFL(sp.len);
-            } else if (mode == 1) {
-                break;  // needs chaining with a minMatches nobody proposed for: the next spec pass does it
             } else {
                 if (DP_PROFILING && A.prof && mode == 2 && lane == 0) {  // (what the final walk still chains, and how much of it because of the slim layout)
                     atomicAdd(&A.cursor[20], 1u);
@@ -2881,7 +2846,7 @@ struct chain_walk_kernel {
                 }
                 chained = true;
                 pf.chained++;
-                WK_TICK(pair)
+                CHAIN_TICK(wprof, pf, tprev, pair)
             }
             if (A.paths && lane == 0)  // (a proposal that is taken keeps what the pass that made it wrote)
                 A.pspec[p].pad = (chained ? CPATH_CHAINED | (SLIM ? CPATH_SLIM : 0u) | tier : c >= mm ? sp.pad : 0u) | (spmm == -2 ? CPATH_MARKED : 0u) |
@@ -2923,30 +2888,18 @@ struct chain_walk_kernel {
             if (algBytes) atomicAdd((unsigned long long*)(A.cursor + 32) + (q & 63u), (unsigned long long)algBytes);
             if (mode == 0 && i < cnt) A.cursor[8] = 1u;  // a query is open ahead of proposal pass 0 (a flag: every writer stores 1)
         }
-        WK_TICK(out)
+        CHAIN_TICK(wprof, pf, tprev, out)
     }
-    if (wprof && lane == 0) {
-        unsigned long long* slot = A.prof + 16 * ((size_t)A.prof_walk_slot + gw);
-        slot[0] = pf.pairs, slot[1] = pf.chained, slot[2] = pf.rec, slot[3] = pf.stagea, slot[4] = pf.pre, slot[5] = pf.pair;
-        slot[6] = pf.stageb, slot[7] = pf.initial, slot[8] = pf.walk, slot[9] = pf.out;
-        slot[10] = tkernel0;
-        slot[11] = wall_clock64();
-        slot[12] = pf.bev, slot[13] = pf.nev, slot[14] = pf.nperfect, slot[15] = pf.why;
-    }
-#undef WK_TICK
+    if (wprof && lane == 0) chain_prof_store(A.prof + 16 * ((size_t)A.prof_walk_slot + gw), pf, tkernel0);
 }
-};
-
-__device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane);
 
 // one wave per open pair: prefilter + chain with the minMatches its query has reached; stored as a proposal.
 // (Round 6: the later passes on the full layout - four waves a CU, every pair the slim layout cannot hold chained in parallel instead of
 // by the final walk - were built and measured SLOWER at k = 13 and at k = 10, profiles/r06/ab_launch_diet_k13.txt, ab_full_from_k10.txt:
 // workgroups that want 131 KB of a CU's LDS are placed late.  What made the difference was the slim layout's geometry, see CSlim.)
-struct chain_spec_kernel {
+__global__ __launch_bounds__(64 * S_WAVES) void chain_spec_kernel(const ChainArgs A, const u64* __restrict__ totals) {
     typedef CSlim LW;
-    enum { WAVES = S_WAVES, THREADS = 64 * WAVES };
-    static __device__ void run(const ChainArgs A, const u64* __restrict__ totals) {
+    enum { WAVES = S_WAVES };
     __shared__ LW sh[WAVES];
     LW& L = sh[threadIdx.x >> 6];
     const int lane = dp_lane();
@@ -2957,18 +2910,12 @@ struct chain_spec_kernel {
     const uint32_t total = (uint32_t)min(totals[0], (u64)A.pair_cap);
     // DP_DEBUG=chain_prof: every wave keeps its own sums (ticks of 10 ns) and stores them into its own slot of the pass - no shared
     // counters (ten thousand atomics on one word take longer than the kernel)
+    const bool sprof = DP_PROFILING && A.prof;
     ChainProf pf = {};
     unsigned long long tprev = 0;
-#define SP_TICK(f_)                                                  \
-    if ((DP_PROFILING && A.prof)) {                                  \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  \
-        const unsigned long long now_ = wall_clock64();              \
-        pf.f_ += now_ - tprev;                                       \
-        tprev = now_;                                                \
-    }
-    const unsigned long long tkernel0 = (DP_PROFILING && A.prof) ? wall_clock64() : 0ull;
+    const unsigned long long tkernel0 = sprof ? wall_clock64() : 0ull;
     for (uint32_t p = gw; p < total; p += waves) {
-        if ((DP_PROFILING && A.prof)) tprev = wall_clock64();
+        if (sprof) tprev = wall_clock64();
         // A pair is a chain of dependent loads (pair -> query -> its records -> its segments -> probes of the target's set ...) at
         // 1-2 us per level under this kernel's own load: everything whose address is known is asked for at once, ahead of the
         // tests that may drop the pair (a load behind a branch waits for the branch), the target's reference included.
@@ -2994,9 +2941,9 @@ struct chain_spec_kernel {
         const u64* qset = A.qsets + (uint64_t)q * A.SW;
         const bool aStaged = aN <= (int)LW::ACAP;
         pf.pairs++;
-        SP_TICK(rec)  // the pair's own records (query state, proposal, candidate)
+        CHAIN_TICK(sprof, pf, tprev, rec)  // the pair's own records (query state, proposal, candidate)
         const u64* qs = chain_stage_a(L, aSeg, aN, qset, A.SW, aStaged);
-        SP_TICK(stagea)  // query side staged
+        CHAIN_TICK(sprof, pf, tprev, stagea)  // query side staged
         int c = RFL(sp.c);
         bool haveMask = false;
         u64 aMask = 0;
@@ -3008,19 +2955,19 @@ struct chain_spec_kernel {
                 c = chain_prefilter(A.seedsets + (uint64_t)t * A.SW, qs, A.SW);
             }
         }
-        SP_TICK(pre)  // prefilter
+        CHAIN_TICK(sprof, pf, tprev, pre)  // prefilter
         int len = 0, pmm = mm;
         uint32_t tier = 0;
         if (c >= mm) {
             pf.chained++;
             len = chain_pair(L, (CNode*)nullptr, A, aSeg, aN, aStaged, qs, qset, t, mm, A.sa + ib + (u64)i * nSeeds, A.sb + ib + (u64)i * nSeeds,
-                             haveMask, aMask, &rT, (DP_PROFILING && A.prof) ? &pf : (ChainProf*)nullptr, &tier);
+                             haveMask, aMask, &rT, sprof ? &pf : (ChainProf*)nullptr, &tier);
             if (len < 0) {  // does not fit the slim layout: no proposal (-2: no slim pass tries again), the final walk chains it
                 len = 0;
                 pmm = -2;
             }
         }
-        SP_TICK(pair)  // chain_pair
+        CHAIN_TICK(sprof, pf, tprev, pair)  // chain_pair
         if (lane == 0) {
             PSpec o = {c, pmm, len, (A.paths && c >= mm && pmm != -2) ? (CPATH_CHAINED | CPATH_SLIM | tier) : 0u};
             A.pspec[p] = o;
@@ -3028,21 +2975,9 @@ struct chain_spec_kernel {
         __builtin_amdgcn_wave_barrier();
         } while (0);
     }
-    if ((DP_PROFILING && A.prof) && lane == 0) {
-        unsigned long long* slot = A.prof + 16 * ((size_t)A.pass * A.prof_stride + gw);
-        slot[0] = pf.pairs, slot[1] = pf.chained, slot[2] = pf.rec, slot[3] = pf.stagea, slot[4] = pf.pre, slot[5] = pf.pair;
-        slot[6] = pf.stageb, slot[7] = pf.initial, slot[8] = pf.walk, slot[9] = pf.out;
-        slot[10] = tkernel0;
-        slot[11] = wall_clock64();
-        slot[12] = pf.bev, slot[13] = pf.nev, slot[14] = pf.nperfect, slot[15] = pf.why;
-    }
-#undef SP_TICK
+    if (sprof && lane == 0) chain_prof_store(A.prof + 16 * ((size_t)A.pass * A.prof_stride + gw), pf, tkernel0);
 }
-};
 
-// One wave per query: replays the ratchet over the proposals of its open pairs - 64 pairs at a time, one per lane, the
-// serial part is a register loop - and makes every pair up to the first one that needs another minMatches final: packed
-// chain, record, algorithmic bytes.  Everything that touches memory is lane-parallel.
 // One query of the resolve step: replays the ratchet over the proposals of its open pairs - 64 pairs at a time, one per lane, the
 // serial part is a register loop - and makes every pair up to the first one that needs another minMatches final: packed
 // chain, record, algorithmic bytes.  Everything that touches memory is lane-parallel.
@@ -3144,15 +3079,12 @@ __device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane) {
     }
 }
 
-struct chain_resolve_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const ChainArgs A) {
+__global__ __launch_bounds__(256) void chain_resolve_kernel(const ChainArgs A) {
     const int lane = dp_lane();
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
     if (A.cursor[3] != 0 || A.cursor[8 + A.pass] == 0) return;  // buffers overflowed (stage is repeated) / no query was open before this pass
     for (uint32_t q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < A.nq; q += waves) chain_resolve_query(A, q, lane);
 }
-};
 
 // What the host sends for the query stage - query offsets, query segments, the minCount table - as one block in the context's
 // pinned staging area, laid out as it will lie on the device.  Returns the block's size (0: nothing to send).
@@ -3232,18 +3164,18 @@ static int query_stage_sparse(dp_ctx* ctx, uint32_t nq, const uint8_t* up, size_
     }
     DP_HIP(dp_mark(ctx, 4));
     const uint32_t n_glob = ctx->global_n_seqs ? ctx->global_n_seqs : M;
-    dp_launch<query_sparse_kernel<false>>(ctx, dim3(nq), dim3(64 * Q_WAVES), ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ix->d_sp_post_off.p,
-                                          (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W, d_mc, mc_n,
-                                          (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)nullptr, 0u);
+    hipLaunchKernelGGL((query_sparse_kernel<false>), dim3(nq), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
+                       (const u64*)ix->d_sp_post_off.p, (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W,
+                       d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)nullptr, 0u);
     if (maxSeeds > Q_MAXSETS) {
         const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
         if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return DP_ERR_HIP;
-        dp_launch<query_sparse_kernel<true>>(ctx, dim3(nq), dim3(64 * Q_WAVES), ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ix->d_sp_post_off.p,
-                                             (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W, d_mc, mc_n,
-                                             (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)ctx->d_qbig.p, stride);
+        hipLaunchKernelGGL((query_sparse_kernel<true>), dim3(nq), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
+                           (const u64*)ix->d_sp_post_off.p, (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W,
+                           d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)ctx->d_qbig.p, stride);
     }
-    if (nq) dp_launch<window_list_kernel>(ctx, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), ctx->qsegs_dev, ctx->qoff_dev, nq,
-                                          (uint32_t*)ctx->d_wlist.p);
+    if (nq) hipLaunchKernelGGL(window_list_kernel, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), 0, ctx->stream, ctx->qsegs_dev,
+                               ctx->qoff_dev, nq, (uint32_t*)ctx->d_wlist.p);
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 5));
     *d_qmeta_out = d_qmeta;
@@ -3310,35 +3242,34 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
         if (int rc = dp_zero_fetch_regions(ctx, z, own_rows ? 0 : 4, &f, on_device ? 0 : 1)) return rc;  // (nothing at all: no launch)
     }
     DP_HIP(dp_mark(ctx, 4));
-    dp_launch<query_kernel<false>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
-                       ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
-                       (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
-                       (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
+    hipLaunchKernelGGL((query_kernel<false>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
+                       (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W,
+                       (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
                        ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)ctx->d_qsets.p, SW,
                        query_dbg, q_split, own_rows ? (u64*)ctx->d_cursor.p : (u64*)nullptr, (uint32_t*)nullptr, 0u);
     // the 16-ladder / exact-count regimes start at minCount 13: only a batch with a query of that many seeds needs the heavy variant
-    if (mcLast >= 13) dp_launch<query_kernel<true>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
-                       ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
-                       (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
-                       (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
-                       ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)ctx->d_qsets.p, SW,
-                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)nullptr, 0u);
+    if (mcLast >= 13) hipLaunchKernelGGL((query_kernel<true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev,
+                                         ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p,
+                                         ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p,
+                                         d_qmeta, d_words, d_qcnt, ctx->word_base,
+                                         ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr,
+                                         (u64*)ctx->d_qsets.p, SW, query_dbg, q_split, (u64*)nullptr, (uint32_t*)nullptr, 0u);
     if (maxSeeds > Q_MAXSETS) {
         // a query may hold more sets than the kernel's LDS lists (round 6): the BIG variants, lists in global memory, for those queries
         const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
         if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * q_split * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return DP_ERR_HIP;
-        dp_launch<query_kernel<false, true>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
-                       ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
-                       (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
-                       (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
-                       ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW,
-                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
-        if (mcLast >= 13) dp_launch<query_kernel<true, true>>(ctx, dim3(nq * q_split), dim3(64 * Q_WAVES),
-                       ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
-                       (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n,
-                       (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
-                       ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW,
-                       query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+        hipLaunchKernelGGL((query_kernel<false, true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev,
+                           ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p,
+                           ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta,
+                           d_words, d_qcnt, ctx->word_base,
+                           ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW, query_dbg,
+                           q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+        if (mcLast >= 13) hipLaunchKernelGGL((query_kernel<true, true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream,
+                                             ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
+                                             (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W,
+                                             (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
+                                             ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr,
+                                             (u64*)nullptr, SW, query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
     }
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 5));
@@ -3457,14 +3388,13 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
     A.sint_cap = st.sint_cap;
     A.int_cap = st.int_cap;
     A.cursor = d_cur;
-    A.walk_blocks = st.walk_blocks;
-    A.walk0_blocks = std::max<uint32_t>(1, std::min<uint32_t>(1024, (nq + S_WAVES - 1) / S_WAVES));
+    const uint32_t walk0_blocks = std::max<uint32_t>(1, std::min<uint32_t>(1024, (nq + S_WAVES - 1) / S_WAVES));  // grid of the slim walk
     A.n_refs = std::max<uint32_t>(1, ctx->n_seqs);
     A.prof = nullptr;
     A.prof_walk_slot = 0;
     A.prof_stride = 0;
     if (ctx->dbg.chain_prof) {
-        const size_t pb = ((size_t)st.passes * st.spec_blocks * S_WAVES + (size_t)A.walk0_blocks * S_WAVES) * 128;
+        const size_t pb = ((size_t)st.passes * st.spec_blocks * S_WAVES + (size_t)walk0_blocks * S_WAVES) * 128;
         if (dev_reserve(ctx, ctx->d_sched, pb + 128)) return DP_ERR_HIP;
         A.prof = (unsigned long long*)ctx->d_sched.p;
         A.prof_walk_slot = (uint32_t)(st.passes * st.spec_blocks * S_WAVES);
@@ -3473,24 +3403,25 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
     }
     if (st.attempt > 0) DP_HIP(hipMemsetAsync(ctx->d_cursor.p, 0, C_CURSOR_BYTES, ctx->stream));  // (attempt 0: zeroed with the query stage's buffers)
     DP_HIP(dp_mark(ctx, 6));
-    dp_launch<pair_scan_kernel>(ctx, dim3(1), dim3(1024), (const uint32_t*)st.d_qcnt, ctx->qoff_dev, nq, d_pbase, d_ibase, d_totals);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)st.d_qcnt, ctx->qoff_dev, nq, d_pbase,
+                       d_ibase, d_totals);
     // mode 0 on the slim layout (a forced tier is the full layout's business)
     const uint32_t spec_blocks = st.spec_blocks;
     if (A.tier == 0 && st.passes > 0) {
-        dp_launch<chain_walk_kernel<1>>(ctx, dim3(A.walk0_blocks), dim3(64 * S_WAVES), A, 0);
+        hipLaunchKernelGGL((chain_walk_kernel<1>), dim3(walk0_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, 0);
     } else {
-        dp_launch<chain_walk_kernel<0>>(ctx, dim3(st.walk_blocks), dim3(64 * C_WAVES), A, 0);
+        hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(st.walk_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 0);
     }
     for (int ps = 0; ps < st.passes; ps++) {
         A.pass = ps;
-        dp_launch<chain_spec_kernel>(ctx, dim3(spec_blocks), dim3(64 * S_WAVES), A, (const u64*)d_totals);
-        dp_launch<chain_resolve_kernel>(ctx, dim3(std::min<uint32_t>(1024, (nq + 3) / 4)), dim3(256), A);
+        hipLaunchKernelGGL(chain_spec_kernel, dim3(spec_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, (const u64*)d_totals);
+        hipLaunchKernelGGL(chain_resolve_kernel, dim3(std::min<uint32_t>(1024, (nq + 3) / 4)), dim3(256), 0, ctx->stream, A);
     }
     A.pass = st.passes;
     // the final walk rarely has a query to do after the passes: a quarter of the workgroups (each wants 128 KB of a CU's LDS before it
     // can look whether there is anything to do) - a query that is still open finds a wave among 192
-    if (st.passes > 0) A.walk_blocks = std::min<uint32_t>(st.walk_blocks, 48);
-    dp_launch<chain_walk_kernel<0>>(ctx, dim3(A.walk_blocks), dim3(64 * C_WAVES), A, 2);
+    const uint32_t final_blocks = st.passes > 0 ? std::min<uint32_t>(st.walk_blocks, 48) : st.walk_blocks;
+    hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(final_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 2);
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 7));
     {
@@ -3784,10 +3715,10 @@ int dp_match_anchors_launch(dp_ctx* ctx, const dp_fetch_region* fetch, uint32_t*
         F.n8[i] = fr[i] ? (unsigned long long)((fr[i]->bytes + 7) / 8) : 0ull;
     }
     const u64* d_totals = (const u64*)((const uint8_t*)ctx->d_cursor.p + 64);
-    dp_launch<match_anchor_kernel>(ctx, dim3(std::min<uint32_t>(8192, (nslots + 3) / 4)), dim3(256),
+    hipLaunchKernelGGL(match_anchor_kernel, dim3(std::min<uint32_t>(8192, (nslots + 3) / 4)), dim3(256), 0, ctx->stream,
                        (const MRec*)ctx->d_mrec.p, (const uint32_t*)d_totals, nslots, (const int32_t*)dp_chain_b(ctx),
-                       (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, ctx->last_k, (int32_t*)ctx->d_manchor.p,
-                       F, zero_word, (const int32_t*)dp_chain_a(ctx), (const int32_t*)ctx->qsegs_dev, (const u64*)ctx->qoff_dev,
+                       (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, ctx->last_k, (int32_t*)ctx->d_manchor.p, F,
+                       zero_word, (const int32_t*)dp_chain_a(ctx), (const int32_t*)ctx->qsegs_dev, (const u64*)ctx->qoff_dev,
                        (int32_t*)ctx->d_manchor.p + 2 * (size_t)nslots);
     ctx->mcover_off = 2 * (size_t)nslots;
     DP_HIP(hipGetLastError());
@@ -3799,10 +3730,9 @@ int dp_match_anchors_launch(dp_ctx* ctx, const dp_fetch_region* fetch, uint32_t*
 // Chains left in their scratch columns (ChainArgs.pack == 0), for a host consumer after all: copied into ma/mb densely, the
 // records' offsets rewritten.  One wave per record; the order of the chains in ma/mb is whatever the atomics make it (the
 // records say where each one is).
-struct chain_pack_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(MRec* __restrict__ recs, uint32_t nslots, const int32_t* __restrict__ sa, const int32_t* __restrict__ sb,
-                               int32_t* __restrict__ ma, int32_t* __restrict__ mb, uint32_t* __restrict__ total) {
+__global__ __launch_bounds__(256) void chain_pack_kernel(MRec* __restrict__ recs, uint32_t nslots, const int32_t* __restrict__ sa,
+                                                         const int32_t* __restrict__ sb, int32_t* __restrict__ ma, int32_t* __restrict__ mb,
+                                                         uint32_t* __restrict__ total) {
     const int lane = threadIdx.x & 63;
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
     for (uint32_t slot = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); slot < nslots; slot += waves) {
@@ -3818,7 +3748,6 @@ struct chain_pack_kernel {
         if (lane == 0) recs[slot].off = off;
     }
 }
-};
 
 int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out) {
     if (!ctx->find_valid) return dp_fail(ctx, DP_ERR_STATE, "dp_fetch_overlaps: no chaining stage output on this context");
@@ -3832,8 +3761,9 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
         if (dev_reserve(ctx, ctx->d_mb, (size_t)bound * 4)) return DP_ERR_HIP;
         uint32_t* d_total = (uint32_t*)ctx->d_cursor.p;  // (the stage's cursor block is free again: word 0 counted packed ints anyway)
         DP_HIP(hipMemsetAsync(d_total, 0, 4, ctx->stream));
-        dp_launch<chain_pack_kernel>(ctx, dim3(std::min<uint32_t>(2048, (ctx->n_pairs + 3) / 4)), dim3(256), (MRec*)ctx->d_mrec.p, ctx->n_pairs,
-                                     (const int32_t*)ctx->d_sa.p, (const int32_t*)ctx->d_sb.p, (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, d_total);
+        hipLaunchKernelGGL(chain_pack_kernel, dim3(std::min<uint32_t>(2048, (ctx->n_pairs + 3) / 4)), dim3(256), 0, ctx->stream,
+                           (MRec*)ctx->d_mrec.p, ctx->n_pairs, (const int32_t*)ctx->d_sa.p, (const int32_t*)ctx->d_sb.p,
+                           (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, d_total);
         DP_HIP(hipGetLastError());
         if (pin_reserve(ctx, ctx->h_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
         DP_HIP(hipMemcpyAsync(ctx->h_cursor.p, d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -3856,7 +3786,7 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
     const int32_t* ta = (const int32_t*)ctx->h_ta.p;
     const int32_t* tb = (const int32_t*)ctx->h_tb.p;
     if (nslots) {
-        dp_launch<match_anchor_kernel>(ctx, dim3(std::min<uint32_t>(1024, (nslots + 3) / 4)), dim3(256),
+        hipLaunchKernelGGL(match_anchor_kernel, dim3(std::min<uint32_t>(1024, (nslots + 3) / 4)), dim3(256), 0, ctx->stream,
                            (const MRec*)ctx->d_mrec.p, (const uint32_t*)d_totals, nslots, (const int32_t*)ctx->d_mb.p,
                            (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, k, (int32_t*)ctx->d_manchor.p,
                            AnchorFetch{{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {0, 0, 0}}, (uint32_t*)nullptr,

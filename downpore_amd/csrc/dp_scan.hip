@@ -32,7 +32,6 @@
 #include <vector>
 
 #include "dp_common.h"
-#include "dp_launch.h"
 
 static std::string g_create_err;
 // The scan kernels are persistent and fill every CU: two of them running at once (several contexts on one device) only
@@ -112,8 +111,6 @@ const void* dp_stage(dp_ctx* ctx, const void* src, size_t bytes) {
     ctx->stage_used = at + bytes;
     return dst;
 }
-
-hipStream_t dp_ctx_stream(const dp_ctx* ctx) { return ctx->stream; }
 
 static bool wait_spins(const dp_ctx* ctx) { return ctx->wait.spin >= 0 ? ctx->wait.spin == 1 : g_wait_spin.load(std::memory_order_relaxed) != 0; }
 hipError_t dp_stream_sync(dp_ctx* ctx) {
@@ -424,9 +421,7 @@ struct ZeroArgs {
     const unsigned long long* src[2];
     unsigned long long m8[2];
 };
-struct zero_regions_kernel {
-    enum { THREADS = 256 };
-    static __device__ void run(const ZeroArgs a) {
+__global__ __launch_bounds__(256) void zero_regions_kernel(const ZeroArgs a) {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (unsigned long long)gridDim.x * blockDim.x;
 #pragma unroll
     for (int r = 0; r < 2; r++)  // (the fetches first: their loads cross the link while the stores below go out)
@@ -435,7 +430,6 @@ struct zero_regions_kernel {
     for (int r = 0; r < 4; r++)
         for (unsigned long long j = i; j < a.n8[r]; j += stride) a.p[r][j] = 0ull;
 }
-};
 // (a round has a dozen buffers to clear, and every hipMemsetAsync is a dispatch of its own: the command processor, not the
 // memory, is what they cost - tools/micro/launch_rate.hip)
 int dp_zero_fetch_regions(dp_ctx* ctx, const dp_zero_region* z, int nz, const dp_fetch_region* f, int nf) {
@@ -454,7 +448,7 @@ int dp_zero_fetch_regions(dp_ctx* ctx, const dp_zero_region* z, int nz, const dp
     }
     if (!most) return DP_OK;
     const uint32_t blocks = (uint32_t)std::min<unsigned long long>(4096, (most + 1023) / 1024);
-    dp_launch<zero_regions_kernel>(ctx, dim3(std::max(1u, blocks)), dim3(256), a);
+    hipLaunchKernelGGL(zero_regions_kernel, dim3(std::max(1u, blocks)), dim3(256), 0, ctx->stream, a);
     DP_HIP(hipGetLastError());
     return DP_OK;
 }
@@ -2084,13 +2078,11 @@ extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items,
 // ---------------------------------------------------------------------------------------------------------------
 // dp_scan_reads: items generated and survivors compacted on the device
 
-struct make_read_items_kernel {
-    enum { THREADS = 256 };
-    // flag_src (or null): the flags' pinned host copy, newer than the device's - this launch brings the block over as well (eight bytes
-    // per thread, flag_words of them; its own read's flag every thread takes from the source itself)
-    static __device__ void run(const uint32_t* __restrict__ len, const uint8_t* __restrict__ ignore, uint32_t lo,
-                                       uint32_t hi, int k, int top_level, uint32_t min_seeds, dp_scan_item* __restrict__ items,
-                                       const unsigned long long* __restrict__ flag_src, unsigned long long* __restrict__ flag_dst, uint32_t flag_words) {
+// flag_src (or null): the flags' pinned host copy, newer than the device's - this launch brings the block over as well (eight bytes
+// per thread, flag_words of them; its own read's flag every thread takes from the source itself)
+__global__ __launch_bounds__(256) void make_read_items_kernel(const uint32_t* __restrict__ len, const uint8_t* __restrict__ ignore,
+        uint32_t lo, uint32_t hi, int k, int top_level, uint32_t min_seeds, dp_scan_item* __restrict__ items,
+        const unsigned long long* __restrict__ flag_src, unsigned long long* __restrict__ flag_dst, uint32_t flag_words) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (flag_src) {
         if (i < flag_words) flag_dst[i] = flag_src[i];
@@ -2114,7 +2106,6 @@ struct make_read_items_kernel {
     }
     items[i] = it;
 }
-};
 
 // tile sums / compaction of the survivor FLAG (count >= min_seeds), same tiling as the offsets scan
 __global__ __launch_bounds__(OFF_TILE) void flag_tile_sums(const dp_scan_item* __restrict__ items, const uint32_t* __restrict__ counts,
@@ -2332,7 +2323,7 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     if (n_read_items && (ctx->items_ptr != d_items || ctx->items_epoch != ignore_epoch || ctx->items_lo != lo || ctx->items_hi != hi ||
                          ctx->items_min != min_seeds || ctx->items_top != top_level || ctx->items_k != k)) {
         const uint32_t fw = flags_dirty ? (uint32_t)(nr8 / 8) : 0u;
-        dp_launch<make_read_items_kernel>(ctx, dim3((std::max(n_read_items, fw) + 255) / 256), dim3(256),
+        hipLaunchKernelGGL(make_read_items_kernel, dim3((std::max(n_read_items, fw) + 255) / 256), dim3(256), 0, ctx->stream,
                            (const uint32_t*)ctx->d_len.p, (const uint8_t*)ctx->d_ignore.p, lo, hi, k, top_level, min_seeds, d_items,
                            flags_dirty ? (const unsigned long long*)ctx->h_ignore.p : (const unsigned long long*)nullptr,
                            (unsigned long long*)ctx->d_ignore.p, fw);

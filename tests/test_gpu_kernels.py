@@ -367,6 +367,52 @@ def test_index_mode_write_sort_tiers(ctx, n_seeds):
         del os.environ["DP_SCAN_INDEX"]
 
 
+def test_index_mode_largest_sort_tier_and_beyond():
+    """The largest sort tier of the index-mode write step, from both of its launch sites, and the step's way out above it - on a
+    context of its own, because the one-go form sizes its sort from the context's previous round (sort_cap in scan_reads_body,
+    dp_scan.hip: 1.25 x the previous largest count; the tiers end at 128 / 512 / KX_SORT_LDS = 4096 hits, dp_kindex_count and
+    dp_kindex_write in dp_kindex.hip).  5000-base reads:
+      call 1  300 000 of the 4^10 k-mers are seeds, ~1 400 hits per read; the fresh context guessed the smallest sort, so fill and sort are
+              repeated by dp_kindex_write with the round's real maximum: kidx_sortwrite<KX_SORT_LDS>
+      call 2  the same round again: the one-go form now launches kidx_sortwrite<KX_SORT_LDS> itself
+      call 3  1 000 000 seeds, ~4 700 hits per read: more than the LDS sort holds - dp_kindex_write gives up, kidx_unlink_extra takes the
+              extra item off its read, and the scan kernels answer the round (index_mode 0 although the index was asked for)
+      call 4  the first round once more in index mode: what call 3 left behind must not show
+    The scan kernels' answer is the check, field by field."""
+    import downpore_amd
+    c = downpore_amd.Context(0)
+    k, N = 10, 120
+    bases, off = O.gen_reads(22, 60000, N, 5000, 0.01, False)
+    c.upload_reads(bases, off)
+    rng = np.random.default_rng(5)
+    kmers = np.arange(1, 4 ** k, dtype=np.uint32)
+    seeds = {n: np.sort(rng.choice(kmers, size=n, replace=False)) for n in (300000, 1000000)}
+    ignore = np.zeros(N, dtype=np.uint8)
+    extra = [(7, 10, 900, 0)]
+    fields = ("read", "n_seeds", "seg_off", "extra_n_seeds", "segs")
+    os.environ["DP_SCAN_INDEX"] = "1"
+    try:
+        c.scan_prepare(k)
+        want = {}
+        for n in seeds:
+            os.environ["DP_SCAN_INDEX"] = "0"
+            c.round_begin(k, seeds[n])
+            got = c.scan_reads(ignore, 3, 0, N, False, 20, extra)
+            assert got["index_mode"] == 0
+            want[n] = {f: np.array(got[f]).copy() for f in fields}
+        assert 512 < int(want[300000]["n_seeds"].max()) <= 4096 and int(want[1000000]["n_seeds"].max()) > 4096
+        os.environ["DP_SCAN_INDEX"] = "1"
+        for call, (n, index_mode) in enumerate([(300000, 1), (300000, 1), (1000000, 0), (300000, 1)]):
+            c.round_begin(k, seeds[n])
+            got = c.scan_reads(ignore, 3, 0, N, False, 20, extra)
+            assert got["index_mode"] == index_mode, call
+            for f in fields:
+                assert np.array_equal(got[f], want[n][f]), (call, f)
+    finally:
+        del os.environ["DP_SCAN_INDEX"]
+        c.close()
+
+
 def test_scan_reads_compaction_matches_itemwise_scan(ctx):
     """dp_scan_reads (items generated and survivors compacted on the device) == dp_scan item by item + host filter."""
     k = 10

@@ -229,12 +229,14 @@ def test_overlap_kmer_index_mode(mode):
 
 
 @pytest.mark.parametrize("env", [{"DP_KX_BINS": "0"}, {"DP_KX_BINS_CAP": "300"}, {"DP_KX_BINS_CAP": "40"}, {"DP_KX_ONESHOT": "0"}, {"DP_KX_FUSE": "0"},
-                                 {"DP_KX_DENSE": "1"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "300"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "40"}])
+                                 {"DP_KX_DENSE": "1"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "300"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "40"},
+                                 {"DP_TUNE": "kx_bin_waves=4"}])
 def test_kmer_index_counting_step_variants(monkeypatch, env):
     """The counting step of an index-mode round (dp_kindex.hip): hits binned by read range and counted in LDS (round 5, the default),
     round 4's hit records with one atomic per hit (DP_KX_BINS=0), bins that overflow - a workgroup's share that does not fit is
     counted the old way, what it reserved is marked unwritten, the fill pass walks the buckets (DP_KX_BINS_CAP: some bins at 300,
-    every bin at 40) - the two-wait form (DP_KX_ONESHOT=0), the count in a launch of its own instead of inside kidx_offsets (DP_KX_FUSE=0) and
+    every bin at 40) - the two-wait form (DP_KX_ONESHOT=0), the count in a launch of its own instead of inside kidx_offsets (DP_KX_FUSE=0), walk
+    workgroups of four waves instead of eight (DP_TUNE=kx_bin_waves=4) and
     the dense regime's small bins filled and sorted in LDS with batched reservations (round 6, DP_KX_DENSE=1 forces it on these small
     inputs; with bins that overflow too).  All read per call, so a variant set here is the variant that runs.  Same PAF, same ignore flags as the oracle: dense seeds (k = 10, hundreds
     of hits per read), sparse seeds (k = 13), reads that get flagged, five slots."""
@@ -246,6 +248,49 @@ def test_kmer_index_counting_step_variants(monkeypatch, env):
     _, st = _run_both(114, 1200000, 2000, 12000, 13, 0.002, True, max_rounds=4, slots=5)
     assert st["idx_rounds"] > 0 and st["idx_hits"] > 0
     _run_both(7, 100000, 300, 4000, 10, himem=False, max_rounds=3)
+
+
+@pytest.mark.parametrize("N,L,overlap_size,env", [(132000, 600, 500, {"DP_KX_FUSE": "0", "DP_KX_DENSE": "0"}), (1049000, 260, 200, {})],
+                         ids=["bins_of_1024_reads", "bins_of_8192_reads"])
+def test_kmer_index_bins_of_many_reads(monkeypatch, N, L, overlap_size, env):
+    """The bins of the counting step hold 512 reads up to 131 072 read items, 1 024 - 4 096 up to 1 048 576 and 8 192 - 16 384 beyond
+    (at most 256 bins, dp_kindex_count): kidx_bin_count / kidx_bin_fill have an instantiation per size class, and the two larger ones
+    need that many reads - the smallest counts that select them, of the shortest reads that still overlap (k = 10, two rounds, one
+    slot; 132 000 reads: the count in a launch of its own and the dense form off, so that both kernels of the class run in both
+    rounds; beyond 524 288 reads there is no dense form).  Same PAF per round, same flagged reads as the oracle.
+    Nothing the library reports says which size class ran: the coupling is to the `bshift` loop of dp_kindex_count (dp_kindex.hip,
+    "> 256 && bshift < KXB_RIB_BITS") and to the `B.bshift <= 9 / <= 12` selectors of its launches - if those move, these read
+    counts move with them (DP_DEBUG=kx_bins prints the class: "bins of 1024 reads", "bins of 8192 reads")."""
+    import ctypes as C
+    from downpore_amd.overlap import OverlapPipeline, Reads
+    monkeypatch.setenv("DP_SCAN_INDEX", "1")
+    for kk, vv in env.items():
+        monkeypatch.setenv(kk, vv)
+    bases, off = O.gen_reads(77, N * L // 20, N, L, 0.0, False)
+    rs = O.ReadSet(bases, off, min_len=overlap_size)
+    limit = 2
+    orun = O.OverlapRun(rs, k=10, max_rounds=limit, traces=True, overlap_size=overlap_size)
+    assert orun.rounds == limit and orun.paf.count("\n") > 100
+    reads = Reads(bases, off, min_len=overlap_size)
+    pipe = OverlapPipeline(reads, k=10, slots=1, overlap_size=overlap_size)
+    pipe.H.dph_overlap_set_round_limit.restype = None
+    pipe.H.dph_overlap_set_round_limit.argtypes = [C.c_void_p, C.c_int64]
+    pipe.H.dph_overlap_set_round_limit(pipe.h, limit)
+    rounds = 0
+    while rounds < limit:
+        c = pipe.step()
+        if c == 0:
+            break
+        assert rounds + c <= limit
+        d = first_diff(pipe.round_paf(), "".join(orun.trace_paf(r) for r in range(rounds, rounds + c)))
+        assert d is None, "PAF differs in rounds %d..%d: %s" % (rounds, rounds + c - 1, d)
+        rounds += c
+    assert rounds == limit
+    flagged = sorted(set(int(x) for r in range(rounds) for x in orun.trace(r, "newlyIgnored")))
+    assert sorted(np.nonzero(reads.ignore())[0].tolist()) == flagged
+    st = pipe.stats()
+    pipe.close()
+    assert st["idx_rounds"] > 0 and st["idx_hits"] > 0
 
 
 @pytest.mark.parametrize("env", [{"DP_KINDEX_WIDE": "1"}, {"DP_TUNE": "kb_b1=9"}, {"DP_KB_MIN_PBITS": "22"}, {"DP_KB_MIN_PBITS": "30"}, {"DP_TUNE": "kindex_atomic=1"}])

@@ -26,7 +26,9 @@ def short(name):
     if "rocprim" in n:
         n = "rocprim::" + n.split("::")[-1][:60]
     n = n.strip()
-    if n.startswith("dp_kernel<"):  # round 6: per-round kernels are dp_kernel<kernel> (dp_launch.h): the kernel's own name
+    # per-round kernels are plain kernels under their own names; traces of round 6 show them as dp_kernel<kernel> (the launch wrapper
+    # of that time): both forms give the kernel's own name
+    if n.startswith("dp_kernel<"):
         n = n[len("dp_kernel<"):].rstrip()
         if n.endswith(">"):
             n = n[:-1].rstrip()
