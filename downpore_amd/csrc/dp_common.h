@@ -58,7 +58,7 @@ struct dp_ctx {
     std::vector<uint32_t> qc_ids, qc_meta;
     uint32_t last_n_extra = 0;    // extra items of the last dp_scan_reads
     uint32_t kx_seq = 0;          // sequence number the sort pass of a one-go index step stores into h_total[15] when its output is complete
-    uint32_t kx_maxlen = 0;       // longest read (hit records hold 24 bits of position)
+    uint32_t kx_maxlen = 0;       // longest read (a bin's hit record holds 24 bits of position)
     size_t kx_maxlen_reads = 0;   // ... of a read set of this many reads
     uint32_t kx_head_reads = 0;  // reads the zeroed extra-item list heads (d_kx_lo) are sized for
     hipStream_t stream = nullptr;
@@ -68,7 +68,7 @@ struct dp_ctx {
     // settings read when the context is created (dp_env.h, CREATE): what its rounds consult many times
     dp_wait_mode wait;
     struct {
-        bool kx = false, kx_bins = false, kx_oneshot = false, cons = false, cons_why = false, chain_prof = false, map_prof = false;
+        bool kx_bins = false, kx_oneshot = false, cons = false, cons_why = false, chain_prof = false, map_prof = false;
     } dbg;
     bool stream_priority_set = false;  // (dp_ctx_set_priority: such a stream is destroyed with its context instead of being parked)
     std::string err;
@@ -252,15 +252,14 @@ int dp_zero_fetch_regions(dp_ctx* ctx, const dp_zero_region* z, int nz, const dp
     } while (0)
 
 // resident k-mer position index (dp_kindex.hip)
-struct dp_kindex_fast {   // the count walk's short cut for views served whole (dp_kindex.hip, KxRec)
+struct dp_kindex_fast {   // the count walk's short cut for views served whole (dp_kindex.hip: kidx_walk, KxBins)
     const uint8_t* ign;   // device: one byte per read, != 0 = ignored (null: the walk reads the items)
     uint32_t qlo, qspan;  // reads that may carry extra items
 };
 struct dp_kindex_oneshot {  // the index step of a round launched in one go, sized from guesses (dp_kindex_count)
-    uint64_t hits_guess;    // seed occurrences expected (sizes the record shards)
+    uint64_t hits_guess;    // seed occurrences expected (sizes the bins)
     uint32_t surv_guess;    // survivors expected (grid of the sort pass)
     uint32_t sort_cap;      // 256 / 1024 / 4096: hits of the largest survivor the sort pass is launched for
-    uint32_t min_seeds;     // chunkWorker's filter for read items (extra items carry their own)
     int32_t* d_segs;        // segment buffer, seg_cap ints
     uint64_t seg_cap;
     int32_t* host_segs;     // pinned mirror for the extra items' segments (or null)

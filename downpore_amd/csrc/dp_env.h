@@ -36,10 +36,8 @@ inline constexpr Setting kSettings[] = {
     {VAR, "DP_KINDEX_WIDE", CALL, "set: index entries of eight bytes throughout"},
     {VAR, "DP_KINDEX_MAX_K", CALL, "n: no index above k = n (at most 14)"},
     {VAR, "DP_KB_MIN_PBITS", CALL, "n: a floor for the index's position bits, at most 32 (tests reach every entry format on small inputs)"},
-    {VAR, "DP_KX_BINS", CALL, "0: round 4's hit records instead of bins"},
     {VAR, "DP_KX_BINS_CAP", CALL, "n: capacity of a bin, at least 16 (tests: bins that overflow)"},
     {VAR, "DP_KX_ONESHOT", CALL, "0: count, wait, fill instead of the index step in one go"},
-    {VAR, "DP_KX_FUSE", CALL, "0: the bin count as a launch of its own"},
     {VAR, "DP_KX_DENSE", CALL, "0/1: the dense regime's kernels never / always"},
     {VAR, "DP_INDEX_FILL_ROWS", CALL, "0/1: bit matrices by atomics / seed-set rows in LDS + transpose (default: by size)"},
     {VAR, "DP_CHAIN_PASSES", CALL, "n: proposal passes of the chaining stage, 0..6 (default 3; 0 = the serial walk alone)"},
@@ -68,8 +66,6 @@ inline constexpr Setting kSettings[] = {
     {VAR, "DPH_PROFILE", CREATE, "set: host pipeline counters and set-up marks on stderr"},
     // ---- DP_TUNE keys: numbers that experiments vary
     {TUNE, "spec_blocks", CALL, "workgroups of the chaining stage's proposal passes (default 1024)"},
-    {TUNE, "kx_bin_waves", CALL, "waves of a walk workgroup of the index step: 4, 8 or 16 (default 8)"},
-    {TUNE, "kx_walk_blocks", CALL, "workgroups of the count walk striding over its work (default 0: all of it at once)"},
     {TUNE, "scan_wg_per_cu", CALL, "persistent scan workgroups per CU, 1..2 (default 2)"},
     {TUNE, "query_split", CALL, "workgroups per query of the query kernel, up to 16 (default 0 = one, which also clears its own rows)"},
     {TUNE, "upload_threads", PROCESS, "helper threads of the shared pinned upload ring, 0..16 (default 4)"},
@@ -101,7 +97,6 @@ inline constexpr Setting kSettings[] = {
     {TUNE, "scan_debug", CALL, "debug bits handed to the scan kernels"},
     // ---- DP_DEBUG tokens: diagnosis output, no change of behaviour
     {DEBUG, "alloc", CALL, "one line per growth of a buffer (read where a buffer grows, not per round)"},
-    {DEBUG, "kx", CREATE, "the index step's per-wave timers (make PROF=1)"},
     {DEBUG, "kx_bins", CREATE, "how full the index step's bins are (waits for the stream)"},
     {DEBUG, "kx_oneshot", CREATE, "every one-go index step that had to be repeated"},
     {DEBUG, "cons", CREATE, "per-window records of the consensus kernel"},

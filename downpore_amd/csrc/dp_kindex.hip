@@ -364,17 +364,27 @@ void dp_kindex_free(dp_ctx* ctx) {
 }
 
 // ---- per round -------------------------------------------------------------------------------------------------------
-// The counting step of a round, straight from the index (no sort, no host round trip before the survivors are known):
-//   kidx_count   every occurrence of every seed k-mer bumps the counter of the read item it falls into and of the extra
-//                items (query windows) of its read;
-//   kidx_offsets one single-pass scan (decoupled look-back) over the items: segment offsets of the survivors, their
-//                compacted list, the totals;
-//   kidx_fill    the occurrences of surviving items go, unordered, into the item's own segment slice as (position, seed);
-//   kidx_sortwrite  one wave per survivor sorts its slice by position and turns it into [gap, seed, ..., gap] in place.
-// Since round 5 the default form of the first three is (see "round 5" below): kidx_walk_bin writes every hit as a record into the bin of
-// its read and touches no counter, kidx_offsets' tiles count their own bins' records in LDS before they scan, kidx_bin_fill places the
-// survivors' records with LDS slot counters; the kernels named above remain as DP_KX_BINS=0 and as the fallback of a round whose bins
-// overflowed.
+// The index step of a round, straight from the index (no host round trip before the survivors are known).  Two forms:
+//
+// One go (dp_kindex_count with `one`; "hits binned by read range" below) - everything launched before the caller's one wait, into
+// buffers sized from the context's previous round:
+//   kidx_walk_bin   every hit of a seed k-mer on a read item becomes a record in the bin of its read; no counter is touched.  Hits on
+//                   the extra items (query windows) are counted directly and kept in a list of their own;
+//   kidx_offsets    its tiles count their own bins' records in LDS (bins of more than a tile's 4 096 reads: kidx_bin_count in front
+//                   of it), then one single-pass scan (decoupled look-back) over the items: segment offsets of the survivors, their
+//                   compacted list, the totals;
+//   sparse regime   kidx_bin_fill places the survivors' records in their segment slices, kidx_sortwrite sorts each slice by position
+//                   and turns it into [gap, seed, ..., gap] in place;
+//   dense regime    (the previous round had 16 and more hits per read: small bins) kidx_bin_count as a launch of its own,
+//                   kidx_bin_sort_dense fills and sorts a bin in LDS, kidx_sortwrite sorts the extra items' slices alone.
+//
+// Fallback (count, wait, fill) - where the bins cannot be set up, where the caller does not ask for one go (DP_KX_ONESHOT=0, read sets
+// beyond 2^24 reads or bases per read), and as the second attempt of a one-go round that outgrew a guess (a bin, the segment buffer
+// or the sort tier: dp_kindex_refill + dp_kindex_write):
+//   kidx_walk<false>  every hit bumps the counter of the read item it falls into and of the extra items of its read;
+//   kidx_offsets      the scan alone;
+//   kidx_walk<true>   after the caller's wait: the hits of surviving items go, unordered, into the item's segment slice;
+//   kidx_sortwrite    as above.
 
 #define KX_PARTS 4  // waves that share one seed's bucket
 
@@ -410,118 +420,17 @@ __global__ __launch_bounds__(256) void kidx_unlink_extra(const dp_scan_item* __r
     head[items[n_read_items + e].read] = 0;
 }
 
-#ifdef DP_PROF_BUILD
-#define KX_PROFILING 1
-#else
-#define KX_PROFILING 0
-#endif
-// ---- hit records of the count pass (round 4) -------------------------------------------------------------------------
-// [63] the read carries extra items (query windows)  [62] the hit counts for its read item (in range, inside the item)
-// [61:38] read  [37:24] rank among the read's hits (the counter's value before this hit)  [23:0] position
-#define KX_REC_X (1ull << 63)
-#define KX_REC_V (1ull << 62)
-struct KxRec {
-    unsigned long long* rec;  // [64 * shard_cap] (null: no records this round)
-    uint32_t* kb;             // [2 * groups]: where the group's records start (0xffffffff: its shard was full), how many
-    uint32_t* flags;          // [0] a shard was full
-    uint32_t shard_cap;
-    // the count walk's short cut (round 4): views served whole (not top-level) have a k-mer at every indexed position, so "inside
-    // the item" is "the read is not ignored" - a byte per read instead of its 16-byte item - and only reads in [qlo, qlo + qspan)
-    // carry extra items (the round's query reads are consecutive): two dependent table reads per hit fewer.  ign == null: off.
-    const uint8_t* ign;
-    uint32_t qlo, qspan;
-};
-__device__ __forceinline__ unsigned long long kx_rec(bool x, bool v, uint32_t r, uint32_t rank, uint32_t p) {
-    return (x ? KX_REC_X : 0ull) | (v ? KX_REC_V : 0ull) | ((unsigned long long)(r & 0xffffffu) << 38) |
-           ((unsigned long long)(rank & 0x3fffu) << 24) | (unsigned long long)(p & 0xffffffu);
-}
-
-// the fill pass from records: same thread layout as the count pass (a group's lanes over its stretch), no bucket walk
-__global__ __launch_bounds__(256) void kidx_fill_rec(const KxRec R, uint32_t n_groups, uint32_t lps, const dp_scan_item* __restrict__ items,
-                                                     uint32_t lo, uint32_t n_read_items, uint32_t min_seeds,
-                                                     const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
-                                                     const uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
-                                                     const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
-                                                     const uint64_t* __restrict__ totals, uint64_t seg_cap) {
-    if (R.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
-    const int lane = dp_lane();
-    const uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    uint32_t grp, s, j0, step;
-    if (lps == 64) {
-        grp = w;
-        s = w / KX_PARTS;
-        j0 = 4u * (uint32_t)lane;  // (four consecutive records per lane and trip: two 16-byte loads; the buffer ends in 64 bytes of slack)
-        step = 64;
-    } else {
-        grp = w * 4 + ((uint32_t)lane >> 4);
-        s = grp;
-        j0 = 4u * ((uint32_t)lane & 15u);
-        step = 16;
-    }
-    if (grp >= n_groups) return;
-    const uint32_t at = R.kb[2 * (size_t)grp], gn = R.kb[2 * (size_t)grp + 1];
-    if (at == 0xffffffffu) return;
-    for (uint32_t jb = j0; jb < gn; jb += 4 * step) {
-        unsigned long long e[4];
-        {
-            struct __attribute__((packed, aligned(8))) Rec4 {
-                unsigned long long a, b, c, d;
-            };
-            const Rec4 q = *(const Rec4*)(R.rec + (size_t)at + jb);
-            e[0] = q.a;
-            e[1] = jb + 1 < gn ? q.b : 0ull;
-            e[2] = jb + 2 < gn ? q.c : 0ull;
-            e[3] = jb + 3 < gn ? q.d : 0ull;
-        }
-        uint32_t cnt[4];
-        uint64_t so[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t it = (uint32_t)(e[u] >> 38) & 0xffffffu;
-            const bool val = (e[u] & KX_REC_V) != 0;
-            cnt[u] = val ? counts[it - lo] : 0u;
-            so[u] = val ? segoff[it - lo] : 0ull;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t r = (uint32_t)(e[u] >> 38) & 0xffffffu, p = (uint32_t)e[u] & 0xffffffu;
-            if ((e[u] & KX_REC_V) && cnt[u] >= min_seeds) {
-                const uint64_t to = so[u] + 2ull * ((uint32_t)(e[u] >> 24) & 0x3fffu);
-                segs[to] = (int32_t)p;
-                segs[to + 1] = (int32_t)s;
-            }
-            if (e[u] & KX_REC_X) {
-                for (uint32_t x = head[r]; x; x = next[x - 1]) {  // the round's extra items on this read (query windows)
-                    const uint32_t it = n_read_items + x - 1;
-                    const dp_scan_item xi = items[it];
-                    if (p - xi.start < xi.n_kmers && p >= xi.start && counts[it] >= xi.min_seeds) {
-                        const uint32_t slot = atomicAdd(&fillc[it], 1u);
-                        const uint64_t to = segoff[it] + 2ull * slot;
-                        segs[to] = (int32_t)(p - xi.start);
-                        segs[to + 1] = (int32_t)s;
-                    }
-                }
-            }
-        }
-    }
-}
-
+// The fallback's walk (FILL = false: count, FILL = true: fill).  F, the count walk's short cut (dp_kindex_fast; F.ign == null: off):
+// views served whole (not top-level) have a k-mer at every indexed position, so "inside the item" is "the read is not ignored" - a
+// byte per read instead of its 16-byte item - and only reads in [qlo, qlo + qspan) carry extra items (the round's query reads are
+// consecutive): two dependent table reads per hit fewer.
 template <bool FILL>
 __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
                               const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi, uint32_t n_read_items,
                               const uint32_t* __restrict__ head, const uint32_t* __restrict__ next, uint32_t* __restrict__ counts,
                               uint32_t* __restrict__ fillc, const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
-                              unsigned long long* __restrict__ n_hits, uint32_t lps, unsigned long long* __restrict__ dbg, const KxRec R) {
+                              unsigned long long* __restrict__ n_hits, uint32_t lps, const dp_kindex_fast F) {
     const int lane = dp_lane();
-    // DP_DEBUG=kx: when a wave started, had its bucket bounds, its entries, its items, and was done (100 MHz ticks since dbg[15],
-    // sums over waves in dbg[0..4], maxima in dbg[5..9], waves in dbg[10])
-#define KX_TICK(i_)                                                                                     \
-    if (KX_PROFILING && dbg) {                                                                          \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                      \
-        const unsigned long long n_ = wall_clock64();                                                   \
-        if (lane == 0) dbg[8 * (size_t)w + (i_)] = n_;                                                  \
-    }
-    KX_TICK(0)
     // lps = lanes per seed.  64: KX_PARTS waves share one seed's bucket (dense seeds: buckets of hundreds to thousands);
     // 16: four seeds per wave (k = 13 at config 2: ~20 occurrences per seed - a whole wave per quarter bucket left 59 lanes idle
     // and made 40 k waves of a 10 k-seed round)
@@ -554,30 +463,8 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
         grp = s;
         gleader = (lane & 15) == 0;
     }
-    KX_TICK(1)
-    // Hit records (round 4): the count pass keeps every hit - {read, position, the rank the read's counter returned} - in a
-    // stretch of R.rec of its group's own, so that the fill pass is one streaming pass over records (R.rec[at + j] -> the
-    // survivor's slice at slot `rank`) instead of a second walk over seeds, buckets, items and counters.  Stretches are handed out
-    // from 64 shards (the seed-occurrence counters of before, now read back: one returning atomic per group); a shard that is full
-    // sets R.flags[0] and the round's fill pass walks the buckets as it used to.
-    uint32_t rec_at = 0xffffffffu;
-    if (!FILL) {
-        const uint32_t gn = i1 > gfirst ? i1 - gfirst : 0u;
-        unsigned long long old = 0;
-        if (gleader && gn) old = atomicAdd(&n_hits[grp & 63u], (unsigned long long)gn);  // (64 slots: 10 k same-address atomics serialise)
-        if (R.rec) {
-            if (gleader) {
-                if (old + gn <= R.shard_cap) {
-                    rec_at = (grp & 63u) * R.shard_cap + (uint32_t)old;
-                } else if (gn) {
-                    R.flags[0] = 1u;
-                }
-                R.kb[2 * (size_t)grp] = rec_at;
-                R.kb[2 * (size_t)grp + 1] = gn;
-            }
-            rec_at = (uint32_t)__shfl((int)rec_at, lps == 64 ? 0 : (lane & 48), 64);
-        }
-    }
+    // seed occurrences of the round (totals[2]): one atomic per group (64 slots: 10 k same-address atomics serialise)
+    if (!FILL && gleader && i1 > gfirst) atomicAdd(&n_hits[grp & 63u], (unsigned long long)(i1 - gfirst));
     // Four entries per lane and trip: a hit is a chain of dependent loads (entry -> the read's item and list head -> counter), each
     // link a trip to HBM through a TLB that an 8 GB table defeats; the links of four entries travel together instead of one
     // after the other (a seed of config 2 has 20-40 entries: one trip of a 16-lane group instead of three)
@@ -590,7 +477,6 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
             v[u] = ib + (uint32_t)u < i1;
             e[u] = v[u] ? e[u] : 0ull;
         }
-        KX_TICK(2)
         dp_scan_item item[4];
         uint32_t hd[4];
         bool in[4];
@@ -598,16 +484,15 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
         for (int u = 0; u < 4; u++) {
             const uint32_t r = (uint32_t)(e[u] >> 32);
             in[u] = v[u] && r >= lo && r < hi;
-            if (!FILL && R.ign) {
+            if (!FILL && F.ign) {
                 item[u] = dp_scan_item{};
-                item[u].n_kmers = (in[u] && !R.ign[r]) ? 0xffffffffu : 0u;
-                hd[u] = (v[u] && r - R.qlo < R.qspan) ? head[r] : 0u;
+                item[u].n_kmers = (in[u] && !F.ign[r]) ? 0xffffffffu : 0u;
+                hd[u] = (v[u] && r - F.qlo < F.qspan) ? head[r] : 0u;
             } else {
                 item[u] = in[u] ? items[r - lo] : dp_scan_item{};
                 hd[u] = v[u] ? head[r] : 0u;
             }
         }
-        KX_TICK(3)
         uint32_t cnt[4] = {0, 0, 0, 0};
         uint64_t so[4] = {0, 0, 0, 0};
         if (FILL) {
@@ -626,15 +511,7 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
             const uint32_t r = (uint32_t)(e[u] >> 32), p = (uint32_t)e[u];
             if (!FILL) {
                 // (ignored reads carry n_kmers == 0; a top-level read with len % 4 == 0 four k-mers less)
-                const bool valid = in[u] && p < item[u].n_kmers;
-                if (R.rec) {
-                    uint32_t rank = 0;
-                    if (valid) rank = atomicAdd(&counts[r - lo], 1u);
-                    if (v[u] && rec_at != 0xffffffffu)
-                        R.rec[(size_t)rec_at + (ib + (uint32_t)u - gfirst)] = kx_rec(hd[u] != 0, valid, r, rank, p);
-                } else if (valid) {
-                    atomicAdd(&counts[r - lo], 1u);
-                }
+                if (in[u] && p < item[u].n_kmers) atomicAdd(&counts[r - lo], 1u);
             } else if (in[u] && cnt[u] >= item[u].min_seeds) {
                 const uint32_t slot = atomicAdd(&fillc[r - lo], 1u);
                 const uint64_t at = so[u] + 2ull * slot;
@@ -657,26 +534,25 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
             }
         }
     }
-    KX_TICK(4)
-#undef KX_TICK
 }
-// (round 4: a launch may be narrower than its work - `n_waves` wave-sized pieces, walked with the grid's stride: the count
-// walk's 160 k lanes of dependent random loads and atomics are what slows every other round's kernels, HISTORY.md 5.7)
+// (`n_waves` wave-sized pieces, walked with the grid's stride.  Both launches bring a wave per piece, so the loop runs once - it stays
+// because the body placed directly in the kernel compiles kidx_walk<true> to 99 more instructions and two more VGPRs:
+// profiles/index_step_one_form_resources.txt)
 template <bool FILL>
 __global__ __launch_bounds__(256) void kidx_walk(const uint32_t* __restrict__ seeds, uint32_t n_seeds, const uint64_t* __restrict__ off,
                                                  const KxPos pos, const dp_scan_item* __restrict__ items, uint32_t lo, uint32_t hi,
                                                  uint32_t n_read_items, const uint32_t* __restrict__ head, const uint32_t* __restrict__ next,
                                                  uint32_t* __restrict__ counts, uint32_t* __restrict__ fillc,
                                                  const uint64_t* __restrict__ segoff, int32_t* __restrict__ segs,
-                                                 unsigned long long* __restrict__ n_hits, uint32_t lps, unsigned long long* __restrict__ dbg,
-                                                 const KxRec R, uint32_t n_waves) {
+                                                 unsigned long long* __restrict__ n_hits, uint32_t lps, const dp_kindex_fast F,
+                                                 uint32_t n_waves) {
     const uint32_t stride = gridDim.x * (blockDim.x >> 6);
     for (uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_waves; w += stride)
-        kidx_walk_one<FILL>(w, seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, fillc, segoff, segs, n_hits, lps, dbg, R);
+        kidx_walk_one<FILL>(w, seeds, n_seeds, off, pos, items, lo, hi, n_read_items, head, next, counts, fillc, segoff, segs, n_hits, lps, F);
 }
 
-// ---- round 5: the counting step without scattered atomics - hits binned by read range, counted in LDS ---------------------------
-// The count walk of rounds 1 - 4 bumps a counter per hit: 450 k memory-side atomics per config-2 round (10 M in the dense regime),
+// ---- the one-go form: the counting step without scattered atomics - hits binned by read range, counted in LDS -------------------
+// The fallback's count walk bumps a counter per hit: 450 k memory-side atomics per config-2 round (10 M in the dense regime),
 // each a 64-byte request of its own - 6.8 x the step's algorithmic bytes (profiles/kindex_traffic.json, round 4).  Here the walk
 // writes every hit that counts as an 8-byte record into the BIN of its read (bin = item >> bshift: a few hundred bins of 512 .. 16 k
 // consecutive reads) and touches no counter:
@@ -1463,9 +1339,6 @@ __device__ __forceinline__ void kx_sort_one(unsigned long long* keys, const int 
 
 // one wave per survivor: its slice holds c unordered (position, seed) pairs -> sorted by position -> [gap, seed, ..., gap]
 #define KX_SORT_LDS 4096
-// (round 4's hit records - DP_KX_BINS=0 - keep a hit's rank among its read's hits in 14 bits, read and position in 24 each: the one-go
-// step is only taken while no survivor has more hits than the LDS sort holds and reads / positions stay below 2^24, dp_scan.hip)
-static_assert(KX_SORT_LDS <= (1 << 14), "kx_rec keeps the rank of a hit in 14 bits: the LDS sort's capacity bounds it");
 // CAP = keys the block's LDS holds (the launch picks the smallest that fits the round's largest survivor: a CU then holds
 // eight times as many waves for the usual few dozen hits per read as for the rare thousands)
 template <int CAP>
@@ -1674,18 +1547,51 @@ static uint32_t kidx_walk_blocks(const dp_kindex* ix, int k, uint32_t S) {
     return (waves + 3) / 4;
 }
 
-// workgroups of the count walk's launch: all of its work at once (default), or DP_TUNE=kx_walk_blocks of them striding over it
-static uint32_t kidx_walk_grid(const dp_kindex* ix, int k, uint32_t S) {
-    const uint32_t lim = (uint32_t)std::max(0L, dp_tune("kx_walk_blocks", 0));
-    const uint32_t all = kidx_walk_blocks(ix, k, S);
-    return lim ? std::min(lim, all) : all;
+// Geometry of a one-go round's bins (pointers left null), and the regime.  `total`: records all bins share, 1.5 x the hits expected.
+//   sparse  bins of 512 .. 16 k reads, at most 256 of them while that keeps a bin's counters inside a workgroup's LDS;
+//   dense   (this context's previous round had 16 and more hits per read - k = 10: ~100 - and the small sort tiers hold its largest
+//           survivor; DP_KX_DENSE=0/1: never / whatever the hit density - tests reach both sides on small inputs): bins of 64 .. 256
+//           reads whose workgroup fills AND sorts in LDS (kidx_bin_sort_dense).  More than half a million reads: no such bins, sparse.
+// A bin holds its share of the records - and ONE bin also holds the round's query reads, consecutive reads that contain every seed
+// of the round by construction: + 2 S (measured at config 2: mean 2.3 k records per bin, 7.4 k in the query reads' bin).
+// The caller takes the one-go form only if n_bins <= KX_MAXBINS and cap < 2^31 (a larger cap comes back as 0xffffffff).
+struct KxGeometry {
+    KxBins B;
+    bool dense;
+};
+static KxGeometry kidx_bin_geometry(const dp_kindex_oneshot* one, uint32_t lps, uint32_t n_read_items, uint32_t S, uint64_t total) {
+    auto n_bins_at = [&](uint32_t bshift) { return (n_read_items + (1u << bshift) - 1) >> bshift; };
+    const int dense_env = dp_env_tristate("DP_KX_DENSE");
+    bool dense = one->sort_cap <= 1024 && (dense_env == 1 ? true
+                                           : dense_env != 0 && lps == 64 && one->hits_guess >= 16ull * n_read_items &&
+                                             one->hits_guess >= (1ull << 20));
+    uint32_t bshift = 6;
+    if (dense) {
+        while (n_bins_at(bshift) > KX_MAXBINS && bshift < 8) bshift++;
+        dense = n_bins_at(bshift) <= KX_MAXBINS;
+    }
+    if (!dense) {
+        bshift = 9;
+        while (n_bins_at(bshift) > 256 && bshift < KXB_RIB_BITS) bshift++;
+    }
+    KxGeometry G{};
+    G.dense = dense;
+    G.B.bshift = bshift;
+    G.B.n_bins = n_bins_at(bshift);
+    uint64_t cap = total / G.B.n_bins + std::min<uint64_t>(2 * (uint64_t)S, dense ? ((uint64_t)128 << bshift) : ~0ull) + 1024;
+    cap = (uint64_t)dp_env_long("DP_KX_BINS_CAP", (long)cap, 16);  // (test hook: bins that overflow)
+    G.B.cap = (uint32_t)std::min<uint64_t>(cap, 0xffffffffu);
+    G.B.xcap = (uint32_t)std::max<uint64_t>(65536, total / 8);
+    G.B.batch = 1u;
+    return G;
 }
 
-// Counting step of a round from the index: counts, segment offsets, compacted survivor list and totals for all items, with
+// Index step of a round from the index: counts, segment offsets, compacted survivor list and totals for all items, with
 // no host round trip.  d_work = [counts n | fill cursors n | tile status (tiles + 1) u64 | ticket, max count] (zeroed here).
-// `one` (round 4, may be null): the whole index step in one go - the count pass keeps hit records, and behind the offsets scan the
-// fill pass (from the records) and the sort/write pass are launched at once into a segment buffer sized from the round before;
-// the caller waits once and repeats fill + sort (dp_kindex_refill) for the rare round that outgrew a guess.
+// `one` (may be null): the whole step in one go - the walk bins its hits, and behind the offsets scan the fill and the sort/write
+// pass are launched at once into a segment buffer sized from the round before; the caller waits once and repeats fill + sort
+// (dp_kindex_refill + dp_kindex_write) for the rare round that outgrew a guess.  Returns 2 where `one` was given and the bins could
+// not be set up: the count alone was launched, and the caller goes on as if it had not asked (wait, dp_kindex_write).
 int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo, uint32_t hi, uint32_t n_read_items, uint32_t n_extra,
                     uint32_t* d_counts, uint64_t* d_segoff, uint32_t* s_item, uint32_t* s_count, uint64_t* s_off, uint4* s_pack,
                     uint64_t* d_totals, unsigned long long* host_totals, const dp_kindex_oneshot* one, const dp_kindex_fast* fast) {
@@ -1722,123 +1628,58 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
                            ctx->extras_staged ? (const dp_scan_item*)ctx->h_extra.p : (const dp_scan_item*)nullptr);
         ctx->extras_staged = false;
     }
-    // hit records: 64 shards of (estimated hits / 64) * 1.5 + 4096 records, two words per group
-    KxRec R{nullptr, nullptr, nullptr, 0u, nullptr, 0u, 0u};
-    if (fast && fast->ign) {
-        R.ign = fast->ign;
-        R.qlo = fast->qlo;
-        R.qspan = fast->qspan;
-    }
+    const dp_kindex_fast F = fast ? *fast : dp_kindex_fast{nullptr, 0u, 0u};
     const uint32_t lps = kidx_lps(ix, k);
-    const uint32_t n_groups = lps == 64 ? S * KX_PARTS : S;
-    if (one && S) {
+    const uint32_t n_waves = kidx_walk_blocks(ix, k, S) * 4;
+    // One go: the bins are set up (B.rec != null) where there are seeds and read items, a seed fits the record's KXB_SEED_BITS and the
+    // record buffer stays below 32 bits of index.  Otherwise: the fallback's count, and 2 for a caller that asked for one go.
+    KxBins B{};
+    bool dense = false;
+    if (one && S && n_read_items && S < (1u << KXB_SEED_BITS)) {
         // (no round of this context yet: three times the seeds' share of all positions - seeds are the commoner k-mers)
         const uint64_t first_guess = (uint64_t)((double)S * (double)(ix->n_pos) / (double)((uint64_t)1 << (2 * k)) * 3.0);
         const uint64_t est = std::max<uint64_t>(one->hits_guess ? one->hits_guess : first_guess, 65536);
-        const uint64_t shard = est / 64 + est / 128 + 4096;
-        if (shard * 64 < 0xfffffff0ull) {
-            if (dev_reserve(ctx, ctx->d_kx_keys, (size_t)shard * 64 * 8 + 64)) return DP_ERR_HIP;
-            if (dev_reserve(ctx, ctx->d_kx_tmp, (size_t)n_groups * 8 + 64)) return DP_ERR_HIP;
-            R.rec = (unsigned long long*)ctx->d_kx_keys.p;
-            R.kb = (uint32_t*)ctx->d_kx_tmp.p;
-            R.flags = (uint32_t*)(d_totals + 6);
-            R.shard_cap = (uint32_t)shard;
-        }
-    }
-    // round 5: hits binned by read range and counted in LDS instead of one memory-side atomic per hit (DP_KX_BINS=0: the records of
-    // round 4).  Bins of 512 .. 16 k reads, at most 256 of them while that keeps a bin inside the LDS; the bins share the record
-    // buffer of the shards (1.5 x the previous round's hits + 4096 each), the extra items' list lives in the group table's place.
-    KxBins B{};
-    const bool bins_on = dp_env_tristate("DP_KX_BINS") != 0;
-    // round 6, the dense regime (this context's previous round had 16 and more hits per read - k = 10: ~100): small bins whose
-    // workgroup fills AND sorts in LDS (kidx_bin_sort_dense), eight trips of a walk workgroup per bin reservation, the count as a launch
-    // of its own (one workgroup per bin instead of one per 4 096 reads inside kidx_offsets).  DP_KX_DENSE=0: off (A/B runs)
-    const int dense_env = dp_env_tristate("DP_KX_DENSE");
-    bool dense = false;
-    if (one && R.rec && bins_on && n_read_items && S < (1u << KXB_SEED_BITS)) {
-        uint32_t bshift = 9;
-        while (((n_read_items + (1u << bshift) - 1) >> bshift) > 256 && bshift < KXB_RIB_BITS) bshift++;
-        // (DP_KX_DENSE=1, tests: whatever the hit density - small inputs reach the dense kernels through it)
-        dense = one->sort_cap <= 1024 && (dense_env == 1 ? true
-                                          : dense_env != 0 && lps == 64 && one->hits_guess >= 16ull * n_read_items &&
-                                            one->hits_guess >= (1ull << 20));
-        if (dense) {
-            bshift = 6;
-            while (((n_read_items + (1u << bshift) - 1) >> bshift) > KX_MAXBINS && bshift < 8) bshift++;
-            if (((n_read_items + (1u << bshift) - 1) >> bshift) > KX_MAXBINS) {  // (more than half a million reads: the bins of round 5)
-                dense = false;
-                bshift = 9;
-                while (((n_read_items + (1u << bshift) - 1) >> bshift) > 256 && bshift < KXB_RIB_BITS) bshift++;
-            }
-        }
-        const uint32_t n_bins = (n_read_items + (1u << bshift) - 1) >> bshift;
-        const uint64_t total = (uint64_t)R.shard_cap * 64;
-        const uint64_t xcap = std::max<uint64_t>(65536, total / 8);
-        // a bin holds its share of the hits (1.5 x the round before, as the shards) - and ONE bin also holds the round's query reads,
-        // consecutive reads that contain every seed of the round by construction: + 2 S (measured at config 2: mean 2.3 k records per
-        // bin, 7.4 k in the query reads' bin)
-        uint64_t cap = total / n_bins + std::min<uint64_t>(2 * (uint64_t)S, dense ? ((uint64_t)128 << bshift) : ~0ull) + 1024;
-        cap = (uint64_t)dp_env_long("DP_KX_BINS_CAP", (long)cap, 16);  // (test hook: bins that overflow)
-        if (n_bins <= KX_MAXBINS && cap < 0x7fffffffu) {
-            if (dev_reserve(ctx, ctx->d_kx_tmp, std::max((size_t)n_groups * 8, (size_t)xcap * 16) + 64)) return DP_ERR_HIP;
-            if (dev_reserve(ctx, ctx->d_kx_keys, (size_t)cap * n_bins * 8 + 64)) return DP_ERR_HIP;
-            R.rec = (unsigned long long*)ctx->d_kx_keys.p;
-            B.rec = R.rec;
+        const uint64_t total = 64 * (est / 64 + est / 128 + 4096);
+        const KxGeometry G = kidx_bin_geometry(one, lps, n_read_items, S, total);
+        if (total < 0xfffffff0ull && G.B.n_bins <= KX_MAXBINS && G.B.cap < 0x7fffffffu) {
+            if (dev_reserve(ctx, ctx->d_kx_tmp, (size_t)G.B.xcap * 16 + 64)) return DP_ERR_HIP;
+            if (dev_reserve(ctx, ctx->d_kx_keys, (size_t)G.B.cap * G.B.n_bins * 8 + 64)) return DP_ERR_HIP;
+            B = G.B;
+            dense = G.dense;
+            B.rec = (unsigned long long*)ctx->d_kx_keys.p;
             B.cursor = bin_cursor;
-            B.flags = R.flags;
-            B.cap = (uint32_t)cap;
-            B.n_bins = n_bins;
-            B.bshift = bshift;
+            B.flags = (uint32_t*)(d_totals + 6);
             B.xrec = (uint4*)ctx->d_kx_tmp.p;
             B.xcursor = bin_cursor + KX_MAXBINS;
-            B.xcap = (uint32_t)xcap;
-            B.ign = R.ign;
-            B.qlo = R.qlo;
-            B.qspan = R.qspan;
-            B.batch = 1u;
-        } else {
-            dense = false;
+            B.ign = F.ign;
+            B.qlo = F.qlo;
+            B.qspan = F.qspan;
         }
     }
-    const bool kx_debug = ctx->dbg.kx;
-    unsigned long long* dbg = nullptr;
-    const size_t n_dbg_waves = (size_t)kidx_walk_blocks(ix, k, S) * 4;
-    if (kx_debug) {
-        DP_HIP(dp_dev_malloc((void**)&dbg, n_dbg_waves * 64));
-        DP_HIP(hipMemsetAsync(dbg, 0, n_dbg_waves * 64, ctx->stream));
-    }
-    bool count_in_offsets = false;
-    if (S && B.rec) {
-        const uint32_t n_waves = kidx_walk_blocks(ix, k, S) * 4;
-        const int bin_waves = (int)dp_tune("kx_bin_waves", 8);
-#define KX_WALK_BIN(W_)                                                                                                                \
-    hipLaunchKernelGGL((kidx_walk_bin<W_>), dim3((n_waves + W_ - 1) / W_), dim3(64 * W_), 0, ctx->stream, dp_seeds_ptr(ctx), S,        \
-                       (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head, (const uint32_t*)next, \
-                       d_counts, n_hits, lps, B, n_waves)
-        // (dense: 16 waves - four seeds a trip; measured at k = 10, five slots: 0.582 against 0.606 s per job, profiles/r06/k10_knobs.txt)
+    // bins no larger than a tile of kidx_offsets are counted by that kernel (one launch less per round); the dense regime's small bins
+    // and bins of more than 4 096 reads by kidx_bin_count, one workgroup per bin
+    const bool count_in_offsets = B.rec && !dense && (1u << B.bshift) <= KX_TILE * KX_IPT;
+    if (B.rec) {
         if (dense) {
-            // (trips per reservation: as many as make ONE workgroup per CU cover the round's waves - a 16-wave workgroup with its 105 VGPRs
-            // is alone on its CU, and 313 of them on 256 CUs were two rounds of workgroups for 1.2 rounds of work)
+            // 16 waves - four seeds a trip (measured at k = 10, five slots: 0.582 against 0.606 s per job, profiles/r06/k10_knobs.txt).
+            // Trips per reservation: as many as make ONE workgroup per CU cover the round's waves - a 16-wave workgroup with its 105 VGPRs
+            // is alone on its CU, and 313 of them on 256 CUs were two rounds of workgroups for 1.2 rounds of work
             B.batch = std::max<uint32_t>(1u, std::min<uint32_t>(32u, (n_waves + 16u * 256u - 1) / (16u * 256u)));
             const uint32_t per = 16u * B.batch;
             hipLaunchKernelGGL((kidx_walk_bin<16>), dim3((n_waves + per - 1) / per), dim3(64 * 16), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                                (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
                                (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves);
-        } else if (bin_waves <= 4) KX_WALK_BIN(4);
-        else if (bin_waves <= 8) KX_WALK_BIN(8);
-        else KX_WALK_BIN(16);
-#undef KX_WALK_BIN
-        // bins no larger than a tile of kidx_offsets are counted by that kernel (one launch less per round; DP_KX_FUSE=0: as before.
-        // Fill + sort in one launch for the sparse regime - DP_KX_FUSE=2 in round 5 - was slower and is gone: profiles/r05/ab12_fusions.txt)
-        const bool fuse_off = dp_env_tristate("DP_KX_FUSE") == 0;
-        count_in_offsets = !fuse_off && !dense && (1u << B.bshift) <= KX_TILE * KX_IPT;
-        if (count_in_offsets) {
-        } else if (B.bshift <= 9)
-            hipLaunchKernelGGL((kidx_bin_count<512>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
-        else if (B.bshift <= 12)
-            hipLaunchKernelGGL((kidx_bin_count<4096>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
-        else
-            hipLaunchKernelGGL((kidx_bin_count<16384>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
+        } else {
+            hipLaunchKernelGGL((kidx_walk_bin<8>), dim3((n_waves + 7) / 8), dim3(64 * 8), 0, ctx->stream, dp_seeds_ptr(ctx), S,
+                               (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
+                               (const uint32_t*)next, d_counts, n_hits, lps, B, n_waves);
+        }
+        if (!count_in_offsets) {
+            if (B.bshift <= 9)
+                hipLaunchKernelGGL((kidx_bin_count<512>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
+            else
+                hipLaunchKernelGGL((kidx_bin_count<16384>), dim3(B.n_bins), dim3(512), 0, ctx->stream, B, d_counts, n_read_items, lo);
+        }
         if (ctx->dbg.kx_bins) {  // (diagnosis: waits for the stream) how full the bins and the extra list are
             std::vector<uint32_t> cur((size_t)KX_MAXBINS + 2);
             uint64_t fl = 0;
@@ -1853,35 +1694,9 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
                     (unsigned long long)(one ? one->hits_guess : 0));
         }
     } else if (S)
-        hipLaunchKernelGGL((kidx_walk<false>), dim3(kidx_walk_grid(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
+        hipLaunchKernelGGL((kidx_walk<false>), dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                            (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
-                           (const uint32_t*)next, d_counts, fillc, (const uint64_t*)nullptr, (int32_t*)nullptr, n_hits, kidx_lps(ix, k),
-                           dbg, R, kidx_walk_blocks(ix, k, S) * 4);
-    if (kx_debug) {
-        std::vector<unsigned long long> h(n_dbg_waves * 8);
-        hipStreamSynchronize(ctx->stream);
-        hipMemcpy(h.data(), dbg, n_dbg_waves * 64, hipMemcpyDeviceToHost);
-        dp_dev_free(dbg);
-        unsigned long long first = ~0ull, lastStart = 0, lastEnd = 0;
-        double sum[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0};
-        size_t nw = 0;
-        for (size_t w = 0; w < n_dbg_waves; w++) {
-            const unsigned long long* t = &h[8 * w];
-            if (!t[0] || !t[4]) continue;
-            nw++;
-            first = std::min(first, t[0]);
-            lastStart = std::max(lastStart, t[0]);
-            lastEnd = std::max(lastEnd, t[4]);
-            for (int i = 1; i < 5; i++) {
-                const double d = (double)(t[i] - t[i - 1]) / 100.0;
-                sum[i] += d;
-                mx[i] = std::max(mx[i], d);
-            }
-        }
-        if (nw)
-            fprintf(stderr, "[kx] %zu waves, first start .. last start %.1f us, first start .. last end %.1f us | us per phase mean/max: bounds %.1f/%.1f entries %.1f/%.1f items %.1f/%.1f counters %.1f/%.1f\n",
-                    nw, (lastStart - first) / 100.0, (lastEnd - first) / 100.0, sum[1] / nw, mx[1], sum[2] / nw, mx[2], sum[3] / nw, mx[3], sum[4] / nw, mx[4]);
-    }
+                           (const uint32_t*)next, d_counts, fillc, (const uint64_t*)nullptr, (int32_t*)nullptr, n_hits, lps, F, n_waves);
     // totals[2] = seed occurrences in the read set, totals[3] = largest survivor count (both written by the kernel)
     {
         KxBins Bo = B;
@@ -1892,13 +1707,13 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
     }
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 1));
-    if (one && R.rec) {
+    if (B.rec) {  // one go: fill and sort behind the count, no wait in between
         DP_HIP(dp_mark(ctx, 2));
-        if (B.rec && dense) {
+        if (dense) {
             hipLaunchKernelGGL((kidx_bin_sort_dense<8192>), dim3(B.n_bins + KX_XBLOCKS), dim3(512), 0, ctx->stream, B, d_items,
                                n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff, one->d_segs,
                                (const uint64_t*)d_totals, one->seg_cap, k, (uint32_t*)(d_totals + 4));
-        } else if (B.rec) {
+        } else {
             const dim3 fg(B.n_bins + KX_XBLOCKS), fb(512);
             if (B.bshift <= 9)
                 hipLaunchKernelGGL((kidx_bin_fill<512>), fg, fb, 0, ctx->stream, B, d_items, n_read_items, (const uint32_t*)d_counts, fillc,
@@ -1909,10 +1724,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             else
                 hipLaunchKernelGGL((kidx_bin_fill<16384>), fg, fb, 0, ctx->stream, B, d_items, n_read_items, (const uint32_t*)d_counts,
                                    fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
-        } else
-            hipLaunchKernelGGL(kidx_fill_rec, dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, R, n_groups, lps, d_items, lo,
-                               n_read_items, one->min_seeds, (const uint32_t*)head, (const uint32_t*)next, (const uint32_t*)d_counts,
-                               fillc, (const uint64_t*)d_segoff, one->d_segs, (const uint64_t*)d_totals, one->seg_cap);
+        }
         // (the survivor count is on the device only: the grid covers the most survivors a round of this context has had so far,
         // the kernel strides over the rest)
         const dim3 sg(dense ? std::max<uint32_t>(64u, std::min<uint32_t>(n_extra, 16384))
@@ -1934,13 +1746,12 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         DP_HIP(hipGetLastError());
         DP_HIP(dp_mark(ctx, 3));
     }
-    (void)k;
-    return (one && !R.rec) ? 2 : DP_OK;  // 2: the one-go form was asked for and could not be launched (no seeds / too many records)
+    return (one && !B.rec) ? 2 : DP_OK;  // 2: one go was asked for and the bins could not be set up
 }
 
-// Second attempt of a round whose one-go fill + sort gave up (segment buffer or record shards too small, a survivor with more hits
-// than the guessed sort holds): the extra items are linked to their reads again (the sort pass has unlinked them), the fill cursors
-// go back to zero, then the bucket-walking fill and the sort with the right capacity - dp_kindex_write as before round 4.
+// Second attempt of a round whose one-go fill + sort gave up (segment buffer or a bin too small, a survivor with more hits than the
+// guessed sort holds): the extra items are linked to their reads again (the sort pass has unlinked them), the fill cursors go back
+// to zero, then the fallback's fill and the sort with the right capacity - dp_kindex_write.
 int dp_kindex_refill(dp_ctx* ctx, const dp_scan_item* d_items, uint32_t n_read_items, uint32_t n_extra) {
     const uint32_t n_items = n_read_items + n_extra;
     uint32_t* head = (uint32_t*)ctx->d_kx_lo.p;
@@ -1972,8 +1783,7 @@ int dp_kindex_write(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             hipLaunchKernelGGL((kidx_walk<true>), dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                                (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
                                (const uint32_t*)next, (uint32_t*)d_counts, fillc, d_segoff, d_segs, (unsigned long long*)nullptr,
-                               kidx_lps(ix, k), (unsigned long long*)nullptr, KxRec{nullptr, nullptr, nullptr, 0u, nullptr, 0u, 0u},
-                               kidx_walk_blocks(ix, k, S) * 4);
+                               kidx_lps(ix, k), dp_kindex_fast{nullptr, 0u, 0u}, kidx_walk_blocks(ix, k, S) * 4);
         const dim3 sg(std::min<uint32_t>(n_sel, 16384)), sb(64);
         uint32_t* ovf = (uint32_t*)(d_totals + 4);
         const uint32_t* nsp = (const uint32_t*)(d_totals + 1);

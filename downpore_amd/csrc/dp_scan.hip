@@ -533,7 +533,6 @@ extern "C" int dp_ctx_create(int device, dp_ctx** out) {
     dp_ctx* ctx = new dp_ctx();
     ctx->device = device;
     ctx->wait = dp_wait_mode_read();
-    ctx->dbg.kx = dp_debug("kx");
     ctx->dbg.kx_bins = dp_debug("kx_bins");
     ctx->dbg.kx_oneshot = dp_debug("kx_oneshot");
     ctx->dbg.cons = dp_debug("cons");
@@ -2380,10 +2379,10 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
         if (rc > 0) use_index = false;  // k > 14 or not enough free HBM for 8 B per base: scan
     }
     out->index_hits = 0;
-    // Round 4: the index step in one go - count (+ hit records), offsets, fill from the records and sort/write are all launched
+    // The index step in one go - the walk that bins its hits, offsets, fill from the bins and sort/write are all launched
     // before the one wait, into buffers sized from this context's previous index-mode round (twice its segments, 1.5 x its hits, the
-    // sort tier of 1.25 x its largest survivor); the rare round that outgrows a guess repeats fill + sort the old way after the
-    // wait.  DP_KX_ONESHOT=0: count, wait, size, fill, sort, wait - as before.
+    // sort tier of 1.25 x its largest survivor); the rare round that outgrows a guess repeats fill + sort with the bucket walk after
+    // the wait.  DP_KX_ONESHOT=0, or a round whose bins cannot be set up: count, wait, size, fill, sort, wait.
     const bool oneshot_env = dp_env_tristate("DP_KX_ONESHOT") != 0;
     bool oneshot = false;
     dp_kindex_oneshot one;
@@ -2391,7 +2390,7 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     const bool mirror_wanted = ctx->scan_fetch_extras_only && n_extra > 0;
     if (use_index) {
         const std::vector<uint32_t>& lens = ctx->owner ? ctx->owner->h_len : ctx->h_len;
-        if (ctx->kx_maxlen_reads != lens.size()) {  // (records hold 24 bits of read id and of position)
+        if (ctx->kx_maxlen_reads != lens.size()) {  // (a bin's record holds 24 bits of position)
             uint32_t mx = 0;
             for (uint32_t L : lens) mx = std::max(mx, L);
             ctx->kx_maxlen = mx;
@@ -2403,7 +2402,6 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
             one.surv_guess = ctx->kx_prev_surv ? ctx->kx_prev_surv + ctx->kx_prev_surv / 4 : 8192;
             const uint32_t mxg = ctx->kx_prev_max + ctx->kx_prev_max / 4;
             one.sort_cap = mxg <= 128 ? 256u : (mxg <= 512 ? 1024u : 4096u);
-            one.min_seeds = min_seeds;
             const uint64_t want = std::max<uint64_t>(2 * ctx->kx_prev_segs + 65536, 1u << 20);
             if (dev_reserve(ctx, ctx->d_segs, want * 4 + 64)) return DP_ERR_HIP;
             one.seg_cap = (ctx->d_segs.cap - 64) / 4;
@@ -2436,7 +2434,7 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
         int rc = dp_kindex_count(ctx, k, d_items, lo, hi, n_read_items, n_extra, (uint32_t*)ctx->d_counts.p, (uint64_t*)ctx->d_segoff.p,
                                  s_item, s_count, s_off, s_pack, totals, (unsigned long long*)ctx->h_total.p, oneshot ? &one : nullptr, &fastArgs);
         if (rc < 0) return rc;
-        if (rc == 2) oneshot = false;   // (records not possible this round: the two-step form follows)
+        if (rc == 2) oneshot = false;   // (no bins this round: the two-wait form follows)
         else if (rc > 0) use_index = false;  // more items than its scan handles: this round is scanned
     }
     if (!use_index) oneshot = false;

@@ -51,18 +51,18 @@ int main(int argc, char** argv) {
     unsetenv("DP_TUNE");
     unsetenv("DP_DEBUG");
     CHECK(dp_tune("spec_blocks", 7) == 7);
-    CHECK(!dp_debug("kx"));
+    CHECK(!dp_debug("kx_bins"));
     setenv("DP_TUNE", "", 1);
     setenv("DP_DEBUG", "", 1);
     CHECK(dp_tune("spec_blocks", 7) == 7);
-    CHECK(!dp_debug("kx"));
+    CHECK(!dp_debug("kx_bins"));
     setenv("DP_TUNE", "host_select,spec_blocks=3,,kb_b1=", 1);  // a -> 1, b=3 -> 3, an empty token, c= -> 0
     CHECK(dp_tune("host_select", 0) == 1);
     CHECK(dp_tune("spec_blocks", 7) == 3);
     CHECK(dp_tune("kb_b1", 8) == 0);
     CHECK(dp_tune("query_split", 5) == 5);
-    setenv("DP_DEBUG", "kx,,cons=", 1);
-    CHECK(dp_debug("kx") && dp_debug("cons") && !dp_debug("alloc"));
+    setenv("DP_DEBUG", "kx_bins,,cons=", 1);
+    CHECK(dp_debug("kx_bins") && dp_debug("cons") && !dp_debug("alloc"));
     // ---- a value that changes between two reads
     setenv("DP_TUNE", "spec_blocks=9", 1);
     CHECK(dp_tune("spec_blocks", 7) == 9);
@@ -70,7 +70,7 @@ int main(int argc, char** argv) {
     unsetenv("DP_TUNE");
     CHECK(dp_tune("spec_blocks", 7) == 7);
     setenv("DP_DEBUG", "alloc", 1);
-    CHECK(dp_debug("alloc") && !dp_debug("kx"));
+    CHECK(dp_debug("alloc") && !dp_debug("kx_bins"));
 
     // ---- string, long (default as it is, the variable's value clamped), tristate, word list
     unsetenv("DP_MAP_DEVICES");
@@ -146,8 +146,8 @@ int main(int argc, char** argv) {
             (void)dp_tune("spec_blocks", 0);
             setenv("DP_TUNE", "old_name=1", 1);  // a text that has had its line already
             (void)dp_tune("spec_blocks", 0);
-            setenv("DP_DEBUG", "kx,plannner", 1);
-            (void)dp_debug("kx");
+            setenv("DP_DEBUG", "kx_bins,plannner", 1);
+            (void)dp_debug("kx_bins");
             (void)dp_debug("planner");
         });
         CHECK(count(w3, "\n") == 1 && count(w3, "DP_DEBUG") == 1 && count(w3, "plannner") == 1);
@@ -160,7 +160,7 @@ int main(int argc, char** argv) {
     {
         for (int i = 1; i >= 0; i--) {
             setenv("DP_TUNE", i & 1 ? "spec_blocks=2,kb_b1=6" : "spec_blocks=1", 1);
-            setenv("DP_DEBUG", i & 1 ? "kx,cons" : "kx", 1);
+            setenv("DP_DEBUG", i & 1 ? "kx_bins,cons" : "kx_bins", 1);
         }
         std::atomic<bool> stop{false};
         std::atomic<int> bad{0};
@@ -170,13 +170,13 @@ int main(int argc, char** argv) {
                 if (v != 1 && v != 2) bad++;
                 const long b1 = dp_tune("kb_b1", 8);
                 if (b1 != 8 && b1 != 6) bad++;
-                if (!dp_debug("kx")) bad++;
+                if (!dp_debug("kx_bins")) bad++;
             }
         };
         std::thread a(reader), b(reader);
         for (int i = 0; i < 2000; i++) {
             setenv("DP_TUNE", i & 1 ? "spec_blocks=2,kb_b1=6" : "spec_blocks=1", 1);
-            setenv("DP_DEBUG", i & 1 ? "kx,cons" : "kx", 1);
+            setenv("DP_DEBUG", i & 1 ? "kx_bins,cons" : "kx_bins", 1);
         }
         stop = true;
         a.join();

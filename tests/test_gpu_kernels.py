@@ -337,6 +337,55 @@ def test_scan_prepare_index_and_scan_modes_agree(ctx):
         ctx.set_priority(False)
 
 
+def test_index_mode_round_without_read_items(ctx):
+    """A round with no read items (lo == hi) and two query windows: the index step has no bins to set up, so dp_kindex_count
+    launches the count alone and dp_scan_reads goes on in the two-wait form (count, wait, dp_kindex_write).  Same answer as the
+    two-wait form asked for by name (DP_KX_ONESHOT=0) and as the scan kernels; the next round over the whole range, one go again,
+    still equals its own scan-mode answer - the context is in order after the fallback."""
+    k = 10
+    bases, off = O.gen_reads(16, 80000, 300, 3000, 0.01, True)
+    N = 300
+    ctx.upload_reads(bases, off)
+    ctx.kmer_values(k)
+    rng = np.random.default_rng(3)
+    ignore = (rng.random(N) < 0.1).astype(np.uint8)
+    extra = [(5, 100, 500, 0), (9, 0, 300, 0)]
+    fields = ("read", "n_seeds", "seg_off", "extra_n_seeds", "segs")
+    saved = {name: os.environ.get(name) for name in ("DP_SCAN_INDEX", "DP_KX_ONESHOT")}
+
+    def call(lo, hi, index, oneshot):
+        os.environ["DP_SCAN_INDEX"] = index
+        os.environ.pop("DP_KX_ONESHOT", None)
+        if oneshot is not None:
+            os.environ["DP_KX_ONESHOT"] = oneshot
+        got = ctx.scan_reads(ignore, 11, lo, hi, False, 20, extra)
+        return int(got["index_mode"]), {f: np.array(got[f]).copy() for f in fields}
+
+    try:
+        os.environ["DP_SCAN_INDEX"] = "1"
+        ctx.scan_prepare(k)
+        ctx.round_begin(k, np.unique(rng.integers(1, 4 ** k, 6000)).astype(np.uint32))
+        empty = [call(7, 7, "1", None), call(7, 7, "1", "0"), call(7, 7, "0", None)]
+        assert [mode for mode, _ in empty] == [1, 1, 0]
+        first = empty[0][1]
+        assert len(first["read"]) == 0 and len(first["extra_n_seeds"]) == len(extra)
+        for _, other in empty[1:]:
+            for f in fields:
+                assert np.array_equal(first[f], other[f]), f
+        mode, whole = call(0, N, "1", None)
+        assert mode == 1 and len(whole["read"]) > 0
+        mode, scanned = call(0, N, "0", None)
+        assert mode == 0
+        for f in fields:
+            assert np.array_equal(whole[f], scanned[f]), f
+    finally:
+        for name, value in saved.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
+
+
 @pytest.mark.parametrize("n_seeds", [40000, 150000, 400000, 800000])
 def test_index_mode_write_sort_tiers(ctx, n_seeds):
     """The index-mode write step sorts a read's hits inside one wave's LDS: shuffle ranks up to 64 hits, an LDS rank sort up to

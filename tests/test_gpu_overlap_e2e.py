@@ -228,15 +228,13 @@ def test_overlap_kmer_index_mode(mode):
         del os.environ["DP_SCAN_INDEX"]
 
 
-@pytest.mark.parametrize("env", [{"DP_KX_BINS": "0"}, {"DP_KX_BINS_CAP": "300"}, {"DP_KX_BINS_CAP": "40"}, {"DP_KX_ONESHOT": "0"}, {"DP_KX_FUSE": "0"},
-                                 {"DP_KX_DENSE": "1"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "300"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "40"},
-                                 {"DP_TUNE": "kx_bin_waves=4"}])
+@pytest.mark.parametrize("env", [{"DP_KX_BINS_CAP": "300"}, {"DP_KX_BINS_CAP": "40"}, {"DP_KX_ONESHOT": "0"},
+                                 {"DP_KX_DENSE": "1"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "300"}, {"DP_KX_DENSE": "1", "DP_KX_BINS_CAP": "40"}])
 def test_kmer_index_counting_step_variants(monkeypatch, env):
     """The counting step of an index-mode round (dp_kindex.hip): hits binned by read range and counted in LDS (round 5, the default),
-    round 4's hit records with one atomic per hit (DP_KX_BINS=0), bins that overflow - a workgroup's share that does not fit is
+    bins that overflow - a workgroup's share that does not fit is
     counted the old way, what it reserved is marked unwritten, the fill pass walks the buckets (DP_KX_BINS_CAP: some bins at 300,
-    every bin at 40) - the two-wait form (DP_KX_ONESHOT=0), the count in a launch of its own instead of inside kidx_offsets (DP_KX_FUSE=0), walk
-    workgroups of four waves instead of eight (DP_TUNE=kx_bin_waves=4) and
+    every bin at 40) - the two-wait form (DP_KX_ONESHOT=0) and
     the dense regime's small bins filled and sorted in LDS with batched reservations (round 6, DP_KX_DENSE=1 forces it on these small
     inputs; with bins that overflow too).  All read per call, so a variant set here is the variant that runs.  Same PAF, same ignore flags as the oracle: dense seeds (k = 10, hundreds
     of hits per read), sparse seeds (k = 13), reads that get flagged, five slots."""
@@ -250,17 +248,18 @@ def test_kmer_index_counting_step_variants(monkeypatch, env):
     _run_both(7, 100000, 300, 4000, 10, himem=False, max_rounds=3)
 
 
-@pytest.mark.parametrize("N,L,overlap_size,env", [(132000, 600, 500, {"DP_KX_FUSE": "0", "DP_KX_DENSE": "0"}), (1049000, 260, 200, {})],
+@pytest.mark.parametrize("N,L,overlap_size,env", [(132000, 600, 500, {"DP_KX_DENSE": "0"}), (1049000, 260, 200, {})],
                          ids=["bins_of_1024_reads", "bins_of_8192_reads"])
 def test_kmer_index_bins_of_many_reads(monkeypatch, N, L, overlap_size, env):
     """The bins of the counting step hold 512 reads up to 131 072 read items, 1 024 - 4 096 up to 1 048 576 and 8 192 - 16 384 beyond
-    (at most 256 bins, dp_kindex_count): kidx_bin_count / kidx_bin_fill have an instantiation per size class, and the two larger ones
-    need that many reads - the smallest counts that select them, of the shortest reads that still overlap (k = 10, two rounds, one
-    slot; 132 000 reads: the count in a launch of its own and the dense form off, so that both kernels of the class run in both
-    rounds; beyond 524 288 reads there is no dense form).  Same PAF per round, same flagged reads as the oracle.
-    Nothing the library reports says which size class ran: the coupling is to the `bshift` loop of dp_kindex_count (dp_kindex.hip,
-    "> 256 && bshift < KXB_RIB_BITS") and to the `B.bshift <= 9 / <= 12` selectors of its launches - if those move, these read
-    counts move with them (DP_DEBUG=kx_bins prints the class: "bins of 1024 reads", "bins of 8192 reads")."""
+    (at most 256 bins, kidx_bin_geometry): kidx_bin_fill has an instantiation per size class, kidx_bin_count one for the largest, and
+    the two larger classes need that many reads - the smallest counts that select them, of the shortest reads that still overlap
+    (k = 10, two rounds, one slot; 132 000 reads: the dense form off, so that kidx_bin_fill<4096> runs in both rounds - the count
+    of this size class always runs inside kidx_offsets; beyond 524 288 reads there is no dense form, and the count is
+    kidx_bin_count<16384>).  Same PAF per round, same flagged reads as the oracle.
+    Nothing the library reports says which size class ran: the coupling is to the `bshift` loop of kidx_bin_geometry (dp_kindex.hip,
+    "> 256 && bshift < KXB_RIB_BITS") and to the `B.bshift <= 9 / <= 12` selectors of dp_kindex_count's launches - if those move,
+    these read counts move with them (DP_DEBUG=kx_bins prints the class: "bins of 1024 reads", "bins of 8192 reads")."""
     import ctypes as C
     from downpore_amd.overlap import OverlapPipeline, Reads
     monkeypatch.setenv("DP_SCAN_INDEX", "1")

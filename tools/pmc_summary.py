@@ -116,12 +116,12 @@ def traffic(fn, workload, desc, kernels, rounds_of):
 CHAIN = ["pair_scan_kernel", "chain_walk_kernel", "chain_spec_kernel", "chain_resolve_kernel", "match_anchor_kernel"]
 traffic("chain_traffic.json", "main", "chaining stage (pair_scan + chain_walk + chain_spec + chain_resolve + match_anchor)", CHAIN, "pair_scan_kernel")
 traffic("query_traffic.json", "main", "query_kernel<false> (+ <true> where launched)", ["query_kernel"], "pair_scan_kernel")
-traffic("kindex_traffic.json", "main", "index-mode counting step (kidx_prepare + kidx_walk_bin + kidx_bin_count [round 4: kidx_walk<false>] + kidx_offsets)",
+traffic("kindex_traffic.json", "main", "index-mode counting step (kidx_prepare + kidx_walk_bin + kidx_bin_count [fallback: kidx_walk<false>] + kidx_offsets)",
         ["kidx_prepare", "kidx_walk_bin", "kidx_bin_count", "kidx_walk<false>", "kidx_offsets"], "kidx_offsets")
-traffic("kindex_write_traffic.json", "main", "index-mode write step (kidx_bin_fill [round 4: kidx_fill_rec] / kidx_walk<true> + kidx_sortwrite)",
-        ["kidx_bin_fill", "kidx_fill_rec", "kidx_walk<true>", "kidx_sortwrite"], "kidx_offsets")
+traffic("kindex_write_traffic.json", "main", "index-mode write step (kidx_bin_fill [fallback: kidx_walk<true>] + kidx_sortwrite)",
+        ["kidx_bin_fill", "kidx_walk<true>", "kidx_sortwrite"], "kidx_offsets")
 traffic("dense_kindex_traffic.json", "dense", "index-mode counting + write steps at k = 10 (all kidx_* kernels)",
-        ["kidx_prepare", "kidx_walk_bin", "kidx_bin_count", "kidx_walk<false>", "kidx_offsets", "kidx_bin_fill", "kidx_fill_rec", "kidx_walk<true>", "kidx_sortwrite",
+        ["kidx_prepare", "kidx_walk_bin", "kidx_bin_count", "kidx_walk<false>", "kidx_offsets", "kidx_bin_fill", "kidx_walk<true>", "kidx_sortwrite",
          "kidx_bin_sort_dense"], "kidx_offsets")
 INDEX = ["chunk_kernel", "index_fill_kernel", "index_fill_rows_kernel", "posting_transpose_kernel", "posting_meta_kernel", "zero_regions_kernel"]
 traffic("index_build_traffic.json", "main", "index build of a round (chunk + index_fill(_rows) + posting_transpose + posting_meta + zero_regions)", INDEX, "pair_scan_kernel")
