@@ -867,7 +867,7 @@ struct ArgTable {
     bool parse(int argc, char** argv, std::string& err);
 };
 
-// test hooks (host_capi.cpp: dph_hand_*)
+// test hooks (host_testhooks.cpp: dph_hand_*, dph_test_coroutines)
 void trimBestIndices(int upto, const std::vector<SeedMatch*>& ms, int minMatch, int length, int* bestOut, int* backOut);  // host_seq.cpp
 long coroSelfTest(int nTasks, int yields);  // host_map.cpp: the read tasks' stack switch by itself
 bool handIsConsistent(const i64* l, const i64* r, bool circular, i64 refLen);                                                // host_map.cpp

@@ -1459,7 +1459,7 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     return 0;
 }
 
-// ---- self-test of the coroutine switch (include/downpore_host.h, test hooks): n_tasks coroutines on recycled stacks, every one adds
+// ---- self-test of the coroutine switch (dph_testhooks.h: dph_test_coroutines): n_tasks coroutines on recycled stacks, every one adds
 // its number `yields` times with a switch back to the caller in between and touches its stack deeply; returns the sum (-1: a task
 // was resumed with a damaged frame).  What the mapper does with its read tasks, without a GPU - and under the sanitizer builds.
 namespace {

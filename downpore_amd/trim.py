@@ -8,7 +8,8 @@ from .hip import DpError, load_library
 from .overlap import load_host
 
 TRIM_STAT_FIELDS = ["seen", "none", "reads", "front_adapters", "back_adapters", "t_determine_s", "t_extract_s", "upload_ms", "kernel_ms",
-                    "download_ms", "t_apply_s", "t_write_s", "determine_kernel_ms", "bytes_up", "bytes_down"]
+                    "download_ms", "t_apply_s", "t_write_s", "determine_kernel_ms", "bytes_up", "bytes_down",
+                    "reserved"]  # (the writer's sixteenth double, always 0: the list is as long as DPH_TRIM_STATS says)
 #: columns of the per-read table
 TRIM_TABLE_FIELDS = ["front_trim", "back_trim", "ignore", "front_adapter", "back_adapter"]
 #: fields of one edge record (dp_trim_rec)
@@ -77,7 +78,7 @@ class TrimResult:
         H.dph_trim_table(h, self.table.ctypes.data, nr)
         ad = C.string_at(H.dph_trim_adapters(h, C.byref(n)), n.value).decode()
         self.adapters = [(ln.split("\t")[0], ln.split("\t")[1], int(ln.split("\t")[2])) for ln in ad.splitlines()]
-        st = np.zeros(16, dtype=np.float64)
+        st = np.zeros(len(TRIM_STAT_FIELDS), dtype=np.float64)
         H.dph_trim_stats(h, st.ctypes.data)
         self.stats = dict(zip(TRIM_STAT_FIELDS, st.tolist()))
         # the middle stage (empty / zero when it did not run)
@@ -89,7 +90,7 @@ class TrimResult:
 
         self.plan, self.splits, self.applied = ints(0, 6), ints(1, 4), ints(2, 6)
         self.extras = C.string_at(H.dph_trim_extras(h, C.byref(n)), n.value).decode().splitlines()
-        ms = np.zeros(12, dtype=np.float64)
+        ms = np.zeros(len(TRIM_MID_STAT_FIELDS), dtype=np.float64)
         H.dph_trim_mid_stats(h, ms.ctypes.data)
         self.stats.update(zip(TRIM_MID_STAT_FIELDS, ms.tolist()))
         self._H, self._h = H, h

@@ -16,6 +16,9 @@
  * (dph_last_error gives the text); returned text / byte pointers belong to the handle and stay valid until the next call of the
  * same function on it.  One caller thread per handle (the library runs its own threads behind it).  No CPU fallback: the calls
  * fail without a GPU.
+ *
+ * Everything declared here is exported under the version node DPH.  What the library exports for its own tests alone (version node
+ * DPH_TEST) is declared in downpore_amd/csrc/host/dph_testhooks.h, not here: no embedder calls it.
  */
 #ifndef DOWNPORE_HOST_H
 #define DOWNPORE_HOST_H
@@ -92,8 +95,9 @@ DPH_API const double* dph_overlap_values(void* h, int64_t* n);
 DPH_API void* dph_overlap_ctx(void* h);
 /* out[3]: seconds spent creating the context, uploading + packing the reads, in the last dph_overlap_init */
 DPH_API void dph_overlap_setup_times(void* h, double* out);
-/* statistics of the last committed round / summed over the job: out[31] doubles in the order of downpore_amd/overlap.py
- * STAT_FIELDS (host seconds per phase, kernel milliseconds, algorithmic bytes, counts) */
+/* statistics of the last committed round / summed over the job: out[DPH_OVERLAP_STATS] doubles in the order of
+ * downpore_amd/overlap.py STAT_FIELDS (host seconds per phase, kernel milliseconds, algorithmic bytes, counts) */
+#define DPH_OVERLAP_STATS 32
 DPH_API void dph_overlap_stats(void* h, double* out);
 DPH_API void dph_overlap_stats_total(void* h, double* out);
 
@@ -138,7 +142,7 @@ DPH_API int dph_overlap_commit_blobs(void* h, const uint8_t* blobs, const uint64
  * The whole command: reference = first sequence of `ref` (a read set opened with himem = 0), reads top-level.  params[6] =
  * circular, k, query_size, min_length, chunk_size, seed_rate.  DP_MAP_SHARDS / DP_MAP_DEVICES in the environment spread the
  * reference index over several contexts / GPUs (BASELINE config 5).  Returns a handle holding the PAF (read order) and the
- * reference's stderr lines, or NULL.  dph_map_stats: out[13] = chunks, seeds, windows, chains, batches, scan kernel ms, map
+ * reference's stderr lines, or NULL.  dph_map_stats: out[DPH_MAP_STATS] = chunks, seeds, windows, chains, batches, scan kernel ms, map
  * kernel ms, seconds of set-up / window scans / dp_map_windows / host, algorithmic bytes of the map kernels (index query +
  * prefilter + chaining) and of the window scans (packed bases). */
 DPH_API void* dph_map_run(void* ref, void* reads, const int64_t* params, int device);
@@ -159,6 +163,7 @@ DPH_API void* dph_map_run_ex(void* ref, void* reads, const int64_t* params, int 
 DPH_API void dph_map_free(void* m);
 DPH_API const char* dph_map_paf(void* m, int64_t* n);
 DPH_API const char* dph_map_errtext(void* m, int64_t* n);
+#define DPH_MAP_STATS 13
 DPH_API void dph_map_stats(void* m, double* out);
 /* The run's reference index: out[0..9] = layout (1 dense, 2 sparse), device bytes of the indexes built, the dense estimate D, the
  * device's total memory, H (seed hits in chunks), contexts that built an index, then the queries by regime: 4/8-ladder (minCount
@@ -178,7 +183,7 @@ DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
  * dph_trim_output: the trimmed FASTA / FASTQ text; dph_trim_errtext: the reference's log lines without their timestamps.
  * dph_trim_table: int32[reads][5] = front_trim, back_trim, ignore, front adapter index or -1, back adapter index or -1; returns the
  * number of reads.  dph_trim_adapters: "F|B <tab> name <tab> matches" lines, the adapters after determination in the trimmer's order.
- * dph_trim_stats: out[16] = seen, none, reads, front adapters, back adapters, determination s, end extraction s, upload ms, kernel
+ * dph_trim_stats: out[DPH_TRIM_STATS] = seen, none, reads, front adapters, back adapters, determination s, end extraction s, upload ms, kernel
  * ms, download ms, host apply s, write s, determination kernel ms, bytes up, bytes down, 0.
  * dph_trim_demultiplex: <dir>/<label>.fasta|.fastq per barcode label (seqio.go:460-523); returns the number of files or < 0.
  * dph_trim_index: setupIndex (trim.go:57-99) in the layout dp_trim_setup takes - kmer_seed[4^k], segs[seg_cap], seg_off[n + 1],
@@ -194,6 +199,7 @@ DPH_API const char* dph_trim_output(void* t, int64_t* n);
 DPH_API const char* dph_trim_errtext(void* t, int64_t* n);
 DPH_API int64_t dph_trim_table(void* t, int32_t* out, int64_t cap_reads);
 DPH_API const char* dph_trim_adapters(void* t, int64_t* n);
+#define DPH_TRIM_STATS 16
 DPH_API void dph_trim_stats(void* t, double* out);
 DPH_API int dph_trim_demultiplex(void* t, const char* dir);
 DPH_API int64_t dph_trim_index(void* front, void* back, int k, uint16_t* kmer_seed, int32_t* segs, int64_t seg_cap, uint64_t* seg_off,
@@ -214,7 +220,7 @@ DPH_API int64_t dph_trim_index(void* front, void* back, int k, uint16_t* kmer_se
  * bases covered, chain length - in any order: they are applied batch by batch, adapter by adapter, in chunk and ordinal order.
  * dph_trim_mid_ints: which = 0 the plan (read, start, end, remainder, seeds, indexed per chunk), 1 the splits (read, aEnd, bStart,
  * kept halves: bit 0 left, bit 1 right), 2 the records applied; returns the number of int32.  dph_trim_extras: the halves' names,
- * one per line.  dph_trim_mid_stats: out[12] = chunks, seeds, batches, candidate pairs, records applied, overflow pairs,
+ * one per line.  dph_trim_mid_stats: out[DPH_TRIM_MID_STATS] = chunks, seeds, batches, candidate pairs, records applied, overflow pairs,
  * out-of-range halves (a right half whose start is negative is skipped, counted and named in the log), upload / scan / index /
  * query / kernel ms. */
 DPH_API void* dph_trim_apply_mid(void* reads, void* front, void* back, const int64_t* params, int n_params, const uint8_t* enabled,
@@ -223,45 +229,10 @@ DPH_API void* dph_trim_apply_mid(void* reads, void* front, void* back, const int
 DPH_API int64_t dph_trim_chunk_plan(int64_t length, int64_t chunk_size, int32_t* out, int64_t cap);
 DPH_API int64_t dph_trim_mid_ints(void* t, int which, int32_t* out, int64_t cap);
 DPH_API const char* dph_trim_extras(void* t, int64_t* n);
+#define DPH_TRIM_MID_STATS 12
 DPH_API void dph_trim_mid_stats(void* t, double* out);
-/* test hook: the exact host Match that the (chunk, front adapter) pairs beyond the matching kernel's working set are given to, with
- * the identity test; segments as [gap, seed, ..., gap]; out = six int32 per passing match; returns their number */
-DPH_API int64_t dph_hand_trim_match(const int32_t* chunk_segs, int n_chunk, const int32_t* adapter_segs, int n_adapter, int adapter_len,
-                                    int n_seeds, int k, int threshold, int adapter, int chunk, int32_t* out, int64_t cap);
 
-/* ---- test hooks (host logic without a GPU, counters) ------------------------------------------------------------------------ */
-DPH_API const char* dph_reads_dump(void* reads, int64_t* n);
-DPH_API void dph_values_from_counts(uint64_t* counts, int k, double* out);
-
-/* ---- test hooks (not part of the boundary): decision rules of the host side on bare numbers, held by tests/test_hand_known_answers.py
- * to answers worked by hand from the reference's Go text (the files under tests/golden/hand).
- * dph_hand_is_consistent   mapping.isConsistent (mapping/mapping.go:131-160): left5 = {RC, Query.Len(), QueryInset, Start, End},
- *                          right4 = {RC, QueryOffset, Start, End}
- * dph_hand_remove_dominated  removeDominated (mapping.go:387-428): maps3 = n x {QueryOffset, QueryInset, ids}; kept[] = the survivors'
- *                          indices in the order the function returns them; returns their number
- * dph_hand_trim_indices    step 1 of trimToBestSeed (overlap/combine.go:24-58): match i's MatchA = match_a[off[i] .. off[i + 1]);
- *                          out2 = {bestIndex, backIndex}
- * dph_test_coroutines     the mapper's read tasks are stackful coroutines (host/host_coro.hpp): n_tasks of them on recycled stacks,
- *                          each resumed `yields` times; returns the sum of id x yields over the tasks, -1 if a frame came back damaged.
- */
-DPH_API long dph_test_coroutines(int n_tasks, int yields);
-/* packBytes of a whole read as `map` hands its reads to the device (sequence/sequence.go:59-93); out: ceil(n / 4) bytes; scalar_only:
-   without the AVX2 path */
-DPH_API void dph_pack_bases(const char* bases, int64_t n, uint8_t* out, int scalar_only);
-/* SeedIndex.AddSeeds (seeds/seeds.go:62-156) of one top-level sequence into an empty index, as the planner's host selection does it: the index's
-   seedMap (k-mers in seed-id order); returns their number, -1 when cap is too small */
-DPH_API int dph_hand_add_seeds(const char* bases, int64_t len, int k, int num_seeds, const double* values, uint32_t* seed_map, int cap);
-/* SeedMatch.GetBasesCovered (seeds/sequence.go:830-858: the PAF line's tenth column) on raw segment arrays and matched seed indices;
-   out2 = {countA, countB}; returns 1 where the reference would panic */
-DPH_API int dph_hand_bases_covered(const int32_t* a_seg, int a_n, const int32_t* b_seg, int b_n, const int32_t* match_a, const int32_t* match_b, int n,
-                                   int k, int64_t* out2);
-/* multiAligner.Consensus of the host's consensus path (seeds/alignment.go:23-268) on raw segment arrays: sequence i = segs[off[i] .. off[i + 1]);
-   the consensus' segments, the indices of the sequences whose match was kept (>= 3 pairs) in the order returned, their pairs */
-DPH_API int dph_hand_consensus(const int32_t* segs, const int64_t* off, int n_seqs, int k, int32_t* cons_out, int64_t cons_cap, int64_t* cons_n,
-                               int* kept, int64_t* out_counts, int32_t* out_a, int32_t* out_b, int64_t cap, int64_t* n_matches);
-DPH_API int dph_hand_is_consistent(const int64_t* left5, const int64_t* right4, int circular, int64_t ref_len);
-DPH_API int dph_hand_remove_dominated(const int64_t* maps3, int n, int64_t query_len, int* kept);
-DPH_API void dph_hand_trim_indices(int upto, const int32_t* match_a, const int64_t* off, int n_matches, int min_match, int length, int* out2);
+/* ---- process-wide: profile, pipeline counters, kept buffers ------------------------------------------------------------------ */
 DPH_API void dph_profile_print(void);
 /* process-wide pipeline counters since the process started: 0 plans computed, 1 thrown away, 2 erased by a commit's flags, 3 rounds
    executed, 4 rejected at the commit, 5 committed, 6 us in plan computes (wall, all lanes), 7 us the slots waited for plans,
@@ -275,24 +246,6 @@ DPH_API int64_t dph_planner_counter(int which);
  * the last `map` command (reference + reads, ~400 MB at BASELINE config 3).  A long-lived embedder calls this after its last job
  * (or whenever it wants the memory back; a running job simply allocates again).  Returns the bytes released. */
 DPH_API int64_t dph_release_caches(void);
-DPH_API int dph_selftest_planner_flags(void* reads, int k, int64_t seed_batch_size, const double* values);
-DPH_API int dph_selftest_planner_lanes(void* reads, int k, int64_t seed_batch_size, const double* values, int lanes, int flag_every,
-                                       int64_t* n_rounds);
-/* the plan chain of a round-parallel run of `world` ranks whose planners compute only their own rounds' plans and guess the rest
- * (Planner::setOwnership), played against a commit that accepts a plan iff it starts at the committed firstSequence */
-DPH_API int dph_selftest_planner_sparse(void* reads, int k, int64_t seed_batch_size, const double* values, int world, int flag_every,
-                                        int64_t* n_rounds, int64_t* n_redone);
-DPH_API int dph_selftest_touch(int k, const uint32_t* seeds, int64_t n_seeds, const uint32_t* kmers, int64_t n_windows, int64_t stride,
-                               uint8_t* res, int* isa_mask);
-/* finalCheckWorker (commands/overlap.go:197-233) over externally supplied queries, indexed sequences and matches (flat arrays
- * in the reference's segment layout): returns the round's PAF text and applies SetIgnore to `reads` */
-DPH_API const char* dph_finalcheck(void* reads, int k, int64_t overlap_size, const uint32_t* seed_kmers, int64_t n_seeds,
-                                   const int32_t* q_segs, const int64_t* q_off, const int64_t* q_id, const int64_t* q_seq_id,
-                                   const int64_t* q_len, const int64_t* q_offset, const int64_t* q_inset, int64_t n_q,
-                                   const int32_t* i_segs, const int64_t* i_off, const int64_t* i_id, const int64_t* i_len,
-                                   const int64_t* i_offset, const int64_t* i_inset, int64_t n_i, const int64_t* m_query,
-                                   const int64_t* m_target, const int64_t* m_off, const int32_t* m_a, const int32_t* m_b,
-                                   int64_t n_m, int64_t num_query_seqs, int64_t* out_len, int64_t* out_stats);
 
 #ifdef __cplusplus
 }
