@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "downpore_hip.h"
+#include "dp_chunk_bound.h"  // dp_chunk_walk_bounded: the chunk parameters the device accepts
 #include "dp_env.h"  // every run-time setting: the table, dp_tune / dp_debug, and when each is read
 
 // make COPYLOG=1: every hipMemcpyAsync of the library is counted per call site (file:line, direction, calls, bytes) and the table is

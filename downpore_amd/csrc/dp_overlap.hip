@@ -480,7 +480,9 @@ __global__ __launch_bounds__(1024) void chunk_kernel(const ChunkParams P, unsign
 }
 
 // upper bound of the chunks chunkWorker makes of a read with `numSeeds` hits: every chunk but the last holds >= minSeeds seeds
-// and the walk backs up at most 5 seeds (or overlap/2 bases) after each
+// and the walk backs up at most 5 seeds (or overlap/2 bases) after each.  Holds - and the kernel's loop ends - for the parameters
+// dp_chunk_walk_bounded (dp_chunk_bound.h) admits; the two entry points refuse every other set before anything is launched or armed.
+#define CHUNK_UNBOUNDED_MSG(fn_) fn_ ": the device chunks only with 6 <= min_seeds <= 100 and overlap / 2 <= chunk_size (the walk is not bounded otherwise)"
 static uint32_t chunk_cap_of(uint32_t numSeeds, long long length, long long chunkSize, int minSeeds) {
     if (length / chunkSize + 1 == 1 || (int)numSeeds < minSeeds * 3 || numSeeds <= 150) return 1;  // (<= 150 seeds: the walk ends at once)
     const int step = std::max(1, minSeeds - 5);
@@ -614,6 +616,11 @@ static int index_chunked_launch(dp_ctx* ctx, int64_t chunk_size, int64_t overlap
 // again, the old way, for the rare round that outgrew them).
 extern "C" int dp_index_prechain(dp_ctx* ctx, int64_t chunk_size, int64_t overlap, uint32_t min_seeds, int32_t inset) {
     if (!ctx || chunk_size < 1) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_index_prechain: bad arguments") : DP_ERR_ARG;
+    if (!dp_chunk_walk_bounded(chunk_size, overlap, min_seeds)) {  // (nothing is armed: the next scan launches no chunk stage)
+        ctx->pc_armed = false;
+        ctx->pc_launched = false;
+        return dp_fail(ctx, DP_ERR_ARG, CHUNK_UNBOUNDED_MSG("dp_index_prechain"));
+    }
     ctx->pc_armed = true;
     ctx->pc_launched = false;
     ctx->pc_chunk_size = chunk_size;
@@ -646,6 +653,7 @@ void dp_index_prechain_cancel(dp_ctx* ctx) { ctx->pc_launched = false; }
 extern "C" int dp_index_build_chunked(dp_ctx* ctx, int64_t chunk_size, int64_t overlap, uint32_t min_seeds, int32_t inset,
                                       uint32_t n_survivors, uint32_t* n_seqs_cap) {
     if (!ctx || chunk_size < 1 || !n_seqs_cap) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_index_build_chunked: bad arguments") : DP_ERR_ARG;
+    if (!dp_chunk_walk_bounded(chunk_size, overlap, min_seeds)) return dp_fail(ctx, DP_ERR_ARG, CHUNK_UNBOUNDED_MSG("dp_index_build_chunked"));
     if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_index_build_chunked before dp_round_begin");
     if (!ctx->h_surv.p || !ctx->d_surv.p) return dp_fail(ctx, DP_ERR_STATE, "dp_index_build_chunked: no dp_scan_reads result on this context");
     hipSetDevice(ctx->device);

@@ -251,7 +251,7 @@ int Overlapper::ScanLocal(size_t lo, size_t hi, Survivors& local, RoundStats& st
     dp_scan_fetch_mode(ctx_, deviceChunkWanted_ ? 1 : 0);
     // the chunk stage of IndexSurvivors goes behind the scan's own kernels (dp_index_prechain) when this context will chunk its own
     // survivors on the device; survivors gathered from other ranks are chunked after the exchange, as before
-    if (deviceChunkWanted_ && minSeeds_ > 5 && prechainOk_) dp_index_prechain(ctx_, chunkSize_, overlap_, (uint32_t)minSeeds_, (int32_t)reads_.servedInset());
+    if (deviceChunkWanted_ && dp_chunk_walk_bounded(chunkSize_, overlap_, minSeeds_) && prechainOk_) dp_index_prechain(ctx_, chunkSize_, overlap_, (uint32_t)minSeeds_, (int32_t)reads_.servedInset());
     int rc = dp_scan_reads(ctx_, ignore_, ignoreEpoch_, (uint32_t)lo, (uint32_t)hi, reads_.himem ? 0 : 1, (uint32_t)minSeeds_,
                            items.data(), (uint32_t)items.size(), &b);
     if (rc != 0) {
@@ -392,9 +392,10 @@ void Overlapper::chunkAndAdd(SeedSeq* s, uint64_t segBase, Arena& ar, std::vecto
 int Overlapper::IndexSurvivors(const Survivors& all, RoundStats& st) {
     double tp0 = now();
     chunksOnDevice_ = false;
-    // (minSeeds <= 5: the reference's walk backs up as many seeds as a chunk holds - no bound on the number of chunks to size the
-    // device buffers from; the host loop below does what the reference does)
-    if (deviceChunkWanted_ && minSeeds_ > 5 && all.deviceResident && all.chunkCtx == ctx_) {
+    // (outside dp_chunk_walk_bounded - minSeeds <= 5, say: the reference's walk backs up as many seeds as a chunk holds - there is no
+    // bound on the number of chunks to size the device buffers from, nor on the kernel's loop, and the library refuses; the host
+    // loop below does what the reference does)
+    if (deviceChunkWanted_ && dp_chunk_walk_bounded(chunkSize_, overlap_, minSeeds_) && all.deviceResident && all.chunkCtx == ctx_) {
         // A12 + A13 on the device: the survivors of this context's own scan - or the set gathered from every rank - still in
         // its scan buffer
         index_.sequences.clear();

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "../dp_chunk_bound.h"  // dp_chunk_walk_bounded: the chunk parameters the device accepts
 #include "../dp_env.h"  // every run-time setting: the table, dp_tune / dp_debug, and when each is read
 #include "dph.hpp"
 

@@ -512,7 +512,12 @@ DP_API int dp_consensus_paf(dp_ctx* ctx, const dp_seq_meta* metas, uint32_t n_se
  * dp_scan_reads, in file order, then AddSequence + IndexSequences as dp_index_build does.  The chunks never leave the device:
  * *n_seqs_cap is an upper bound of their number (it sizes the bit matrices; dp_consensus_paf reports the exact count and takes
  * the chunks' {read, length, offset, inset} from the device when its `metas` is NULL; `inset` = the served view's inset);
- * dp_index_chunks copies them to the host for a caller that needs them there. */
+ * dp_index_chunks copies them to the host for a caller that needs them there.
+ * Limits: 6 <= min_seeds <= 100 and overlap / 2 <= chunk_size.  Only there does every turn of the reference's walk move on (a piece
+ * of min_seeds seeds is followed by a back-up of up to five; fewer than min_seeds seeds inside chunk_size bases are followed by a
+ * back-up of overlap / 2 bases less the bases counted), so only there the kernel's loop ends and the bound holds.  Any other set is
+ * refused with DP_ERR_ARG, by this call and by dp_index_prechain, before anything is launched or announced: chunk such a job on
+ * the host and use dp_index_build. */
 DP_API int dp_index_build_chunked(dp_ctx* ctx, int64_t chunk_size, int64_t overlap, uint32_t min_seeds, int32_t inset, uint32_t n_survivors,
                            uint32_t* n_seqs_cap);
 DP_API int dp_index_chunks(dp_ctx* ctx, dp_seq_ref* refs_out, dp_seq_meta* metas_out, uint32_t cap, uint32_t* n_out);
@@ -523,7 +528,8 @@ DP_API int dp_index_chunks(dp_ctx* ctx, dp_seq_ref* refs_out, dp_seq_meta* metas
  * a sequence as soon as AddSequences has produced it, overlap/overlap.go:217-250).  dp_index_build_chunked with the same
  * parameters then only checks the guesses against the exact bound, and launches the old way for the rare round that outgrew them
  * (or whenever nothing was launched: a scanned round, the first round of a context).  dp_index_prechained: 1 if the last
- * dp_scan_reads did launch the chunk stage (dp_query_prestage has nothing to ride on then). */
+ * dp_scan_reads did launch the chunk stage (dp_query_prestage has nothing to ride on then).  dp_index_prechain takes the parameters
+ * dp_index_build_chunked takes (6 <= min_seeds <= 100, overlap / 2 <= chunk_size) and returns DP_ERR_ARG for any other. */
 DP_API int dp_index_prechain(dp_ctx* ctx, int64_t chunk_size, int64_t overlap, uint32_t min_seeds, int32_t inset);
 DP_API int dp_index_prechained(const dp_ctx* ctx);
 /* The match lists of the last dp_find_overlaps on this context (what that call returns itself unless bit 1 of

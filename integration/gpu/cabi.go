@@ -687,6 +687,9 @@ func (c *Context) ScanFetchMode(extrasOnly bool) error {
 
 // IndexBuildChunked is chunkWorker (overlap/overlap.go:253-318) + AddSequence + IndexSequences for the first nSurvivors
 // survivors of the last ScanReads, all on the device.  Returns an upper bound of the number of chunks.
+// The device chunks only with 6 <= minSeeds <= 100 and overlap / 2 <= chunkSize: outside that set the reference's walk is not
+// bounded (a back-up can undo a whole piece) and the call fails with DP_ERR_ARG before anything is launched - chunk on the host
+// and call IndexBuild then.
 func (c *Context) IndexBuildChunked(chunkSize, overlap int64, minSeeds, inset, nSurvivors int) (int, error) {
 	var cap C.uint32_t
 	rc := C.dp_index_build_chunked(c.h, C.int64_t(chunkSize), C.int64_t(overlap), C.uint32_t(minSeeds), C.int32_t(inset), C.uint32_t(nSurvivors), &cap)
@@ -697,7 +700,8 @@ func (c *Context) IndexBuildChunked(chunkSize, overlap int64, minSeeds, inset, n
 }
 
 // IndexPrechain announces the IndexBuildChunked call that follows the next ScanReads: an index-mode scan then launches the chunk
-// stage itself, behind its own kernels, and returns as soon as its own output has arrived (dp_index_prechain).
+// stage itself, behind its own kernels, and returns as soon as its own output has arrived (dp_index_prechain).  The same limits
+// as IndexBuildChunked: 6 <= minSeeds <= 100 and overlap / 2 <= chunkSize, or DP_ERR_ARG and nothing is announced.
 func (c *Context) IndexPrechain(chunkSize, overlap int64, minSeeds, inset int) error {
 	if rc := C.dp_index_prechain(c.h, C.int64_t(chunkSize), C.int64_t(overlap), C.uint32_t(minSeeds), C.int32_t(inset)); rc != 0 {
 		return fail(c.h, "dp_index_prechain", rc)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import oracle_lib as O
+from tests.index_cases import expected_segments as _expected_segments
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +26,6 @@ def _case(seed, G, N, L, k, e=0.0, variable=False, rounds=2, **kw):
     values = rs.kmer_values(k)
     run = O.OverlapRun(rs, k=k, values=values, max_rounds=rounds, traces=True, **kw)
     return bases, off, rs, values, run
-
-
-def _expected_segments(read_str, k, seed_kmers, start=None, end=None):
-    table = np.zeros(4 ** k, dtype=np.uint8)
-    table[seed_kmers] = 1
-    kmap = {int(km): i for i, km in enumerate(seed_kmers)}
-    s = O.Seq(read_str)
-    v = s.sub(0 if start is None else start, len(read_str) if end is None else end)
-    seg = v.write_segments(k, table)
-    seg[1::2] = [kmap[int(x)] for x in seg[1::2]]
-    return seg
 
 
 def test_pack_matches_reference_encoding(ctx):
