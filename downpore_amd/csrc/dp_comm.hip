@@ -334,7 +334,7 @@ static int allgather_survivors_impl(dp_comm* c, dp_ctx* ctx, const dp_survivor_b
     uint32_t* d_read = (uint32_t*)c->d_pay.p;
     uint32_t* d_nseeds = d_read + ns;
     if (ns) {
-        hipLaunchKernelGGL(comm_pack_meta, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, s_item, s_count, ns, ctx->cached_lo, d_read,
+        hipLaunchKernelGGL(comm_pack_meta, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, s_item, s_count, ns, ctx->flags.view.lo, d_read,
                            d_nseeds);
         DP_HIP(hipGetLastError());
     }

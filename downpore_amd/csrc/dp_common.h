@@ -12,6 +12,7 @@
 #include "downpore_hip.h"
 #include "dp_chunk_bound.h"  // dp_chunk_walk_bounded: the chunk parameters the device accepts
 #include "dp_env.h"  // every run-time setting: the table, dp_tune / dp_debug, and when each is read
+#include "dp_scan_flags.h"  // dp_scan_reads' host bookkeeping of the ignore flags
 
 // make COPYLOG=1: every hipMemcpyAsync of the library is counted per call site (file:line, direction, calls, bytes) and the table is
 // printed when the process ends - the tool that names the call sites behind the runtime's copy kernels in a profile
@@ -58,7 +59,7 @@ struct dp_ctx {
     std::vector<uint64_t> qc_off;            // dp_query_candidates' result (ordinary host memory)
     std::vector<uint32_t> qc_ids, qc_meta;
     uint32_t last_n_extra = 0;    // extra items of the last dp_scan_reads
-    uint32_t kx_seq = 0;          // sequence number the sort pass of a one-go index step stores into h_total[15] when its output is complete
+    uint32_t kx_seq = 0;          // sequence number the sort pass of a one-go index step stores into h_total[DP_TOT_DONE] when its output is complete
     uint32_t kx_maxlen = 0;       // longest read (a bin's hit record holds 24 bits of position)
     size_t kx_maxlen_reads = 0;   // ... of a read set of this many reads
     uint32_t kx_head_reads = 0;  // reads the zeroed extra-item list heads (d_kx_lo) are sized for
@@ -119,13 +120,14 @@ struct dp_ctx {
     bool extras_staged = false;       // ... and have not been brought to d_items yet (the index step's first kernel or a fetch launch does)
     PinBuf h_extra;                   // the extra scan items (query windows) of a round, staged for the device to fetch
     PinBuf h_spack;                   // the survivor list as the compaction kernel writes it (pinned, written by the device)
-    uint64_t ignore_epoch = ~0ull;
     PinBuf h_ignore;              // the flags as the device holds them (pinned: the device's copy is refreshed from here by a kernel of the stream)
-    bool ignore_shadow_valid = false;
-    uint64_t cached_bases = 0;
-    uint32_t cached_reads = 0, cached_lo = 0, cached_hi = 0;
+    struct {                      // ... and what the last dp_scan_reads left of them (dp_scan_flags.h)
+        bool valid = false;       // h_ignore, the device's copy and `sums` belong to `epoch` and `view` (false: the next call starts from scratch)
+        uint64_t epoch = 0;
+        dp_flag_view view = {0, 0, 0, 0};
+        dp_flag_sums sums = {0, 0};
+    } flags;
     uint32_t chunk_lo = 0;            // what turns d_surv's survivor entries into read ids: the scanned range's first read, or 0 once dp_allgather_survivors installed the gathered list
-    int cached_top = -1, cached_k = 0;
     // the read items on the device (make_read_items_kernel) are regenerated only when what they are made from changes
     const void* items_ptr = nullptr;
     uint64_t items_epoch = ~0ull;
@@ -251,6 +253,22 @@ int dp_zero_fetch_regions(dp_ctx* ctx, const dp_zero_region* z, int nz, const dp
         hipError_t _e = (call);                                               \
         if (_e != hipSuccess) return dp_fail(ctx, DP_ERR_HIP, #call, _e);     \
     } while (0)
+
+// The 64-bit words of a round's totals block: ctx->d_total on the device, ctx->h_total its pinned mirror.  The index step's kernels
+// (dp_kindex.hip) or the offsets scans of the scan-kernel path (dp_scan.hip) write them, dp_scan_reads reads the mirror after its
+// first wait, and the chunk stage launched behind an un-waited scan reads the device's (dp_overlap.hip: chunk_kernel).
+enum dp_tot {
+    DP_TOT_SEGS = 0,        // ints of segment output
+    DP_TOT_SURV = 1,        // surviving reads + all extra items
+    DP_TOT_HITS = 2,        // index step: seed occurrences of the round
+    DP_TOT_MAX_COUNT = 3,   // index step: hits of the largest survivor (32 bits)
+    DP_TOT_OVERFLOW = 4,    // index step: a sort pass met a survivor larger than it holds (32 bits).  The scan-kernel path, which has
+                            // no use for this word and those behind it, keeps its tile sums from here on
+    DP_TOT_EXTRA_SEG0 = 5,  // index step: where the extra items' segments start
+    DP_TOT_BIN_FLAGS = 6,   // index step in one go: a bin or the extra list was full (32 bits)
+    DP_TOT_WORDS = 8,       // words the index step zeroes before a round and mirrors after it
+    DP_TOT_DONE = 15,       // pinned mirror only (32 bits): dp_kindex_oneshot.done_flag
+};
 
 // resident k-mer position index (dp_kindex.hip)
 struct dp_kindex_fast {   // the count walk's short cut for views served whole (dp_kindex.hip: kidx_walk, KxBins)

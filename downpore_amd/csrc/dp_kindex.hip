@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void kidx_prepare(uint32_t* __restrict__ work,
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_work) work[i] = 0;
     if (i < n_counts) counts[i] = 0;
-    if (i < 16) totals16[i] = 0;
+    if (i < 2 * DP_TOT_WORDS) totals16[i] = 0;
     if (i < n_extra) {
         // extra_src: the round's extra items still sit in the caller's pinned staging block - this thread brings its item over
         // (no upload of its own for ten kilobytes)
@@ -463,7 +463,7 @@ __device__ void kidx_walk_one(const uint32_t w, const uint32_t* __restrict__ see
         grp = s;
         gleader = (lane & 15) == 0;
     }
-    // seed occurrences of the round (totals[2]): one atomic per group (64 slots: 10 k same-address atomics serialise)
+    // seed occurrences of the round (DP_TOT_HITS): one atomic per group (64 slots: 10 k same-address atomics serialise)
     if (!FILL && gleader && i1 > gfirst) atomicAdd(&n_hits[grp & 63u], (unsigned long long)(i1 - gfirst));
     // Four entries per lane and trip: a hit is a chain of dependent loads (entry -> the read's item and list head -> counter), each
     // link a trip to HBM through a TLB that an 8 GB table defeats; the links of four entries travel together instead of one
@@ -776,7 +776,7 @@ __device__ void kidx_walk_bin_one_trip(const uint32_t* __restrict__ seeds, uint3
             base[t] = b;
             hist[t] = 0u;
         }
-        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
+        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (DP_TOT_HITS)
         if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
             const uint32_t c = xs[0];
             uint32_t xb = 0u;
@@ -941,7 +941,7 @@ __global__ __launch_bounds__(64 * WAVES) void kidx_walk_bin(const uint32_t* __re
             base[t] = b;
             hist[t] = 0u;
         }
-        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (totals[2])
+        if (threadIdx.x == 0 && sh_hits) atomicAdd(&n_hits[blockIdx.x & 63u], sh_hits);  // seed occurrences of the round (DP_TOT_HITS)
         if (threadIdx.x == THREADS - 1) {  // the workgroup's stretch of the extra items' list
             const uint32_t c = xs[0];
             uint32_t xb = 0u;
@@ -1031,7 +1031,7 @@ __global__ __launch_bounds__(512) void kidx_bin_fill(const KxBins B, const dp_sc
                                                      const uint64_t* __restrict__ totals, uint64_t seg_cap) {
     enum { THREADS = 512 };
     __shared__ uint32_t cnt[RB];
-    if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
+    if (B.flags[0] || totals[DP_TOT_SEGS] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
     if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
         const uint32_t xb = blockIdx.x - B.n_bins;
         if (xb >= KX_XBLOCKS) return;
@@ -1197,8 +1197,8 @@ __global__ __launch_bounds__(KX_TILE) void kidx_offsets(const dp_scan_item* __re
             excl_s = excl;
             if (((uint64_t)tile + 1) * KX_TILE * KX_IPT >= n) {  // last tile: totals
                 const unsigned long long all = excl + own;
-                totals[0] = all & ((1ull << 38) - 1);
-                totals[1] = all >> 38;
+                totals[DP_TOT_SEGS] = all & ((1ull << 38) - 1);
+                totals[DP_TOT_SURV] = all >> 38;
             }
         }
     }
@@ -1211,7 +1211,7 @@ __global__ __launch_bounds__(KX_TILE) void kidx_offsets(const dp_scan_item* __re
         const uint32_t i = i0 + u;
         if (i < n) {
             segoff[i] = so;
-            if (i == n_read_items) totals[5] = so;  // where the extra items' (query windows') segments start
+            if (i == n_read_items) totals[DP_TOT_EXTRA_SEG0] = so;  // where the extra items' (query windows') segments start
             if (flv[u]) {
                 s_item[slot] = i;
                 s_count[slot] = cc[u];
@@ -1228,7 +1228,7 @@ __global__ __launch_bounds__(KX_TILE) void kidx_offsets(const dp_scan_item* __re
         unsigned long long h = n_hits[threadIdx.x];
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) h += __shfl_xor(h, d, 64);
-        if (threadIdx.x == 0) totals[2] = h;
+        if (threadIdx.x == 0) totals[DP_TOT_HITS] = h;
     }
     // the round's totals go to the host's pinned block with the tile that finishes last (no launch of their own): every tile
     // publishes its stores and counts itself in; the one that counts the last sees them all
@@ -1241,7 +1241,7 @@ __global__ __launch_bounds__(KX_TILE) void kidx_offsets(const dp_scan_item* __re
             if (seen == n_tiles) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #pragma unroll
-                for (int w = 0; w < 8; w++)
+                for (int w = 0; w < DP_TOT_WORDS; w++)
                     host_totals[w] = __hip_atomic_load((const unsigned long long*)&totals[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -1359,7 +1359,7 @@ __global__ __launch_bounds__(64) void kidx_sortwrite(const dp_scan_item* __restr
     for (uint32_t e = blockIdx.x * 64 + lane; e < n_extra; e += gridDim.x * 64) head[items[n_read_items + e].read] = 0;
     // launched without a wait behind the counting step (round 4): the segment buffer was sized from the round before - a round
     // that needs more, or whose records did not fit, is filled and sorted again by the host's second attempt
-    const bool gave_up = totals && (totals[0] > seg_cap || (uint32_t)totals[6] != 0u);
+    const bool gave_up = totals && (totals[DP_TOT_SEGS] > seg_cap || (uint32_t)totals[DP_TOT_BIN_FLAGS] != 0u);
     const uint32_t sv0 = (extras_only && n_sel >= n_extra) ? n_sel - n_extra : 0u;
     for (uint32_t sv = sv0 + blockIdx.x; sv < n_sel && !gave_up; sv += gridDim.x) {
         const uint32_t it = sel[sv];
@@ -1429,7 +1429,7 @@ __global__ __launch_bounds__(512) void kidx_bin_sort_dense(const KxBins B, const
     __shared__ uint32_t cnt[RBMAX], offs[RBMAX + 1], cur[RBMAX], nks[RBMAX];
     __shared__ unsigned long long sout[RBMAX];
     __shared__ uint32_t g_hi_s;
-    if (B.flags[0] || totals[0] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
+    if (B.flags[0] || totals[DP_TOT_SEGS] > seg_cap) return;  // (the host repeats the fill with the bucket walk / a larger buffer)
     if (blockIdx.x >= B.n_bins) {  // the extra items' hits: a slot from the item's fill cursor, as ever
         const uint32_t xb = blockIdx.x - B.n_bins;
         if (xb >= KX_XBLOCKS) return;
@@ -1648,7 +1648,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             dense = G.dense;
             B.rec = (unsigned long long*)ctx->d_kx_keys.p;
             B.cursor = bin_cursor;
-            B.flags = (uint32_t*)(d_totals + 6);
+            B.flags = (uint32_t*)(d_totals + DP_TOT_BIN_FLAGS);
             B.xrec = (uint4*)ctx->d_kx_tmp.p;
             B.xcursor = bin_cursor + KX_MAXBINS;
             B.ign = F.ign;
@@ -1685,7 +1685,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
             uint64_t fl = 0;
             hipStreamSynchronize(ctx->stream);
             hipMemcpy(cur.data(), B.cursor, cur.size() * 4, hipMemcpyDeviceToHost);
-            hipMemcpy(&fl, d_totals + 6, 8, hipMemcpyDeviceToHost);
+            hipMemcpy(&fl, d_totals + DP_TOT_BIN_FLAGS, 8, hipMemcpyDeviceToHost);
             uint32_t mx = 0;
             uint64_t sum = 0;
             for (uint32_t b = 0; b < B.n_bins; b++) mx = std::max(mx, cur[b]), sum += cur[b];
@@ -1697,12 +1697,12 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         hipLaunchKernelGGL((kidx_walk<false>), dim3(kidx_walk_blocks(ix, k, S)), dim3(256), 0, ctx->stream, dp_seeds_ptr(ctx), S,
                            (const uint64_t*)ix->off.p, ix->view(), d_items, lo, hi, n_read_items, (const uint32_t*)head,
                            (const uint32_t*)next, d_counts, fillc, (const uint64_t*)nullptr, (int32_t*)nullptr, n_hits, lps, F, n_waves);
-    // totals[2] = seed occurrences in the read set, totals[3] = largest survivor count (both written by the kernel)
+    // DP_TOT_HITS = seed occurrences in the read set, DP_TOT_MAX_COUNT = largest survivor count (both written by the kernel)
     {
         KxBins Bo = B;
         if (!count_in_offsets) Bo.rec = nullptr;
         hipLaunchKernelGGL(kidx_offsets, dim3(n_tiles), dim3(KX_TILE), 0, ctx->stream, d_items, d_counts, n_items, status, ticket, d_segoff,
-                           s_item, s_count, s_off, s_pack, d_totals, n_read_items, (uint32_t*)(d_totals + 3),
+                           s_item, s_count, s_off, s_pack, d_totals, n_read_items, (uint32_t*)(d_totals + DP_TOT_MAX_COUNT),
                            (const unsigned long long*)n_hits, host_totals, Bo, lo);
     }
     DP_HIP(hipGetLastError());
@@ -1712,7 +1712,7 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         if (dense) {
             hipLaunchKernelGGL((kidx_bin_sort_dense<8192>), dim3(B.n_bins + KX_XBLOCKS), dim3(512), 0, ctx->stream, B, d_items,
                                n_read_items, (const uint32_t*)d_counts, fillc, (const uint64_t*)d_segoff, one->d_segs,
-                               (const uint64_t*)d_totals, one->seg_cap, k, (uint32_t*)(d_totals + 4));
+                               (const uint64_t*)d_totals, one->seg_cap, k, (uint32_t*)(d_totals + DP_TOT_OVERFLOW));
         } else {
             const dim3 fg(B.n_bins + KX_XBLOCKS), fb(512);
             if (B.bshift <= 9)
@@ -1729,8 +1729,8 @@ int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
         // the kernel strides over the rest)
         const dim3 sg(dense ? std::max<uint32_t>(64u, std::min<uint32_t>(n_extra, 16384))
                             : std::max<uint32_t>(256u, std::min<uint32_t>(one->surv_guess, 16384))), sb(64);
-        uint32_t* ovf = (uint32_t*)(d_totals + 4);
-        const uint32_t* nsp = (const uint32_t*)(d_totals + 1);
+        uint32_t* ovf = (uint32_t*)(d_totals + DP_TOT_OVERFLOW);
+        const uint32_t* nsp = (const uint32_t*)(d_totals + DP_TOT_SURV);
         if (one->sort_cap <= 256)
             hipLaunchKernelGGL((kidx_sortwrite<256>), sg, sb, 0, ctx->stream, d_items, (const uint32_t*)s_item, nsp,
                                (const uint32_t*)d_counts, (const uint64_t*)d_segoff, one->d_segs, k, ovf, n_read_items, n_extra, head,
@@ -1785,8 +1785,8 @@ int dp_kindex_write(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo
                                (const uint32_t*)next, (uint32_t*)d_counts, fillc, d_segoff, d_segs, (unsigned long long*)nullptr,
                                kidx_lps(ix, k), dp_kindex_fast{nullptr, 0u, 0u}, kidx_walk_blocks(ix, k, S) * 4);
         const dim3 sg(std::min<uint32_t>(n_sel, 16384)), sb(64);
-        uint32_t* ovf = (uint32_t*)(d_totals + 4);
-        const uint32_t* nsp = (const uint32_t*)(d_totals + 1);
+        uint32_t* ovf = (uint32_t*)(d_totals + DP_TOT_OVERFLOW);
+        const uint32_t* nsp = (const uint32_t*)(d_totals + DP_TOT_SURV);
         if (max_count <= 128)
             hipLaunchKernelGGL((kidx_sortwrite<256>), sg, sb, 0, ctx->stream, d_items, d_sel, nsp, d_counts, d_segoff, d_segs, k, ovf,
                                n_read_items, n_extra, head, host_segs, (const uint64_t*)nullptr, (uint64_t)0, 0u);

@@ -381,9 +381,10 @@ __global__ __launch_bounds__(1024) void chunk_kernel(const ChunkParams P, unsign
     if (P.done_flag && blockIdx.x == 0 && threadIdx.x == 0)
         __hip_atomic_store(P.done_flag, P.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     if (P.scan_totals) {
-        const u64 all = P.scan_totals[1];
+        const u64 all = P.scan_totals[DP_TOT_SURV];
         ns = all > P.n_extra ? (uint32_t)(all - P.n_extra) : 0u;
-        const bool scan_failed = P.scan_totals[0] > P.seg_cap || (uint32_t)P.scan_totals[4] != 0u || (uint32_t)P.scan_totals[6] != 0u;
+        const bool scan_failed = P.scan_totals[DP_TOT_SEGS] > P.seg_cap || (uint32_t)P.scan_totals[DP_TOT_OVERFLOW] != 0u ||
+                                 (uint32_t)P.scan_totals[DP_TOT_BIN_FLAGS] != 0u;
         if (scan_failed || (ns + 1023u) / 1024u > P.grid_tiles) {  // nothing to chunk / not enough tiles: the host launches again
             if (blockIdx.x == 0 && threadIdx.x == 0) {
                 P.n_out[0] = 0u;

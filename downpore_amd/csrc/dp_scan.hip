@@ -903,8 +903,7 @@ static int reads_upload_prepare(dp_ctx* ctx, const uint8_t* bases, const int64_t
             }
     }
     ctx->n_reads = n_reads;
-    ctx->ignore_epoch = ~0ull;  // (cached per-read-set state of dp_scan_reads)
-    ctx->ignore_shadow_valid = false;
+    ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
     ctx->items_ptr = nullptr;
     ctx->h_boff.swap(h_boff);
     ctx->h_len.swap(h_len);
@@ -1049,8 +1048,7 @@ extern "C" int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t 
             qb->cap = 0;
         }
     ctx->n_reads = n_out;
-    ctx->ignore_epoch = ~0ull;  // (cached per-read-set state of dp_scan_reads)
-    ctx->ignore_shadow_valid = false;
+    ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
     ctx->items_ptr = nullptr;
     ctx->h_boff.swap(h_boff);
     ctx->h_len.swap(h_len);
@@ -1973,6 +1971,83 @@ __global__ __launch_bounds__(OFF_TILE) void offsets_write(const dp_scan_item* __
     if (i < n) segoff[i] = tile_base[blockIdx.x] + (uint64_t)(x - v);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// dp_scan and dp_scan_reads: the steps of a call
+
+// What the steps of one call share: the call's arguments and the pointers into the context's buffers, set up once (dp_scan:
+// in place; dp_scan_reads: scan_prepare_items).  dp_scan has no range, no extra items and no survivor list (tilesB, s_*: null).
+struct ScanRound {
+    uint32_t lo, hi;  // the reads the read items are made of
+    int top_level, k;
+    uint32_t min_seeds;
+    const dp_scan_item* extra;  // the caller's extra items, behind the read items
+    uint32_t n_extra;
+    uint32_t n_read_items, n_items, n_tiles;  // n_tiles: tiles of OFF_TILE items
+    uint32_t grid;                            // workgroups of the scan kernels
+    bool v2;                                  // k >= 9: the scan kernels' second filter
+    dp_scan_item* d_items;
+    uint64_t* totals;           // d_total: the totals block (dp_tot)
+    uint64_t *tilesA, *tilesB;  // inside d_total: tile sums of the offsets scan / of the survivor compaction, n_tiles + 1 words each
+    uint32_t *s_item, *s_count;  // d_surv: the survivor list
+    uint64_t* s_off;
+    uint4* s_pack;  // h_spack: {item, count, offset} per survivor, written by the device into pinned memory
+};
+// the totals of a round as the host reads them after its first wait
+struct ScanTotals {
+    uint64_t n_segs, n_surv_all;  // n_surv_all: surviving reads + all extra items
+};
+static ScanTotals scan_totals_read(const dp_ctx* ctx) {
+    const uint64_t* h = (const uint64_t*)ctx->h_total.p;
+    return ScanTotals{h[DP_TOT_SEGS], h[DP_TOT_SURV]};
+}
+
+// an item of the caller's: its read exists, and every base it examines lies inside the read
+static int scan_item_check(dp_ctx* ctx, const dp_scan_item& it, int k) {
+    if (it.read >= ctx->n_reads) return dp_fail(ctx, DP_ERR_ARG, "scan item: read index out of range");
+    // the examined k-mers may run past the read end only in the reference's over-scan corner cases (<~8+k bases),
+    // which the caller must not batch; enforce that every examined base lies inside the read
+    if ((uint64_t)it.start + it.n_kmers + (it.n_kmers ? k - 1 : 0) > ctx->h_len[it.read])
+        return dp_fail(ctx, DP_ERR_ARG, "scan item: k-mer range exceeds the read");
+    return DP_OK;
+}
+static uint64_t scan_item_bases(const dp_scan_item& it, int k) { return it.n_kmers ? (uint64_t)it.n_kmers + k - 1 : 0; }
+
+// persistent workgroups of the scan kernels: wg_per_cu per CU (one where k < 9), and no more than a wave per item needs
+static uint32_t scan_grid(const dp_ctx* ctx, bool v2, int wg_per_cu, uint32_t n_items) {
+    int dev_cus = 256;
+    hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    return (uint32_t)std::min<uint64_t>((uint64_t)dev_cus * (v2 ? wg_per_cu : 1), ((uint64_t)n_items + 15) / 16);
+}
+
+// Count pass of the scan kernels and the segment offsets.  On the stream: mark 0, the count kernel (dbg: DP_TUNE=scan_debug, bit 1
+// the FILTER 3 variant), mark 1, the three offsets launches.  Behind them d_counts holds the items' hits, d_segoff their segment
+// offsets and R.totals[DP_TOT_SEGS] the segments' total; R.tilesA is used up.
+static int scan_count_pass(dp_ctx* ctx, const ScanRound& R, uint32_t dbg) {
+    DP_HIP(dp_mark(ctx, 0));
+    hipLaunchKernelGGL(((dbg & 2) ? scan_kernel<0, 3> : R.v2 ? scan_kernel<0, 2> : scan_kernel<0, 1>), dim3(R.grid), dim3(SCAN_THREADS), 0,
+                       ctx->stream, (const uint8_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)R.d_items, R.n_items,
+                       R.k, (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p, (const int32_t*)ctx->d_kmap.p,
+                       (uint32_t*)ctx->d_counts.p, (const uint64_t*)nullptr, (int32_t*)nullptr, dbg, (const uint32_t*)nullptr, 0u);
+    DP_HIP(hipGetLastError());
+    DP_HIP(dp_mark(ctx, 1));
+    hipLaunchKernelGGL(offsets_tile_sums, dim3(R.n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)R.d_items,
+                       (const uint32_t*)ctx->d_counts.p, R.n_items, R.tilesA);
+    hipLaunchKernelGGL(offsets_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, R.tilesA, R.n_tiles, R.totals + DP_TOT_SEGS,
+                       (uint64_t*)ctx->d_segoff.p, R.n_items);
+    hipLaunchKernelGGL(offsets_write, dim3(R.n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)R.d_items,
+                       (const uint32_t*)ctx->d_counts.p, R.n_items, (const uint64_t*)R.tilesA, (uint64_t*)ctx->d_segoff.p);
+    return DP_OK;
+}
+
+// Write pass of the scan kernels: one launch that leaves the segments in d_segs.  sel (or null: every item, strided): the items to
+// write, one wave each.
+static void scan_write_pass(dp_ctx* ctx, const ScanRound& R, uint32_t grid, const uint32_t* sel, uint32_t n_sel) {
+    hipLaunchKernelGGL((R.v2 ? scan_kernel<1, 2> : scan_kernel<1, 1>), dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream,
+                       (const uint8_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)R.d_items, R.n_items, R.k,
+                       (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p, (const int32_t*)ctx->d_kmap.p,
+                       (uint32_t*)ctx->d_counts.p, (const uint64_t*)ctx->d_segoff.p, (int32_t*)ctx->d_segs.p, 0u, sel, n_sel);
+}
+
 extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items, dp_seedseq_batch* out) {
     if (!ctx || !out || (n_items && !items)) return DP_ERR_ARG;
     if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_scan before dp_round_begin");
@@ -1980,13 +2055,8 @@ extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items,
     const int k = ctx->k;
     uint64_t bases = 0;
     for (uint32_t i = 0; i < n_items; i++) {
-        const dp_scan_item& it = items[i];
-        if (it.read >= ctx->n_reads) return dp_fail(ctx, DP_ERR_ARG, "scan item: read index out of range");
-        // the examined k-mers may run past the read end only in the reference's over-scan corner cases (<~8+k bases),
-        // which the caller must not batch; enforce that every examined base lies inside the read
-        if ((uint64_t)it.start + it.n_kmers + (it.n_kmers ? k - 1 : 0) > ctx->h_len[it.read])
-            return dp_fail(ctx, DP_ERR_ARG, "scan item: k-mer range exceeds the read");
-        bases += it.n_kmers ? (uint64_t)it.n_kmers + k - 1 : 0;
+        if (int rc = scan_item_check(ctx, items[i], k)) return rc;
+        bases += scan_item_bases(items[i], k);
     }
     if (dev_reserve(ctx, ctx->d_items, (size_t)n_items * sizeof(dp_scan_item) + 16)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_counts, (size_t)n_items * 4 + 16)) return DP_ERR_HIP;
@@ -2012,56 +2082,40 @@ extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items,
     }
     ctx->items_ptr = nullptr;  // (dp_scan_reads' resident read items are overwritten)
     DP_HIP(hipMemcpyAsync(ctx->d_items.p, items, (size_t)n_items * sizeof(dp_scan_item), hipMemcpyHostToDevice, ctx->stream));
-    int dev_cus = 256;
-    hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const bool v2 = k >= 9;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)dev_cus * (v2 ? 2 : 1), ((uint64_t)n_items + 15) / 16);
+    ScanRound R{};
+    R.k = k;
+    R.n_items = n_items;
+    R.n_tiles = (n_items + OFF_TILE - 1) / OFF_TILE;
+    R.v2 = k >= 9;
+    R.grid = scan_grid(ctx, R.v2, 2, n_items);
+    R.d_items = (dp_scan_item*)ctx->d_items.p;
+    R.totals = (uint64_t*)ctx->d_total.p;
+    R.tilesA = R.totals + DP_TOT_SURV + 1;  // (no index step on this block: the tile sums follow the two totals of a scan)
     const uint32_t dbg = (uint32_t)dp_tune("scan_debug", 0);
     if (int rc = seed_tables_ensure(ctx)) return rc;
     std::unique_lock<ScanGate> scan_lock(g_scan_mu);
-    DP_HIP(dp_mark(ctx, 0));
-    hipLaunchKernelGGL(((dbg & 2) ? scan_kernel<0, 3> : v2 ? scan_kernel<0, 2> : scan_kernel<0, 1>), dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream, (const uint8_t*)ctx->d_packed.p,
-                       (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)ctx->d_items.p, n_items, k,
-                       (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p,
-                       (const int32_t*)ctx->d_kmap.p, (uint32_t*)ctx->d_counts.p, (const uint64_t*)nullptr, (int32_t*)nullptr, dbg, (const uint32_t*)nullptr, 0u);
+    if (int rc = scan_count_pass(ctx, R, dbg)) return rc;
     DP_HIP(hipGetLastError());
-    DP_HIP(dp_mark(ctx, 1));
-    {
-        const uint32_t n_tiles = (n_items + OFF_TILE - 1) / OFF_TILE;
-        uint64_t* tiles = (uint64_t*)ctx->d_total.p + 2;
-        hipLaunchKernelGGL(offsets_tile_sums, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)ctx->d_items.p,
-                           (const uint32_t*)ctx->d_counts.p, n_items, tiles);
-        hipLaunchKernelGGL(offsets_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles, (uint64_t*)ctx->d_total.p,
-                           (uint64_t*)ctx->d_segoff.p, n_items);
-        hipLaunchKernelGGL(offsets_write, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)ctx->d_items.p,
-                           (const uint32_t*)ctx->d_counts.p, n_items, (const uint64_t*)tiles, (uint64_t*)ctx->d_segoff.p);
-        DP_HIP(hipGetLastError());
-    }
     DP_HIP(dp_mark(ctx, 4));
     DP_HIP(hipMemcpyAsync(ctx->h_total.p, ctx->d_total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     DP_HIP(hipMemcpyAsync(ctx->h_counts.p, ctx->d_counts.p, (size_t)n_items * 4, hipMemcpyDeviceToHost, ctx->stream));
     DP_HIP(hipMemcpyAsync(ctx->h_segoff.p, ctx->d_segoff.p, ((size_t)n_items + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     DP_HIP(dp_stream_sync(ctx));
-    const uint64_t n_segs = *(uint64_t*)ctx->h_total.p;
+    const uint64_t n_segs = scan_totals_read(ctx).n_segs;
     if (dev_reserve(ctx, ctx->d_segs, n_segs * 4 + 64)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_segs, n_segs * 4 + 64)) return DP_ERR_HIP;
-    float ms0 = 0, ms1 = 0, msoff = 0;
-    ms0 = dp_elapsed(ctx, 0, 1);
-    msoff = dp_elapsed(ctx, 1, 4);
+    const float ms0 = dp_elapsed(ctx, 0, 1), msoff = dp_elapsed(ctx, 1, 4);
+    float ms1 = 0;
     if (n_segs) {
         DP_HIP(dp_mark(ctx, 2));
-        hipLaunchKernelGGL((v2 ? scan_kernel<1, 2> : scan_kernel<1, 1>), dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream,
-                           (const uint8_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)ctx->d_items.p,
-                           n_items, k, (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p,
-                           (const int32_t*)ctx->d_kmap.p, (uint32_t*)ctx->d_counts.p, (const uint64_t*)ctx->d_segoff.p,
-                           (int32_t*)ctx->d_segs.p, 0u, (const uint32_t*)nullptr, 0u);
+        scan_write_pass(ctx, R, R.grid, nullptr, 0u);
         DP_HIP(hipGetLastError());
         DP_HIP(dp_mark(ctx, 3));
         DP_HIP(hipMemcpyAsync(ctx->h_segs.p, ctx->d_segs.p, n_segs * 4, hipMemcpyDeviceToHost, ctx->stream));
         DP_HIP(dp_stream_sync(ctx));
         ms1 = dp_elapsed(ctx, 2, 3);
     }
-    if (scan_lock.owns_lock()) scan_lock.unlock();
+    scan_lock.unlock();
     ctx->n_segs = n_segs;
     out->n_seeds = (const uint32_t*)ctx->h_counts.p;
     out->seg_off = (const uint64_t*)ctx->h_segoff.p;
@@ -2072,6 +2126,7 @@ extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items,
     out->write_kernel_ms = ms1;
     return DP_OK;
 }
+
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2165,10 +2220,106 @@ extern "C" int dp_scan_release(dp_ctx* ctx) {
     return DP_OK;
 }
 
-#define DP_SCAN_AGAIN 1000  // internal: the index could not answer this round, run it again with the scan kernels
+// Argument checks of dp_scan_reads.  Leaves *out zeroed.
+static int scan_reads_check(dp_ctx* ctx, const uint8_t* ignore, uint32_t lo, uint32_t hi, const dp_scan_item* extra, uint32_t n_extra,
+                            dp_survivor_batch* out) {
+    if (!ctx || !out || !ignore || lo > hi || hi > ctx->n_reads || (n_extra && !extra)) return DP_ERR_ARG;
+    if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_scan_reads before dp_round_begin");
+    memset(out, 0, sizeof(*out));
+    for (uint32_t i = 0; i < n_extra; i++)
+        if (int rc = scan_item_check(ctx, extra[i], ctx->k)) return rc;
+    return DP_OK;
+}
 
-static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_epoch, uint32_t lo, uint32_t hi, int top_level,
-                           uint32_t min_seeds, const dp_scan_item* extra, uint32_t n_extra, dp_survivor_batch* out, bool allow_index);
+// The flags step: bases examined over the non-ignored reads, and the flags on the device, brought up to date when the flags (epoch)
+// or the view change - which is nearly every round (a round's commit flags its query reads).  Round 6: the context keeps a pinned copy
+// of the flags as the device holds them; a call compares the caller's array with it eight bytes at a time, adjusts the two sums by the
+// reads whose flag changed (dp_scan_flags.h) and lets a kernel of the stream fetch the block - where it walked all reads (100 k
+// branches a round) and handed 100 KB of pageable memory to the runtime's copy path (a slot thread spent ~0.15 of its round's 0.73 ms
+// there; five slots entering that path together at a job's start could wait 8 ms for one another: profiles/r06/job_start_stall.txt).
+// Leaves ctx->flags and the shadow (h_ignore) at this call's flags and view, nothing on the stream; *dirty: the device's copy is
+// older than the shadow, and the launch that makes the read items - or one of its own - has to bring it over (scan_prepare_items).
+static int scan_flags_step(dp_ctx* ctx, const uint8_t* ignore, uint64_t epoch, const dp_flag_view& view, bool* dirty) {
+    if (ctx->flags.valid && ctx->flags.epoch == epoch && dp_flag_view_same(ctx->flags.view, view)) return DP_OK;
+    const size_t nr8 = ((size_t)ctx->n_reads + 7) & ~(size_t)7;
+    const bool grown = !ctx->h_ignore.p || ctx->h_ignore.cap < nr8 + 64;
+    if (pin_reserve(ctx, ctx->h_ignore, nr8 + 64)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_ignore, nr8 + 16)) return DP_ERR_HIP;
+    const bool same_view = ctx->flags.valid && !grown && dp_flag_view_same(ctx->flags.view, view);
+    ctx->flags.sums = dp_scan_flags_update((uint8_t*)ctx->h_ignore.p, nr8 + 64, ignore, ctx->n_reads, ctx->h_len.data(), view, same_view,
+                                           ctx->flags.sums);
+    ctx->flags.valid = true;
+    ctx->flags.epoch = epoch;
+    ctx->flags.view = view;
+    *dirty = true;
+    return DP_OK;
+}
+
+// the staged extra items into d_items behind the read items, by a launch of the stream (the index step's first kernel does this
+// itself: dp_kindex_count)
+static int scan_fetch_extras(dp_ctx* ctx, const ScanRound& R) {
+    if (!ctx->extras_staged) return DP_OK;
+    ctx->extras_staged = false;
+    const dp_fetch_region f = {R.d_items + R.n_read_items, ctx->h_extra.p, (size_t)R.n_extra * sizeof(dp_scan_item)};
+    return dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1);
+}
+
+// Item preparation: the buffers of a round reserved and R's pointers into them set.  On the stream: make_read_items_kernel where the
+// resident read items are not this call's (the flags ride along if *flags_dirty), else a fetch of the flags if they are dirty.  The
+// extra items are staged in h_extra (ctx->extras_staged) for the step that follows to fetch.
+static int scan_prepare_items(dp_ctx* ctx, uint64_t epoch, bool* flags_dirty, ScanRound& R) {
+    R.n_tiles = (R.n_items + OFF_TILE - 1) / OFF_TILE;
+    if (dev_reserve(ctx, ctx->d_items, (size_t)R.n_items * sizeof(dp_scan_item) + 16)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_counts, (size_t)R.n_items * 4 + 16)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_segoff, ((size_t)R.n_items + 1) * 8)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_total, 64 + ((size_t)R.n_tiles + 2) * 16)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_surv, (size_t)R.n_items * 32 + 128)) return DP_ERR_HIP;
+    R.d_items = (dp_scan_item*)ctx->d_items.p;
+    const size_t nr8 = ((size_t)ctx->n_reads + 7) & ~(size_t)7;
+    // the read items are a function of the read lengths, the flags and these arguments: they stay on the device from round to
+    // round (the kernels only read them; the extra items behind them are this round's)
+    if (R.n_read_items && (ctx->items_ptr != R.d_items || ctx->items_epoch != epoch || ctx->items_lo != R.lo || ctx->items_hi != R.hi ||
+                           ctx->items_min != R.min_seeds || ctx->items_top != R.top_level || ctx->items_k != R.k)) {
+        const uint32_t fw = *flags_dirty ? (uint32_t)(nr8 / 8) : 0u;
+        hipLaunchKernelGGL(make_read_items_kernel, dim3((std::max(R.n_read_items, fw) + 255) / 256), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)ctx->d_len.p, (const uint8_t*)ctx->d_ignore.p, R.lo, R.hi, R.k, R.top_level, R.min_seeds, R.d_items,
+                           *flags_dirty ? (const unsigned long long*)ctx->h_ignore.p : (const unsigned long long*)nullptr,
+                           (unsigned long long*)ctx->d_ignore.p, fw);
+        *flags_dirty = false;
+        ctx->items_ptr = R.d_items;
+        ctx->items_epoch = epoch;
+        ctx->items_lo = R.lo;
+        ctx->items_hi = R.hi;
+        ctx->items_min = R.min_seeds;
+        ctx->items_top = R.top_level;
+        ctx->items_k = R.k;
+    }
+    if (*flags_dirty) {  // (no read items were made in this call)
+        const dp_fetch_region f = {ctx->d_ignore.p, ctx->h_ignore.p, nr8};
+        if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1)) return rc;
+        *flags_dirty = false;
+    }
+    if (R.n_extra) {  // (borrowed from the caller: staged in a pinned block, fetched by a kernel of this stream)
+        if (pin_reserve(ctx, ctx->h_extra, (size_t)R.n_extra * sizeof(dp_scan_item) + 64)) return DP_ERR_HIP;
+        memcpy(ctx->h_extra.p, R.extra, (size_t)R.n_extra * sizeof(dp_scan_item));
+    }
+    ctx->extras_staged = R.n_extra > 0;
+    R.v2 = R.k >= 9;
+    // persistent workgroups per CU: 2 fill every wave slot and all LDS of the CU (fastest scan in isolation) - and keep every
+    // other slot's kernels out until the scan is done; DP_TUNE=scan_wg_per_cu=1 leaves half of each CU to them
+    R.grid = scan_grid(ctx, R.v2, (int)std::max(1L, std::min(2L, dp_tune("scan_wg_per_cu", 2))), R.n_items);
+    R.totals = (uint64_t*)ctx->d_total.p;
+    R.tilesA = R.totals + DP_TOT_OVERFLOW;  // (the scan-kernel path's: see dp_tot)
+    R.tilesB = R.tilesA + R.n_tiles + 1;
+    R.s_item = (uint32_t*)ctx->d_surv.p;
+    R.s_count = R.s_item + R.n_items;
+    R.s_off = (uint64_t*)(R.s_count + R.n_items + (R.n_items & 1));
+    // {item, count, offset} per survivor: what the host wants of the compaction.  The kernel that makes the list writes it into a
+    // pinned host block directly (nobody reads it on the device) - a 100 KB copy per round that is never submitted
+    if (pin_reserve(ctx, ctx->h_spack, (size_t)R.n_items * 16 + 64)) return DP_ERR_HIP;
+    R.s_pack = (uint4*)ctx->h_spack.p;
+    return DP_OK;
+}
 
 // Waits for the sequence number the sort pass of a one-go index step stores into the pinned flag when the scan's output is
 // complete - not for the stream, which may already carry the chunk stage (dp_index_prechain).  Spins or polls as dp_stream_sync
@@ -2194,386 +2345,262 @@ static hipError_t kx_wait_done(dp_ctx* ctx, const uint32_t* flag, uint32_t seq) 
     }
 }
 
-extern "C" int dp_scan_reads(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_epoch, uint32_t lo, uint32_t hi, int top_level,
-                             uint32_t min_seeds, const dp_scan_item* extra, uint32_t n_extra, dp_survivor_batch* out) {
-    int rc = scan_reads_body(ctx, ignore, ignore_epoch, lo, hi, top_level, min_seeds, extra, n_extra, out, true);
-    if (rc == DP_SCAN_AGAIN) rc = scan_reads_body(ctx, ignore, ignore_epoch, lo, hi, top_level, min_seeds, extra, n_extra, out, false);
-    return rc;
+// The plan of the index step.  In one go - the walk that bins its hits, offsets, fill from the bins and sort/write are all launched
+// before the one wait, into buffers sized from this context's previous index-mode round (twice its segments, 1.5 x its hits, the
+// sort tier of 1.25 x its largest survivor); the rare round that outgrows a guess repeats fill + sort with the bucket walk after
+// the wait.  DP_KX_ONESHOT=0, or a round whose bins cannot be set up: count, wait, size, fill, sort, wait.
+// Leaves *oneshot and, where it is set, `one`: the guesses from kx_prev_*, the segment buffer (and its pinned mirror in fetch mode 1
+// with extras) reserved at seg_cap, the done word of the pinned totals block zeroed and a fresh done_seq.  Nothing on the stream.
+static int index_plan(dp_ctx* ctx, const ScanRound& R, dp_kindex_oneshot& one, bool* oneshot) {
+    memset(&one, 0, sizeof one);
+    const std::vector<uint32_t>& lens = ctx->owner ? ctx->owner->h_len : ctx->h_len;
+    if (ctx->kx_maxlen_reads != lens.size()) {  // (a bin's record holds 24 bits of position)
+        uint32_t mx = 0;
+        for (uint32_t L : lens) mx = std::max(mx, L);
+        ctx->kx_maxlen = mx;
+        ctx->kx_maxlen_reads = lens.size();
+    }
+    *oneshot = dp_env_tristate("DP_KX_ONESHOT") != 0 && ctx->n_seeds > 0 && ctx->n_reads < (1u << 24) && ctx->kx_maxlen < (1u << 24);
+    if (!*oneshot) return DP_OK;
+    one.hits_guess = ctx->kx_prev_hits ? ctx->kx_prev_hits + ctx->kx_prev_hits / 2 : 0;
+    one.surv_guess = ctx->kx_prev_surv ? ctx->kx_prev_surv + ctx->kx_prev_surv / 4 : 8192;
+    const uint32_t mxg = ctx->kx_prev_max + ctx->kx_prev_max / 4;
+    one.sort_cap = mxg <= 128 ? 256u : (mxg <= 512 ? 1024u : 4096u);
+    const uint64_t want = std::max<uint64_t>(2 * ctx->kx_prev_segs + 65536, 1u << 20);
+    if (dev_reserve(ctx, ctx->d_segs, want * 4 + 64)) return DP_ERR_HIP;
+    one.seg_cap = (ctx->d_segs.cap - 64) / 4;
+    if (ctx->scan_fetch_extras_only && R.n_extra > 0) {
+        if (pin_reserve(ctx, ctx->h_segs, one.seg_cap * 4 + 64)) return DP_ERR_HIP;
+        one.host_segs = (int32_t*)ctx->h_segs.p;
+    }
+    one.d_segs = (int32_t*)ctx->d_segs.p;
+    // (where a chunk stage launched behind the step says that the step's own kernels are done)
+    one.done_flag = (uint32_t*)((uint64_t*)ctx->h_total.p + DP_TOT_DONE);
+    one.done_seq = ++ctx->kx_seq ? ctx->kx_seq : ++ctx->kx_seq;
+    __atomic_store_n(one.done_flag, 0u, __ATOMIC_RELEASE);  // (whatever an earlier round or a fresh block left there)
+    return DP_OK;
 }
 
-static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_epoch, uint32_t lo, uint32_t hi, int top_level,
-                           uint32_t min_seeds, const dp_scan_item* extra, uint32_t n_extra, dp_survivor_batch* out, bool allow_index) {
-    if (!ctx || !out || !ignore || lo > hi || hi > ctx->n_reads || (n_extra && !extra)) return DP_ERR_ARG;
-    if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_scan_reads before dp_round_begin");
-    hipSetDevice(ctx->device);
-    memset(out, 0, sizeof(*out));
-    const int k = ctx->k;
-    const uint32_t n_read_items = hi - lo, n_items = n_read_items + n_extra;
-    for (uint32_t i = 0; i < n_extra; i++) {
-        const dp_scan_item& it = extra[i];
-        if (it.read >= ctx->n_reads) return dp_fail(ctx, DP_ERR_ARG, "scan item: read index out of range");
-        if ((uint64_t)it.start + it.n_kmers + (it.n_kmers ? k - 1 : 0) > ctx->h_len[it.read])
-            return dp_fail(ctx, DP_ERR_ARG, "scan item: k-mer range exceeds the read");
-    }
-    // bases examined over the non-ignored reads, and the flags on the device: brought up to date when the flags (epoch) or the range change -
-    // which is nearly every round (a round's commit flags its query reads).  Round 6: the context keeps a pinned copy of the flags as the
-    // device holds them; a call compares the caller's array with it eight bytes at a time, adjusts the two sums by the reads whose flag
-    // changed and lets a kernel of the stream fetch the block - where it walked all reads (100 k branches a round) and handed 100 KB of
-    // pageable memory to the runtime's copy path (a slot thread spent ~0.15 of its round's 0.73 ms there; five slots entering that path
-    // together at a job's start could wait 8 ms for one another: profiles/r06/job_start_stall.txt).
-    bool flags_dirty = false;
-    struct FlagsGuard {  // (a way out of this call before the launch that brings the flags over: the next call starts from scratch)
-        dp_ctx* c;
-        bool& dirty;
-        ~FlagsGuard() {
-            if (dirty) {
-                c->ignore_shadow_valid = false;
-                c->ignore_epoch = ~0ull;
-            }
+// The launch of the index step: counts, segment offsets, survivor list and totals in three launches, no sort and no host round
+// trip (dp_kindex.hip) - and, in one go, fill and sort behind them, then the chunk stage of the caller's coming
+// dp_index_build_chunked (dp_index_prechain).  Leaves *launched (false: more items than the index handles, nothing is on the
+// stream), *oneshot cleared where the bins could not be set up (the two-wait form follows), and *wait_flag: the chunk stage's first
+// kernel tells the host that the scan's own kernels are done - the host waits for that word, not for the stream.
+static int index_launch(dp_ctx* ctx, const ScanRound& R, const dp_kindex_oneshot& one, bool* oneshot, bool* launched, bool* wait_flag) {
+    *launched = *wait_flag = false;
+    // (views served whole - top_level == 0 - have a k-mer at every indexed position: the walk tests the ignore byte instead of
+    // reading the read's item, and looks for extra items only on the round's query reads)
+    dp_kindex_fast fastArgs = {nullptr, 0u, 0u};
+    if (!R.top_level && ctx->d_ignore.p) {
+        uint32_t qmin = 0xffffffffu, qmax = 0;
+        for (uint32_t i = 0; i < R.n_extra; i++) {
+            qmin = std::min(qmin, R.extra[i].read);
+            qmax = std::max(qmax, R.extra[i].read);
         }
-    } flagsGuard{ctx, flags_dirty};
-    const size_t nr8 = ((size_t)ctx->n_reads + 7) & ~(size_t)7;
-    if (ctx->ignore_epoch != ignore_epoch || ctx->cached_lo != lo || ctx->cached_hi != hi || ctx->cached_top != top_level ||
-        ctx->cached_k != k) {
-        const bool grown = !ctx->h_ignore.p || ctx->h_ignore.cap < nr8 + 64;
-        if (pin_reserve(ctx, ctx->h_ignore, nr8 + 64)) return DP_ERR_HIP;
-        if (dev_reserve(ctx, ctx->d_ignore, nr8 + 16)) return DP_ERR_HIP;
-        uint8_t* shadow = (uint8_t*)ctx->h_ignore.p;
-        auto kmers_of = [&](uint32_t r) -> uint64_t {
-            int64_t n = (int64_t)ctx->h_len[r] - k + 1;
-            if (top_level && (ctx->h_len[r] & 3u) == 0) n -= 4;
-            return n > 0 ? (uint64_t)n + k - 1 : 0ull;
-        };
-        const bool same_view = ctx->ignore_shadow_valid && !grown && ctx->cached_lo == lo && ctx->cached_hi == hi && ctx->cached_top == top_level &&
-                               ctx->cached_k == k;
-        if (!same_view) {  // a new view (or the first call): everything once
-            memcpy(shadow, ignore, ctx->n_reads);
-            memset(shadow + ctx->n_reads, 0, nr8 + 64 - ctx->n_reads);
-            uint64_t b = 0;
-            uint32_t nr = 0;
-            for (uint32_t r = lo; r < hi; r++) {
-                if (shadow[r]) continue;
-                b += kmers_of(r);
-                nr++;
-            }
-            ctx->cached_bases = b;
-            ctx->cached_reads = nr;
-            ctx->ignore_shadow_valid = true;
-        } else {  // the reads whose flag changed since the last call (the caller's array may change under this loop: what is READ here is
-                  // what the device gets - the commit's speculation check covers flags set after a round's snapshot)
-            const size_t words = (size_t)ctx->n_reads / 8;
-            for (size_t w = 0; w < words; w++) {
-                uint64_t now_w, old_w;
-                memcpy(&now_w, ignore + 8 * w, 8);
-                memcpy(&old_w, shadow + 8 * w, 8);
-                if (now_w == old_w) continue;
-                for (uint32_t r = (uint32_t)(8 * w); r < (uint32_t)(8 * w + 8); r++) {
-                    const uint8_t v = (uint8_t)(now_w >> (8 * (r & 7u)));
-                    if (v == shadow[r]) continue;
-                    if (r >= lo && r < hi && (v != 0) != (shadow[r] != 0)) {
-                        if (v) ctx->cached_bases -= kmers_of(r), ctx->cached_reads--;
-                        else ctx->cached_bases += kmers_of(r), ctx->cached_reads++;
-                    }
-                    shadow[r] = v;
-                }
-            }
-            for (uint32_t r = (uint32_t)(8 * words); r < ctx->n_reads; r++) {
-                const uint8_t v = ignore[r];
-                if (v == shadow[r]) continue;
-                if (r >= lo && r < hi && (v != 0) != (shadow[r] != 0)) {
-                    if (v) ctx->cached_bases -= kmers_of(r), ctx->cached_reads--;
-                    else ctx->cached_bases += kmers_of(r), ctx->cached_reads++;
-                }
-                shadow[r] = v;
-            }
-        }
-        flags_dirty = true;  // (brought over by the launch that makes the read items - below - or by one of its own)
-        ctx->ignore_epoch = ignore_epoch;
-        ctx->cached_lo = lo;
-        ctx->cached_hi = hi;
-        ctx->cached_top = top_level;
-        ctx->cached_k = k;
+        fastArgs.ign = (const uint8_t*)ctx->d_ignore.p;
+        fastArgs.qlo = R.n_extra ? qmin : 0u;
+        fastArgs.qspan = R.n_extra ? qmax - qmin + 1 : 0u;
     }
-    uint64_t bases = ctx->cached_bases;
-    for (uint32_t i = 0; i < n_extra; i++) bases += extra[i].n_kmers ? (uint64_t)extra[i].n_kmers + k - 1 : 0;
-    out->bases_scanned = bases;
-    out->reads_scanned = ctx->cached_reads;
-    out->n_extra = n_extra;
-    out->index_mode = 0;
-    out->index_hits = 0;
-    ctx->scan_items = n_items;
-    ctx->chunk_lo = lo;
-    if (pin_reserve(ctx, ctx->h_total, 128)) return DP_ERR_HIP;
-    ctx->last_n_extra = n_extra;
+    const int rc = dp_kindex_count(ctx, R.k, R.d_items, R.lo, R.hi, R.n_read_items, R.n_extra, (uint32_t*)ctx->d_counts.p,
+                                   (uint64_t*)ctx->d_segoff.p, R.s_item, R.s_count, R.s_off, R.s_pack, R.totals,
+                                   (unsigned long long*)ctx->h_total.p, *oneshot ? &one : nullptr, &fastArgs);
+    if (rc < 0) return rc;
+    if (rc == 2) *oneshot = false;  // (no bins this round: the two-wait form follows)
+    else if (rc > 0) return DP_OK;  // more items than its scan handles: this round is scanned
+    *launched = true;
+    if (*oneshot) {
+        if (int rc2 = dp_index_prechain_launch(ctx, R.totals, R.n_extra, one.seg_cap, one.done_flag, one.done_seq)) return rc2;
+        *wait_flag = ctx->pc_launched && !ctx->timing_on;
+    }
+    return DP_OK;
+}
+
+// The settling of a one-go step after its wait: did the guesses hold?  (the kernels behind the count step gave up on their own where
+// a buffer was too small)  Leaves this round in kx_prev_* for the next plan, *done = the segments are written; where they are not,
+// the chunk stage is cancelled (it found nothing to chunk and said so) and dp_kindex_refill is on the stream - unless the largest
+// survivor is beyond every sort tier, which dp_kindex_write answers.
+static int index_settle(dp_ctx* ctx, const ScanRound& R, const dp_kindex_oneshot& one, const ScanTotals& T, uint32_t kx_max_count, bool* done) {
+    const uint64_t* h = (const uint64_t*)ctx->h_total.p;
+    const bool rec_full = (uint32_t)h[DP_TOT_BIN_FLAGS] != 0;
+    *done = T.n_segs <= one.seg_cap && !rec_full && kx_max_count <= one.sort_cap;
+    ctx->kx_oneshot_rounds++;
+    if (!*done) ctx->kx_oneshot_redone++;
+    ctx->kx_prev_hits = h[DP_TOT_HITS];
+    ctx->kx_prev_segs = T.n_segs;
+    ctx->kx_prev_max = kx_max_count;
+    ctx->kx_prev_surv = (uint32_t)T.n_surv_all;
+    if (*done) return DP_OK;
+    if (ctx->dbg.kx_oneshot)
+        fprintf(stderr, "[kx] one-go step repeated: segs %llu / cap %llu, records %s, largest survivor %u / sort %u (%llu of %llu rounds)\n",
+                (unsigned long long)T.n_segs, (unsigned long long)one.seg_cap, rec_full ? "full" : "ok", kx_max_count, one.sort_cap,
+                (unsigned long long)ctx->kx_oneshot_redone, (unsigned long long)ctx->kx_oneshot_rounds);
     dp_index_prechain_cancel(ctx);
-    if (n_items == 0) {
-        ctx->n_segs = 0;
-        return DP_OK;
+    if (kx_max_count <= 4096) return dp_kindex_refill(ctx, R.d_items, R.n_read_items, R.n_extra);
+    return DP_OK;
+}
+
+// the segment buffers and the host's survivor arrays, sized from the totals the first wait brought
+static int scan_size_outputs(dp_ctx* ctx, const ScanTotals& T) {
+    if (dev_reserve(ctx, ctx->d_segs, T.n_segs * 4 + 64)) return DP_ERR_HIP;
+    if (pin_reserve(ctx, ctx->h_segs, T.n_segs * 4 + 64)) return DP_ERR_HIP;
+    if (pin_reserve(ctx, ctx->h_surv, T.n_surv_all * 32 + 128)) return DP_ERR_HIP;
+    ctx->last_surv_all = (uint32_t)T.n_surv_all;
+    return DP_OK;
+}
+
+// dense-seed regime (more than 8 MiB of segments): tens of MB go back to the host - the caller lets the next slot's scan start while
+// they travel, once this has waited for the write pass (mark 3)
+static int scan_wait_write_pass(dp_ctx* ctx) {
+    if (!ctx->timing_on) DP_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
+    DP_HIP(hipEventSynchronize(ctx->ev[3]));
+    return DP_OK;
+}
+
+// The fetch of the segments.  dp_scan_fetch_mode(1): the survivors' segments stay on the device (the caller chunks and indexes them
+// there); only the extra items' - the query windows', which follow the survivors in the scan output - come to the host, at their
+// offsets; mirror_extras: the index step's sort kernel has stored those into the pinned block as it wrote them.  On the stream: nothing,
+// a store launch (up to 1 MiB of ints) or a copy; *queued says which.
+static int scan_fetch_segs(dp_ctx* ctx, const ScanRound& R, uint64_t n_segs, bool index_mode, bool mirror_extras, bool* queued) {
+    uint64_t from = 0;
+    if (ctx->scan_fetch_extras_only) {
+        if (!R.n_extra || mirror_extras) from = n_segs;
+        else if (index_mode) from = std::min<uint64_t>(n_segs, ((const uint64_t*)ctx->h_total.p)[DP_TOT_EXTRA_SEG0]);
     }
-    const uint32_t n_tiles = (n_items + OFF_TILE - 1) / OFF_TILE;
-    if (dev_reserve(ctx, ctx->d_items, (size_t)n_items * sizeof(dp_scan_item) + 16)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_counts, (size_t)n_items * 4 + 16)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_segoff, ((size_t)n_items + 1) * 8)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_total, 64 + ((size_t)n_tiles + 2) * 16)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_surv, (size_t)n_items * 32 + 128)) return DP_ERR_HIP;
-    dp_scan_item* d_items = (dp_scan_item*)ctx->d_items.p;
-    // the read items are a function of the read lengths, the flags and these arguments: they stay on the device from round to
-    // round (the kernels only read them; the extra items behind them are this round's)
-    if (n_read_items && (ctx->items_ptr != d_items || ctx->items_epoch != ignore_epoch || ctx->items_lo != lo || ctx->items_hi != hi ||
-                         ctx->items_min != min_seeds || ctx->items_top != top_level || ctx->items_k != k)) {
-        const uint32_t fw = flags_dirty ? (uint32_t)(nr8 / 8) : 0u;
-        hipLaunchKernelGGL(make_read_items_kernel, dim3((std::max(n_read_items, fw) + 255) / 256), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)ctx->d_len.p, (const uint8_t*)ctx->d_ignore.p, lo, hi, k, top_level, min_seeds, d_items,
-                           flags_dirty ? (const unsigned long long*)ctx->h_ignore.p : (const unsigned long long*)nullptr,
-                           (unsigned long long*)ctx->d_ignore.p, fw);
-        flags_dirty = false;
-        ctx->items_ptr = d_items;
-        ctx->items_epoch = ignore_epoch;
-        ctx->items_lo = lo;
-        ctx->items_hi = hi;
-        ctx->items_min = min_seeds;
-        ctx->items_top = top_level;
-        ctx->items_k = k;
-    }
-    if (flags_dirty) {  // (no read items were made in this call)
-        const dp_fetch_region f = {ctx->d_ignore.p, ctx->h_ignore.p, nr8};
-        if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1)) return rc;
-        flags_dirty = false;
-    }
-    if (n_extra) {  // (borrowed from the caller: staged in a pinned block, fetched by a kernel of this stream)
-        if (pin_reserve(ctx, ctx->h_extra, (size_t)n_extra * sizeof(dp_scan_item) + 64)) return DP_ERR_HIP;
-        memcpy(ctx->h_extra.p, extra, (size_t)n_extra * sizeof(dp_scan_item));
-    }
-    ctx->extras_staged = n_extra > 0;
-    auto fetch_extras = [&]() -> int {  // (the index step's first kernel does this itself: dp_kindex_count)
-        if (!ctx->extras_staged) return DP_OK;
-        ctx->extras_staged = false;
-        const dp_fetch_region f = {d_items + n_read_items, ctx->h_extra.p, (size_t)n_extra * sizeof(dp_scan_item)};
+    *queued = from < n_segs;
+    if (!*queued) return DP_OK;
+    if (n_segs - from <= ((uint64_t)1 << 20)) {  // a few hundred KB: stored by a launch of this stream (8-byte words)
+        const uint64_t f0 = from & ~(uint64_t)1;
+        const dp_fetch_region f = {(int32_t*)ctx->h_segs.p + f0, (const int32_t*)ctx->d_segs.p + f0, (n_segs - f0) * 4};
         return dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1);
-    };
-    int dev_cus = 256;
-    hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    const bool v2 = k >= 9;
-    // persistent workgroups per CU: 2 fill every wave slot and all LDS of the CU (fastest scan in isolation) - and keep every
-    // other slot's kernels out until the scan is done; DP_TUNE=scan_wg_per_cu=1 leaves half of each CU to them
-    const int wg_per_cu = (int)std::max(1L, std::min(2L, dp_tune("scan_wg_per_cu", 2)));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)dev_cus * (v2 ? wg_per_cu : 1), ((uint64_t)n_items + 15) / 16);
-    uint64_t* totals = (uint64_t*)ctx->d_total.p;  // [0] n_segs, [1] n_survivors
-    uint64_t* tilesA = totals + 4;
-    uint64_t* tilesB = tilesA + n_tiles + 1;
-    uint32_t* s_item = (uint32_t*)ctx->d_surv.p;
-    uint32_t* s_count = s_item + n_items;
-    uint64_t* s_off = (uint64_t*)(s_count + n_items + (n_items & 1));
-    // {item, count, offset} per survivor: what the host wants of the compaction.  The kernel that makes the list writes it into a
-    // pinned host block directly (nobody reads it on the device) - a 100 KB copy per round that is never submitted
-    if (pin_reserve(ctx, ctx->h_spack, (size_t)n_items * 16 + 64)) return DP_ERR_HIP;
-    uint4* s_pack = (uint4*)ctx->h_spack.p;
-    // Resident k-mer position index instead of scanning (dp_kindex.hip): DP_SCAN_INDEX=1 forces it, =0 forbids it; by
-    // default it is used from 1 Gbase up.  That is the break-even of a whole job: the build costs ~0.13 s per Gbase, a
-    // round saves (scan 0.5 ms per Gbase) - (index step 0.25 ms), and a job has ~600 rounds per Gbase of 10 kb reads.
-    bool use_index = allow_index && scan_wants_index(ctx);
-    std::unique_lock<ScanGate> scan_lock(g_scan_mu, std::defer_lock);
-    if (use_index) {
-        int rc = dp_kindex_ensure(ctx, k);
-        if (rc < 0) return rc;
-        if (rc > 0) use_index = false;  // k > 14 or not enough free HBM for 8 B per base: scan
     }
-    out->index_hits = 0;
-    // The index step in one go - the walk that bins its hits, offsets, fill from the bins and sort/write are all launched
-    // before the one wait, into buffers sized from this context's previous index-mode round (twice its segments, 1.5 x its hits, the
-    // sort tier of 1.25 x its largest survivor); the rare round that outgrows a guess repeats fill + sort with the bucket walk after
-    // the wait.  DP_KX_ONESHOT=0, or a round whose bins cannot be set up: count, wait, size, fill, sort, wait.
-    const bool oneshot_env = dp_env_tristate("DP_KX_ONESHOT") != 0;
-    bool oneshot = false;
+    DP_HIP(hipMemcpyAsync((int32_t*)ctx->h_segs.p + from, (const int32_t*)ctx->d_segs.p + from, (n_segs - from) * 4, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    return DP_OK;
+}
+
+// kernel times of a call whose marks have all been waited for (one-go step: fill + sort lie between marks 1 and 4, and are the
+// write time)
+static void scan_times(dp_ctx* ctx, bool oneshot, uint64_t n_segs, dp_survivor_batch* out) {
+    const float ms0 = dp_elapsed(ctx, 0, 1), msoff = oneshot ? 0.f : dp_elapsed(ctx, 1, 4), ms1 = n_segs ? dp_elapsed(ctx, 2, 3) : 0.f;
+    out->kernel_ms = (double)ms0 + (double)msoff + (double)ms1;
+    out->count_kernel_ms = ms0;
+    out->write_kernel_ms = ms1;
+}
+
+// What the index step says of a round.  Scan: the index could not answer it - it cannot be used for this k or read set, the round
+// has more items than its scan handles, or a survivor more hits than its sort holds - and the scan kernels do.
+enum class KxAnswer { Answered, Scan };
+
+// The index step: the round answered from the resident k-mer position index (dp_kindex.hip) - plan, launch, wait, settle, write
+// where the one go did not, fetch.  Answered: everything scan_publish reads has arrived, *T holds the totals, and what may still be
+// queued - the chunk stage behind a one-go step that held - is not this call's to wait for.  Scan: the stream is idle or untouched,
+// and the extra items are staged (again) for the scan kernels' path.
+static int index_step(dp_ctx* ctx, const ScanRound& R, dp_survivor_batch* out, ScanTotals* T, KxAnswer* ans) {
+    *ans = KxAnswer::Scan;
+    int rc = dp_kindex_ensure(ctx, R.k);
+    if (rc) return rc < 0 ? rc : DP_OK;  // > 0: k > 14 or not enough free HBM for 8 B per base
     dp_kindex_oneshot one;
-    memset(&one, 0, sizeof one);
-    const bool mirror_wanted = ctx->scan_fetch_extras_only && n_extra > 0;
-    if (use_index) {
-        const std::vector<uint32_t>& lens = ctx->owner ? ctx->owner->h_len : ctx->h_len;
-        if (ctx->kx_maxlen_reads != lens.size()) {  // (a bin's record holds 24 bits of position)
-            uint32_t mx = 0;
-            for (uint32_t L : lens) mx = std::max(mx, L);
-            ctx->kx_maxlen = mx;
-            ctx->kx_maxlen_reads = lens.size();
-        }
-        oneshot = oneshot_env && ctx->n_seeds > 0 && ctx->n_reads < (1u << 24) && ctx->kx_maxlen < (1u << 24);
-        if (oneshot) {
-            one.hits_guess = ctx->kx_prev_hits ? ctx->kx_prev_hits + ctx->kx_prev_hits / 2 : 0;
-            one.surv_guess = ctx->kx_prev_surv ? ctx->kx_prev_surv + ctx->kx_prev_surv / 4 : 8192;
-            const uint32_t mxg = ctx->kx_prev_max + ctx->kx_prev_max / 4;
-            one.sort_cap = mxg <= 128 ? 256u : (mxg <= 512 ? 1024u : 4096u);
-            const uint64_t want = std::max<uint64_t>(2 * ctx->kx_prev_segs + 65536, 1u << 20);
-            if (dev_reserve(ctx, ctx->d_segs, want * 4 + 64)) return DP_ERR_HIP;
-            one.seg_cap = (ctx->d_segs.cap - 64) / 4;
-            if (mirror_wanted) {
-                if (pin_reserve(ctx, ctx->h_segs, one.seg_cap * 4 + 64)) return DP_ERR_HIP;
-                one.host_segs = (int32_t*)ctx->h_segs.p;
-            }
-            one.d_segs = (int32_t*)ctx->d_segs.p;
-            // (where a chunk stage launched behind the step says that the step's own kernels are done)
-            one.done_flag = (uint32_t*)ctx->h_total.p + 30;
-            one.done_seq = ++ctx->kx_seq ? ctx->kx_seq : ++ctx->kx_seq;
-            __atomic_store_n(one.done_flag, 0u, __ATOMIC_RELEASE);  // (whatever an earlier round or a fresh block left there)
-        }
-    }
-    if (use_index) {
-        // counts, segment offsets, survivor list and totals in three launches, no sort and no host round trip (dp_kindex.hip)
-        // (views served whole - top_level == 0 - have a k-mer at every indexed position: the walk tests the ignore byte instead of
-        // reading the read's item, and looks for extra items only on the round's query reads)
-        dp_kindex_fast fastArgs = {nullptr, 0u, 0u};
-        if (!top_level && ctx->d_ignore.p) {
-            uint32_t qmin = 0xffffffffu, qmax = 0;
-            for (uint32_t i = 0; i < n_extra; i++) {
-                qmin = std::min(qmin, extra[i].read);
-                qmax = std::max(qmax, extra[i].read);
-            }
-            fastArgs.ign = (const uint8_t*)ctx->d_ignore.p;
-            fastArgs.qlo = n_extra ? qmin : 0u;
-            fastArgs.qspan = n_extra ? qmax - qmin + 1 : 0u;
-        }
-        int rc = dp_kindex_count(ctx, k, d_items, lo, hi, n_read_items, n_extra, (uint32_t*)ctx->d_counts.p, (uint64_t*)ctx->d_segoff.p,
-                                 s_item, s_count, s_off, s_pack, totals, (unsigned long long*)ctx->h_total.p, oneshot ? &one : nullptr, &fastArgs);
-        if (rc < 0) return rc;
-        if (rc == 2) oneshot = false;   // (no bins this round: the two-wait form follows)
-        else if (rc > 0) use_index = false;  // more items than its scan handles: this round is scanned
-    }
-    if (!use_index) oneshot = false;
-    bool wait_flag = false;
-    if (oneshot) {
-        // dp_index_prechain: the chunk stage of the caller's coming dp_index_build_chunked goes behind the scan right now
-        if (int rc = dp_index_prechain_launch(ctx, totals, n_extra, one.seg_cap, one.done_flag, one.done_seq)) return rc;
-        // (its first kernel tells the host that the scan's own kernels are done: the host waits for that word, not for the stream)
-        wait_flag = ctx->pc_launched && !ctx->timing_on;
-    }
-    out->index_mode = use_index ? 1u : 0u;
-    if (!use_index) {
-        if (int rc = fetch_extras()) return rc;
-        if (int rc = seed_tables_ensure(ctx)) return rc;
-        scan_lock.lock();  // (see dp_scan)
-        DP_HIP(dp_mark(ctx, 0));
-        hipLaunchKernelGGL((v2 ? scan_kernel<0, 2> : scan_kernel<0, 1>), dim3(grid), dim3(SCAN_THREADS), 0, ctx->stream,
-                           (const uint8_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)d_items, n_items, k,
-                           (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p,
-                           (const int32_t*)ctx->d_kmap.p, (uint32_t*)ctx->d_counts.p, (const uint64_t*)nullptr, (int32_t*)nullptr, 0u,
-                           (const uint32_t*)nullptr, 0u);
-        DP_HIP(hipGetLastError());
-        DP_HIP(dp_mark(ctx, 1));
-        hipLaunchKernelGGL(offsets_tile_sums, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)d_items,
-                           (const uint32_t*)ctx->d_counts.p, n_items, tilesA);
-        hipLaunchKernelGGL(offsets_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tilesA, n_tiles, totals, (uint64_t*)ctx->d_segoff.p, n_items);
-        hipLaunchKernelGGL(offsets_write, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)d_items,
-                           (const uint32_t*)ctx->d_counts.p, n_items, (const uint64_t*)tilesA, (uint64_t*)ctx->d_segoff.p);
-        hipLaunchKernelGGL(flag_tile_sums, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)d_items,
-                           (const uint32_t*)ctx->d_counts.p, n_items, tilesB);
-        hipLaunchKernelGGL(offsets_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tilesB, n_tiles, totals + 1, tilesB + n_tiles, 0u);
-        hipLaunchKernelGGL(compact_write, dim3(n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)d_items,
-                           (const uint32_t*)ctx->d_counts.p, n_items, (const uint64_t*)tilesB, (const uint64_t*)ctx->d_segoff.p, s_item,
-                           s_count, s_off, s_pack);
-    }
+    bool oneshot = false, launched = false, wait_flag = false, done = false, queued = false;
+    if ((rc = index_plan(ctx, R, one, &oneshot))) return rc;
+    if ((rc = index_launch(ctx, R, one, &oneshot, &launched, &wait_flag))) return rc;
+    if (!launched) return DP_OK;
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 4));
-    if (!use_index) {  // (stored into the pinned block by a launch of this stream, not copied by the runtime; the index step's
-                       // last kernel has stored them itself)
-        const dp_fetch_region f = {ctx->h_total.p, totals, 48};
-        if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1)) return rc;
-    }
     if (wait_flag) DP_HIP(kx_wait_done(ctx, one.done_flag, one.done_seq));
     else DP_HIP(dp_stream_sync(ctx));
-    const uint64_t n_segs = ((uint64_t*)ctx->h_total.p)[0];
-    const uint64_t n_surv_all = ((uint64_t*)ctx->h_total.p)[1];  // surviving reads + all extra items
-    if (use_index) {
-        ctx->kx_hits = ((uint64_t*)ctx->h_total.p)[2];
-        out->index_hits = ctx->kx_hits;
+    *T = scan_totals_read(ctx);  // (the index step's last kernel has stored them into the pinned block itself)
+    ctx->kx_hits = ((const uint64_t*)ctx->h_total.p)[DP_TOT_HITS];
+    const uint32_t kx_max_count = (uint32_t)((const uint64_t*)ctx->h_total.p)[DP_TOT_MAX_COUNT];
+    if (oneshot && (rc = index_settle(ctx, R, one, *T, kx_max_count, &done))) return rc;
+    if ((rc = scan_size_outputs(ctx, *T))) return rc;
+    // dp_scan_fetch_mode(1) with the index step: the only segments the host wants are the extra items' - the sort kernel stores
+    // them into the pinned block as it writes them (no store launch afterwards)
+    const bool mirror_extras = ctx->scan_fetch_extras_only && R.n_extra > 0;
+    if (T->n_segs) {
+        if (!done) {  // (else fill + sort ran behind the counting step already)
+            DP_HIP(dp_mark(ctx, 2));
+            rc = dp_kindex_write(ctx, R.k, R.d_items, R.lo, R.hi, R.n_read_items, R.n_extra, (const uint32_t*)R.s_item, (uint32_t)T->n_surv_all,
+                                 kx_max_count, (const uint32_t*)ctx->d_counts.p, (const uint64_t*)ctx->d_segoff.p, (const uint64_t*)R.totals,
+                                 (int32_t*)ctx->d_segs.p, mirror_extras ? (int32_t*)ctx->h_segs.p : (int32_t*)nullptr);
+            if (rc < 0) return rc;
+            if (rc > 0) {  // a survivor with more hits than the in-LDS sort holds: the scan kernels answer this round
+                DP_HIP(dp_stream_sync(ctx));
+                ctx->extras_staged = R.n_extra > 0;  // (dp_kindex_count consumed the staged block, which h_extra still holds)
+                return DP_OK;
+            }
+        }
+        DP_HIP(hipGetLastError());
+        if (!done) DP_HIP(dp_mark(ctx, 3));
+        if (T->n_segs * 4 > ((uint64_t)8 << 20) && !done)
+            if ((rc = scan_wait_write_pass(ctx))) return rc;
+        if ((rc = scan_fetch_segs(ctx, R, T->n_segs, true, mirror_extras, &queued))) return rc;
     }
-    const uint32_t kx_max_count = (uint32_t)((uint64_t*)ctx->h_total.p)[3];
-    bool oneshot_done = false, queued_more = false;
-    if (oneshot) {
-        // did the guesses hold?  (the kernels behind the count step gave up on their own where a buffer was too small)
-        const bool rec_full = (uint32_t)((uint64_t*)ctx->h_total.p)[6] != 0;
-        oneshot_done = n_segs <= one.seg_cap && !rec_full && kx_max_count <= one.sort_cap;
-        ctx->kx_oneshot_rounds++;
-        if (!oneshot_done) ctx->kx_oneshot_redone++;
-        ctx->kx_prev_hits = ((uint64_t*)ctx->h_total.p)[2];
-        ctx->kx_prev_segs = n_segs;
-        ctx->kx_prev_max = kx_max_count;
-        ctx->kx_prev_surv = (uint32_t)n_surv_all;
-        if (ctx->dbg.kx_oneshot && !oneshot_done)
-            fprintf(stderr, "[kx] one-go step repeated: segs %llu / cap %llu, records %s, largest survivor %u / sort %u (%llu of %llu rounds)\n",
-                    (unsigned long long)n_segs, (unsigned long long)one.seg_cap, rec_full ? "full" : "ok", kx_max_count, one.sort_cap,
-                    (unsigned long long)ctx->kx_oneshot_redone, (unsigned long long)ctx->kx_oneshot_rounds);
-        if (!oneshot_done) dp_index_prechain_cancel(ctx);  // (the chunk stage behind it found nothing to chunk and said so)
-        if (!oneshot_done && kx_max_count <= 4096)
-            if (int rc = dp_kindex_refill(ctx, (const dp_scan_item*)d_items, n_read_items, n_extra)) return rc;
+    if (!done || queued) DP_HIP(dp_stream_sync(ctx));
+    scan_times(ctx, oneshot, T->n_segs, out);
+    out->index_mode = 1u;
+    out->index_hits = ctx->kx_hits;
+    *ans = KxAnswer::Answered;
+    return DP_OK;
+}
+
+// Count pass of the scan-kernel path: counts, segment offsets (scan_count_pass) and the survivor compaction behind them.  Leaves the
+// survivor list in d_surv and, for the host, in h_spack; R.totals[DP_TOT_SEGS] and [DP_TOT_SURV] are set.
+static int scan_count_compact(dp_ctx* ctx, const ScanRound& R) {
+    if (int rc = scan_count_pass(ctx, R, 0u)) return rc;
+    hipLaunchKernelGGL(flag_tile_sums, dim3(R.n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)R.d_items,
+                       (const uint32_t*)ctx->d_counts.p, R.n_items, R.tilesB);
+    hipLaunchKernelGGL(offsets_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, R.tilesB, R.n_tiles, R.totals + DP_TOT_SURV,
+                       R.tilesB + R.n_tiles, 0u);
+    hipLaunchKernelGGL(compact_write, dim3(R.n_tiles), dim3(OFF_TILE), 0, ctx->stream, (const dp_scan_item*)R.d_items,
+                       (const uint32_t*)ctx->d_counts.p, R.n_items, (const uint64_t*)R.tilesB, (const uint64_t*)ctx->d_segoff.p, R.s_item,
+                       R.s_count, R.s_off, R.s_pack);
+    DP_HIP(hipGetLastError());
+    return DP_OK;
+}
+
+// The scan-kernel path: the round answered by scanning the reads, under the scan gate (see dp_scan).  Everything scan_publish reads
+// has arrived when it returns, *T holds the totals and the stream is idle.
+static int scan_kernel_step(dp_ctx* ctx, const ScanRound& R, dp_survivor_batch* out, ScanTotals* T) {
+    if (int rc = scan_fetch_extras(ctx, R)) return rc;
+    if (int rc = seed_tables_ensure(ctx)) return rc;
+    std::unique_lock<ScanGate> scan_lock(g_scan_mu);
+    if (int rc = scan_count_compact(ctx, R)) return rc;
+    DP_HIP(dp_mark(ctx, 4));
+    {  // (stored into the pinned block by a launch of this stream, not copied by the runtime)
+        const dp_fetch_region f = {ctx->h_total.p, R.totals, (DP_TOT_EXTRA_SEG0 + 1) * 8};
+        if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1)) return rc;
     }
-    if (dev_reserve(ctx, ctx->d_segs, n_segs * 4 + 64)) return DP_ERR_HIP;
-    if (pin_reserve(ctx, ctx->h_segs, n_segs * 4 + 64)) return DP_ERR_HIP;
-    if (pin_reserve(ctx, ctx->h_surv, n_surv_all * 32 + 128)) return DP_ERR_HIP;
-    ctx->last_surv_all = (uint32_t)n_surv_all;
-    float ms0 = 0, ms1 = 0, msoff = 0;
-    ms0 = dp_elapsed(ctx, 0, 1);
-    msoff = oneshot ? 0.f : dp_elapsed(ctx, 1, 4);  // (one-go step: fill + sort lie between these two marks, and are ms1 below)
+    DP_HIP(dp_stream_sync(ctx));
+    *T = scan_totals_read(ctx);
+    if (int rc = scan_size_outputs(ctx, *T)) return rc;
+    if (T->n_segs) {
+        DP_HIP(dp_mark(ctx, 2));
+        // one wave per SURVIVOR (the compacted list), not a strided walk over every item
+        const uint32_t wgrid = (uint32_t)std::min<uint64_t>(R.grid, (T->n_surv_all + 15) / 16);
+        scan_write_pass(ctx, R, std::max(1u, wgrid), (const uint32_t*)R.s_item, (uint32_t)T->n_surv_all);
+        DP_HIP(hipGetLastError());
+        DP_HIP(dp_mark(ctx, 3));
+        if (T->n_segs * 4 > ((uint64_t)8 << 20)) {
+            if (int rc = scan_wait_write_pass(ctx)) return rc;
+            scan_lock.unlock();
+        }
+        bool queued = false;
+        if (int rc = scan_fetch_segs(ctx, R, T->n_segs, false, false, &queued)) return rc;
+    }
+    DP_HIP(dp_stream_sync(ctx));
+    scan_times(ctx, false, T->n_segs, out);
+    return DP_OK;
+}
+
+// The publishing of out: the survivor list unpacked from h_spack into the host's arrays (h_surv), item indices turned into read
+// ids, the extra items' entries behind the reads'.
+static int scan_publish(dp_ctx* ctx, const ScanRound& R, const ScanTotals& T, dp_survivor_batch* out) {
+    const uint64_t n_surv_all = T.n_surv_all;
     uint32_t* h_item = (uint32_t*)ctx->h_surv.p;
     uint32_t* h_count = h_item + n_surv_all;
     uint64_t* h_off = (uint64_t*)(h_count + n_surv_all + (n_surv_all & 1));
     const uint32_t* h_pack = (const uint32_t*)ctx->h_spack.p;  // (complete since the wait after the count pass)
-    // dp_scan_fetch_mode(1) with the index step: the only segments the host wants are the extra items' - the sort kernel stores
-    // them into the pinned block as it writes them (no store launch afterwards)
-    const bool mirror_extras = use_index && ctx->scan_fetch_extras_only && n_extra > 0;
-    if (n_segs) {
-        if (!oneshot_done) DP_HIP(dp_mark(ctx, 2));
-        if (oneshot_done) {
-            // (fill + sort ran behind the counting step already)
-        } else if (use_index) {
-            int rc = dp_kindex_write(ctx, k, (const dp_scan_item*)d_items, lo, hi, n_read_items, n_extra, (const uint32_t*)s_item,
-                                     (uint32_t)n_surv_all, kx_max_count, (const uint32_t*)ctx->d_counts.p, (const uint64_t*)ctx->d_segoff.p,
-                                     (const uint64_t*)totals, (int32_t*)ctx->d_segs.p, mirror_extras ? (int32_t*)ctx->h_segs.p : (int32_t*)nullptr);
-            if (rc < 0) return rc;
-            if (rc > 0) {  // a survivor with more hits than the in-LDS sort holds: the scan kernels answer this round
-                DP_HIP(dp_stream_sync(ctx));
-                return DP_SCAN_AGAIN;
-            }
-        } else {
-            // one wave per SURVIVOR (the compacted list), not a strided walk over every item
-            const uint32_t wgrid = (uint32_t)std::min<uint64_t>(grid, (n_surv_all + 15) / 16);
-            hipLaunchKernelGGL((v2 ? scan_kernel<1, 2> : scan_kernel<1, 1>), dim3(std::max(1u, wgrid)), dim3(SCAN_THREADS), 0, ctx->stream,
-                               (const uint8_t*)ctx->d_packed.p, (const uint64_t*)ctx->d_boff.p, (const dp_scan_item*)d_items, n_items, k,
-                               (const uint32_t*)ctx->d_seeds.p, ctx->n_seeds, (const uint32_t*)ctx->d_bits.p,
-                               (const int32_t*)ctx->d_kmap.p, (uint32_t*)ctx->d_counts.p, (const uint64_t*)ctx->d_segoff.p,
-                               (int32_t*)ctx->d_segs.p, 0u, (const uint32_t*)s_item, (uint32_t)n_surv_all);
-        }
-        DP_HIP(hipGetLastError());
-        if (!oneshot_done) DP_HIP(dp_mark(ctx, 3));
-        if (n_segs * 4 > ((uint64_t)8 << 20) && !oneshot_done) {
-            // dense-seed regime: tens of MB go back to the host; let the next slot's scan start while they travel
-            if (!ctx->timing_on) DP_HIP(hipEventRecord(ctx->ev[3], ctx->stream));
-            DP_HIP(hipEventSynchronize(ctx->ev[3]));
-            if (scan_lock.owns_lock()) scan_lock.unlock();
-        }
-        // dp_scan_fetch_mode(1): the survivors' segments stay on the device (the caller chunks and indexes them there); only the
-        // extra items' - the query windows', which follow the survivors in the scan output - come to the host, at their offsets
-        uint64_t from = 0;
-        if (ctx->scan_fetch_extras_only) {
-            if (!n_extra || mirror_extras) from = n_segs;
-            else if (use_index) from = std::min<uint64_t>(n_segs, ((uint64_t*)ctx->h_total.p)[5]);
-        }
-        if (from < n_segs) {
-            if (n_segs - from <= ((uint64_t)1 << 20)) {  // a few hundred KB: stored by a launch of this stream (8-byte words)
-                const uint64_t f0 = from & ~(uint64_t)1;
-                const dp_fetch_region f = {(int32_t*)ctx->h_segs.p + f0, (const int32_t*)ctx->d_segs.p + f0, (n_segs - f0) * 4};
-                if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, &f, 1)) return rc;
-            } else {
-                DP_HIP(hipMemcpyAsync((int32_t*)ctx->h_segs.p + from, (const int32_t*)ctx->d_segs.p + from, (n_segs - from) * 4,
-                                      hipMemcpyDeviceToHost, ctx->stream));
-            }
-            queued_more = true;
-        }
-    }
-    // (a one-go step that held: everything the host reads arrived with the first wait, and what may be queued behind it - the
-    // chunk stage - is not this call's to wait for)
-    if (!oneshot_done || queued_more) DP_HIP(dp_stream_sync(ctx));
-    if (n_segs) ms1 = dp_elapsed(ctx, 2, 3);
-    if (scan_lock.owns_lock()) scan_lock.unlock();
-    ctx->n_segs = n_segs;
+    ctx->n_segs = T.n_segs;
     for (uint64_t i = 0; i < n_surv_all; i++) {
         h_item[i] = h_pack[4 * i];
         h_count[i] = h_pack[4 * i + 1];
@@ -2581,9 +2608,9 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     }
     // survivors of the read range come first (item index < n_read_items), the extra items after them (all present)
     uint64_t ns = 0;
-    while (ns < n_surv_all && h_item[ns] < n_read_items) ns++;
-    if (n_surv_all - ns != n_extra) return dp_fail(ctx, DP_ERR_STATE, "dp_scan_reads: internal compaction mismatch");
-    for (uint64_t i = 0; i < ns; i++) h_item[i] += lo;  // item index -> read id
+    while (ns < n_surv_all && h_item[ns] < R.n_read_items) ns++;
+    if (n_surv_all - ns != R.n_extra) return dp_fail(ctx, DP_ERR_STATE, "dp_scan_reads: internal compaction mismatch");
+    for (uint64_t i = 0; i < ns; i++) h_item[i] += R.lo;  // item index -> read id
     out->n_survivors = (uint32_t)ns;
     out->read = h_item;
     out->n_seeds = h_count;
@@ -2591,12 +2618,53 @@ static int scan_reads_body(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_e
     out->extra_n_seeds = h_count + ns;
     out->extra_seg_off = h_off + ns;
     out->segs = (const int32_t*)ctx->h_segs.p;
-    out->n_segs = n_segs;
-    out->kernel_ms = (double)ms0 + (double)msoff + (double)ms1;
-    out->count_kernel_ms = ms0;
-    out->write_kernel_ms = ms1;
+    out->n_segs = T.n_segs;
     return DP_OK;
 }
+
+extern "C" int dp_scan_reads(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_epoch, uint32_t lo, uint32_t hi, int top_level,
+                             uint32_t min_seeds, const dp_scan_item* extra, uint32_t n_extra, dp_survivor_batch* out) {
+    if (int rc = scan_reads_check(ctx, ignore, lo, hi, extra, n_extra, out)) return rc;
+    hipSetDevice(ctx->device);
+    ScanRound R{};
+    R.lo = lo, R.hi = hi, R.top_level = top_level, R.k = ctx->k, R.min_seeds = min_seeds;
+    R.extra = extra, R.n_extra = n_extra;
+    R.n_read_items = hi - lo, R.n_items = R.n_read_items + n_extra;
+    bool flags_dirty = false;
+    struct FlagsGuard {  // (a way out of this call before the launch that brings the flags over: the next call starts from scratch)
+        dp_ctx* c;
+        bool& dirty;
+        ~FlagsGuard() {
+            if (dirty) c->flags.valid = false;
+        }
+    } flagsGuard{ctx, flags_dirty};
+    if (int rc = scan_flags_step(ctx, ignore, ignore_epoch, dp_flag_view{lo, hi, top_level, R.k}, &flags_dirty)) return rc;
+    out->bases_scanned = ctx->flags.sums.bases;
+    for (uint32_t i = 0; i < n_extra; i++) out->bases_scanned += scan_item_bases(extra[i], R.k);
+    out->reads_scanned = ctx->flags.sums.reads;
+    out->n_extra = n_extra;
+    ctx->scan_items = R.n_items;
+    ctx->chunk_lo = lo;
+    if (pin_reserve(ctx, ctx->h_total, 128)) return DP_ERR_HIP;
+    ctx->last_n_extra = n_extra;
+    dp_index_prechain_cancel(ctx);
+    if (R.n_items == 0) {
+        ctx->n_segs = 0;
+        return DP_OK;
+    }
+    if (int rc = scan_prepare_items(ctx, ignore_epoch, &flags_dirty, R)) return rc;
+    // Resident k-mer position index instead of scanning (dp_kindex.hip): DP_SCAN_INDEX=1 forces it, =0 forbids it; by
+    // default it is used from 1 Gbase up.  That is the break-even of a whole job: the build costs ~0.13 s per Gbase, a
+    // round saves (scan 0.5 ms per Gbase) - (index step 0.25 ms), and a job has ~600 rounds per Gbase of 10 kb reads.
+    KxAnswer ans = KxAnswer::Scan;
+    ScanTotals T{0, 0};
+    if (scan_wants_index(ctx))
+        if (int rc = index_step(ctx, R, out, &T, &ans)) return rc;
+    if (ans == KxAnswer::Scan)
+        if (int rc = scan_kernel_step(ctx, R, out, &T)) return rc;
+    return scan_publish(ctx, R, T, out);
+}
+
 
 extern "C" int dp_scan_fetch_mode(dp_ctx* ctx, int extras_only) {
     if (!ctx) return DP_ERR_ARG;

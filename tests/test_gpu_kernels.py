@@ -408,7 +408,7 @@ def test_index_mode_write_sort_tiers(ctx, n_seeds):
 
 def test_index_mode_largest_sort_tier_and_beyond():
     """The largest sort tier of the index-mode write step, from both of its launch sites, and the step's way out above it - on a
-    context of its own, because the one-go form sizes its sort from the context's previous round (sort_cap in scan_reads_body,
+    context of its own, because the one-go form sizes its sort from the context's previous round (sort_cap in index_plan,
     dp_scan.hip: 1.25 x the previous largest count; the tiers end at 128 / 512 / KX_SORT_LDS = 4096 hits, dp_kindex_count and
     dp_kindex_write in dp_kindex.hip).  5000-base reads:
       call 1  300 000 of the 4^10 k-mers are seeds, ~1 400 hits per read; the fresh context guessed the smallest sort, so fill and sort are
@@ -450,6 +450,80 @@ def test_index_mode_largest_sort_tier_and_beyond():
     finally:
         del os.environ["DP_SCAN_INDEX"]
         c.close()
+
+
+def test_scan_reads_flags_change_between_calls():
+    """The ignore flags change between two dp_scan_reads calls of one context: the library diffs the caller's array against its
+    shadow (dp_scan_flags.h) and adjusts bases_scanned / reads_scanned - what a fresh context, which counts everything once, must
+    agree with field by field, and what lengths, flags, range, k and top_level say.  43 reads: the last flag word is a partial one.
+    Both paths (scan kernels, index step), on contexts of their own."""
+    import downpore_amd
+    k, N = 10, 43
+    bases, off = O.gen_reads(31, 20000, N, 3000, 0.01, True)
+    lens = np.diff(off)
+    rng = np.random.default_rng(43)
+    seeds = np.unique(rng.integers(1, 4 ** k, 6000)).astype(np.uint32)
+    extra = [(5, 100, 500, 0), (9, 0, 300, 0)]
+    flags_a = (rng.random(N) < 0.2).astype(np.uint8)
+    flags_a[[3, 10, 40]] = 1
+    flags_a[[4, 20, 41, 42]] = 0
+    flags_b = flags_a.copy()
+    flags_b[[3, 40]] = 0  # cleared: in a full word and in the partial last one
+    flags_b[[4, 20, 42]] = 1  # set
+    flags_b[10] = 2  # non-zero to non-zero: no read more or less
+    steps = [(flags_a, 1, 0, N, False), (flags_b, 2, 0, N, False), (flags_b, 2, 0, N, False), (flags_b, 3, 7, 31, False), (flags_b, 4, 0, N, True)]
+    fields = ("read", "n_seeds", "seg_off", "extra_n_seeds", "extra_seg_off", "segs", "bases_scanned", "reads_scanned", "index_mode")
+
+    def counted(flags, lo, hi, top_level):
+        bases_scanned = sum(nk + k - 1 for _, _, nk, _ in extra if nk)
+        reads_scanned = 0
+        for r in range(lo, hi):
+            if flags[r]:
+                continue
+            n = int(lens[r]) - k + 1 - (4 if top_level and lens[r] % 4 == 0 else 0)
+            bases_scanned += n + k - 1 if n > 0 else 0
+            reads_scanned += 1
+        return bases_scanned, reads_scanned
+
+    def context(mode):
+        c = downpore_amd.Context(0)
+        c.upload_reads(bases, off)
+        if mode == "1":
+            c.scan_prepare(k)
+        c.round_begin(k, seeds)
+        return c
+
+    def call(c, step):
+        flags, epoch, lo, hi, top_level = step
+        got = c.scan_reads(flags, epoch, lo, hi, top_level, 20, extra)
+        return {f: np.array(got[f]).copy() for f in fields}
+
+    saved = os.environ.get("DP_SCAN_INDEX")
+    try:
+        for mode in ("0", "1"):
+            os.environ["DP_SCAN_INDEX"] = mode
+            c = context(mode)
+            try:
+                for i, step in enumerate(steps):
+                    got = call(c, step)
+                    fresh = context(mode)
+                    try:
+                        want = call(fresh, step)
+                    finally:
+                        fresh.close()
+                    assert int(got["index_mode"]) == int(mode), (mode, i)
+                    if i == 0:
+                        assert 0 < len(got["read"]) < int(got["reads_scanned"]), (mode, len(got["read"]), int(got["reads_scanned"]))
+                    for f in fields:
+                        assert np.array_equal(got[f], want[f]), (mode, i, f)
+                    assert (int(got["bases_scanned"]), int(got["reads_scanned"])) == counted(step[0], step[2], step[3], step[4]), (mode, i)
+            finally:
+                c.close()
+    finally:
+        if saved is None:
+            os.environ.pop("DP_SCAN_INDEX", None)
+        else:
+            os.environ["DP_SCAN_INDEX"] = saved
 
 
 def test_scan_reads_compaction_matches_itemwise_scan(ctx):
