@@ -300,8 +300,12 @@ struct dp_kindex_shard {
     int kmer_shift = 0;
     uint64_t total = 0;
 };
+struct dp_kindex_geom {  // the digit widths and the read-id bits dp_kindex_build_sorted chose (dp_kindex_dump reports them)
+    int b1 = 0, b2 = 0, r = 0, rbits = 0;
+};
 int dp_kindex_build_sorted(dp_ctx* ctx, dp_ctx* ow, int k, uint32_t* d_counts, uint64_t* d_off, void** d_pos_out, void** d_pos_hi_out,
-                           int* fmt_out, int* pbits_out, uint64_t* n_pos_out, float* ms_out, dp_kindex_shard* shard = nullptr);  // dp_kbuild.hip
+                           int* fmt_out, int* pbits_out, uint64_t* n_pos_out, float* ms_out, dp_kindex_geom* geom_out,
+                           dp_kindex_shard* shard = nullptr);  // dp_kbuild.hip
 void dp_kindex_free(dp_ctx* ctx);
 int dp_kindex_count(dp_ctx* ctx, int k, const dp_scan_item* d_items, uint32_t lo, uint32_t hi, uint32_t n_read_items, uint32_t n_extra,
                     uint32_t* d_counts, uint64_t* d_segoff, uint32_t* s_item, uint32_t* s_count, uint64_t* s_off, uint4* s_pack, uint64_t* d_totals,

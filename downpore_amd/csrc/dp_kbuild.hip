@@ -477,7 +477,8 @@ __global__ __launch_bounds__(1024) void kb_scan_write(const kb_u64* __restrict__
 // released before returning.  *fmt_out / *pbits_out say how an entry is stored (KbPosOut).
 // Returns 1 when this path does not apply (k < 9 or > 14, more than 2^36 bases): the caller uses the atomic scatter.
 int dp_kindex_build_sorted(dp_ctx* ctx, dp_ctx* ow, int k, uint32_t* d_counts, uint64_t* d_off, void** d_pos_out, void** d_pos_hi_out,
-                           int* fmt_out, int* pbits_out, uint64_t* n_pos_out, float* ms_out, dp_kindex_shard* shard) {
+                           int* fmt_out, int* pbits_out, uint64_t* n_pos_out, float* ms_out, dp_kindex_geom* geom_out,
+                           dp_kindex_shard* shard) {
     if (k < 9 || k > 14 || ow->n_reads == 0) return 1;
     if (dp_tune("kindex_atomic", 0)) return 1;  // (tests: the count -> offsets -> atomic scatter build of dp_kindex_ensure)
     const uint64_t n_groups = (ow->packed_bytes * 4 + 31) / 32;
@@ -660,5 +661,6 @@ int dp_kindex_build_sorted(dp_ctx* ctx, dp_ctx* ow, int k, uint32_t* d_counts, u
     *fmt_out = fmt;
     *pbits_out = G.pbits;
     *n_pos_out = n;
+    if (geom_out) *geom_out = dp_kindex_geom{G.b1, G.b2, G.r, G.rbits};
     return DP_OK;
 }

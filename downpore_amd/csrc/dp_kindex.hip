@@ -26,6 +26,8 @@ struct dp_kindex {
                  // (read << pbits | position) in 32 bits (4) / 40 bits with the top byte in pos_hi (5): KxPos, dp_common.h
     DevBuf pos_hi;
     int pos_fmt = 8, pbits = 32;
+    bool sorted = false;  // the radix build (dp_kbuild.hip) made this index, with the widths in `geom`; false: the atomic scatter below
+    dp_kindex_geom geom;
     KxPos view() const { return KxPos{pos.p, (const uint8_t*)pos_hi.p, (uint32_t)pos_fmt, (uint32_t)pbits}; }
 };
 
@@ -198,6 +200,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
         uint64_t n_pos = 0;
         float ms = 0;
         int fmt = 8, pbits = 32;
+        dp_kindex_geom geom;
         dp_kindex_shard shard;
         if (sharded) {
             shard.rank = dp_comm_rank(ow->kx_comm);
@@ -205,7 +208,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
         }
         int rc = pre != DP_OK ? pre
                               : dp_kindex_build_sorted(ctx, ow, k, (uint32_t*)d_cnt, (uint64_t*)ix->off.p, &d_pos, &d_pos_hi, &fmt, &pbits, &n_pos, &ms,
-                                                       sharded ? &shard : nullptr);
+                                                       &geom, sharded ? &shard : nullptr);
         if (sharded) {
             // the ranks agree on how it went before anybody waits in a collective for a rank that fell back
             const uint8_t mine = (uint8_t)(rc == 0 ? 0 : rc > 0 ? 1 : 2);
@@ -233,7 +236,7 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
                 // rank FAILED, falls back alike; the rank without room scans, as it would have without a communicator)
                 rc = worst == 2 && rc >= 0 ? 1 : rc;
                 if (rc >= 0 && pre == DP_OK)
-                    rc = dp_kindex_build_sorted(ctx, ow, k, (uint32_t*)d_cnt, (uint64_t*)ix->off.p, &d_pos, &d_pos_hi, &fmt, &pbits, &n_pos, &ms, nullptr);
+                    rc = dp_kindex_build_sorted(ctx, ow, k, (uint32_t*)d_cnt, (uint64_t*)ix->off.p, &d_pos, &d_pos_hi, &fmt, &pbits, &n_pos, &ms, &geom, nullptr);
             }
             if (pre == 1 && rc >= 0) {
                 ix->unavailable = true;
@@ -253,6 +256,8 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
             ix->pos_hi.cap = d_pos_hi ? n_pos + 64 : 0;
             ix->pos_fmt = fmt;
             ix->pbits = pbits;
+            ix->sorted = true;
+            ix->geom = geom;
             ix->n_pos = n_pos;
             ix->built = true;
             ix->build_ms = ms;
@@ -301,6 +306,8 @@ int dp_kindex_ensure(dp_ctx* ctx, int k) {
     if (dev_reserve(ctx, ix->pos, total * 8 + 64)) return DP_ERR_HIP;
     ix->pos_fmt = 8;
     ix->pbits = 32;
+    ix->sorted = false;
+    ix->geom = dp_kindex_geom{};
     DP_HIP(hipMemsetAsync(d_counts, 0, nk * 4, ctx->stream));
     if (ow->n_reads)
         hipLaunchKernelGGL(kidx_scatter_kernel, dim3(2048), dim3(256), 0, ctx->stream, (const uint8_t*)ow->d_packed.p,
@@ -351,6 +358,58 @@ extern "C" int dp_kindex_digest(dp_ctx* ctx, int k, uint64_t* out) {
     DP_HIP(dp_stream_sync(ctx));
     out[0] = ix->n_pos;
     dp_dev_free(d);
+    return DP_OK;
+}
+
+// every entry as read << 32 | position, through the readers the rounds use.  phase < 0: kx_entry(i), a thread per entry.  phase 0..3:
+// thread t reads the four entries from phase + 4t with kx_entry4 (what lies beyond n_pos is masked, as the walks mask what lies beyond
+// their stretch), the entries in front of `phase` come from kx_entry: the four phases are the four alignments of format 5's byte stream
+__global__ __launch_bounds__(256) void kidx_dump_kernel(const KxPos pos, uint64_t n_pos, int phase, uint64_t* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (phase < 0) {
+        if (t < n_pos) out[t] = kx_entry(pos, t);
+        return;
+    }
+    if (t < (uint64_t)phase && t < n_pos) out[t] = kx_entry(pos, t);
+    const uint64_t i = (uint64_t)phase + 4 * t;
+    if (i >= n_pos) return;
+    uint64_t e[4];
+    kx_entry4(pos, i, e);
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+        if (i + (uint64_t)u < n_pos) out[i + u] = e[u];
+}
+extern "C" int dp_kindex_dump(dp_ctx* ctx, int k, int phase, uint64_t* info, uint64_t* off, uint64_t* entries, uint32_t* counts) {
+    if (!ctx || !info || phase < -1 || phase > 3) return DP_ERR_ARG;
+    dp_ctx* ow = kidx_owner(ctx);
+    dp_kindex* ix = ow->kidx;
+    if (!ix) return dp_fail(ctx, DP_ERR_STATE, "dp_kindex_dump: no index built for this k");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (!ix->built || ix->k != k) return dp_fail(ctx, DP_ERR_STATE, "dp_kindex_dump: no index built for this k");
+    hipSetDevice(ctx->device);
+    const uint64_t nk = (uint64_t)1 << (2 * k);
+    const bool have_counts = ow->d_kcounts && ow->kcounts_k == k;
+    const uint64_t head[DP_KINDEX_DUMP_INFO] = {ix->n_pos, (uint64_t)ix->pos_fmt, (uint64_t)ix->pbits, ix->sorted ? 1u : 0u, (uint64_t)ix->geom.b1,
+                                                (uint64_t)ix->geom.b2, (uint64_t)ix->geom.r, (uint64_t)ix->geom.rbits, have_counts ? 1u : 0u};
+    memcpy(info, head, sizeof(head));
+    if (off) DP_HIP(hipMemcpyAsync(off, ix->off.p, (nk + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts && have_counts) DP_HIP(hipMemcpyAsync(counts, ow->d_kcounts, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    void* d = nullptr;
+    if (entries && ix->n_pos) {
+        DP_HIP(dp_dev_malloc(&d, ix->n_pos * 8));
+        const uint64_t threads = phase < 0 ? ix->n_pos : (ix->n_pos + 3) / 4 + 4;
+        hipLaunchKernelGGL(kidx_dump_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, ix->view(), ix->n_pos, phase, (uint64_t*)d);
+        int rc = hipGetLastError() == hipSuccess ? DP_OK : dp_fail(ctx, DP_ERR_HIP, "kidx_dump_kernel");
+        if (rc == DP_OK && hipMemcpyAsync(entries, d, ix->n_pos * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            rc = dp_fail(ctx, DP_ERR_HIP, "dp_kindex_dump: copy of the entries");
+        if (rc != DP_OK) {
+            dp_dev_free(d);
+            return rc;
+        }
+    }
+    const hipError_t e = dp_stream_sync(ctx);
+    if (d) dp_dev_free(d);
+    DP_HIP(e);
     return DP_OK;
 }
 

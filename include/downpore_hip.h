@@ -584,6 +584,15 @@ DP_API int dp_kindex_set_comm(dp_ctx* ctx, dp_comm* comm);
  * mix(k-mer, bucket start), out[2] = sum over the entries of mix(k-mer of the entry's bucket, read, position).  Two builds of the same
  * reads agree on all three whatever the order of the entries inside a bucket. */
 DP_API int dp_kindex_digest(dp_ctx* ctx, int k, uint64_t* out /* [3] */);
+/* Test hook: the resident index of `ctx` (built for k) copied out, for a comparison with a plain reference (tests only).
+ * info[DP_KINDEX_DUMP_INFO] = entries, entry format (4 / 5 / 8), position bits, 1 where the radix build made the index and 0 where
+ * the atomic scatter did, the radix build's widths b1, b2, r and its read-id bits (0 after the atomic scatter), 1 where the k-mer
+ * histogram of this k is on the context.  off[4^k + 1] = the bucket starts; entries[info[0]] = every entry as read << 32 | position,
+ * read by the rounds' own readers: phase -1 one entry at a time, phase 0 .. 3 four at a time starting from entry `phase` (the four
+ * alignments of format 5's byte stream); counts[4^k] = the histogram, written only where info[8] is 1.  off, entries and counts may
+ * each be NULL: a first call learns the sizes. */
+#define DP_KINDEX_DUMP_INFO 9
+DP_API int dp_kindex_dump(dp_ctx* ctx, int k, int phase, uint64_t* info, uint64_t* off, uint64_t* entries, uint32_t* counts);
 /* Gather of one variable-size byte string per rank to rank `root` only: the PAF text of the round-parallel layout's rounds, which only
  * the rank that prints needs (finalCheckWorker's fmt.Print, commands/overlap.go:225-228, happens in one process; at 8 ranks every rank
  * otherwise receives and copies all 235 MB of a config-2 job's text).  sizes[n_ranks] = every rank's length, the same array on every
