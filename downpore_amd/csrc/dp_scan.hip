@@ -1176,6 +1176,155 @@ extern "C" int dp_reads_upload_packed_rc(dp_ctx* ctx, const uint8_t* packed, con
     return DP_OK;
 }
 
+// ---- dp_reads_respan with the layout of dp_reads_upload_rc (`map` with the trim in front: the trimmed reads are cut from the resident raw
+// ones and their reverse strands made in the same pass).  repack_spans_rc_kernel: one thread per output dword.  Device read lo is span
+// lo below first_paired, span first_paired + (lo - first_paired) / 2 from there on, the odd ones of those reverse-complemented.  A forward
+// dword is made as in repack_spans_kernel.  The 16 bases of a reverse dword are the span's bases t .. t + 15 with t = len - 16 - base0
+// (t < 0: the window hangs over the span's start and only bases 0 .. 15 + t exist): they begin (start + max(t, 0)) % 16 bases into a
+// source dword and end in the next one at most, so the byte-swapped pair is one 64-bit funnel; its top 16 bases are shifted right by the
+// overhang, reversed and complemented as in place_packed_kernel, and the bases beyond the span's end masked.  The second source dword is
+// loaded only when a base that is wanted lies in it - never past the source read's own padded end.
+__global__ void repack_spans_rc_kernel(const uint32_t* __restrict__ src, const uint64_t* __restrict__ sboff, const dp_read_span* __restrict__ spans,
+                                       const uint64_t* __restrict__ boff, uint32_t n_reads, uint32_t first_paired, uint32_t* __restrict__ packed,
+                                       uint64_t n_dwords) {
+    const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_dwords) return;
+    const uint64_t byte = d * 4;
+    uint32_t lo = 0, hi = n_reads;  // binary search: last device read with boff[r] <= byte
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (boff[mid] <= byte) lo = mid;
+        else hi = mid;
+    }
+    const bool rc = lo >= first_paired && ((lo - first_paired) & 1u) != 0;
+    const dp_read_span sp = spans[lo < first_paired ? lo : first_paired + ((lo - first_paired) >> 1)];
+    const uint64_t base0 = (byte - boff[lo]) * 4;
+    uint32_t out = 0;
+    if (base0 < sp.len) {
+        const uint32_t nb = (uint32_t)(sp.len - base0 < 16 ? sp.len - base0 : 16);  // bases of this dword
+        const uint32_t over = 16 - nb;                                              // reverse strand: the window's overhang, -t
+        const uint32_t first = rc ? sp.len - (uint32_t)base0 - nb : (uint32_t)base0;  // first span base wanted: max(t, 0) | base0
+        const uint32_t p = sp.start + first, sh = p & 15u;
+        const uint32_t* w = src + sboff[sp.read] / 4 + (p >> 4);
+        uint64_t v = (uint64_t)__builtin_bswap32(w[0]) << 32;
+        if (sh + nb > 16) v |= __builtin_bswap32(w[1]);
+        uint32_t be = (uint32_t)((v << (2 * sh)) >> 32);  // span bases first .. first + 15, the first on top
+        if (!rc) {
+            if (nb < 16) be &= ~0u << (2 * over);
+        } else {
+            if (nb < 16) be >>= 2 * over;  // ... bases 0 .. nb - 1 at the bottom, nothing above them
+            be = __builtin_bswap32(be);
+            be = ((be & 0x0f0f0f0fu) << 4) | ((be >> 4) & 0x0f0f0f0fu);
+            be = ((be & 0x33333333u) << 2) | ((be >> 2) & 0x33333333u);  // base order reversed: span base len - 1 - base0 on top
+            be = ~be;
+            if (nb < 16) be &= ~0u << (2 * over);  // bases beyond the span's end
+        }
+        out = __builtin_bswap32(be);
+    }
+    packed[d] = out;
+}
+
+// What dp_reads_respan does, with every output read r >= first_paired stored as the pair (forward, reverse complement).  Unlike
+// dp_reads_respan it does not mind a value table on the context: `map` makes the reference's table before its reads arrive, and
+// dp_reads_upload_rc leaves it in place too.  A k-mer histogram goes as it does there.
+extern "C" int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out, uint32_t first_paired) {
+    if (!ctx || (n_out && !spans)) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan_rc: bad arguments") : DP_ERR_ARG;
+    if (first_paired > n_out) {
+        const std::string msg = "dp_reads_respan_rc: first_paired " + std::to_string(first_paired) + " is beyond the " + std::to_string(n_out) + " spans";
+        return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+    }
+    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_rc on a context that borrows its reads");
+    if (ctx->n_borrowers.load() > 0) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_rc while contexts borrowing these reads exist");
+    {
+        std::lock_guard<std::mutex> lk(ctx->upload_mu);
+        if (ctx->upload) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_rc while an upload of dp_reads_upload_rc_begin is pending");
+    }
+    if (ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_rc after dp_round_begin: a round has been made on these reads");
+    if (ctx->kidx) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_rc after a k-mer position index has been made of these reads");
+    const uint64_t nd64 = (uint64_t)first_paired + 2ull * (n_out - first_paired);
+    if (nd64 > 0x7fffffffull) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan_rc: too many reads (more than 2147483647 with the reverse strands)");
+    const uint32_t n_dev = (uint32_t)nd64;
+    std::vector<uint64_t> h_boff((size_t)n_dev + 1, 0);
+    std::vector<uint32_t> h_len(n_dev, 0);
+    uint64_t pos = 0, total = 0;
+    for (uint32_t r = 0, d = 0; r < n_out; r++) {
+        const dp_read_span& sp = spans[r];
+        if (sp.read >= ctx->n_reads || (uint64_t)sp.start + sp.len > ctx->h_len[sp.read]) {
+            const std::string msg = "dp_reads_respan_rc: span " + std::to_string(r) + " lies outside its read";
+            return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+        }
+        for (int strand = 0; strand < (r < first_paired ? 1 : 2); strand++, d++) {
+            h_boff[d] = pos;
+            h_len[d] = sp.len;
+            pos += ((uint64_t)(sp.len + 3) / 4 + 15) & ~(uint64_t)15;
+            total += sp.len;
+        }
+    }
+    h_boff[n_dev] = pos;
+    hipSetDevice(ctx->device);
+    // both sets side by side: the new blocks are made, filled from the old ones, and only then take their place
+    DevBuf nb[3];
+    const size_t need[3] = {(size_t)pos + 64, ((size_t)n_dev + 1) * 8, (size_t)n_dev * 4 + 4};
+    void* d_spans = nullptr;
+    auto drop = [&] {
+        hipStreamSynchronize(ctx->stream);
+        for (DevBuf& b : nb)
+            if (b.p) dp_dev_free(b.p);
+        if (d_spans) dp_dev_free(d_spans);
+    };
+#define RS_HIP(call)                                                      \
+    do {                                                                  \
+        const hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) {                                           \
+            drop();                                                       \
+            return dp_fail(ctx, DP_ERR_HIP, "dp_reads_respan_rc: " #call, e_); \
+        }                                                                 \
+    } while (0)
+    for (int i = 0; i < 3; i++) {
+        nb[i].cap = (need[i] + 255) & ~(size_t)255;
+        RS_HIP(dp_dev_malloc(&nb[i].p, nb[i].cap));
+    }
+    RS_HIP(hipMemcpyAsync(nb[1].p, h_boff.data(), ((size_t)n_dev + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_dev) RS_HIP(hipMemcpyAsync(nb[2].p, h_len.data(), (size_t)n_dev * 4, hipMemcpyHostToDevice, ctx->stream));
+    RS_HIP(hipMemsetAsync((uint8_t*)nb[0].p + pos, 0, 64, ctx->stream));
+    if (pos) {
+        RS_HIP(dp_dev_malloc(&d_spans, (size_t)n_out * sizeof(dp_read_span)));
+        RS_HIP(hipMemcpyAsync(d_spans, spans, (size_t)n_out * sizeof(dp_read_span), hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t n_dwords = pos / 4;
+        hipLaunchKernelGGL(repack_spans_rc_kernel, dim3((uint32_t)((n_dwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_packed.p,
+                           (const uint64_t*)ctx->d_boff.p, (const dp_read_span*)d_spans, (const uint64_t*)nb[1].p, n_dev, first_paired, (uint32_t*)nb[0].p,
+                           n_dwords);
+        RS_HIP(hipGetLastError());
+    }
+    RS_HIP(dp_stream_sync(ctx));
+#undef RS_HIP
+    if (d_spans) dp_dev_free(d_spans);
+    DevBuf* res[3] = {&ctx->d_packed, &ctx->d_boff, &ctx->d_len};
+    for (int i = 0; i < 3; i++) {
+        if (res[i]->p) dp_dev_free(res[i]->p);  // (back to the block cache)
+        *res[i] = nb[i];
+    }
+    for (DevBuf* qb : {&ctx->d_qual, &ctx->d_qualoff, &ctx->d_hasq})  // the old set's quality bytes are void
+        if (qb->p) {
+            dp_dev_free(qb->p);
+            qb->p = nullptr;
+            qb->cap = 0;
+        }
+    if (ctx->d_kcounts) {  // ... and so is its k-mer histogram (the value table stays, as dp_reads_upload_rc leaves it)
+        dp_dev_free(ctx->d_kcounts);
+        ctx->d_kcounts = nullptr;
+        ctx->kcounts_k = 0;
+    }
+    ctx->n_reads = n_dev;
+    ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
+    ctx->items_ptr = nullptr;
+    ctx->h_boff.swap(h_boff);
+    ctx->h_len.swap(h_len);
+    ctx->packed_bytes = pos;
+    ctx->total_bases = total;
+    return DP_OK;
+}
+
 // ---- a read set that travels while its first reads are already worked on (round 5: `map` maps read 0 while read 40 000 is on the link)
 struct dp_ctx::ReadsUpload {
     std::thread th;

@@ -778,8 +778,13 @@ struct MapStats {
 // Runs the whole command on HIP device `device`: reference = first sequence of refSet (top-level, cache=false; every sequence of it
 // with p.allSequences), reads top-level.  paf receives the PAF lines (read order), errText the reference's stderr lines.
 size_t releaseMapStaging();  // dph_release_caches: the staging block kept for the process's next map command
+// trim (dph_map_run_trim): `reads` is the raw read set (loaded with trim's minimum length); it goes up once, packed and unpaired, in front of
+// the reference sequences and join chunks, runTrim runs on that resident copy, trimmedReadSet (minimum length p.minLength) gives the
+// set that is mapped, and one dp_reads_respan_rc puts the device set into map's order with the reverse strands.  Forward declared: the
+// trim's types follow below.
+struct MapTrim;
 int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
-           MapStats* stats, std::string& error);
+           MapStats* stats, std::string& error, MapTrim* trim = nullptr);
 
 // ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------
 struct TrimParams {  // flag table commands/trim.go:17-20
@@ -846,6 +851,13 @@ int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const Tri
 // the read set `downpore trim`'s output gives when it is read back with minimum length minLen - without writing it - and the span of
 // `raw` (the reads the trim ran on) behind each of its records; pure host code
 void trimmedReadSet(const ReadSet& raw, const TrimResult& res, i64 minLen, bool himem, ReadSet& out, std::vector<dp_read_span>& spans);
+// what runMap needs to trim first: the raw reads (runTrim writes their ignore flags and trims), the adapters, and where the results go
+struct MapTrim {
+    ReadSet* raw = nullptr;
+    const ReadSet *front = nullptr, *back = nullptr;
+    TrimParams params;
+    TrimResult* res = nullptr;  // the trim run's log (no "Writing" line), table and stats
+};
 // the middle stage's matching results: seedCounts[planned chunks] and the matches, in any order
 struct TrimMidInput {
     const int32_t* seedCounts = nullptr;

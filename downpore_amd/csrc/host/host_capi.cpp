@@ -637,21 +637,21 @@ struct MapH {
     MapStats st;
 };
 }  // namespace
-extern "C" void* dph_map_run_ex(void* refH, void* readsH, const int64_t* params, int n_params, int device) {
-    if (!refH || !readsH || !params || n_params < 6 || n_params > 8) {
-        g_err = "dph_map_run_ex: bad arguments (6, 7 or 8 parameters)";
-        return nullptr;
+namespace {
+// the parameter block of dph_map_run_ex and dph_map_run_trim (6, 7 or 8 values); false with g_err set, before any device call
+bool mapParamsFrom(const char* who, bool handles, const int64_t* params, int n_params, MapParams& p) {
+    if (!handles || !params || n_params < 6 || n_params > 8) {
+        g_err = std::string(who) + ": bad arguments (6, 7 or 8 parameters)";
+        return false;
     }
-    if (n_params >= 7 && (params[6] < 0 || params[6] > 2)) {  // (refused before any device call)
-        g_err = "dph_map_run_ex: index layout " + std::to_string((long long)params[6]) + " (0 = auto, 1 = dense, 2 = sparse)";
-        return nullptr;
+    if (n_params >= 7 && (params[6] < 0 || params[6] > 2)) {
+        g_err = std::string(who) + ": index layout " + std::to_string((long long)params[6]) + " (0 = auto, 1 = dense, 2 = sparse)";
+        return false;
     }
     if (n_params == 8 && params[7] != 0 && params[7] != 1) {
-        g_err = "dph_map_run_ex: all sequences " + std::to_string((long long)params[7]) + " (0 = the first sequence of the reference, 1 = all of them)";
-        return nullptr;
+        g_err = std::string(who) + ": all sequences " + std::to_string((long long)params[7]) + " (0 = the first sequence of the reference, 1 = all of them)";
+        return false;
     }
-    MapH* h = new MapH();
-    MapParams p;
     p.indexLayout = n_params >= 7 ? (int)params[6] : 0;
     p.allSequences = n_params == 8 && params[7] == 1;
     p.circular = params[0] != 0;
@@ -660,6 +660,13 @@ extern "C" void* dph_map_run_ex(void* refH, void* readsH, const int64_t* params,
     p.minLength = params[3];
     p.chunkSize = params[4];
     p.seedRate = params[5];
+    return true;
+}
+}  // namespace
+extern "C" void* dph_map_run_ex(void* refH, void* readsH, const int64_t* params, int n_params, int device) {
+    MapParams p;
+    if (!mapParamsFrom("dph_map_run_ex", refH && readsH, params, n_params, p)) return nullptr;
+    MapH* h = new MapH();
     std::string error;
     int rc = runMap(((ReadsH*)refH)->set, ((ReadsH*)readsH)->set, p, device, h->paf, h->err, &h->st, error);
     if (rc != 0) {
@@ -901,6 +908,36 @@ extern "C" void* dph_overlap_open_trim(void* reads, void* front, void* back, con
 extern "C" void* dph_overlap_reads(void* hh) {
     OverlapH* h = (OverlapH*)hh;
     return h->trimmed;
+}
+// `map` with the trim in front: the raw reads go up once, packed; the trim runs on the resident copy; the trimmed read set (minimum length
+// params[3]) is cut from it on the device with its reverse strands, and the run goes on as dph_map_run_ex does on that set.  *trim_out: the
+// trim run's handle, as dph_overlap_open_trim gives it.
+extern "C" void* dph_map_run_trim(void* refH, void* readsH, void* frontH, void* backH, const int64_t* trim_params, int n_trim, const int64_t* params,
+                                  int n_params, int device, void** trim_out) {
+    if (trim_out) *trim_out = nullptr;
+    MapTrim mt;
+    if (!refH || !readsH || !frontH || !backH || !trim_out || !trimParamsFrom(trim_params, n_trim, mt.params)) {
+        g_err = "dph_map_run_trim: bad arguments (8 trim parameters, or 14 with the middle stage's)";
+        return nullptr;
+    }
+    MapParams p;
+    if (!mapParamsFrom("dph_map_run_trim", true, params, n_params, p)) return nullptr;
+    MapH* h = new MapH();
+    TrimH* th = new TrimH();
+    th->reads = &((ReadsH*)readsH)->set;
+    mt.raw = th->reads;
+    mt.front = &((ReadsH*)frontH)->set;
+    mt.back = &((ReadsH*)backH)->set;
+    mt.res = &th->res;
+    std::string error;
+    if (runMap(((ReadsH*)refH)->set, *mt.raw, p, device, h->paf, h->err, &h->st, error, &mt) != 0) {
+        g_err = error;
+        delete h;
+        delete th;
+        return nullptr;
+    }
+    *trim_out = th;
+    return h;
 }
 extern "C" const char* dph_trim_output(void* h, int64_t* n) {
     *n = (int64_t)((TrimH*)h)->res.out.size();

@@ -579,8 +579,12 @@ size_t releaseMapStaging() {
     return freed;
 }
 
-int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
-           MapStats* stats, std::string& error) {
+int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int device, std::string& paf, std::string& errText,
+           MapStats* stats, std::string& error, MapTrim* trim) {
+    // upSet: the reads that go up.  Without a trim they are the reads that are mapped; with one they are the raw reads, and the set
+    // that is mapped is made from them once the trim has run on the device's copy
+    ReadSet trimmedSet;
+    const ReadSet& reads = trim ? trimmedSet : upSet;
     const double tRun0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     const bool prof = dp_profile_on();
     double tMark = tRun0;
@@ -626,6 +630,10 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             return DP_ERR_ARG;
         }
     }
+    if (trim) {  // what the trim refuses about its adapters and k, refused before anything is packed or allocated on the device
+        TrimIndex ix;
+        if (!trimBuildIndex(*trim->front, *trim->back, trim->params.k, ix, error)) return DP_ERR_ARG;
+    }
     if (p.indexLayout < 0 || p.indexLayout > 2) {
         error = "map: reference index layout " + std::to_string(p.indexLayout) + " (0 = auto, 1 = dense, 2 = sparse)";
         return DP_ERR_ARG;
@@ -657,13 +665,17 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     size_t head = 0;
     for (size_t c = 0; c < T; c++) head += (size_t)refLens[c];
     for (const std::string& j : joins) head += j.size();
-    const size_t readBytes = reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
+    const size_t readBytes = !trim && reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
     // Round 6: the reads cross PCIe the way the reference holds them - 2 bits per base (sequence.packedSequence) - packed here by
     // the worker pool straight into a pinned block in the device's own layout (every read on a 16-byte boundary) and put in place by
     // dp_reads_upload_packed_rc, which also makes the reverse strands: 100 MB instead of 400 at config 3, one copy instead of three
     // (staging, pinned ring, link).  DP_TUNE=map_ascii_upload=1: the ASCII path below, as before (it is what map_async_upload uses).
-    const bool asyncUpload = dp_tune("map_async_upload", 0) != 0;
-    const bool packedUpload = !asyncUpload && !dp_tune("map_ascii_upload", 0);
+    // With a trim the packed path is the only one and neither key is consulted: the device set is then [raw reads | reference sequences
+    // | join chunks] without pairs, so that the trim's id lists and spans name raw read r as device read r, and dp_reads_respan_rc
+    // makes map's order and the reverse strands from it afterwards.
+    const bool asyncUpload = !trim && dp_tune("map_async_upload", 0) != 0;
+    const bool packedUpload = trim || (!asyncUpload && !dp_tune("map_ascii_upload", 0));
+    const size_t headAt = trim ? upSet.size() : 0, readsAt = trim ? 0 : (size_t)firstPaired;  // device ids of the first sequence / read as uploaded
     const bool packScalar = dp_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
     std::vector<uint32_t> plens;
     std::vector<uint64_t> poff;
@@ -675,12 +687,12 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
         }
     } pinnedBack{pinned};
     if (packedUpload) {
-        const size_t n = firstPaired + reads.size();
+        const size_t n = firstPaired + upSet.size();
         plens.resize(n);
         poff.assign(n + 1, 0);
-        for (size_t c = 0; c < T; c++) plens[c] = (uint32_t)refLens[c];
-        for (size_t j = 0; j < joins.size(); j++) plens[T + j] = (uint32_t)joins[j].size();
-        for (size_t r = 0; r < reads.size(); r++) plens[firstPaired + r] = (uint32_t)reads.length(r);
+        for (size_t c = 0; c < T; c++) plens[headAt + c] = (uint32_t)refLens[c];
+        for (size_t j = 0; j < joins.size(); j++) plens[headAt + T + j] = (uint32_t)joins[j].size();
+        for (size_t r = 0; r < upSet.size(); r++) plens[readsAt + r] = (uint32_t)upSet.length(r);
         for (size_t r = 0; r < n; r++) poff[r + 1] = poff[r] + ((((uint64_t)plens[r] + 3) / 4 + 15) & ~(uint64_t)15);
         pinned = (uint8_t*)dp_host_alloc((size_t)poff[n] + 64);
         if (!pinned) {
@@ -692,21 +704,21 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
     std::unique_ptr<char[]> staging = packedUpload ? std::unique_ptr<char[]>() : stagingTake(head + readBytes + 1, &stagingCap);
     std::thread concatThread([&] {
         if (packedUpload) {
-            for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned + poff[c], packScalar);
-            for (size_t j = 0; j < joins.size(); j++) packBases(joins[j].data(), joins[j].size(), pinned + poff[T + j], packScalar);
+            for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned + poff[headAt + c], packScalar);
+            for (size_t j = 0; j < joins.size(); j++) packBases(joins[j].data(), joins[j].size(), pinned + poff[headAt + T + j], packScalar);
             // pieces of about 2 M bases: whole reads
             std::vector<size_t> cut(1, 0);
             i64 acc = 0;
-            for (size_t r = 0; r < reads.size(); r++) {
-                acc += reads.length(r);
+            for (size_t r = 0; r < upSet.size(); r++) {
+                acc += upSet.length(r);
                 if (acc >= ((i64)2 << 20)) {
                     cut.push_back(r + 1);
                     acc = 0;
                 }
             }
-            if (cut.back() != reads.size()) cut.push_back(reads.size());
+            if (cut.back() != upSet.size()) cut.push_back(upSet.size());
             parallelFor(cut.size() - 1, [&](size_t i) {
-                for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(reads.seq(r), (size_t)reads.length(r), pinned + poff[firstPaired + r], packScalar);
+                for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(upSet.seq(r), (size_t)upSet.length(r), pinned + poff[readsAt + r], packScalar);
             });
             return;
         }
@@ -855,6 +867,12 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             if (t.joinable()) t.join();
         }
     } seedJoin{seedThread};
+    // ... and a way out that destroys the context joins it first: with device seeds the thread walks ssb's arrays, which are host memory of
+    // the context
+    auto failJoined = [&](int rc2) {
+        if (seedThread.joinable()) seedThread.join();
+        return fail(rc2);
+    };
     // device ids: 0 reference, 1 join chunk, then (forward, reverse complement) per read; the reverse strands are made
     // on the device
     concatThread.join();
@@ -876,11 +894,34 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
             if (st) stagingPut(std::move(st), cap);
         }
     } stagingBack{ctx, staging, stagingCap};
-    rc = packedUpload  ? dp_reads_upload_packed_rc(ctx, pinned, plens.data(), (uint32_t)plens.size(), firstPaired)
+    rc = packedUpload  ? dp_reads_upload_packed_rc(ctx, pinned, plens.data(), (uint32_t)plens.size(), trim ? (uint32_t)plens.size() : firstPaired)
          : asyncUpload ? dp_reads_upload_rc_begin(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired, firstPaired)
                        : dp_reads_upload_rc(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired);
-    if (rc) return fail(rc);
-    mark(packedUpload ? "packed upload + reverse strands" : asyncUpload ? "upload begun (reference packed)" : "upload + pack (both strands)");
+    if (rc) return failJoined(rc);
+    mark(trim ? "packed upload (raw reads)" : packedUpload ? "packed upload + reverse strands" : asyncUpload ? "upload begun (reference packed)" : "upload + pack (both strands)");
+    if (trim) {
+        // ---- the trim on the device's copy, the trimmed read set on the host, and the device set cut and paired from the raw one: the
+        // reference sequences and join chunks first, whole and unpaired, then every trimmed read with its reverse strand
+        std::string trimError;
+        if (runTrim(*trim->raw, *trim->front, *trim->back, trim->params, device, *trim->res, trimError, ctx) != 0) {
+            if (seedThread.joinable()) seedThread.join();  // (it reads memory of the context)
+            error = trimError;
+            dp_ctx_destroy(ctx), ctx = nullptr;
+            return -1;
+        }
+        mark("trim on resident reads");
+        std::vector<dp_read_span> cut;
+        trimmedReadSet(*trim->raw, *trim->res, p.minLength, trim->raw->himem, trimmedSet, cut);
+        mark("trimmed read set");
+        std::vector<dp_read_span> order;
+        order.reserve((size_t)firstPaired + cut.size());
+        for (size_t c = 0; c < T; c++) order.push_back(dp_read_span{(uint32_t)(headAt + c), 0u, (uint32_t)refLens[c]});
+        for (size_t j = 0; j < joins.size(); j++) order.push_back(dp_read_span{(uint32_t)(headAt + T + j), 0u, (uint32_t)joins[j].size()});
+        order.insert(order.end(), cut.begin(), cut.end());
+        rc = dp_reads_respan_rc(ctx, order.data(), (uint32_t)order.size(), firstPaired);
+        if (rc) return failJoined(rc);
+        mark("respan + reverse strands");
+    }
     seedThread.join();
     mark("AddSingleSeeds (waited for)");
     // ---- chunk schedule mapping.go:79-96, canonical generation order; sequence after sequence, the chunk ids running on

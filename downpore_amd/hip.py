@@ -97,7 +97,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_kindex_dump", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
-           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan",
+           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan", "dp_reads_respan_rc",
            "dp_debug_chain_paths"]
 
 _lib = None
@@ -237,6 +237,16 @@ class Context:
         self.L.dp_reads_respan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         self._chk(self.L.dp_reads_respan(self.h, sp.ctypes.data if len(sp) else None, len(sp)))
         self.read_len = sp[:, 2].astype(np.int64)
+
+    def respan_rc(self, spans, first_paired):
+        """dp_reads_respan_rc: respan with the layout of upload_reads_rc - spans >= first_paired are stored as (forward, reverse
+        complement) pairs, the second strand made on the device.  A value table on the context is no reason to refuse (DpError for a
+        round, a k-mer position index, borrowed or lent reads, a pending upload, a span outside its read, first_paired > n)."""
+        sp = np.ascontiguousarray(spans, dtype=np.uint32).reshape(-1, 3)
+        self.L.dp_reads_respan_rc.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        self._chk(self.L.dp_reads_respan_rc(self.h, sp.ctypes.data if len(sp) else None, len(sp), first_paired))
+        ln = sp[:, 2].astype(np.int64)
+        self.read_len = np.concatenate([ln[:first_paired], np.repeat(ln[first_paired:], 2)])
 
     # ---- A22
     def kmer_histogram(self, k):

@@ -23,15 +23,41 @@ def index_layout_code(index):
     raise DpError("map_reads: index must be 'auto', 'dense' or 'sparse' (0, 1, 2), not %r" % (index,))
 
 
+def _trim_block(trim):
+    """map_reads' trim=dict(front=Reads, back=Reads, **keyword arguments of trim_params) -> (front, back, parameter block); a missing
+    front / back or an unknown key raises DpError before any library call."""
+    import inspect
+
+    from . import trim as T
+    if not isinstance(trim, dict):
+        raise DpError("map_reads: trim must be a dict(front=Reads, back=Reads, ...), not %r" % (type(trim).__name__,))
+    kw = dict(trim)
+    missing = [key for key in ("front", "back") if kw.get(key) is None]
+    if missing:
+        raise DpError("map_reads: trim lacks %s (the adapter files as Reads loaded with min_len=0)" % " and ".join(repr(m) for m in missing))
+    front, back = kw.pop("front"), kw.pop("back")
+    known = list(inspect.signature(T.trim_params).parameters)
+    unknown = sorted(key for key in kw if key not in known)
+    if unknown:
+        raise DpError("map_reads: unknown trim key %s (known: front, back, %s)" % (", ".join(repr(u) for u in unknown), ", ".join(known)))
+    return front, back, T.trim_params(**kw)
+
+
 def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
-              index="auto", all_sequences=False):
+              index="auto", all_sequences=False, trim=None):
     """ref / reads: downpore_amd.overlap.Reads (reference loaded with min_len=0, reads with min_len=min_length; both are
     treated as top-level sequences exactly like commands/map.go does).  index: the reference index's layout ("auto" takes the
     sparse one when the dense one would not fit the device; both give the same PAF).  all_sequences: map against every sequence of
     ref (one seed index and one chunk index over all of them; a PAF line names the sequence it lies on), not the first one only.
+    trim: dict(front=Reads, back=Reads, **keyword arguments of trim_reads) = `downpore trim` first, on the reads the device holds
+    anyway (dph_map_run_trim): `reads` (then loaded with min_len=50, as `trim` loads them) go up once, 2-bit packed, both trim stages
+    run on the resident copy, and the reads that are mapped are cut from it on the device with their reverse strands - the PAF is
+    that of map_reads(ref, trim_reads(reads, ...).reads(min_length), ...) without the bases crossing the link again.  The trim runs
+    on `device`; stats["trim"] is its TrimResult (no output text; keep `reads` alive while it is in use).
     Returns (paf, stderr_text, stats);
     stats["index"] describes the index (MAP_INDEX_FIELDS, layout "dense" / "sparse")."""
     layout = index_layout_code(index)
+    trim_block = None if trim is None else _trim_block(trim)
     H = load_host()
     H.dph_map_run_ex.restype = C.c_void_p
     H.dph_map_run_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
@@ -43,9 +69,22 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     H.dph_map_index_info.restype = C.c_int
     H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout, 1 if all_sequences else 0], dtype=np.int64)
-    h = H.dph_map_run_ex(ref.h, reads.h, p.ctypes.data, len(p), device)
-    if not h:
-        raise DpError("dph_map_run: " + H.dph_last_error(None).decode())
+    trim_result = None
+    if trim_block is None:
+        h = H.dph_map_run_ex(ref.h, reads.h, p.ctypes.data, len(p), device)
+        if not h:
+            raise DpError("dph_map_run: " + H.dph_last_error(None).decode())
+    else:
+        from . import trim as T
+        front, back, tp = trim_block
+        H.dph_map_run_trim.restype = C.c_void_p
+        H.dph_map_run_trim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p)]
+        th = C.c_void_p()
+        h = H.dph_map_run_trim(ref.h, reads.h, front.h, back.h, tp.ctypes.data, len(tp), p.ctypes.data, len(p), device, C.byref(th))
+        if not h:
+            raise DpError("dph_map_run_trim: " + H.dph_last_error(None).decode())
+        trim_result = T.TrimResult(T._host(), th)
     n = C.c_int64(0)
     paf = C.string_at(H.dph_map_paf(h, C.byref(n)), n.value).decode()
     err = C.string_at(H.dph_map_errtext(h, C.byref(n)), n.value).decode()
@@ -58,4 +97,6 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     info = dict(zip(MAP_INDEX_FIELDS[:got], (int(v) for v in ix[:got])))
     info["layout"] = {1: "dense", 2: "sparse"}.get(info.get("layout", 0), "none")
     stats["index"] = info
+    if trim_result is not None:
+        stats["trim"] = trim_result
     return paf, err, stats

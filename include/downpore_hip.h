@@ -700,6 +700,18 @@ DP_API int dp_trim_edges_resident(dp_trim* t, dp_ctx* ctx, const uint32_t* reads
 DP_API int dp_trim_scan_chunks_resident(dp_trim* t, dp_ctx* ctx, const dp_read_span* spans, uint32_t n_chunks, uint32_t* n_seeds_out,
                                         double* times_ms);
 DP_API int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out);
+/* dp_reads_respan with the layout of dp_reads_upload_rc (`map` with the trim in front, dph_map_run_trim): output reads r < first_paired
+ * are stored once, every output read r >= first_paired twice - device read first_paired + 2 (r - first_paired) is the span, the next
+ * id its reverse complement (reversed, 3 - code per base), made on the device in the same pass.  Every device read starts on a 16-byte
+ * boundary; bases past a read's end, the padding up to the next read and the 64 slack bytes behind the last read are zero.  n_out = 0
+ * and first_paired = n_out (no pairs) are valid.  What the call does to the context is what dp_reads_respan does.  Refused, each with
+ * a message that starts with the call's name, and with nothing changed: a span outside its read, first_paired > n_out, more than
+ * 2^31 - 1 device reads (DP_ERR_ARG); a context that borrows its reads or lends them, a pending dp_reads_upload_rc_begin, an open
+ * round, a resident k-mer position index (DP_ERR_STATE).
+ * The one difference from dp_reads_respan: a k-mer histogram or a value table on the context is NOT a reason to refuse.  `map` makes
+ * the reference's value table before its reads arrive; dp_reads_upload_rc leaves that table in place and so does this call (the
+ * histogram, which counted the old set, is dropped as dp_reads_upload_rc drops it). */
+DP_API int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out, uint32_t first_paired);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,24 @@ DPH_API void* dph_map_run(void* ref, void* reads, const int64_t* params, int dev
  * bases (the error names it) and 2^32 or more seed windows or chunks in total are refused before anything is allocated; a
  * reference without any chunk leaves every read unmapped.  With one sequence in `ref` the output is that of params[7] = 0. */
 DPH_API void* dph_map_run_ex(void* ref, void* reads, const int64_t* params, int n_params, int device);
+/* dph_map_run_trim   `trim` in front of `map` on one upload.  reads: the raw read set, loaded with trim's minimum length 50; front / back
+ *                    and trim_params[n_trim] (8, or 14 with the middle stage) as dph_trim_run and dph_overlap_open_trim take them;
+ *                    params[n_params] (6, 7 or 8) as dph_map_run_ex takes them.  The PAF of the handle that comes back is byte for
+ *                    byte what dph_map_run_ex gives on the read set `downpore trim` would write for `reads`, read back with minimum
+ *                    length params[3] (dph_trim_reads' rule: a record of n bases is kept iff n + 1 >= min_len and n > 0; the halves of
+ *                    split reads follow the file's reads; names as tagged); dph_map_errtext is map's own text over that set.
+ *                    The bases cross the link once, 2-bit packed: the device read set goes up as [raw reads | reference sequences |
+ *                    join chunks] without pairs, both trim stages run on that copy (ids and spans go up), and one dp_reads_respan_rc
+ *                    makes map's own set from it - reference sequences and join chunks, then (forward, reverse complement) of every
+ *                    trimmed read.  From there the run is dph_map_run_ex's: shards (DP_MAP_SHARDS / DP_MAP_DEVICES), both index
+ *                    layouts, all sequences.  The packed upload is the only one here: DP_TUNE=map_async_upload and
+ *                    DP_TUNE=map_ascii_upload are not consulted.
+ *                    *trim_out receives the trim run's handle, on `device` like the context: its log without the line about writing,
+ *                    table and stats, no output text; dph_trim_reads works on it; dph_trim_free frees it.  The raw read set must
+ *                    outlive it; the run overwrites its ignore flags and trims.  NULL on failure (dph_last_error(NULL)), with
+ *                    *trim_out = NULL and nothing left behind. */
+DPH_API void* dph_map_run_trim(void* ref, void* reads, void* front, void* back, const int64_t* trim_params, int n_trim,
+                               const int64_t* params, int n_params, int device, void** trim_out);
 DPH_API void dph_map_free(void* m);
 DPH_API const char* dph_map_paf(void* m, int64_t* n);
 DPH_API const char* dph_map_errtext(void* m, int64_t* n);

@@ -361,3 +361,57 @@ func RunMap(ref, reads *Reads, p MapParams, device int) (*MapResult, error) {
 	res.ErrText = string(text(pe, n))
 	return res, nil
 }
+
+// TrimParams is the flag table of `downpore trim` (commands/trim.go:17-20); Middle adds the search for adapters in the middle of reads.
+type TrimParams struct {
+	K, CheckReads, AdapterThreshold, ExtraEndTrim        int
+	TagAdapters, RequirePairs, DetermineAdapters         bool
+	Verbosity                                            int
+	Middle                                               bool
+	ChunkSize, MiddleThreshold, ExtraMiddleTrim          int
+	DiscardMiddle                                        bool
+	FlushSeeds                                           int
+}
+
+// RunMapTrim is RunMap with `downpore trim` in front, on one upload (dph_map_run_trim): reads = the raw read set opened with minLen 50,
+// front / back = the adapter files opened with minLen 0.  The reads go up once, packed; the trim runs on the device's copy; the PAF is
+// what RunMap prints for the read set `trim` would write, read back with minLen = p.MinLength.  The second result is the trim's log
+// (without the line about writing).  The parameter blocks and the handle slot live in this frame for the length of the call, and the
+// four read sets are kept from their finalizers until it has returned.
+func RunMapTrim(ref, reads, front, back *Reads, tp TrimParams, p MapParams, device int) (*MapResult, string, error) {
+	b := func(v bool) C.int64_t {
+		if v {
+			return 1
+		}
+		return 0
+	}
+	trim := [14]C.int64_t{C.int64_t(tp.K), C.int64_t(tp.CheckReads), C.int64_t(tp.AdapterThreshold), C.int64_t(tp.ExtraEndTrim), b(tp.TagAdapters),
+		b(tp.RequirePairs), b(tp.DetermineAdapters), C.int64_t(tp.Verbosity), b(tp.Middle), C.int64_t(tp.ChunkSize), C.int64_t(tp.MiddleThreshold),
+		C.int64_t(tp.ExtraMiddleTrim), b(tp.DiscardMiddle), C.int64_t(tp.FlushSeeds)}
+	nTrim := C.int(8)
+	if tp.Middle {
+		nTrim = 14
+	}
+	params := [8]C.int64_t{b(p.Circular), C.int64_t(p.K), C.int64_t(p.QuerySize), C.int64_t(p.MinLength), C.int64_t(p.ChunkSize), C.int64_t(p.SeedRate), 0, b(p.AllSequences)}
+	// (as in RunMap: cgo pins what the pointer arguments point to for the length of the call, and the library keeps none of them)
+	var th unsafe.Pointer
+	h := C.dph_map_run_trim(ref.h, reads.h, front.h, back.h, &trim[0], nTrim, &params[0], 8, C.int(device), &th)
+	runtime.KeepAlive(ref)
+	runtime.KeepAlive(front)
+	runtime.KeepAlive(back)
+	if h == nil {
+		runtime.KeepAlive(reads)
+		return nil, "", lastError(nil, "dph_map_run_trim")
+	}
+	defer C.dph_map_free(h)
+	var n C.int64_t
+	pp := C.dph_map_paf(h, &n)
+	res := &MapResult{PAF: text(pp, n)}
+	pe := C.dph_map_errtext(h, &n)
+	res.ErrText = string(text(pe, n))
+	pl := C.dph_trim_errtext(th, &n)
+	trimLog := string(text(pl, n))
+	C.dph_trim_free(th)
+	runtime.KeepAlive(reads) // (the trim handle points into the raw read set)
+	return res, trimLog, nil
+}
