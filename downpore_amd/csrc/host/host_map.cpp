@@ -14,6 +14,7 @@
 
 #include "dph.hpp"
 #include "host_util.hpp"
+#include "map_plan.hpp"
 
 #define DPH_CORO_IMPLEMENTATION  // (the switch routine itself lives in this translation unit)
 #include "host_coro.hpp"
@@ -66,10 +67,14 @@ struct WindowResult {
 };
 
 struct Task;
-struct Sched;
 
-struct MapperImpl {
-    dp_ctx* ctx = nullptr;
+struct Sched {
+    CoroPoint main;  // the scheduler's own stack while a coroutine runs
+};
+
+// What is the same for every mapper thread: built once by the run and shared const (chunks[i].seg point into chunkSegs, so it is
+// never copied)
+struct MapIndex {
     int k = 11;
     i64 edgeSize = 1000;
     bool circular = true;
@@ -77,8 +82,17 @@ struct MapperImpl {
     std::vector<std::string> refNames;
     std::vector<Chunk> chunks;
     std::vector<int32_t> chunkSegs;  // host copy of the chunk scan
-    Sched* sched = nullptr;
-    std::string err;
+    MapIndex() = default;
+    MapIndex(const MapIndex&) = delete;
+    MapIndex& operator=(const MapIndex&) = delete;
+};
+
+// One thread's mapper: the shared index, the context its windows go to and the scheduler its read tasks switch back to
+struct MapperImpl {
+    const MapIndex& ix;
+    dp_ctx* ctx = nullptr;
+    Sched sched;
+    explicit MapperImpl(const MapIndex& index) : ix(index) {}
 
     bool isConsistent(const Mapping* l, const Mapping* r) const;
     void matchPairs(std::vector<Mapping*>& openA, std::vector<Mapping*>& openB, std::vector<Mapping*>& matched, bool& matchedNil,
@@ -108,16 +122,12 @@ struct Task {
     }
 };
 
-struct Sched {
-    CoroPoint main;  // the scheduler's own stack while a coroutine runs
-};
-
 // first frame of every coroutine: never returns (the last switch leaves it for good)
 void coroTrampoline(void* arg) {
     Task* t = (Task*)arg;
     t->results = t->m->map(*t);
     t->done = true;
-    coroSwitch(t->at, t->m->sched->main, true);
+    coroSwitch(t->at, t->m->sched.main, true);
 }
 
 // ---- mapping.go:131-160
@@ -126,7 +136,7 @@ bool MapperImpl::isConsistent(const Mapping* left, const Mapping* right) const {
     if (left->RC != right->RC) return false;
     const i64 expectedDistance = right->QueryOffset - left->queryLen + left->QueryInset;
     i64 distance = !left->RC ? right->Start - left->End : left->Start - right->End;
-    if (circular && distance < -50) distance += refLens[(size_t)left->ref];
+    if (ix.circular && distance < -50) distance += ix.refLens[(size_t)left->ref];
     if (distance < 50 && expectedDistance < 50 && distance > -50) return true;
     if (distance < 500) return (expectedDistance < (distance * 3) / 2 && expectedDistance > (distance * 2) / 3);
     if (distance > 5000) return (expectedDistance < (distance * 10) / 9 && expectedDistance > (distance * 9) / 10);
@@ -212,7 +222,7 @@ void MapperImpl::matchPairs(std::vector<Mapping*>& openA, std::vector<Mapping*>&
 
 // ---- findSplitPoint mapping.go:207-288
 void MapperImpl::findSplitPoint(Task& t, std::vector<Mapping*>& openA, std::vector<Mapping*>& openB, i64 left, i64 right) {
-    const i64 qLen = t.L;
+    const i64 qLen = t.L, edgeSize = ix.edgeSize;
     while (right - left >= edgeSize) {
         const i64 start = (right + left - edgeSize) / 2, end = start + edgeSize;
         std::vector<Mapping*> mid = performMapping(t, start, end, false);
@@ -267,7 +277,7 @@ void MapperImpl::findSplitPoint(Task& t, std::vector<Mapping*>& openA, std::vect
 // ---- mapNext mapping.go:305-383 (Go slice aliasing reproduced with value copies, cf. oracle/mapping.cpp notes)
 void MapperImpl::mapNext(Task& t, std::vector<Mapping*>& openA, std::vector<Mapping*>& openB, std::vector<Mapping*>& newA,
                          std::vector<Mapping*>& newB, std::vector<Mapping*>& matched, bool& matchedNil) {
-    const i64 qLen = t.L;
+    const i64 qLen = t.L, edgeSize = ix.edgeSize;
     std::vector<Mapping*> extended;
     bool extNil;
     if (qLen < edgeSize * 4) {
@@ -348,7 +358,7 @@ void MapperImpl::mapNext(Task& t, std::vector<Mapping*>& openA, std::vector<Mapp
 
 // ---- Map mapping.go:430-487
 std::vector<Mapping*> MapperImpl::map(Task& t) {
-    const i64 qLen = t.L;
+    const i64 qLen = t.L, edgeSize = ix.edgeSize;
     std::vector<Mapping*> results;
     if (qLen <= edgeSize * 2) {
         results = removeDominated(performMapping(t, 0, qLen, true), qLen);
@@ -432,9 +442,11 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
     t.req.b = b;
     t.req.whole = whole;
     t.waiting = true;
-    coroSwitch(t.at, sched->main);  // yield until the batch has been processed
+    coroSwitch(t.at, sched.main);  // yield until the batch has been processed
     t.waiting = false;
     const WindowResult& R = t.res;
+    const int k = ix.k;
+    const bool circular = ix.circular;
     const i64 qlen = b - a;
     // view metadata: SubSequence of a top-level read (offset a, inset L-(b-1)); the RC view swaps them (sequence.go:196)
     i64 vOffset = whole ? 0 : a, vInset = whole ? 0 : t.L - (b - 1);
@@ -444,8 +456,8 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
         const int qn = (int)R.seg[s].size();
         const i64 sqOffset = s == 0 ? vOffset : vInset, sqInset = s == 0 ? vInset : vOffset;
         for (const auto& ch : R.chains[s]) {
-            const Chunk& c = chunks[ch.target];
-            const i64 refLen = refLens[(size_t)c.ref];
+            const Chunk& c = ix.chunks[ch.target];
+            const i64 refLen = ix.refLens[(size_t)c.ref];
             i64 start = c.offset + segSeedOffset(c.seg, ch.b[0], k);
             const i64 end = refLen - c.inset - segSeedOffsetFromEnd(c.seg, c.n, ch.b.back(), k);
             if (circular && start > refLen) start -= refLen;
@@ -492,13 +504,13 @@ std::vector<Mapping*> MapperImpl::performMapping(Task& t, i64 a, i64 b, bool who
 
 // ---- AsString mapping.go:112-122
 std::string MapperImpl::asString(const Mapping& m, const std::string& qname, i64 qlen) const {
-    const i64 refLen = refLens[(size_t)m.ref];
+    const i64 refLen = ix.refLens[(size_t)m.ref];
     i64 mappedLength = m.End - m.Start;
-    if (circular && mappedLength < 0) mappedLength = refLen - m.Start + m.End;
+    if (ix.circular && mappedLength < 0) mappedLength = refLen - m.Start + m.End;
     char buf[512];
     snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%s\t", (long long)qlen, (long long)m.QueryOffset, (long long)(qlen - m.QueryInset),
              m.RC ? "-" : "+");
-    std::string s = qname + buf + refNames[(size_t)m.ref];
+    std::string s = qname + buf + ix.refNames[(size_t)m.ref];
     snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld\t%lld\t255", (long long)refLen, (long long)m.Start, (long long)m.End,
              (long long)m.ids, (long long)mappedLength);
     return s + buf;
@@ -510,9 +522,10 @@ std::string MapperImpl::asString(const Mapping& m, const std::string& qname, i64
 // ---- test hooks: the mapper's two decision rules on bare numbers (tests/test_hand_known_answers.py: answers worked from the Go text)
 // l = {RC, Query.Len(), QueryInset, Start, End}, r = {RC, QueryOffset, Start, End}
 bool handIsConsistent(const i64* l, const i64* r, bool circular, i64 refLen) {
-    MapperImpl m;
-    m.circular = circular;
-    m.refLens.assign(1, refLen);
+    MapIndex ix;
+    ix.circular = circular;
+    ix.refLens.assign(1, refLen);
+    MapperImpl m(ix);
     Mapping L, R;
     L.RC = l[0] != 0;
     L.queryLen = l[1];
@@ -540,8 +553,6 @@ int handRemoveDominated(const i64* maps, int n, i64 queryLen, int* kept) {
     for (size_t i = 0; i < out.size(); i++) kept[i] = (int)(out[i] - store.data());
     return (int)out.size();
 }
-namespace {
-}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
 // commands/map.go:33-116 + NewMapper mapping.go:67-109
@@ -579,58 +590,190 @@ size_t releaseMapStaging() {
     return freed;
 }
 
-int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int device, std::string& paf, std::string& errText,
-           MapStats* stats, std::string& error, MapTrim* trim) {
-    // upSet: the reads that go up.  Without a trim they are the reads that are mapped; with one they are the raw reads, and the set
-    // that is mapped is made from them once the trim has run on the device's copy
+namespace {
+
+double wallNow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- owners: everything a run holds that has to be given back.  MapRun declares one of each, in the order that makes a plain
+// `return rc` correct on every way out of runMap (see there)
+struct PinnedBlock {  // the packed reads' pinned block
+    uint8_t* p = nullptr;
+    ~PinnedBlock() {
+        if (p) dp_host_free(p);
+    }
+};
+struct ThreadJoiner {
+    std::thread t;
+    void join() {
+        if (t.joinable()) t.join();
+    }
+    ~ThreadJoiner() { join(); }
+};
+struct CtxOwner {
+    dp_ctx* c = nullptr;
+    void destroy() {
+        if (c) dp_ctx_destroy(c);
+        c = nullptr;
+    }
+    ~CtxOwner() { destroy(); }
+};
+// DP_MAP_SHARDS=N: shard s holds the chunks [c0, c1) (c0 a multiple of 64) on a context of its own
+struct Shard {
+    dp_ctx* ctx = nullptr;
+    uint32_t c0 = 0, c1 = 0;
+};
+struct ShardCtxs {
+    std::vector<Shard> v;
+    ~ShardCtxs() {
+        for (Shard& sh : v)
+            if (sh.ctx) dp_ctx_destroy(sh.ctx);
+    }
+};
+struct WorkerCtxs {  // the contexts of the mapper threads after the first (which works on the main context); slot 0 stays empty
+    std::vector<dp_ctx*> v;
+    void destroy() {
+        for (dp_ctx*& c : v) {
+            if (c) dp_ctx_destroy(c);
+            c = nullptr;
+        }
+    }
+    ~WorkerCtxs() { destroy(); }
+};
+// The ASCII paths' staging block.  Giving 400 MB of staging back to the system is 40 ms of munmap - round 3's profile had booked it
+// as "AddSingleSeeds (waited for)" - and on a thread of its own it holds the address-space lock against this one's allocations just
+// as long: the block is kept for the process's next map command instead, which then also finds its pages touched.  Before it
+// changes hands the upload's thread has read its last byte (the wait) and the thread that fills it has written its last (on a way
+// out before the upload step that thread may still run: it is joined here, ahead of its own joiner).
+struct StagingBlock {
+    std::unique_ptr<char[]> p;
+    size_t cap = 0;
+    CtxOwner& ctx;
+    ThreadJoiner& writer;
+    StagingBlock(CtxOwner& c, ThreadJoiner& w) : ctx(c), writer(w) {}
+    ~StagingBlock() {
+        if (ctx.c) (void)dp_reads_upload_wait(ctx.c, 0xffffffffu);
+        writer.join();
+        if (p) stagingPut(std::move(p), cap);
+    }
+};
+
+struct LoopStats {  // what one mapper thread reports
+    MapStats st;
+    double tScan = 0, tChain = 0, wall = 0;
+    int rc = 0;
+    std::string error;
+};
+
+// One map command: what its steps share.  runMap calls the steps in order; a step that fails has put the text into `error` (of
+// the context that failed, while it still exists) and returns its code.
+struct MapRun {
+    // ---- what the caller gave.  upSet: the reads that go up.  Without a trim they are the reads that are mapped; with one they are
+    // the raw reads, and the set that is mapped (trimmedSet) is made from them once the trim has run on the device's copy
+    const ReadSet& refSet;
+    const ReadSet& upSet;
+    const MapParams& p;
+    const int device;
+    std::string& paf;
+    std::string& errText;
+    MapStats* const stats;
+    std::string& error;
+    MapTrim* const trim;
     ReadSet trimmedSet;
-    const ReadSet& reads = trim ? trimmedSet : upSet;
-    const double tRun0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    const bool prof = dp_profile_on();
-    double tMark = tRun0;
-    auto mark = [&](const char* what) {
+    const ReadSet& reads;
+    const int k;
+    // the sequences mapped against: the first of the reference file (commands/map.go:34-36) or, with -all_sequences, every top-level
+    // sequence of it in file order (DESIGN 4.7: one seed index, chunk ids running on from sequence to sequence)
+    const size_t T;
+    const bool prof;
+    const double tRun0;
+    double tMark, tLoop0 = 0;
+    // ---- layout of the device read set (map_plan.hpp)
+    std::vector<i64> refLens;
+    MapJoins J;
+    size_t head = 0, readBytes = 0;  // ASCII paths: bytes of [reference | join chunks] and of the reads in the staging block
+    bool asyncUpload = false, packedUpload = false, packScalar = false;
+    MapPacked P;
+    std::vector<i64> off;  // ASCII paths: offsets into the staging block
+    // ---- seeds, chunks and the reference index
+    std::vector<double> values;
+    SeedIndex index;
+    dp_single_seed_batch ssb;  // (host arrays of the main context)
+    bool deviceSeeds = false;
+    MapSchedule sched;
+    dp_seedseq_batch sb;  // the chunk scan (host arrays of the main context)
+    std::vector<dp_seq_ref> refs;
+    MapIndex M;
+    int nShards = 1;
+    std::vector<int> devs;
+    uint32_t perShard = 0;
+    bool sparseIndex = false;
+    std::mutex infoMu;  // the mapper threads add their index's bytes to *stats
+    // ---- what the mapper threads leave
+    size_t nThreads = 1;
+    std::vector<std::string> out;  // per read, in read order, whoever mapped it
+    std::vector<int> nmaps;
+    std::vector<LoopStats> lstats;
+    // ---- the owners, declared in the reverse of the order they must go in (everything above outlives them all):
+    PinnedBlock pinned;     // 7. freed last: the packing thread writes it
+    ThreadJoiner concat;    // 6. the packing / concatenating thread (it touches no context)
+    CtxOwner ctx;           // 5. the main context, after everything that uses it or memory it owns:
+    ThreadJoiner seedWalk;  // 4. with device seeds the walk reads ssb's arrays, which are host memory of the main context
+    StagingBlock staging;   // 3. dp_reads_upload_wait(ctx, 0xffffffff), then the block goes back to stagingPut
+    ShardCtxs shards;       // 2. the shard contexts
+    WorkerCtxs workers;     // 1. go first: they share the main context's reads and may borrow its sparse index
+
+    MapRun(const ReadSet& refSet_, const ReadSet& upSet_, const MapParams& p_, int device_, std::string& paf_, std::string& errText_,
+           MapStats* stats_, std::string& error_, MapTrim* trim_)
+        : refSet(refSet_), upSet(upSet_), p(p_), device(device_), paf(paf_), errText(errText_), stats(stats_), error(error_), trim(trim_),
+          reads(trim_ ? trimmedSet : upSet_), k(p_.k), T(p_.allSequences ? refSet_.size() : std::min<size_t>(1, refSet_.size())),
+          prof(dp_profile_on()), tRun0(wallNow()), tMark(tRun0), off(1, 0), index(p_.k), staging(ctx, concat) {
+        memset(&ssb, 0, sizeof ssb);
+        memset(&sb, 0, sizeof sb);
+    }
+    void mark(const char* what) {
         if (!prof) return;
-        const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        const double t = wallNow();
         fprintf(stderr, "[map setup] %-28s %.1f ms\n", what, 1e3 * (t - tMark));
         tMark = t;
-    };
+    }
+    int failed(dp_ctx* c, int rc) {  // the text of the context that failed, taken while it exists
+        error = dp_last_error(c);
+        return rc;
+    }
+    size_t plannedThreads() const;
+    int64_t indexBytes(dp_ctx* c, uint64_t m) const;
+    int buildIndexOn(dp_ctx* c, const dp_seq_ref* r, uint32_t n);
+
+    int check();
+    void layoutAndStage();
+    void packOrConcatenate();
+    int allocBlocks();
+    int openContext();
+    int startSeedWalk();
+    void walkCandidates();
+    void walkOnHost();
+    int uploadReads();
+    int trimAndRespan();
+    int scanChunks();
+    int chooseIndexLayout();
+    int buildIndex();
+    int buildShard(Shard& sh, std::vector<uint32_t>& global, std::vector<uint32_t>& local);
+    int runWorkers();
+    void collectStats();
+    void writeText();
+    void writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped);
+};
+
+// ---- checks: what is refused before anything is packed or allocated on the device
+int MapRun::check() {
     if (refSet.size() == 0) {
         error = "empty reference";
         return -1;
     }
-    const int k = p.k;
-    // the sequences mapped against: the first of the reference file (commands/map.go:34-36) or, with -all_sequences, every top-level
-    // sequence of it in file order (DESIGN 4.7: one seed index, chunk ids running on from sequence to sequence)
-    const size_t T = p.allSequences ? refSet.size() : 1;
-    std::vector<i64> refLens(T);
+    refLens.resize(T);
     for (size_t c = 0; c < T; c++) refLens[c] = refSet.length(c);
-    // positions in the reference travel as 32-bit signed ints (chunk offsets, the reverse strand, the PAF's target fields): a longer
-    // sequence is refused before anything is packed or allocated on the device
-    for (size_t c = 0; c < T; c++)
-        if (refLens[c] > (i64)0x7fffffff) {
-            error = p.allSequences ? "map: the reference sequence " + refSet.names[c] + " is " + std::to_string((long long)refLens[c]) +
-                                         " bases long; at most 2147483647 are supported"
-                                   : "map: the reference sequence is " + std::to_string((long long)refLens[c]) +
-                                         " bases long; at most 2147483647 are supported";
-            return DP_ERR_ARG;
-        }
-    if (p.seedRate > 0 && p.chunkSize * 10 > p.querySize) {  // seed windows and chunks are numbered in 32 bits
-        const i64 step = p.chunkSize * 10 - p.querySize;
-        unsigned long long nWin = 0, nChk = 0;
-        for (size_t c = 0; c < T; c++) {
-            const i64 L = refLens[c];
-            if (L > p.seedRate) nWin += (unsigned long long)((L - 1) / p.seedRate);
-            for (i64 j = 0; j < 10; j++)
-                if (j * p.chunkSize < L - p.chunkSize / 2) nChk += (unsigned long long)((L - p.chunkSize / 2 - j * p.chunkSize + step - 1) / step);
-            nChk += p.circular ? 1 : 0;
-        }
-        if (nWin > 0xffffffffull || nChk > 0xffffffffull) {
-            error = "map: the reference has " + std::to_string(nWin) + " seed windows and " + std::to_string(nChk) +
-                    " chunks; fewer than 4294967296 of each are supported";
-            return DP_ERR_ARG;
-        }
-    }
-    if (trim) {  // what the trim refuses about its adapters and k, refused before anything is packed or allocated on the device
+    if (int rc = mapCheckLimits(p, refLens, refSet.names, error)) return rc;
+    if (trim) {  // what the trim refuses about its adapters and k
         TrimIndex ix;
         if (!trimBuildIndex(*trim->front, *trim->back, trim->params.k, ix, error)) return DP_ERR_ARG;
     }
@@ -638,380 +781,287 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
         error = "map: reference index layout " + std::to_string(p.indexLayout) + " (0 = auto, 1 = dense, 2 = sparse)";
         return DP_ERR_ARG;
     }
-    // ---- device read set: [0] reference, [1] circular join chunk, then (forward, reverse complement) of every read; with
-    // -all_sequences [0 .. T) the reference sequences, then the join chunk of every sequence that has one, then the reads.  Its host
-    // staging copy is made by a thread of its own while the device computes the reference's k-mer table
-    std::vector<i64> off(1, 0);
-    std::vector<std::string> joins;
-    std::vector<int> joinOf(T, -1);  // a sequence's join chunk among `joins`
-    std::string joinNotes;
-    for (size_t c = 0; c < T; c++) {
-        const char* ref = refSet.seq(c);
-        const i64 refLen = refLens[c];
-        if (!p.allSequences) {  // (a slot of its own even when it is empty)
-            joinOf[c] = 0;
-            joins.push_back(p.circular ? std::string(ref + (refLen - p.querySize), (size_t)p.querySize) + std::string(ref, (size_t)p.querySize) : std::string());
-        } else if (p.circular && refLen >= p.querySize) {
-            joinOf[c] = (int)joins.size();
-            joins.push_back(std::string(ref + (refLen - p.querySize), (size_t)p.querySize) + std::string(ref, (size_t)p.querySize));
-        } else if (p.circular) {  // (the reference would slice out of range, mapping.go:93-95)
-            joinNotes += "Sequence " + refSet.names[c] + " (" + std::to_string((long long)refLen) + " bases) is shorter than query_size " +
-                         std::to_string((long long)p.querySize) + ": no circular join chunk\n";
-        }
-    }
-    const uint32_t firstPaired = (uint32_t)(T + joins.size());  // device reads before the (forward, reverse complement) pairs
-    // one staging buffer [reference | join chunk | all reads]; the reads are one contiguous block of the read set, copied
-    // (and its pages first touched) by the worker pool in 4 MiB pieces
-    size_t head = 0;
+    return 0;
+}
+
+// ---- device read set: [0] reference, [1] circular join chunk, then (forward, reverse complement) of every read; with
+// -all_sequences [0 .. T) the reference sequences, then the join chunk of every sequence that has one, then the reads.
+// The reads cross PCIe the way the reference holds them - 2 bits per base (sequence.packedSequence) - packed here by
+// the worker pool straight into a pinned block in the device's own layout (every read on a 16-byte boundary) and put in place by
+// dp_reads_upload_packed_rc, which also makes the reverse strands: 100 MB instead of 400 at config 3, one copy instead of three
+// (staging, pinned ring, link).  DP_TUNE=map_ascii_upload=1: the ASCII path (it is what map_async_upload uses): one staging buffer
+// [reference | join chunk | all reads].  With a trim the packed path is the only one and neither key is consulted: the device set is
+// then [raw reads | reference sequences | join chunks] without pairs, so that the trim's id lists and spans name raw read r as device
+// read r, and dp_reads_respan_rc makes map's order and the reverse strands from it afterwards.
+void MapRun::layoutAndStage() {
+    std::vector<const char*> seqs(T);
+    for (size_t c = 0; c < T; c++) seqs[c] = refSet.seq(c);
+    J = mapJoinChunks(p, refLens, seqs, refSet.names);
     for (size_t c = 0; c < T; c++) head += (size_t)refLens[c];
-    for (const std::string& j : joins) head += j.size();
-    const size_t readBytes = !trim && reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
-    // Round 6: the reads cross PCIe the way the reference holds them - 2 bits per base (sequence.packedSequence) - packed here by
-    // the worker pool straight into a pinned block in the device's own layout (every read on a 16-byte boundary) and put in place by
-    // dp_reads_upload_packed_rc, which also makes the reverse strands: 100 MB instead of 400 at config 3, one copy instead of three
-    // (staging, pinned ring, link).  DP_TUNE=map_ascii_upload=1: the ASCII path below, as before (it is what map_async_upload uses).
-    // With a trim the packed path is the only one and neither key is consulted: the device set is then [raw reads | reference sequences
-    // | join chunks] without pairs, so that the trim's id lists and spans name raw read r as device read r, and dp_reads_respan_rc
-    // makes map's order and the reverse strands from it afterwards.
-    const bool asyncUpload = !trim && dp_tune("map_async_upload", 0) != 0;
-    const bool packedUpload = trim || (!asyncUpload && !dp_tune("map_ascii_upload", 0));
-    const size_t headAt = trim ? upSet.size() : 0, readsAt = trim ? 0 : (size_t)firstPaired;  // device ids of the first sequence / read as uploaded
-    const bool packScalar = dp_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
-    std::vector<uint32_t> plens;
-    std::vector<uint64_t> poff;
-    uint8_t* pinned = nullptr;
-    struct PinnedBack {
-        uint8_t*& p;
-        ~PinnedBack() {
-            if (p) dp_host_free(p);
-        }
-    } pinnedBack{pinned};
-    if (packedUpload) {
-        const size_t n = firstPaired + upSet.size();
-        plens.resize(n);
-        poff.assign(n + 1, 0);
-        for (size_t c = 0; c < T; c++) plens[headAt + c] = (uint32_t)refLens[c];
-        for (size_t j = 0; j < joins.size(); j++) plens[headAt + T + j] = (uint32_t)joins[j].size();
-        for (size_t r = 0; r < upSet.size(); r++) plens[readsAt + r] = (uint32_t)upSet.length(r);
-        for (size_t r = 0; r < n; r++) poff[r + 1] = poff[r] + ((((uint64_t)plens[r] + 3) / 4 + 15) & ~(uint64_t)15);
-        pinned = (uint8_t*)dp_host_alloc((size_t)poff[n] + 64);
-        if (!pinned) {
-            error = "dp_host_alloc: no pinned memory for the packed reads";
-            return DP_ERR_HIP;
-        }
+    for (const std::string& j : J.joins) head += j.size();
+    readBytes = !trim && reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
+    asyncUpload = !trim && dp_tune("map_async_upload", 0) != 0;
+    packedUpload = trim || (!asyncUpload && !dp_tune("map_ascii_upload", 0));
+    packScalar = dp_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
+}
+int MapRun::allocBlocks() {
+    if (!packedUpload) {
+        staging.p = stagingTake(head + readBytes + 1, &staging.cap);
+        return 0;
     }
-    size_t stagingCap = 0;
-    std::unique_ptr<char[]> staging = packedUpload ? std::unique_ptr<char[]>() : stagingTake(head + readBytes + 1, &stagingCap);
-    std::thread concatThread([&] {
-        if (packedUpload) {
-            for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned + poff[headAt + c], packScalar);
-            for (size_t j = 0; j < joins.size(); j++) packBases(joins[j].data(), joins[j].size(), pinned + poff[headAt + T + j], packScalar);
-            // pieces of about 2 M bases: whole reads
-            std::vector<size_t> cut(1, 0);
-            i64 acc = 0;
-            for (size_t r = 0; r < upSet.size(); r++) {
-                acc += upSet.length(r);
-                if (acc >= ((i64)2 << 20)) {
-                    cut.push_back(r + 1);
-                    acc = 0;
-                }
+    P = mapPackedLayout(refLens, J.joins, upSet.off.data(), upSet.size(), trim != nullptr);
+    pinned.p = (uint8_t*)dp_host_alloc((size_t)P.poff.back() + 64);
+    if (!pinned.p) {
+        error = "dp_host_alloc: no pinned memory for the packed reads";
+        return DP_ERR_HIP;
+    }
+    return 0;
+}
+// The host staging copy is made by a thread of its own while the device computes the reference's k-mer table
+void MapRun::packOrConcatenate() {
+    if (packedUpload) {
+        for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned.p + P.poff[P.headAt + c], packScalar);
+        for (size_t j = 0; j < J.joins.size(); j++) packBases(J.joins[j].data(), J.joins[j].size(), pinned.p + P.poff[P.headAt + T + j], packScalar);
+        // pieces of about 2 M bases: whole reads
+        std::vector<size_t> cut(1, 0);
+        i64 acc = 0;
+        for (size_t r = 0; r < upSet.size(); r++) {
+            acc += upSet.length(r);
+            if (acc >= ((i64)2 << 20)) {
+                cut.push_back(r + 1);
+                acc = 0;
             }
-            if (cut.back() != upSet.size()) cut.push_back(upSet.size());
-            parallelFor(cut.size() - 1, [&](size_t i) {
-                for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(upSet.seq(r), (size_t)upSet.length(r), pinned + poff[readsAt + r], packScalar);
-            });
-            return;
         }
-        for (size_t c = 0; c < T; c++) {
-            memcpy(staging.get() + off.back(), refSet.seq(c), (size_t)refLens[c]);
-            off.push_back(off.back() + refLens[c]);
-        }
-        for (const std::string& j : joins) {
-            memcpy(staging.get() + off.back(), j.data(), j.size());
-            off.push_back(off.back() + (i64)j.size());
-        }
-        const char* src = reads.size() ? reads.seq(0) : nullptr;
-        const size_t piece = (size_t)4 << 20, nPieces = (readBytes + piece - 1) / piece;
-        char* dst = staging.get() + head;
-        parallelFor(nPieces, [&](size_t i) {
-            const size_t b = i * piece, e = std::min(readBytes, b + piece);
-            memcpy(dst + b, src + b, e - b);
+        if (cut.back() != upSet.size()) cut.push_back(upSet.size());
+        parallelFor(cut.size() - 1, [&](size_t i) {
+            for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(upSet.seq(r), (size_t)upSet.length(r), pinned.p + P.poff[P.readsAt + r], packScalar);
         });
-        const i64 shift = (i64)head - (reads.size() ? reads.off[0] : 0);
-        for (size_t r = 0; r < reads.size(); r++) off.push_back(reads.off[r + 1] + shift);
+        return;
+    }
+    // the reads are one contiguous block of the read set, copied (and its pages first touched) by the worker pool in 4 MiB pieces
+    for (size_t c = 0; c < T; c++) {
+        memcpy(staging.p.get() + off.back(), refSet.seq(c), (size_t)refLens[c]);
+        off.push_back(off.back() + refLens[c]);
+    }
+    for (const std::string& j : J.joins) {
+        memcpy(staging.p.get() + off.back(), j.data(), j.size());
+        off.push_back(off.back() + (i64)j.size());
+    }
+    const char* src = reads.size() ? reads.seq(0) : nullptr;
+    const size_t piece = (size_t)4 << 20, nPieces = (readBytes + piece - 1) / piece;
+    char* dst = staging.p.get() + head;
+    parallelFor(nPieces, [&](size_t i) {
+        const size_t b = i * piece, e = std::min(readBytes, b + piece);
+        memcpy(dst + b, src + b, e - b);
     });
-    struct ConcatJoin {
-        std::thread& t;
-        ~ConcatJoin() {
-            if (t.joinable()) t.join();
-        }
-    } concatJoin{concatThread};
-    dp_ctx* ctx = nullptr;
-    if (dp_ctx_create(device, &ctx) != 0) {
+    const i64 shift = (i64)head - (reads.size() ? reads.off[0] : 0);
+    for (size_t r = 0; r < reads.size(); r++) off.push_back(reads.off[r + 1] + shift);
+}
+
+// ---- context, reference upload, and the value table from every sequence of the reference file (map.go:45-71)
+int MapRun::openContext() {
+    if (dp_ctx_create(device, &ctx.c) != 0) {
         error = dp_last_error(nullptr);
         return DP_ERR_NODEVICE;
     }
-    auto fail = [&](int rc) {
-        error = dp_last_error(ctx);
-        dp_ctx_destroy(ctx), ctx = nullptr;
-        return rc;
-    };
     mark("context");
-    // ---- value table from every sequence of the reference file (map.go:45-71); KmerOccurrences on the GPU
-    int rc = dp_reads_upload(ctx, (const uint8_t*)refSet.bases.data(), refSet.off.data(), (uint32_t)refSet.size());
-    if (rc) return fail(rc);
-    std::vector<double> values((size_t)1 << (2 * k));
-    rc = dp_kmer_values(ctx, k, values.data());  // KmerOccurrences + value table + 1 % cut on the GPU
-    if (rc) return fail(rc);
+    int rc = dp_reads_upload(ctx.c, (const uint8_t*)refSet.bases.data(), refSet.off.data(), (uint32_t)refSet.size());
+    if (rc) return failed(ctx.c, rc);
+    values.resize((size_t)1 << (2 * k));
+    rc = dp_kmer_values(ctx.c, k, values.data());  // KmerOccurrences + value table + 1 % cut on the GPU
+    if (rc) return failed(ctx.c, rc);
     mark("reference upload + value table");
     errText += "K-mer counting complete. Preparing to start indexing and querying...\n";
-    errText += joinNotes;
+    errText += J.notes;
+    return 0;
+}
 
-    // ---- AddSingleSeeds seeds/seeds.go:160-200 on the (top-level) reference, host, sequential - on a thread of its own while
-    // this one concatenates the reads and the device uploads and packs them (neither needs the seeds)
-    SeedIndex index(k);
-    // Round 4: everything about a window that does not depend on the seeds added before it - its best k-mer, and which k-mers of
-    // its count region are the best of ANY window (only those can ever be seeds) - comes from the device for all windows at once
-    // (dp_single_seed_candidates: the reference and the value table are resident right now); the thread below then walks the
-    // windows in order and probes five or six candidates per window instead of seed_rate k-mers (3.9 s -> 0.1 s per 375 Mb of
-    // reference).  DP_TUNE=map_seeds_host=1: the whole walk on the host as before.
-    // -all_sequences: AddSingleSeeds for one sequence after the other on the ONE index; the device numbers the windows of all sequences
-    // in sequence order and "best of any window" is over all of them (dp_single_seed_candidates_multi), so the walk below is the same.
-    dp_single_seed_batch ssb;
-    memset(&ssb, 0, sizeof ssb);
-    bool deviceSeeds = false;
+// ---- AddSingleSeeds seeds/seeds.go:160-200 on the (top-level) reference, host, sequential - on a thread of its own while
+// this one waits for the concatenated reads and the device uploads and packs them (neither needs the seeds).
+// Everything about a window that does not depend on the seeds added before it - its best k-mer, and which k-mers of
+// its count region are the best of ANY window (only those can ever be seeds) - comes from the device for all windows at once
+// (dp_single_seed_candidates: the reference and the value table are resident right now); the thread then walks the
+// windows in order and probes five or six candidates per window instead of seed_rate k-mers (3.9 s -> 0.1 s per 375 Mb of
+// reference).  DP_TUNE=map_seeds_host=1: the whole walk on the host.
+// -all_sequences: AddSingleSeeds for one sequence after the other on the ONE index; the device numbers the windows of all sequences
+// in sequence order and "best of any window" is over all of them (dp_single_seed_candidates_multi), so the walk is the same.
+int MapRun::startSeedWalk() {
     if (!dp_tune("map_seeds_host", 0)) {  // (tests: AddSingleSeeds walked on the host)
         if (p.allSequences) {
             dp_single_seed_multi_batch mb;
-            rc = dp_single_seed_candidates_multi(ctx, 0, (uint32_t)T, k, p.seedRate, &mb);
-            if (rc) return fail(rc);
+            if (int rc = dp_single_seed_candidates_multi(ctx.c, 0, (uint32_t)T, k, p.seedRate, &mb)) return failed(ctx.c, rc);
             ssb.n_windows = mb.n_windows;
             ssb.best = mb.best;
             ssb.cand_off = mb.cand_off;
             ssb.cand = mb.cand;
         } else {
-            rc = dp_single_seed_candidates(ctx, 0, k, p.seedRate, &ssb);
-            if (rc) return fail(rc);
+            if (int rc = dp_single_seed_candidates(ctx.c, 0, k, p.seedRate, &ssb)) return failed(ctx.c, rc);
         }
         deviceSeeds = true;
         mark("single-seed candidates (device)");
     }
-    std::thread seedThread([&] {
-        if (deviceSeeds) {
-            const double ts0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-            for (uint32_t w = 0; w < ssb.n_windows; w++) {
-                bool any = false;
-                for (uint32_t c = ssb.cand_off[w]; c < ssb.cand_off[w + 1] && !any; c++) any = index.isSeed(ssb.cand[c]);
-                if (!any) index.addSeedKmer(ssb.best[w]);
-            }
-            if (prof)
-                fprintf(stderr, "[map setup] single-seed walk: %u windows, %u candidates, %zu seeds, %.1f ms on its thread\n", ssb.n_windows,
-                        ssb.cand_off[ssb.n_windows], index.seedMap.size(),
-                        1e3 * (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - ts0));
-            return;
-        }
-        const uint32_t mask = (uint32_t)(((uint64_t)1 << (2 * k)) - 1);
-        for (size_t sq = 0; sq < T; sq++) {  // (one sequence after the other on the one index)
-            const char* ref = refSet.seq(sq);
-            const i64 refLen = refLens[sq];
-            const int finalLen = (int)(refLen % 4);  // top-level sequence: 0 when len%4 == 0 (sequence.go:70,88)
-            const i64 skipBack = 4 - finalLen;
-            auto code = [&](i64 pos) -> uint32_t { return pos < refLen ? baseCode((unsigned char)ref[pos]) : 0u; };  // zero padding
-            auto kmerAt = [&](i64 pos) {
-                uint32_t v = 0;
-                for (int j = 0; j < k; j++) v = (v << 2) | code(pos + j);
-                return v;
-            };
-            for (i64 i = 0; i < refLen - p.seedRate; i += p.seedRate) {
-                // CountKmersBetween(i, i+seedRate, 1, ...) == 0 ?  (sequence.go:332-337 + asm:81-203: whole bytes only,
-                // parent's skipBack, do-while group loop)
-                const i64 startB = (i + 3) / 4, endB = (i + p.seedRate) / 4;
-                const i64 nb = endB - startB;
-                const i64 nk = 4 * (nb - 1) - skipBack - k + 1;
-                i64 groups = (nk & ~(i64)3) / 4;
-                if (groups < 1) groups = 1;
-                const i64 P = 4 + 4 * groups + (nk & 3);
-                bool any = false;
-                {
-                    const i64 p0 = startB * 4;
-                    uint32_t km = kmerAt(p0);
-                    for (i64 j = 0; j < P; j++) {
-                        if (j) km = ((km << 2) | code(p0 + j + k - 1)) & mask;
-                        if (index.isSeed(km)) {
-                            any = true;
-                            break;
-                        }
-                    }
-                }
-                if (!any) {
-                    const i64 end = i + p.seedRate;
-                    uint32_t km = kmerAt(i);
-                    double bestValue = values[km];
-                    uint32_t best = km;
-                    for (i64 j = i + k; j < end; j++) {
-                        km = ((km << 2) | code(j)) & mask;
-                        const double v = values[km];
-                        if (v > bestValue) {
-                            bestValue = v;
-                            best = km;
-                        }
-                    }
-                    index.addSeedKmer(best);
-                }
-            }
-        }
-    });
-    struct SeedJoin {  // (every way out of this function waits for the thread)
-        std::thread& t;
-        ~SeedJoin() {
-            if (t.joinable()) t.join();
-        }
-    } seedJoin{seedThread};
-    // ... and a way out that destroys the context joins it first: with device seeds the thread walks ssb's arrays, which are host memory of
-    // the context
-    auto failJoined = [&](int rc2) {
-        if (seedThread.joinable()) seedThread.join();
-        return fail(rc2);
-    };
-    // device ids: 0 reference, 1 join chunk, then (forward, reverse complement) per read; the reverse strands are made
-    // on the device
-    concatThread.join();
-    mark("concatenate reads (waited for)");
-    // Round 5, DP_TUNE=map_async_upload=1: the reads travel while they are mapped (dp_reads_upload_rc_begin: this call returns when the
-    // reference and the join chunk are packed; the mapper threads wait for "reads below n are packed" block by block).  Built, parity
-    // tested and left OFF: set-up 14.5 -> 8 ms and the best run 56.0 -> 54.4 ms, but the runs of a process spread 55 - 107 ms where
-    // they were 56 - 65 (means of 12 runs 69 / 77 against 62 / 69 ms, profiles/r05/map_threads_and_reads_in_flight.txt): the upload's
-    // copy threads and the link compete with six mapper threads for the same host cores and queues.
-    // (giving 400 MB of staging back to the system is 40 ms of munmap - round 3's profile had booked it as "AddSingleSeeds (waited
-    // for)" - and on a thread of its own it holds the address-space lock against this one's allocations just as long: the block is
-    // kept for the process's next map command instead, which then also finds its pages touched)
-    struct StagingBack {  // every way out: the upload's thread has read the last byte before the block changes hands
-        dp_ctx*& c;
-        std::unique_ptr<char[]>& st;
-        size_t& cap;
-        ~StagingBack() {
-            if (c) (void)dp_reads_upload_wait(c, 0xffffffffu);
-            if (st) stagingPut(std::move(st), cap);
-        }
-    } stagingBack{ctx, staging, stagingCap};
-    rc = packedUpload  ? dp_reads_upload_packed_rc(ctx, pinned, plens.data(), (uint32_t)plens.size(), trim ? (uint32_t)plens.size() : firstPaired)
-         : asyncUpload ? dp_reads_upload_rc_begin(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired, firstPaired)
-                       : dp_reads_upload_rc(ctx, (const uint8_t*)staging.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired);
-    if (rc) return failJoined(rc);
-    mark(trim ? "packed upload (raw reads)" : packedUpload ? "packed upload + reverse strands" : asyncUpload ? "upload begun (reference packed)" : "upload + pack (both strands)");
-    if (trim) {
-        // ---- the trim on the device's copy, the trimmed read set on the host, and the device set cut and paired from the raw one: the
-        // reference sequences and join chunks first, whole and unpaired, then every trimmed read with its reverse strand
-        std::string trimError;
-        if (runTrim(*trim->raw, *trim->front, *trim->back, trim->params, device, *trim->res, trimError, ctx) != 0) {
-            if (seedThread.joinable()) seedThread.join();  // (it reads memory of the context)
-            error = trimError;
-            dp_ctx_destroy(ctx), ctx = nullptr;
-            return -1;
-        }
-        mark("trim on resident reads");
-        std::vector<dp_read_span> cut;
-        trimmedReadSet(*trim->raw, *trim->res, p.minLength, trim->raw->himem, trimmedSet, cut);
-        mark("trimmed read set");
-        std::vector<dp_read_span> order;
-        order.reserve((size_t)firstPaired + cut.size());
-        for (size_t c = 0; c < T; c++) order.push_back(dp_read_span{(uint32_t)(headAt + c), 0u, (uint32_t)refLens[c]});
-        for (size_t j = 0; j < joins.size(); j++) order.push_back(dp_read_span{(uint32_t)(headAt + T + j), 0u, (uint32_t)joins[j].size()});
-        order.insert(order.end(), cut.begin(), cut.end());
-        rc = dp_reads_respan_rc(ctx, order.data(), (uint32_t)order.size(), firstPaired);
-        if (rc) return failJoined(rc);
-        mark("respan + reverse strands");
+    seedWalk.t = std::thread([this] { deviceSeeds ? walkCandidates() : walkOnHost(); });
+    return 0;
+}
+void MapRun::walkCandidates() {
+    const double ts0 = wallNow();
+    for (uint32_t w = 0; w < ssb.n_windows; w++) {
+        bool any = false;
+        for (uint32_t c = ssb.cand_off[w]; c < ssb.cand_off[w + 1] && !any; c++) any = index.isSeed(ssb.cand[c]);
+        if (!any) index.addSeedKmer(ssb.best[w]);
     }
-    seedThread.join();
+    if (prof)
+        fprintf(stderr, "[map setup] single-seed walk: %u windows, %u candidates, %zu seeds, %.1f ms on its thread\n", ssb.n_windows,
+                ssb.cand_off[ssb.n_windows], index.seedMap.size(), 1e3 * (wallNow() - ts0));
+}
+void MapRun::walkOnHost() {
+    const uint32_t mask = (uint32_t)(((uint64_t)1 << (2 * k)) - 1);
+    for (size_t sq = 0; sq < T; sq++) {  // (one sequence after the other on the one index)
+        const char* ref = refSet.seq(sq);
+        const i64 refLen = refLens[sq];
+        const int finalLen = (int)(refLen % 4);  // top-level sequence: 0 when len%4 == 0 (sequence.go:70,88)
+        const i64 skipBack = 4 - finalLen;
+        auto code = [&](i64 pos) -> uint32_t { return pos < refLen ? baseCode((unsigned char)ref[pos]) : 0u; };  // zero padding
+        auto kmerAt = [&](i64 pos) {
+            uint32_t v = 0;
+            for (int j = 0; j < k; j++) v = (v << 2) | code(pos + j);
+            return v;
+        };
+        for (i64 i = 0; i < refLen - p.seedRate; i += p.seedRate) {
+            // CountKmersBetween(i, i+seedRate, 1, ...) == 0 ?  (sequence.go:332-337 + asm:81-203: whole bytes only,
+            // parent's skipBack, do-while group loop)
+            const i64 startB = (i + 3) / 4, endB = (i + p.seedRate) / 4;
+            const i64 nb = endB - startB;
+            const i64 nk = 4 * (nb - 1) - skipBack - k + 1;
+            i64 groups = (nk & ~(i64)3) / 4;
+            if (groups < 1) groups = 1;
+            const i64 P = 4 + 4 * groups + (nk & 3);
+            bool any = false;
+            {
+                const i64 p0 = startB * 4;
+                uint32_t km = kmerAt(p0);
+                for (i64 j = 0; j < P; j++) {
+                    if (j) km = ((km << 2) | code(p0 + j + k - 1)) & mask;
+                    if (index.isSeed(km)) {
+                        any = true;
+                        break;
+                    }
+                }
+            }
+            if (!any) {
+                const i64 end = i + p.seedRate;
+                uint32_t km = kmerAt(i);
+                double bestValue = values[km];
+                uint32_t best = km;
+                for (i64 j = i + k; j < end; j++) {
+                    km = ((km << 2) | code(j)) & mask;
+                    const double v = values[km];
+                    if (v > bestValue) {
+                        bestValue = v;
+                        best = km;
+                    }
+                }
+                index.addSeedKmer(best);
+            }
+        }
+    }
+}
+
+// ---- read upload.  Device ids: 0 reference, 1 join chunk, then (forward, reverse complement) per read; the reverse strands are
+// made on the device.
+// DP_TUNE=map_async_upload=1: the reads travel while they are mapped (dp_reads_upload_rc_begin: this call returns when the
+// reference and the join chunk are packed; the mapper threads wait for "reads below n are packed" block by block).  Built, parity
+// tested and left OFF: set-up 14.5 -> 8 ms and the best run 56.0 -> 54.4 ms, but the runs of a process spread 55 - 107 ms where
+// they were 56 - 65 (means of 12 runs 69 / 77 against 62 / 69 ms, profiles/r05/map_threads_and_reads_in_flight.txt): the upload's
+// copy threads and the link compete with six mapper threads for the same host cores and queues.
+int MapRun::uploadReads() {
+    concat.join();
+    mark("concatenate reads (waited for)");
+    const uint32_t firstPaired = J.firstPaired;
+    const int rc = packedUpload  ? dp_reads_upload_packed_rc(ctx.c, pinned.p, P.plens.data(), (uint32_t)P.plens.size(), trim ? (uint32_t)P.plens.size() : firstPaired)
+                   : asyncUpload ? dp_reads_upload_rc_begin(ctx.c, (const uint8_t*)staging.p.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired, firstPaired)
+                                 : dp_reads_upload_rc(ctx.c, (const uint8_t*)staging.p.get(), off.data(), (uint32_t)(off.size() - 1), firstPaired);
+    if (rc) return failed(ctx.c, rc);
+    mark(trim ? "packed upload (raw reads)" : packedUpload ? "packed upload + reverse strands" : asyncUpload ? "upload begun (reference packed)" : "upload + pack (both strands)");
+    return 0;
+}
+
+// ---- the trim on the device's copy, the trimmed read set on the host, and the device set cut and paired from the raw one: the
+// reference sequences and join chunks first, whole and unpaired, then every trimmed read with its reverse strand
+int MapRun::trimAndRespan() {
+    std::string trimError;
+    if (runTrim(*trim->raw, *trim->front, *trim->back, trim->params, device, *trim->res, trimError, ctx.c) != 0) {
+        error = trimError;
+        return -1;
+    }
+    mark("trim on resident reads");
+    std::vector<dp_read_span> cut;
+    trimmedReadSet(*trim->raw, *trim->res, p.minLength, trim->raw->himem, trimmedSet, cut);
+    mark("trimmed read set");
+    std::vector<dp_read_span> order;
+    order.reserve((size_t)J.firstPaired + cut.size());
+    for (size_t c = 0; c < T; c++) order.push_back(dp_read_span{(uint32_t)(P.headAt + c), 0u, (uint32_t)refLens[c]});
+    for (size_t j = 0; j < J.joins.size(); j++) order.push_back(dp_read_span{(uint32_t)(P.headAt + T + j), 0u, (uint32_t)J.joins[j].size()});
+    order.insert(order.end(), cut.begin(), cut.end());
+    if (int rc = dp_reads_respan_rc(ctx.c, order.data(), (uint32_t)order.size(), J.firstPaired)) return failed(ctx.c, rc);
+    mark("respan + reverse strands");
+    return 0;
+}
+
+// ---- chunk scan: the schedule's chunks (map_plan.hpp) scanned with the seeds of the walk, which is waited for here; their segments
+// copied to the host for the mapper threads and the shards.  An empty schedule is left to runMap
+int MapRun::scanChunks() {
+    seedWalk.join();
     mark("AddSingleSeeds (waited for)");
-    // ---- chunk schedule mapping.go:79-96, canonical generation order; sequence after sequence, the chunk ids running on
-    MapperImpl M;
-    M.ctx = ctx;
     M.k = k;
     M.edgeSize = p.querySize;
     M.circular = p.circular;
     M.refLens = refLens;
     M.refNames.assign(refSet.names.begin(), refSet.names.begin() + (i64)T);
-    std::vector<dp_scan_item> items;
-    std::vector<std::pair<i64, i64>> meta;  // offset, inset per chunk
-    std::vector<int> chunkRef;              // its reference sequence
-    for (size_t sq = 0; sq < T; sq++) {
-        const i64 refLen = refLens[sq];
-        for (i64 j = 0; j < 10; j++) {
-            const i64 start = j * p.chunkSize, step = p.chunkSize * 10 - p.querySize;
-            for (i64 i = start; i < refLen - p.chunkSize / 2; i += step) {
-                i64 end = i + p.chunkSize;
-                if (i >= refLen) end = refLen;
-                if (end > refLen) end = refLen;  // SubSequence clamps
-                dp_scan_item it;
-                it.read = (uint32_t)sq;
-                it.start = (uint32_t)i;
-                it.n_kmers = (uint32_t)std::max<i64>(0, (end - i) - k + 1);
-                it.min_seeds = 0;
-                items.push_back(it);
-                meta.push_back({i, refLen - (end - 1)});  // SubSequence: offset+start, inset + length - (end-1)
-                chunkRef.push_back((int)sq);
-            }
-        }
-        if (p.circular && joinOf[sq] >= 0) {
-            // Append(...) is a fresh top-level sequence of 2*edge bases: len%4==0 loses its last 4 k-mers (asm:88-96)
-            const i64 jl = (i64)joins[(size_t)joinOf[sq]].size();
-            i64 nk = jl - k + 1;
-            if (jl % 4 == 0) nk -= 4;
-            dp_scan_item it;
-            it.read = (uint32_t)(T + (size_t)joinOf[sq]);
-            it.start = 0;
-            it.n_kmers = (uint32_t)std::max<i64>(0, nk);
-            it.min_seeds = 0;
-            items.push_back(it);
-            meta.push_back({refLen - p.querySize, refLen - (p.querySize - 1)});  // offset of the first part, inset of the second
-            chunkRef.push_back((int)sq);
-        }
-    }
-    if (items.empty()) {  // no sequence is long enough for a chunk: an empty index matches nothing, every read is unmapped
-        if (stats) stats->n_seeds = index.seedMap.size(), stats->t_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - tRun0;
-        char line[160];
-        snprintf(line, sizeof line, "Uniquely mapped: 0\nMultiple mappings: 0\ntotal: 0\nUnmapped: %lld\n", (long long)reads.size());
-        errText += line;
-        dp_ctx_destroy(ctx), ctx = nullptr;
-        return 0;
-    }
-    rc = dp_round_begin(ctx, k, index.seedMap.data(), (uint32_t)index.seedMap.size());
-    if (rc) return fail(rc);
-    dp_seedseq_batch sb;
-    rc = dp_scan(ctx, items.data(), (uint32_t)items.size(), &sb);
-    if (rc) return fail(rc);
+    sched = mapChunkSchedule(p, refLens, J);
+    if (sched.items.empty()) return 0;
+    int rc = dp_round_begin(ctx.c, k, index.seedMap.data(), (uint32_t)index.seedMap.size());
+    if (rc) return failed(ctx.c, rc);
+    rc = dp_scan(ctx.c, sched.items.data(), (uint32_t)sched.items.size(), &sb);
+    if (rc) return failed(ctx.c, rc);
+    const size_t n = sched.items.size();
     M.chunkSegs.assign(sb.segs, sb.segs + sb.n_segs);
-    std::vector<dp_seq_ref> refs(items.size());
-    M.chunks.resize(items.size());
-    for (size_t i = 0; i < items.size(); i++) {
+    refs.resize(n);
+    M.chunks.resize(n);
+    for (size_t i = 0; i < n; i++) {
         refs[i].seg_off = sb.seg_off[i];
         refs[i].n_seeds = sb.n_seeds[i];
         refs[i].reserved = 0;
         M.chunks[i].seg = M.chunkSegs.data() + sb.seg_off[i];
         M.chunks[i].n = (int)(sb.seg_off[i + 1] - sb.seg_off[i]);
-        M.chunks[i].offset = meta[i].first;
-        M.chunks[i].inset = meta[i].second;
-        M.chunks[i].ref = chunkRef[i];
+        M.chunks[i].offset = sched.meta[i].first;
+        M.chunks[i].inset = sched.meta[i].second;
+        M.chunks[i].ref = sched.chunkRef[i];
     }
-    // ---- DP_MAP_SHARDS=N: the reference index spread over N contexts (DP_MAP_DEVICES=0,1,..: their GPUs, round robin;
-    // default all on this one) - what BASELINE config 5 does with a 3 Gb reference on 8 GPUs.  Shard s holds the chunks
-    // [c0, c1) (c0 a multiple of 64): their segments (imported from the chunk scan above), posting and seed-set words.  The
-    // sets' global windows are combined here once (include/downpore_hip.h, dp_index_set_global).
-    struct Shard {
-        dp_ctx* ctx = nullptr;
-        uint32_t c0 = 0, c1 = 0;
-    };
-    std::vector<Shard> shards;
-    struct ShardGuard {
-        std::vector<Shard>& v;
-        ~ShardGuard() {
-            for (Shard& sh : v)
-                if (sh.ctx) dp_ctx_destroy(sh.ctx);
-        }
-    } shardGuard{shards};
-    const int nShards = (int)dp_env_long("DP_MAP_SHARDS", 1, 1, INT_MAX);
-    std::vector<int> devs;
+    return 0;
+}
+
+// mapper threads (each with a context of its own) when the index is not sharded
+size_t MapRun::plannedThreads() const {
+    const size_t n = (size_t)dp_env_long("DP_MAP_THREADS", hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3, 1);
+    // (fewer reads than that per thread are not worth a context; the key is a test hook)
+    const size_t perThread = (size_t)std::max(1L, dp_tune("map_min_reads_per_thread", 2048));
+    return std::min(n, std::max<size_t>(1, reads.size() / perThread));
+}
+// device bytes of an index of m chunks as dp_index_info counts them (the dense one without asking the device: its build is still queued)
+int64_t MapRun::indexBytes(dp_ctx* c, uint64_t m) const {
+    const uint64_t S64 = index.seedMap.size();
+    if (!sparseIndex) return (int64_t)(mapDenseBytes(S64, m) + 16 * S64 + (uint64_t)sizeof(dp_seq_ref) * m);
+    dp_index_info_t ii;
+    return dp_index_info(c, &ii) == 0 ? (int64_t)ii.device_bytes : 0;
+}
+
+// ---- the reference index's layout (map_plan.hpp: the dense estimate per device against that device's memory), and where it goes:
+// DP_MAP_SHARDS=N: the reference index spread over N contexts (DP_MAP_DEVICES=0,1,..: their GPUs, round robin; default all on this
+// one) - what BASELINE config 5 does with a 3 Gb reference on 8 GPUs.  With the sparse layout the mapper threads' contexts borrow
+// the one index instead of building their own.
+int MapRun::chooseIndexLayout() {
+    nShards = (int)dp_env_long("DP_MAP_SHARDS", 1, 1, INT_MAX);
     if (const char* e = dp_env_str("DP_MAP_DEVICES")) {
         for (const char* q = e; *q;) {
             devs.push_back(atoi(q));
@@ -1020,432 +1070,352 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
         }
     }
     if (devs.empty()) devs.push_back(device);
-    const uint32_t nChunksAll = (uint32_t)items.size();
-    const uint32_t perShard = ((nChunksAll + (uint32_t)nShards - 1) / (uint32_t)nShards + 63) / 64 * 64;  // whole 64-chunk words
-    // mapper threads (each with a context of its own) when the index is not sharded
-    auto plannedThreads = [&]() -> size_t {
-        const size_t n = (size_t)dp_env_long("DP_MAP_THREADS", hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3, 1);
-        // (fewer reads than that per thread are not worth a context; the key is a test hook)
-        const size_t perThread = (size_t)std::max(1L, dp_tune("map_min_reads_per_thread", 2048));
-        return std::min(n, std::max<size_t>(1, reads.size() / perThread));
-    };
-    // ---- the reference index's layout.  Dense: S x ceil(M/64) + M x ceil(S/64) words per context or shard; the estimate D sums them
-    // per device over every context / shard this run would build there.  Sparse (id lists, ~8 bytes per seed hit) when D exceeds a
-    // device's free memory less an eighth of its total: a run that close could already fail in its later allocations.  With the
-    // sparse layout the mapper threads' contexts borrow the one index instead of building their own.
-    bool sparseIndex = p.indexLayout == 2;
-    const uint64_t S64 = index.seedMap.size();
-    auto denseBytes = [&](uint64_t m) { return S64 * ((m + 63) / 64) * 8 + m * ((S64 + 63) / 64) * 8; };
-    // device bytes of an index of m chunks as dp_index_info counts them (the dense one without asking the device: its build is still queued)
-    auto indexBytes = [&](dp_ctx* c, uint64_t m) -> int64_t {
-        if (!sparseIndex) return (int64_t)(denseBytes(m) + 16 * S64 + (uint64_t)sizeof(dp_seq_ref) * m);
-        dp_index_info_t ii;
-        return dp_index_info(c, &ii) == 0 ? (int64_t)ii.device_bytes : 0;
-    };
-    {
-        std::vector<std::pair<int, uint64_t>> perDev;  // device, dense bytes
-        auto addDev = [&](int d, uint64_t b) {
-            for (auto& pd : perDev)
-                if (pd.first == d) return (void)(pd.second += b);
-            perDev.push_back({d, b});
-        };
-        if (nShards > 1) {
-            size_t i = 0;
-            for (uint32_t c0 = 0; c0 < nChunksAll; c0 += perShard, i++) addDev(devs[i % devs.size()], denseBytes(std::min(nChunksAll, c0 + perShard) - c0));
-        } else {
-            addDev(device, (uint64_t)plannedThreads() * denseBytes(nChunksAll));
-        }
-        uint64_t dTotal = 0;
-        bool over = false;
-        for (auto& pd : perDev) {
-            uint64_t fr = 0, tot = 0;
-            rc = dp_device_memory(pd.first, &fr, &tot);
-            if (rc) return fail(rc);
-            dTotal += pd.second;
-            if (pd.second + tot / 8 > fr) over = true;
-            if (pd.first == device && stats) stats->device_total = (int64_t)tot;
-        }
-        if (p.indexLayout == 0) sparseIndex = over;
-        if (stats) {
-            stats->dense_estimate = (int64_t)dTotal;
-            stats->index_layout = sparseIndex ? 2 : 1;
-            for (const dp_seq_ref& r : refs) stats->hits += r.n_seeds;
-        }
-        if (prof) fprintf(stderr, "[map setup] reference index: dense estimate %.3f GB over %zu device(s) -> %s\n", dTotal / 1e9, perDev.size(), sparseIndex ? "sparse" : "dense");
+    const uint32_t nChunksAll = (uint32_t)sched.items.size();
+    perShard = mapChunksPerShard(nChunksAll, (uint32_t)nShards);  // whole 64-chunk words
+    sparseIndex = p.indexLayout == 2;
+    const std::vector<std::pair<int, uint64_t>> perDev =
+        mapDenseEstimate(index.seedMap.size(), nChunksAll, nShards, perShard, devs, device, nShards > 1 ? 0 : plannedThreads());
+    std::vector<std::pair<uint64_t, uint64_t>> mem(perDev.size());  // free, total
+    for (size_t i = 0; i < perDev.size(); i++) {
+        if (int rc = dp_device_memory(perDev[i].first, &mem[i].first, &mem[i].second)) return failed(ctx.c, rc);
+        if (perDev[i].first == device && stats) stats->device_total = (int64_t)mem[i].second;
     }
-    auto buildIndex = [&](dp_ctx* c, const dp_seq_ref* r, uint32_t n) {
-        const auto tb0 = std::chrono::steady_clock::now();
-        const int rc2 = sparseIndex ? dp_index_build_sparse(c, r, n) : dp_index_build(c, r, n);
-        if (prof) fprintf(stderr, "[map setup] %s index of %u chunks built in %.1f ms\n", sparseIndex ? "sparse" : "dense", n,
-                          1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count());
-        if (rc2 == 0 && stats) {
-            stats->index_bytes += indexBytes(c, n);
-            stats->index_builds++;
-        }
-        return rc2;
-    };
+    uint64_t dTotal = 0;
+    const bool over = mapDenseOverAny(perDev, mem, &dTotal);
+    if (p.indexLayout == 0) sparseIndex = over;
+    if (stats) {
+        stats->dense_estimate = (int64_t)dTotal;
+        stats->index_layout = sparseIndex ? 2 : 1;
+        for (const dp_seq_ref& r : refs) stats->hits += r.n_seeds;
+    }
+    if (prof) fprintf(stderr, "[map setup] reference index: dense estimate %.3f GB over %zu device(s) -> %s\n", dTotal / 1e9, perDev.size(), sparseIndex ? "sparse" : "dense");
+    return 0;
+}
+
+// ---- index build: on the main context, or shard after shard.  Shard s holds the chunks [c0, c1): their segments (imported from the
+// chunk scan), posting and seed-set words.  The sets' global windows are combined here once (map_plan.hpp; include/downpore_hip.h,
+// dp_index_set_global).
+int MapRun::buildIndexOn(dp_ctx* c, const dp_seq_ref* r, uint32_t n) {
+    const auto tb0 = std::chrono::steady_clock::now();
+    const int rc = sparseIndex ? dp_index_build_sparse(c, r, n) : dp_index_build(c, r, n);
+    if (prof) fprintf(stderr, "[map setup] %s index of %u chunks built in %.1f ms\n", sparseIndex ? "sparse" : "dense", n,
+                      1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count());
+    if (rc == 0 && stats) {
+        stats->index_bytes += indexBytes(c, n);
+        stats->index_builds++;
+    }
+    return rc;
+}
+int MapRun::buildShard(Shard& sh, std::vector<uint32_t>& global, std::vector<uint32_t>& local) {
+    const uint32_t S = (uint32_t)index.seedMap.size();
+    dp_ctx* sc = sh.ctx;
+    int rc = dp_round_begin(sc, k, index.seedMap.data(), S);
+    if (rc) return failed(sc, rc);
+    const uint64_t s0 = sb.seg_off[sh.c0], s1 = sb.seg_off[sh.c1];
+    rc = dp_scan_import_segments(sc, M.chunkSegs.data() + s0, s1 - s0);
+    if (rc) return failed(sc, rc);
+    std::vector<dp_seq_ref> lrefs(refs.begin() + sh.c0, refs.begin() + sh.c1);
+    for (dp_seq_ref& r : lrefs) r.seg_off -= s0;
+    rc = buildIndexOn(sc, lrefs.data(), (uint32_t)lrefs.size());
+    if (rc) return failed(sc, rc);
+    rc = dp_index_meta(sc, local.data(), S);
+    if (rc) return failed(sc, rc);
+    mapGlobalWindowsMerge(global, local, S, sh.c0 / 64);
+    return 0;
+}
+int MapRun::buildIndex() {
     if (nShards > 1) {
-        const uint32_t nChunks = nChunksAll, S = (uint32_t)index.seedMap.size();
-        const uint32_t per = perShard;
-        std::vector<uint32_t> global((size_t)S * 4), local((size_t)S * 4);
-        for (uint32_t i = 0; i < S; i++) {  // NewIntSet(): count 0, start 1, end 0 (last + 1 = 1)
-            global[4 * (size_t)i + 0] = 0;
-            global[4 * (size_t)i + 1] = 1;
-            global[4 * (size_t)i + 2] = 0;
-            global[4 * (size_t)i + 3] = 1;
-        }
-        for (uint32_t c0 = 0; c0 < nChunks; c0 += per) {
+        const uint32_t nChunks = (uint32_t)sched.items.size(), S = (uint32_t)index.seedMap.size();
+        std::vector<uint32_t> global, local((size_t)S * 4);
+        mapGlobalWindowsInit(global, S);
+        for (uint32_t c0 = 0; c0 < nChunks; c0 += perShard) {
             Shard sh;
             sh.c0 = c0;
-            sh.c1 = std::min(nChunks, c0 + per);
-            if (dp_ctx_create(devs[shards.size() % devs.size()], &sh.ctx) != 0) {
+            sh.c1 = std::min(nChunks, c0 + perShard);
+            if (dp_ctx_create(devs[shards.v.size() % devs.size()], &sh.ctx) != 0) {
                 error = dp_last_error(nullptr);
-                dp_ctx_destroy(ctx), ctx = nullptr;
                 return DP_ERR_NODEVICE;
             }
-            shards.push_back(sh);
-            dp_ctx* sc = sh.ctx;
-            auto sfail = [&](int rc2) {
-                error = dp_last_error(sc);
-                dp_ctx_destroy(ctx), ctx = nullptr;
-                return rc2;
-            };
-            rc = dp_round_begin(sc, k, index.seedMap.data(), S);
-            if (rc) return sfail(rc);
-            const uint64_t s0 = sb.seg_off[sh.c0], s1 = sb.seg_off[sh.c1];
-            rc = dp_scan_import_segments(sc, M.chunkSegs.data() + s0, s1 - s0);
-            if (rc) return sfail(rc);
-            std::vector<dp_seq_ref> lrefs(refs.begin() + sh.c0, refs.begin() + sh.c1);
-            for (dp_seq_ref& r : lrefs) r.seg_off -= s0;
-            rc = buildIndex(sc, lrefs.data(), (uint32_t)lrefs.size());
-            if (rc) return sfail(rc);
-            rc = dp_index_meta(sc, local.data(), S);
-            if (rc) return sfail(rc);
-            const uint32_t wb = sh.c0 / 64;
-            for (uint32_t i = 0; i < S; i++) {
-                const uint32_t cnt = local[4 * (size_t)i];
-                if (!cnt) continue;
-                uint32_t* g = &global[4 * (size_t)i];
-                const uint32_t st = local[4 * (size_t)i + 1] + wb, en = local[4 * (size_t)i + 2] + wb;
-                if (g[0] == 0) {
-                    g[1] = st;
-                    g[2] = en;
-                } else {
-                    g[1] = std::min(g[1], st);
-                    g[2] = std::max(g[2], en);
-                }
-                g[0] += cnt;
-                g[3] = g[2] + 1;
-            }
+            shards.v.push_back(sh);
+            if (int rc = buildShard(shards.v.back(), global, local)) return rc;
         }
-        for (Shard& sh : shards) {
-            rc = dp_index_set_global(sh.ctx, global.data(), S, sh.c0 / 64, nChunks);
-            if (rc) {
-                error = dp_last_error(sh.ctx);
-                dp_ctx_destroy(ctx), ctx = nullptr;
-                return rc;
-            }
-        }
+        for (Shard& sh : shards.v)
+            if (int rc = dp_index_set_global(sh.ctx, global.data(), S, sh.c0 / 64, nChunks)) return failed(sh.ctx, rc);
     } else {
-        rc = buildIndex(ctx, refs.data(), (uint32_t)refs.size());
-        if (rc) return fail(rc);
+        if (int rc = buildIndexOn(ctx.c, refs.data(), (uint32_t)refs.size())) return failed(ctx.c, rc);
     }
     // dp_scan below reuses the device scan buffer: keep the chunk segments in a dedicated import
     // (dp_index_build references the device-resident scan output, so windows must not overwrite it)
-    if (stats) stats->n_chunks = items.size(), stats->n_seeds = index.seedMap.size();
-
+    if (stats) stats->n_chunks = sched.items.size(), stats->n_seeds = index.seedMap.size();
     mark("round begin + chunk scan + index");
-    // ---- Map every read: coroutines + batched windows.  The reads are dealt to a few host threads in contiguous ranges: every
-    // thread runs this loop on a context of its own (the packed reads are shared, the reference index - half a megabyte of
-    // chunk segments at E. coli scale - is built once per context), so one thread's mapper control flow (mapEnds / mapNext /
-    // findSplitPoint of 4 096 reads in flight) runs while another thread's windows are on the GPU.  Output is per read, in read
-    // order, whatever the thread.  (mapping.go:613-619 MapWorker: the reference does the same with goroutines.)
-    auto wallNow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double tLoop0 = wallNow();
-    if (stats) stats->t_setup_s = tLoop0 - tRun0;
-    std::vector<std::string> out(reads.size());
-    std::vector<int> nmaps(reads.size(), 0);
-    i64 unmapped = 0, mapped = 0, multiple = 0, total = 0;
-    size_t nThreadsPlanned = 1;
-    struct LoopStats {
-        MapStats st;
-        double tScan = 0, tChain = 0, wall = 0;
-        int rc = 0;
-        std::string error;
-    };
-    dp_ctx* const ownerCtx = ctx;  // (owns the reads: the threads ask it how far their upload has come)
-    auto mapLoop = [&](dp_ctx* tctx, MapperImpl& Mt, size_t tIdx, size_t nT, LoopStats& ls) {
-    const double tl0 = wallNow();
-    double tScan = 0, tChain = 0;
-    int rc = 0;
-    MapStats* stats = &ls.st;
-    auto fail = [&](int rc2) {
-        ls.error = dp_last_error(tctx);
-        ls.rc = rc2;
-        return rc2;
-    };
-    dp_ctx* ctx = tctx;
-    MapperImpl& M = Mt;
-    Sched sched;
-    M.sched = &sched;
-    // reads in flight per thread = windows per dp_map_windows call (DP_MAP_INFLIGHT: another number; a coroutine's stack is 256 KiB
-    // of address space, touched pages only)
-    // Measured at config 3 (profiles/r05/map_threads_and_reads_in_flight.txt): 3 threads x 1 365 reads = 120 launches, 20.7 ms of
-    // map_kernel, loops of 60 - 70 ms; 4 x 2 730 = 64 launches, 14.5 ms, loops of 41 - 46 ms; 8 192 and more per thread: fewer launches
-    // still (10.6 ms of kernels) but the threads' control flow no longer fits their caches and runs less beside the GPU's work
-    // and once a context's teardown no longer cost 5 ms, more threads paid: 6 x 2 730 = 78 launches, 18 ms of kernels, a run of 58 - 60 ms
-    // (856 k reads/s) against 64 - 70 ms with 4 x 2 730 and 61 - 70 with 8 x 2 048
-    // round 6, once a context no longer costs a thread 4 ms: 8 x 2 048 runs 46 - 47 ms where 6 x 2 730 runs 50 - 51 (three alternations on
-    // one box, profiles/r06/map_threads_sweep.txt)
-    size_t inflight = nThreadsPlanned >= 8 ? 2048 : std::max<size_t>(2730, 10922 / nThreadsPlanned);
-    inflight = (size_t)dp_env_long("DP_MAP_INFLIGHT", (long)inflight, 64);
-    const size_t stackBytes = 256 * 1024;
+    return 0;
+}
+
+// ---- One mapper thread: coroutines + batched windows.  Every thread runs this loop on a context of its own (the packed reads are
+// shared, the reference index - half a megabyte of chunk segments at E. coli scale - is built once per context), so one thread's
+// mapper control flow (mapEnds / mapNext / findSplitPoint of its reads in flight) runs while another thread's windows are on the
+// GPU.  (mapping.go:613-619 MapWorker: the reference does the same with goroutines.)
+// The reads are dealt in blocks of 1 024: thread t takes blocks t, t + nT, ... - so that every thread finds its first block on the
+// device a fraction of a millisecond into the upload (contiguous shares would leave the last thread waiting for five sixths of it).
+// Output is per read, in read order, whoever mapped it.
+struct MapWorker {
+    static constexpr size_t BL = 1024, stackBytes = 256 * 1024;  // (a coroutine's stack is 256 KiB of address space, touched pages only)
+    MapRun& R;
+    const size_t tIdx, nT;
+    LoopStats& ls;
+    MapperImpl M;
+    size_t inflight = 0;  // reads in flight = windows per dp_map_windows call
     std::vector<std::unique_ptr<Task>> live;
     // coroutine stacks: allocated once (never zero-filled) and recycled — 50 k reads x 256 KiB of fresh zeroed vectors
     // used to be most of the run time
     std::vector<std::unique_ptr<char[]>> stackStore;
     std::vector<char*> freeStacks;
-    // The reads are dealt in blocks of 1 024: thread t takes blocks t, t + nT, ... - so that every thread finds its first block on the
-    // device a fraction of a millisecond into the upload (contiguous shares would leave the last thread waiting for five sixths of it).
-    // Output is per read, in read order, whoever mapped it.
-    const size_t nReads = reads.size(), BL = 1024;
-    size_t myCount = 0;
-    for (size_t blk = tIdx; blk * BL < nReads; blk += nT) myCount += std::min(BL, nReads - blk * BL);
-    auto readOf = [&](size_t seq) { return ((seq / BL) * nT + tIdx) * BL + seq % BL; };
-    size_t nextSeq = 0, waitedBelow = 0;
+    size_t myCount = 0, nextSeq = 0, waitedBelow = 0;
+    // a batch: the live tasks' window requests as scan items (forward, reverse complement), then their segments
     std::vector<dp_scan_item> witems;
     std::vector<int32_t> wsegs;
     std::vector<uint64_t> woff;
     std::vector<uint32_t> wlen;
-    double tp[6] = {0, 0, 0, 0, 0, 0};
-    while (nextSeq < myCount || !live.empty()) {
-        double tq = wallNow();
-        auto lap = [&](int i) {
-            const double t = wallNow();
-            tp[i] += t - tq;
-            tq = t;
-        };
-        while (live.size() < inflight && nextSeq < myCount) {
-            const size_t nextRead = readOf(nextSeq);
-            if (nextRead >= waitedBelow) {  // (the block may still be on its way to the device: dp_reads_upload_rc_begin)
-                const size_t upto = std::min(nReads, (nextRead / BL + 1) * BL);
-                rc = dp_reads_upload_wait(ownerCtx, (uint32_t)(firstPaired + upto));  // (the host reads before them: the reference and its join chunks)
-                if (rc) return fail(rc);
-                waitedBelow = upto;
-            }
-            std::unique_ptr<Task> t(new Task());
-            t->m = &M;
-            t->read = (uint32_t)nextRead;
-            t->L = reads.length(nextRead);
-            if (freeStacks.empty()) {
-                stackStore.emplace_back(new char[stackBytes]);
-                freeStacks.push_back(stackStore.back().get());
-            }
-            t->stack = freeStacks.back();
-            freeStacks.pop_back();
-            coroStart(t->at, t->stack, stackBytes, &coroTrampoline, t.get());
-            nextSeq++;
-            coroSwitch(sched.main, t->at);  // run until the first window request (or completion)
-            live.push_back(std::move(t));
-        }
-        // retire finished tasks
-        for (size_t i = 0; i < live.size();) {
-            if (live[i]->done) {
-                Task& t = *live[i];
-                std::string& o = out[t.read];
-                for (Mapping* mm : t.results) o += M.asString(*mm, reads.names[t.read], t.L) + "\n";
-                nmaps[t.read] = (int)t.results.size();
-                coroRelease(t.at);
-                freeStacks.push_back(t.stack);
-                live[i] = std::move(live.back());
-                live.pop_back();
-            } else {
-                i++;
-            }
-        }
-        lap(0);  // new tasks up to their first window + finished ones retired
-        if (live.empty()) continue;
-        // ---- batch: scan the requested windows (forward, reverse complement) ...
-        witems.clear();
-        for (auto& tp : live) {
-            Task& t = *tp;
-            const WindowReq& q = t.req;
-            const uint32_t fr = firstPaired + 2 * q.read, rr = fr + 1;
-            const i64 L = t.L, wl = q.b - q.a;
-            dp_scan_item f, r;
-            f.read = fr;
-            r.read = rr;
-            f.min_seeds = r.min_seeds = 0;
-            i64 nk = wl - k + 1;
-            if (q.whole && (L % 4) == 0) {
-                // top-level query with finalLen == 0: the forward scan loses 4 k-mers; its ReverseComplement() has
-                // firstLen == 0 and the scan starts 4 bases in (sequence.go:196, asm:109-132) — fixed up below
-                f.start = 0;
-                f.n_kmers = (uint32_t)std::max<i64>(0, nk - 4);
-                r.start = 4;
-                r.n_kmers = (uint32_t)std::max<i64>(0, nk - 4);
-            } else {
-                f.start = (uint32_t)q.a;
-                f.n_kmers = (uint32_t)std::max<i64>(0, nk);
-                r.start = (uint32_t)(L - q.b);
-                r.n_kmers = (uint32_t)std::max<i64>(0, nk);
-            }
-            witems.push_back(f);
-            witems.push_back(r);
-        }
-        // the chunk segments live in the device scan buffer; window scans must not clobber them -> the window scan uses a
-        // second context-independent path: scan, then re-import the chunk segments before the map stage
-        lap(1);  // window items
-        dp_seedseq_batch wb;
-        const double ts0 = wallNow();
-        rc = dp_scan(ctx, witems.data(), (uint32_t)witems.size(), &wb);
-        if (rc) return fail(rc);
-        tScan += wallNow() - ts0;
-        if (stats) {
-            stats->k_scan_ms += wb.kernel_ms, stats->n_windows += witems.size() / 2;
-            for (const dp_scan_item& wi : witems) stats->scan_bytes += (double)((wi.n_kmers + 3) / 4);  // packed bases of the window, both strands
-        }
-        wsegs.clear();
-        woff.assign(1, 0);
-        wlen.clear();
-        for (size_t w = 0; w < witems.size(); w++) {
-            Task& t = *live[w / 2];
-            const bool rcside = (w & 1) != 0;
-            const size_t base = wsegs.size();
-            wsegs.insert(wsegs.end(), wb.segs + wb.seg_off[w], wb.segs + wb.seg_off[w + 1]);
-            if (rcside && t.req.whole && (t.L % 4) == 0) {
-                // firstLen==0 quirk: k-mer index 0 duplicates the k-mer at base 4, every later index is shifted by one
-                int32_t* sg = wsegs.data() + base;
-                const size_t n = wsegs.size() - base;
-                if (n >= 3 && sg[0] == 0) {  // the duplicated k-mer is a seed: it appears twice, 1-k apart
-                    std::vector<int32_t> fix;
-                    fix.push_back(0);
-                    fix.push_back(sg[1]);
-                    fix.push_back(1 - k);
-                    fix.insert(fix.end(), sg + 1, sg + n);
-                    wsegs.resize(base);
-                    wsegs.insert(wsegs.end(), fix.begin(), fix.end());
-                } else {
-                    sg[0] += 1;  // all indices shift by one (no hits: the single gap counts the extra k-mer too)
-                }
-            }
-            woff.push_back(wsegs.size());
-            wlen.push_back((uint32_t)(t.req.b - t.req.a));
-        }
-        for (auto& tp : live) {
-            tp->res.seg[0].clear();
-            tp->res.seg[1].clear();
-            tp->res.chains[0].clear();
-            tp->res.chains[1].clear();
-        }
-        for (size_t w = 0; w < witems.size(); w++)
-            live[w / 2]->res.seg[w & 1].assign(wsegs.begin() + (i64)woff[w], wsegs.begin() + (i64)woff[w + 1]);
-        tq = ts0 + (wallNow() - ts0);  // (the scan call itself is tScan)
-        tp[3] += wallNow() - ts0;      // scan call + copying its segments out
-        auto takeChains = [&](const dp_chain_batch& cb, uint32_t chunkBase) {
-            for (uint32_t c = 0; c < cb.n_chains; c++) {
-                const uint32_t w = cb.window[c];
-                WindowResult::ChainRef cr;
-                cr.target = cb.target[c] + chunkBase;
-                cr.a.assign(cb.match_a + cb.off[c], cb.match_a + cb.off[c + 1]);
-                cr.b.assign(cb.match_b + cb.off[c], cb.match_b + cb.off[c + 1]);
-                live[w / 2]->res.chains[w & 1].push_back(std::move(cr));
-            }
-            if (stats) stats->k_map_ms += cb.kernel_ms, stats->n_chains += cb.n_chains, stats->map_bytes += cb.alg_bytes;
-        };
-        tq = wallNow();
-        lap(2);
-        const double tc0 = wallNow();
-        if (shards.empty()) {
-            if (!sparseIndex) {  // (the sparse index holds its own copy of the chunk segments)
-                rc = dp_scan_import_segments(ctx, M.chunkSegs.data(), M.chunkSegs.size());
-                if (rc) return fail(rc);
-            }
-            dp_chain_batch cb;
-            rc = dp_map_windows(ctx, wsegs.data(), woff.data(), wlen.data(), (uint32_t)witems.size(), k, &cb);
-            if (rc) return fail(rc);
-            takeChains(cb, 0);
-        } else {
-            // candidates of a window in ascending chunk id = shard after shard; forward strand over all shards first, its
-            // ratchet raises the reverse threshold too (mapping.go:543-549): the thresholds travel with the batch
-            std::vector<int32_t> thr(witems.size(), -1);
-            for (int phase = 0; phase < 2; phase++)
-                for (Shard& sh : shards) {
-                    dp_chain_batch cb;
-                    rc = dp_map_windows_shard(sh.ctx, wsegs.data(), woff.data(), wlen.data(), (uint32_t)witems.size(), k, phase, thr.data(), &cb);
-                    if (rc) {
-                        ls.error = dp_last_error(sh.ctx);
-                        ls.rc = rc;
-                        return rc;
-                    }
-                    takeChains(cb, sh.c0);
-                }
-        }
-        tChain += wallNow() - tc0;
-        if (stats) stats->n_batches++;
-        tq = wallNow();
-        // ---- ... distribute and resume
-        for (auto& tk : live) coroSwitch(sched.main, tk->at);
-        lap(4);  // coroutines resumed: performMapping's tail + the mapper's control flow up to the next window
+    double tStart = 0, tItems = 0, tScanCopy = 0, tResume = 0;  // the loop's phases, for the profile line
+
+    MapWorker(MapRun& run, size_t t, size_t n) : R(run), tIdx(t), nT(n), ls(run.lstats[t]), M(run.M) {}
+    int failed(dp_ctx* c, int rc) {
+        ls.error = dp_last_error(c);
+        ls.rc = rc;
+        return rc;
     }
-    if (prof)
+    size_t readOf(size_t seq) const { return ((seq / BL) * nT + tIdx) * BL + seq % BL; }
+    void run();
+    int openContext(double tt0);
+    int loop();
+    int startTasks();
+    void retireTasks();
+    void windowItems();
+    int scanWindows();
+    void takeChains(const dp_chain_batch& cb, uint32_t chunkBase);
+    int chainWindows();
+};
+
+void MapWorker::run() {
+    const double tt0 = wallNow();
+    M.ctx = R.ctx.c;
+    if (tIdx > 0 && openContext(tt0) != 0) return;
+    const double tt1 = wallNow();
+    loop();
+    if (R.prof)
+        fprintf(stderr, "[map thread %zu] context + index %.1f ms, loop %.1f (its own clock %.1f), from the loops' start to this thread's end %.1f\n", tIdx, 1e3 * (tt1 - tt0),
+                1e3 * (wallNow() - tt1), 1e3 * ls.wall, 1e3 * (wallNow() - R.tLoop0));
+}
+// a context of its own: shared packed reads, the same seeds, the reference index from the run's chunk scan
+int MapWorker::openContext(double tt0) {
+    dp_ctx*& tc = R.workers.v[tIdx];
+    int rc = dp_ctx_create_shared(R.ctx.c, &tc);
+    const double ta = wallNow();
+    if (rc == 0) rc = dp_round_begin(tc, R.k, R.index.seedMap.data(), (uint32_t)R.index.seedMap.size());
+    const double tb = wallNow();
+    if (rc == 0 && !R.sparseIndex) rc = dp_scan_import_segments(tc, R.M.chunkSegs.data(), R.M.chunkSegs.size());
+    const double tc0 = wallNow();
+    if (rc == 0 && R.sparseIndex) rc = dp_index_borrow(tc, R.ctx.c);  // (the one sparse index, read-only)
+    else if (rc == 0) rc = dp_index_build(tc, R.refs.data(), (uint32_t)R.refs.size());
+    if (rc == 0 && !R.sparseIndex && R.stats) {
+        std::lock_guard<std::mutex> lk(R.infoMu);
+        R.stats->index_bytes += R.indexBytes(tc, R.refs.size());
+        R.stats->index_builds++;
+    }
+    if (R.prof) fprintf(stderr, "[map thread %zu] context %.2f ms, round begin %.2f, import %.2f, index %.2f\n", tIdx, 1e3 * (ta - tt0), 1e3 * (tb - ta), 1e3 * (tc0 - tb), 1e3 * (wallNow() - tc0));
+    if (rc != 0) {
+        ls.rc = rc;
+        ls.error = tc ? dp_last_error(tc) : dp_last_error(nullptr);
+        return rc;
+    }
+    M.ctx = tc;
+    return 0;
+}
+
+// Reads in flight per thread (DP_MAP_INFLIGHT: another number).
+// Measured at config 3 (profiles/r05/map_threads_and_reads_in_flight.txt): 3 threads x 1 365 reads = 120 launches, 20.7 ms of
+// map_kernel, loops of 60 - 70 ms; 4 x 2 730 = 64 launches, 14.5 ms, loops of 41 - 46 ms; 8 192 and more per thread: fewer launches
+// still (10.6 ms of kernels) but the threads' control flow no longer fits their caches and runs less beside the GPU's work
+// and once a context's teardown no longer cost 5 ms, more threads paid: 6 x 2 730 = 78 launches, 18 ms of kernels, a run of 58 - 60 ms
+// (856 k reads/s) against 64 - 70 ms with 4 x 2 730 and 61 - 70 with 8 x 2 048
+// once a context no longer costs a thread 4 ms: 8 x 2 048 runs 46 - 47 ms where 6 x 2 730 runs 50 - 51 (three alternations on
+// one box, profiles/r06/map_threads_sweep.txt)
+int MapWorker::loop() {
+    const double tl0 = wallNow();
+    inflight = nT >= 8 ? 2048 : std::max<size_t>(2730, 10922 / nT);
+    inflight = (size_t)dp_env_long("DP_MAP_INFLIGHT", (long)inflight, 64);
+    const size_t nReads = R.reads.size();
+    for (size_t blk = tIdx; blk * BL < nReads; blk += nT) myCount += std::min(BL, nReads - blk * BL);
+    while (nextSeq < myCount || !live.empty()) {
+        const double t0 = wallNow();
+        if (int rc = startTasks()) return rc;
+        retireTasks();
+        const double t1 = wallNow();
+        tStart += t1 - t0;  // new tasks up to their first window + finished ones retired
+        if (live.empty()) continue;
+        windowItems();
+        const double t2 = wallNow();
+        tItems += t2 - t1;
+        if (int rc = scanWindows()) return rc;
+        const double t3 = wallNow();
+        tScanCopy += t3 - t2;  // scan call + copying its segments out
+        if (int rc = chainWindows()) return rc;
+        const double t4 = wallNow();
+        ls.tChain += t4 - t3;
+        for (auto& tk : live) coroSwitch(M.sched.main, tk->at);  // distribute and resume
+        tResume += wallNow() - t4;  // performMapping's tail + the mapper's control flow up to the next window
+    }
+    if (R.prof)
         fprintf(stderr, "[map loop] thread %zu of %zu: start/retire + upload waits %.1f ms, items %.1f, scan+copy %.1f (scan call %.1f), map call %.1f, resume %.1f\n", tIdx, nT,
-                1e3 * tp[0], 1e3 * tp[1], 1e3 * tp[3], 1e3 * tScan, 1e3 * tChain, 1e3 * tp[4]);
-    ls.tScan = tScan;
-    ls.tChain = tChain;
+                1e3 * tStart, 1e3 * tItems, 1e3 * tScanCopy, 1e3 * ls.tScan, 1e3 * ls.tChain, 1e3 * tResume);
     ls.wall = wallNow() - tl0;
     return 0;
-    };  // mapLoop
-
-    size_t nThreads = 1;
-    if (shards.empty()) nThreads = plannedThreads();
-    nThreadsPlanned = nThreads;
-    std::vector<LoopStats> lstats(nThreads);
-    std::vector<dp_ctx*> tctx(nThreads, nullptr);
-    std::mutex infoMu;
-    std::vector<MapperImpl> Ms(nThreads, M);  // (chunks[i].seg keep pointing into M.chunkSegs, which outlives the threads)
-    tctx[0] = ctx;
-    {
-        std::vector<std::thread> th;
-        for (size_t t = 0; t < nThreads; t++) {
-            th.emplace_back([&, t] {
-                LoopStats& ls = lstats[t];
-                const double tt0 = wallNow();
-                if (t > 0) {  // a context of its own: shared packed reads, the same seeds, the reference index from the chunk scan above
-                    int rc2 = dp_ctx_create_shared(ctx, &tctx[t]);
-                    const double ta = wallNow();
-                    if (rc2 == 0) rc2 = dp_round_begin(tctx[t], k, index.seedMap.data(), (uint32_t)index.seedMap.size());
-                    const double tb = wallNow();
-                    if (rc2 == 0 && !sparseIndex) rc2 = dp_scan_import_segments(tctx[t], M.chunkSegs.data(), M.chunkSegs.size());
-                    const double tc = wallNow();
-                    if (rc2 == 0 && sparseIndex) rc2 = dp_index_borrow(tctx[t], ctx);  // (the one sparse index, read-only)
-                    else if (rc2 == 0) rc2 = dp_index_build(tctx[t], refs.data(), (uint32_t)refs.size());
-                    if (rc2 == 0 && !sparseIndex && stats) {
-                        std::lock_guard<std::mutex> lk(infoMu);
-                        stats->index_bytes += indexBytes(tctx[t], refs.size());
-                        stats->index_builds++;
-                    }
-                    if (prof) fprintf(stderr, "[map thread %zu] context %.2f ms, round begin %.2f, import %.2f, index %.2f\n", t, 1e3 * (ta - tt0), 1e3 * (tb - ta), 1e3 * (tc - tb), 1e3 * (wallNow() - tc));
-                    if (rc2 != 0) {
-                        ls.rc = rc2;
-                        ls.error = tctx[t] ? dp_last_error(tctx[t]) : dp_last_error(nullptr);
-                        return;
-                    }
-                }
-                Ms[t].ctx = tctx[t];
-                const double tt1 = wallNow();
-                mapLoop(tctx[t], Ms[t], t, nThreads, ls);
-                if (prof)
-                    fprintf(stderr, "[map thread %zu] context + index %.1f ms, loop %.1f (its own clock %.1f), from the loops' start to this thread's end %.1f\n", t, 1e3 * (tt1 - tt0),
-                            1e3 * (wallNow() - tt1), 1e3 * ls.wall, 1e3 * (wallNow() - tLoop0));
-            });
+}
+// new read tasks up to `inflight`, each run to its first window request (or completion)
+int MapWorker::startTasks() {
+    const size_t nReads = R.reads.size();
+    while (live.size() < inflight && nextSeq < myCount) {
+        const size_t nextRead = readOf(nextSeq);
+        if (nextRead >= waitedBelow) {  // (the block may still be on its way to the device: dp_reads_upload_rc_begin)
+            const size_t upto = std::min(nReads, (nextRead / BL + 1) * BL);
+            // the main context owns the reads: the threads ask it how far their upload has come (the host reads before them: the
+            // reference and its join chunks)
+            if (int rc = dp_reads_upload_wait(R.ctx.c, (uint32_t)(R.J.firstPaired + upto))) return failed(M.ctx, rc);
+            waitedBelow = upto;
         }
+        std::unique_ptr<Task> t(new Task());
+        t->m = &M;
+        t->read = (uint32_t)nextRead;
+        t->L = R.reads.length(nextRead);
+        if (freeStacks.empty()) {
+            stackStore.emplace_back(new char[stackBytes]);
+            freeStacks.push_back(stackStore.back().get());
+        }
+        t->stack = freeStacks.back();
+        freeStacks.pop_back();
+        coroStart(t->at, t->stack, stackBytes, &coroTrampoline, t.get());
+        nextSeq++;
+        coroSwitch(M.sched.main, t->at);
+        live.push_back(std::move(t));
+    }
+    return 0;
+}
+void MapWorker::retireTasks() {
+    for (size_t i = 0; i < live.size();) {
+        if (live[i]->done) {
+            Task& t = *live[i];
+            std::string& o = R.out[t.read];
+            for (Mapping* mm : t.results) o += M.asString(*mm, R.reads.names[t.read], t.L) + "\n";
+            R.nmaps[t.read] = (int)t.results.size();
+            coroRelease(t.at);
+            freeStacks.push_back(t.stack);
+            live[i] = std::move(live.back());
+            live.pop_back();
+        } else {
+            i++;
+        }
+    }
+}
+void MapWorker::windowItems() {
+    witems.clear();
+    for (auto& tk : live) {
+        const WindowReq& q = tk->req;
+        dp_scan_item f, r;
+        mapWindowItems(R.J.firstPaired, q.read, tk->L, q.a, q.b, q.whole, R.k, f, r);
+        witems.push_back(f);
+        witems.push_back(r);
+    }
+}
+// scan the requested windows and hand every task its two seed sequences
+int MapWorker::scanWindows() {
+    dp_seedseq_batch wb;
+    const double ts0 = wallNow();
+    if (int rc = dp_scan(M.ctx, witems.data(), (uint32_t)witems.size(), &wb)) return failed(M.ctx, rc);
+    ls.tScan += wallNow() - ts0;
+    ls.st.k_scan_ms += wb.kernel_ms, ls.st.n_windows += witems.size() / 2;
+    for (const dp_scan_item& wi : witems) ls.st.scan_bytes += (double)((wi.n_kmers + 3) / 4);  // packed bases of the window, both strands
+    wsegs.clear();
+    woff.assign(1, 0);
+    wlen.clear();
+    for (size_t w = 0; w < witems.size(); w++) {
+        Task& t = *live[w / 2];
+        const size_t base = wsegs.size();
+        wsegs.insert(wsegs.end(), wb.segs + wb.seg_off[w], wb.segs + wb.seg_off[w + 1]);
+        if (mapReverseNeedsFix((w & 1) != 0, t.req.whole, t.L)) mapFixReverseWhole(wsegs, base, R.k);
+        woff.push_back(wsegs.size());
+        wlen.push_back((uint32_t)(t.req.b - t.req.a));
+    }
+    for (auto& tk : live) {
+        tk->res.seg[0].clear();
+        tk->res.seg[1].clear();
+        tk->res.chains[0].clear();
+        tk->res.chains[1].clear();
+    }
+    for (size_t w = 0; w < witems.size(); w++)
+        live[w / 2]->res.seg[w & 1].assign(wsegs.begin() + (i64)woff[w], wsegs.begin() + (i64)woff[w + 1]);
+    return 0;
+}
+void MapWorker::takeChains(const dp_chain_batch& cb, uint32_t chunkBase) {
+    for (uint32_t c = 0; c < cb.n_chains; c++) {
+        const uint32_t w = cb.window[c];
+        WindowResult::ChainRef cr;
+        cr.target = cb.target[c] + chunkBase;
+        cr.a.assign(cb.match_a + cb.off[c], cb.match_a + cb.off[c + 1]);
+        cr.b.assign(cb.match_b + cb.off[c], cb.match_b + cb.off[c + 1]);
+        live[w / 2]->res.chains[w & 1].push_back(std::move(cr));
+    }
+    ls.st.k_map_ms += cb.kernel_ms, ls.st.n_chains += cb.n_chains, ls.st.map_bytes += cb.alg_bytes;
+}
+// the candidate / chaining stage of the batch: on this thread's context, or shard after shard
+int MapWorker::chainWindows() {
+    const uint32_t nW = (uint32_t)witems.size();
+    if (R.shards.v.empty()) {
+        // the window scan has reused the device scan buffer the dense index's chunk segments lived in: they are imported again
+        // before the map stage (the sparse index holds its own copy of the chunk segments)
+        if (!R.sparseIndex)
+            if (int rc = dp_scan_import_segments(M.ctx, R.M.chunkSegs.data(), R.M.chunkSegs.size())) return failed(M.ctx, rc);
+        dp_chain_batch cb;
+        if (int rc = dp_map_windows(M.ctx, wsegs.data(), woff.data(), wlen.data(), nW, R.k, &cb)) return failed(M.ctx, rc);
+        takeChains(cb, 0);
+    } else {
+        // candidates of a window in ascending chunk id = shard after shard; forward strand over all shards first, its
+        // ratchet raises the reverse threshold too (mapping.go:543-549): the thresholds travel with the batch
+        std::vector<int32_t> thr(witems.size(), -1);
+        for (int phase = 0; phase < 2; phase++)
+            for (Shard& sh : R.shards.v) {
+                dp_chain_batch cb;
+                if (int rc = dp_map_windows_shard(sh.ctx, wsegs.data(), woff.data(), wlen.data(), nW, R.k, phase, thr.data(), &cb)) return failed(sh.ctx, rc);
+                takeChains(cb, sh.c0);
+            }
+    }
+    ls.st.n_batches++;
+    return 0;
+}
+
+// ---- Map every read: the reads are dealt to a few host threads; the first works on the main context
+int MapRun::runWorkers() {
+    tLoop0 = wallNow();
+    if (stats) stats->t_setup_s = tLoop0 - tRun0;
+    out.assign(reads.size(), std::string());
+    nmaps.assign(reads.size(), 0);
+    nThreads = shards.v.empty() ? plannedThreads() : 1;
+    lstats.assign(nThreads, LoopStats());
+    workers.v.assign(nThreads, nullptr);
+    {
+        std::vector<std::unique_ptr<MapWorker>> ws;
+        for (size_t t = 0; t < nThreads; t++) ws.emplace_back(new MapWorker(*this, t, nThreads));
+        std::vector<std::thread> th;
+        for (size_t t = 0; t < nThreads; t++) th.emplace_back([&ws, t] { ws[t]->run(); });
         for (auto& t : th) t.join();
     }
     if (stats) {  // queries per regime: every thread's context, or one shard (every shard answers every window)
         std::vector<dp_ctx*> qc;
-        if (shards.empty()) qc = tctx;
-        else qc.push_back(shards[0].ctx);
+        if (shards.v.empty()) {
+            qc = workers.v;
+            qc[0] = ctx.c;
+        } else {
+            qc.push_back(shards.v[0].ctx);
+        }
         for (dp_ctx* c : qc) {
             dp_index_info_t ii;
             if (c && dp_index_info(c, &ii) == 0)
@@ -1453,33 +1423,43 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
         }
     }
     const double tJoin = wallNow();
-    for (size_t t = 1; t < nThreads; t++)
-        if (tctx[t]) dp_ctx_destroy(tctx[t]);
+    workers.destroy();
     if (prof) fprintf(stderr, "[map end] threads joined at %.1f ms after the loops' start, their contexts destroyed in %.1f\n", 1e3 * (tJoin - tLoop0), 1e3 * (wallNow() - tJoin));
     for (size_t t = 0; t < nThreads; t++)
         if (lstats[t].rc != 0) {
             error = lstats[t].error;
-            dp_ctx_destroy(ctx), ctx = nullptr;
             return lstats[t].rc;
         }
-    if (stats) {
-        double tScan = 0, tChain = 0;
-        for (const LoopStats& ls : lstats) {
-            stats->k_scan_ms += ls.st.k_scan_ms;
-            stats->k_map_ms += ls.st.k_map_ms;
-            stats->map_bytes += ls.st.map_bytes;
-            stats->scan_bytes += ls.st.scan_bytes;
-            stats->n_windows += ls.st.n_windows;
-            stats->n_chains += ls.st.n_chains;
-            stats->n_batches += ls.st.n_batches;
-            tScan += ls.tScan / (double)nThreads;   // (means over the threads, which run side by side)
-            tChain += ls.tChain / (double)nThreads;
-        }
-        stats->t_scan_s = tScan;
-        stats->t_chain_s = tChain;
-        stats->t_host_s = (wallNow() - tLoop0) - tScan - tChain;
+    return 0;
+}
+
+void MapRun::collectStats() {
+    if (!stats) return;
+    double tScan = 0, tChain = 0;
+    for (const LoopStats& ls : lstats) {
+        stats->k_scan_ms += ls.st.k_scan_ms;
+        stats->k_map_ms += ls.st.k_map_ms;
+        stats->map_bytes += ls.st.map_bytes;
+        stats->scan_bytes += ls.st.scan_bytes;
+        stats->n_windows += ls.st.n_windows;
+        stats->n_chains += ls.st.n_chains;
+        stats->n_batches += ls.st.n_batches;
+        tScan += ls.tScan / (double)nThreads;   // (means over the threads, which run side by side)
+        tChain += ls.tChain / (double)nThreads;
     }
-    const double tText0 = wallNow();
+    stats->t_scan_s = tScan;
+    stats->t_chain_s = tChain;
+    stats->t_host_s = (wallNow() - tLoop0) - tScan - tChain;
+}
+
+void MapRun::writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped) {
+    char line[160];
+    snprintf(line, sizeof line, "Uniquely mapped: %lld\nMultiple mappings: %lld\ntotal: %lld\nUnmapped: %lld\n", (long long)mapped,
+             (long long)multiple, (long long)total, (long long)unmapped);
+    errText += line;
+}
+void MapRun::writeText() {
+    i64 unmapped = 0, mapped = 0, multiple = 0, total = 0;
     for (size_t r = 0; r < reads.size(); r++) {
         paf += out[r];
         if (nmaps[r] > 0) {
@@ -1490,13 +1470,40 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
             unmapped++;
         }
     }
-    char line[160];
-    snprintf(line, sizeof line, "Uniquely mapped: %lld\nMultiple mappings: %lld\ntotal: %lld\nUnmapped: %lld\n", (long long)mapped,
-             (long long)multiple, (long long)total, (long long)unmapped);
-    errText += line;
+    writeCounts(mapped, multiple, total, unmapped);
+}
+
+}  // namespace
+
+// The whole `map` command as its steps in order.  MapRun's owners make every `return rc` below complete: they go in the order worker
+// contexts, shard contexts, upload wait + staging block, seed-walk thread, main context, packing thread, pinned block.
+int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int device, std::string& paf, std::string& errText,
+           MapStats* stats, std::string& error, MapTrim* trim) {
+    MapRun R(refSet, upSet, p, device, paf, errText, stats, error, trim);
+    int rc;
+    if ((rc = R.check())) return rc;
+    R.layoutAndStage();
+    if ((rc = R.allocBlocks())) return rc;
+    R.concat.t = std::thread([&R] { R.packOrConcatenate(); });
+    if ((rc = R.openContext())) return rc;
+    if ((rc = R.startSeedWalk())) return rc;
+    if ((rc = R.uploadReads())) return rc;
+    if (trim && (rc = R.trimAndRespan())) return rc;
+    if ((rc = R.scanChunks())) return rc;
+    if (R.sched.items.empty()) {  // no sequence is long enough for a chunk: an empty index matches nothing, every read is unmapped
+        if (stats) stats->n_seeds = R.index.seedMap.size(), stats->t_setup_s = wallNow() - R.tRun0;
+        R.writeCounts(0, 0, 0, (i64)R.reads.size());
+        return 0;
+    }
+    if ((rc = R.chooseIndexLayout())) return rc;
+    if ((rc = R.buildIndex())) return rc;
+    if ((rc = R.runWorkers())) return rc;
+    R.collectStats();
+    const double tText0 = wallNow();
+    R.writeText();
     const double tEnd0 = wallNow();
-    dp_ctx_destroy(ctx), ctx = nullptr;
-    if (prof) fprintf(stderr, "[map end] text joined in %.1f ms, context destroyed in %.1f, whole run %.1f\n", 1e3 * (tEnd0 - tText0), 1e3 * (wallNow() - tEnd0), 1e3 * (wallNow() - tRun0));
+    R.ctx.destroy();  // (before the timing line: the owners would do it just as well)
+    if (R.prof) fprintf(stderr, "[map end] text joined in %.1f ms, context destroyed in %.1f, whole run %.1f\n", 1e3 * (tEnd0 - tText0), 1e3 * (wallNow() - tEnd0), 1e3 * (wallNow() - R.tRun0));
     return 0;
 }
 
