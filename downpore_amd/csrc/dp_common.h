@@ -75,6 +75,10 @@ struct dp_ctx {
     bool stream_priority_set = false;  // (dp_ctx_set_priority: such a stream is destroyed with its context instead of being parked)
     std::string err;
     bool borrowed_reads = false;  // d_packed/d_boff/d_len belong to another context
+    // the read set's epoch: the owner's is bumped by every upload, respan and tail replace; a borrower holds the one its copies of the
+    // read-set fields were taken at (dp_ctx_create_shared, dp_ctx_refresh_shared) and is refused while the two differ (dp_reads_stale)
+    std::atomic<uint64_t> reads_epoch{0};
+    uint64_t seen_epoch = 0;
     struct ReadsUpload;           // a read set still on its way to the device (dp_reads_upload_rc_begin, dp_scan.hip)
     std::shared_ptr<ReadsUpload> upload;  // (under upload_mu: a borrower's wait holds its own reference while the owner's final wait lets go)
     std::mutex upload_mu;
@@ -196,6 +200,9 @@ struct dp_ctx {
 };
 
 int dp_fail(dp_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess);
+// 0, or DP_ERR_STATE for a borrowing context whose owner's read set has changed since it last copied the read-set fields: its
+// addresses may name freed memory, so every entry point that reads bases through a context asks this before it launches anything
+int dp_reads_stale(dp_ctx* ctx, const char* who);
 // Waits for everything queued on the context's stream.  The host thread blocks on an interrupt (several executor
 // contexts share few host cores); DP_SPIN_SYNC=1 restores the runtime's polling wait.
 hipError_t dp_stream_sync(dp_ctx* ctx);

@@ -144,6 +144,12 @@ int dp_fail(dp_ctx* ctx, int code, const char* what, hipError_t e) {
     return code;
 }
 
+int dp_reads_stale(dp_ctx* ctx, const char* who) {
+    if (!ctx->owner || ctx->seen_epoch == ctx->owner->reads_epoch.load()) return 0;
+    const std::string msg = std::string(who) + ": the owner's read set has changed since this context copied it; call dp_ctx_refresh_shared first";
+    return dp_fail(ctx, DP_ERR_STATE, msg.c_str());
+}
+
 // Growing a buffer: twice the request (rounds vary in size and every growth is a hipMalloc / hipHostMalloc of megabytes),
 // and the outgrown buffer is NOT freed here - hipFree / hipHostFree wait for the whole device, i.e. for every other
 // executor slot's kernels, which showed up as 20-30 ms stalls a few times per hundred rounds.  Old buffers go to the
@@ -581,6 +587,32 @@ extern "C" int dp_ctx_create_shared(dp_ctx* src, dp_ctx** out) {
     c->d_qual = src->d_qual;
     c->d_qualoff = src->d_qualoff;
     c->d_hasq = src->d_hasq;
+    c->seen_epoch = src->owner ? src->seen_epoch : src->reads_epoch.load();
+    return DP_OK;
+}
+
+// The read-set fields of a borrowing context copied from its owner again, with the owner's epoch (dp_reads_replace_tail_packed_rc may
+// have moved the blocks).  What the borrower cached per read set is void; its round (seeds), imported segments and reference index -
+// built or borrowed - stay.  Not while the owner's read set is being changed: the caller orders the two, as it orders a replace
+// against the borrowers' launches.
+extern "C" int dp_ctx_refresh_shared(dp_ctx* ctx) {
+    if (!ctx) return DP_ERR_ARG;
+    dp_ctx* const src = ctx->owner;
+    if (!src) return dp_fail(ctx, DP_ERR_STATE, "dp_ctx_refresh_shared on a context that borrows no reads");
+    ctx->n_reads = src->n_reads;
+    ctx->total_bases = src->total_bases;
+    ctx->packed_bytes = src->packed_bytes;
+    ctx->d_packed = src->d_packed;
+    ctx->d_boff = src->d_boff;
+    ctx->d_len = src->d_len;
+    ctx->h_boff = src->h_boff;
+    ctx->h_len = src->h_len;
+    ctx->d_qual = src->d_qual;
+    ctx->d_qualoff = src->d_qualoff;
+    ctx->d_hasq = src->d_hasq;
+    ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
+    ctx->items_ptr = nullptr;
+    ctx->seen_epoch = src->reads_epoch.load();
     return DP_OK;
 }
 
@@ -903,6 +935,7 @@ static int reads_upload_prepare(dp_ctx* ctx, const uint8_t* bases, const int64_t
             }
     }
     ctx->n_reads = n_reads;
+    ctx->reads_epoch++;
     ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
     ctx->items_ptr = nullptr;
     ctx->h_boff.swap(h_boff);
@@ -1048,6 +1081,7 @@ extern "C" int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t 
             qb->cap = 0;
         }
     ctx->n_reads = n_out;
+    ctx->reads_epoch++;
     ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
     ctx->items_ptr = nullptr;
     ctx->h_boff.swap(h_boff);
@@ -1065,20 +1099,23 @@ extern "C" int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t 
 // place_packed_kernel: one thread per dword of the device layout.  Forward reads are copied; 16 bases of a reverse strand are the
 // 16 bases of the forward strand that end at len - 1 - base0, their order reversed (byte swap, nibble swap, pair swap) and
 // complemented (3 - code = every bit inverted), bases beyond the read's end zero as everywhere in the layout.
+// A whole upload places the dwords [0, n_dwords) of the device reads [0, n_reads).  A tail replace (dp_reads_replace_tail_packed_rc)
+// places only [d_begin, n_dwords) with d_begin = boff[first_read] / 4: the search never looks below first_read, nothing before
+// d_begin is written, and the host block and srcmap hold the tail alone (srcmap[lo - first_read]: host read << 1 | reverse).
 __global__ void place_packed_kernel(const uint32_t* __restrict__ src, const uint64_t* __restrict__ soff, const uint32_t* __restrict__ slen,
                                     const uint64_t* __restrict__ boff, uint32_t n_reads, uint32_t* __restrict__ packed, uint64_t n_dwords,
-                                    const uint32_t* __restrict__ srcmap) {
-    const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                    const uint32_t* __restrict__ srcmap, uint64_t d_begin, uint32_t first_read) {
+    const uint64_t d = d_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n_dwords) return;
     const uint64_t byte = d * 4;
-    uint32_t lo = 0, hi = n_reads;
+    uint32_t lo = first_read, hi = n_reads;
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
         if (boff[mid] <= byte) lo = mid;
         else hi = mid;
     }
-    const uint32_t src_read = srcmap ? (srcmap[lo] >> 1) : lo;
-    const bool rc = srcmap ? (srcmap[lo] & 1u) != 0 : false;
+    const uint32_t src_read = srcmap ? (srcmap[lo - first_read] >> 1) : lo - first_read;
+    const bool rc = srcmap ? (srcmap[lo - first_read] & 1u) != 0 : false;
     const int64_t len = (int64_t)slen[src_read];
     const uint64_t rel = byte - boff[lo];              // byte of the read this dword starts at
     const uint64_t sbytes = ((uint64_t)len + 3) / 4;   // packed bytes of the read
@@ -1170,9 +1207,124 @@ extern "C" int dp_reads_upload_packed_rc(dp_ctx* ctx, const uint8_t* packed, con
     const uint64_t n_dwords = P.pos / 4;
     hipLaunchKernelGGL(place_packed_kernel, dim3((uint32_t)((n_dwords + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)T.d_src,
                        (const uint64_t*)T.d_soff, (const uint32_t*)T.d_slen, (const uint64_t*)ctx->d_boff.p, P.n_reads, (uint32_t*)ctx->d_packed.p,
-                       n_dwords, (const uint32_t*)P.d_map);
+                       n_dwords, (const uint32_t*)P.d_map, (uint64_t)0, 0u);
     DP_HIP(hipGetLastError());
     DP_HIP(dp_stream_sync(ctx));  // (soff and the caller's lens are read by copies that are through now)
+    return DP_OK;
+}
+
+// ---- the reads behind the first `keep` replaced by a new batch (a mapper's reference and join chunks stay, its reads change).  The
+// device reads [0, keep) are not touched: not their bytes, not their table entries.  Behind them the batch is laid out as
+// dp_reads_upload_packed_rc lays out its paired reads, by the same kernel from boff[keep] on.  A block that is outgrown is replaced by a
+// larger one with the head copied over device to device before the old one goes; the packed reads' block then gets an eighth more
+// than the batch asked for, so a stream of batches of about one size settles after the first.
+// Contexts that borrow these reads may be alive (they must be idle: the caller orders this call against their launches); they hold the
+// old addresses until dp_ctx_refresh_shared, and the epoch bumped here makes every use before that an error code.
+static int tail_grow(dp_ctx* ctx, DevBuf& b, size_t need, size_t slack, size_t head_bytes) {
+    if (need <= b.cap) return 0;
+    DevBuf nb;
+    nb.cap = (need + slack + 255) & ~(size_t)255;
+    DP_HIP(dp_dev_malloc(&nb.p, nb.cap));
+    hipError_t e = hipSuccess;
+    if (b.p && head_bytes) e = hipMemcpyAsync(nb.p, b.p, head_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = dp_stream_sync(ctx);
+    if (e != hipSuccess) {
+        dp_dev_free(nb.p);
+        return dp_fail(ctx, DP_ERR_HIP, "dp_reads_replace_tail_packed_rc: head copy", e);
+    }
+    if (b.p) dp_dev_free(b.p);  // (idle: the stream has drained, and borrowers do not launch during a replace)
+    b = nb;
+    return 0;
+}
+extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_host) {
+    if (!ctx || (n_host && (!lens || !packed))) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: bad arguments") : DP_ERR_ARG;
+    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_replace_tail_packed_rc on a context that borrows its reads");
+    if (keep > ctx->n_reads) {
+        const std::string msg = "dp_reads_replace_tail_packed_rc: keep " + std::to_string(keep) + " is beyond the " + std::to_string(ctx->n_reads) + " device reads";
+        return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+    }
+    const uint64_t nd64 = (uint64_t)keep + 2ull * n_host;
+    if (nd64 > 0x7fffffffull) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: too many reads (more than 2147483647 with the reverse strands)");
+    std::vector<uint64_t> soff((size_t)n_host + 1, 0);
+    for (uint32_t r = 0; r < n_host; r++) {
+        if (lens[r] > 0x7fffffffu) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: read length out of range");
+        soff[(size_t)r + 1] = soff[r] + ((((uint64_t)lens[r] + 3) / 4 + 15) & ~(uint64_t)15);
+    }
+    if (int rc = upload_join(ctx)) return rc;  // (a read set that was still travelling)
+    hipSetDevice(ctx->device);
+    // ---- nothing has been touched up to here.  The tail's entries of the tables:
+    const uint32_t n_dev = (uint32_t)nd64, n_tail = n_dev - keep;
+    const uint64_t pos0 = ctx->h_boff.empty() ? 0 : ctx->h_boff[keep];  // (h_boff has n_reads + 1 entries; none before the first upload)
+    uint64_t pos = pos0, total = 0;
+    for (uint32_t d = 0; d < keep; d++) total += ctx->h_len[d];
+    std::vector<uint64_t> t_boff((size_t)n_tail + 1);
+    std::vector<uint32_t> t_len(n_tail), srcmap(n_tail);
+    for (uint32_t t = 0; t < n_tail; t++) {
+        t_boff[t] = pos;
+        t_len[t] = lens[t >> 1];
+        srcmap[t] = t;  // host read t >> 1, reverse complement when bit 0 is set
+        pos += soff[(size_t)(t >> 1) + 1] - soff[t >> 1];
+        total += lens[t >> 1];
+    }
+    t_boff[n_tail] = pos;
+    // ---- what an upload voids of the previous read set: position index, histogram, quality bytes, dp_scan_reads' caches
+    DP_HIP(dp_stream_sync(ctx));
+    dp_kindex_free(ctx);
+    for (DevBuf* qb : {&ctx->d_qual, &ctx->d_qualoff, &ctx->d_hasq})
+        if (qb->p) {
+            dp_dev_free(qb->p);
+            qb->p = nullptr;
+            qb->cap = 0;
+        }
+    if (ctx->d_kcounts) {
+        dp_dev_free(ctx->d_kcounts);
+        ctx->d_kcounts = nullptr;
+        ctx->kcounts_k = 0;
+    }
+    ctx->flags.valid = false;
+    ctx->items_ptr = nullptr;
+    ctx->reads_epoch++;  // (from here on a borrower's copies may be stale: before the first block moves)
+    if (int rc = tail_grow(ctx, ctx->d_packed, (size_t)pos + 64, (size_t)(pos - pos0) / 8, (size_t)pos0)) return rc;
+    if (int rc = tail_grow(ctx, ctx->d_boff, ((size_t)n_dev + 1) * 8, (size_t)n_tail, (size_t)keep * 8)) return rc;
+    if (int rc = tail_grow(ctx, ctx->d_len, (size_t)n_dev * 4 + 4, (size_t)n_tail / 2, (size_t)keep * 4)) return rc;
+    ctx->h_boff.resize((size_t)keep);
+    ctx->h_boff.insert(ctx->h_boff.end(), t_boff.begin(), t_boff.end());
+    ctx->h_len.resize((size_t)keep);
+    ctx->h_len.insert(ctx->h_len.end(), t_len.begin(), t_len.end());
+    ctx->n_reads = n_dev;
+    ctx->packed_bytes = pos;
+    ctx->total_bases = total;
+    struct Temps {
+        dp_ctx* c;
+        void *d_src = nullptr, *d_soff = nullptr, *d_slen = nullptr, *d_map = nullptr;
+        ~Temps() {
+            hipStreamSynchronize(c->stream);
+            for (void* q : {d_src, d_soff, d_slen, d_map})
+                if (q) dp_dev_free(q);
+        }
+    } T{ctx};
+    DP_HIP(hipMemcpyAsync((uint64_t*)ctx->d_boff.p + keep, t_boff.data(), ((size_t)n_tail + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_tail) DP_HIP(hipMemcpyAsync((uint32_t*)ctx->d_len.p + keep, t_len.data(), (size_t)n_tail * 4, hipMemcpyHostToDevice, ctx->stream));
+    DP_HIP(hipMemsetAsync((uint8_t*)ctx->d_packed.p + pos, 0, 64, ctx->stream));
+    if (pos > pos0) {
+        const uint64_t nsrc = soff[n_host];
+        DP_HIP(dp_dev_malloc(&T.d_src, nsrc + 64));
+        DP_HIP(dp_dev_malloc(&T.d_soff, ((size_t)n_host + 1) * 8));
+        DP_HIP(dp_dev_malloc(&T.d_slen, (size_t)n_host * 4 + 4));
+        DP_HIP(dp_dev_malloc(&T.d_map, (size_t)n_tail * 4));
+        DP_HIP(hipMemcpyAsync(T.d_soff, soff.data(), ((size_t)n_host + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        DP_HIP(hipMemcpyAsync(T.d_slen, lens, (size_t)n_host * 4, hipMemcpyHostToDevice, ctx->stream));
+        DP_HIP(hipMemcpyAsync(T.d_map, srcmap.data(), (size_t)n_tail * 4, hipMemcpyHostToDevice, ctx->stream));
+        DP_HIP(hipMemsetAsync((uint8_t*)T.d_src + nsrc, 0, 64, ctx->stream));
+        if (host_block_is_pinned(packed)) DP_HIP(hipMemcpyAsync(T.d_src, packed, nsrc, hipMemcpyHostToDevice, ctx->stream));
+        else if (int rc = upload_ascii(ctx, T.d_src, packed, nsrc)) return rc;
+        const uint64_t d_begin = pos0 / 4, n_dwords = pos / 4;  // (every read starts on a 16-byte boundary)
+        hipLaunchKernelGGL(place_packed_kernel, dim3((uint32_t)((n_dwords - d_begin + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)T.d_src,
+                           (const uint64_t*)T.d_soff, (const uint32_t*)T.d_slen, (const uint64_t*)ctx->d_boff.p, n_dev, (uint32_t*)ctx->d_packed.p,
+                           n_dwords, (const uint32_t*)T.d_map, d_begin, keep);
+        DP_HIP(hipGetLastError());
+    }
+    DP_HIP(dp_stream_sync(ctx));  // (the tables and the caller's lens are read by copies that are through now)
     return DP_OK;
 }
 
@@ -1316,6 +1468,7 @@ extern "C" int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32
         ctx->kcounts_k = 0;
     }
     ctx->n_reads = n_dev;
+    ctx->reads_epoch++;
     ctx->flags.valid = false;  // (cached per-read-set state of dp_scan_reads)
     ctx->items_ptr = nullptr;
     ctx->h_boff.swap(h_boff);
@@ -1509,7 +1662,9 @@ extern "C" int dp_reads_upload_wait(dp_ctx* ctx, uint32_t host_read_hi) {
 }
 
 extern "C" int dp_reads_packed(dp_ctx* ctx, uint32_t read, uint8_t* out, uint64_t cap, uint64_t* n_bytes) {
-    if (!ctx || read >= ctx->n_reads) return DP_ERR_ARG;
+    if (!ctx) return DP_ERR_ARG;
+    if (int rc = dp_reads_stale(ctx, "dp_reads_packed")) return rc;
+    if (read >= ctx->n_reads) return DP_ERR_ARG;
     hipSetDevice(ctx->device);
     uint64_t nb = ((uint64_t)ctx->h_len[read] + 3) / 4;
     if (n_bytes) *n_bytes = nb;
@@ -2200,6 +2355,7 @@ static void scan_write_pass(dp_ctx* ctx, const ScanRound& R, uint32_t grid, cons
 extern "C" int dp_scan(dp_ctx* ctx, const dp_scan_item* items, uint32_t n_items, dp_seedseq_batch* out) {
     if (!ctx || !out || (n_items && !items)) return DP_ERR_ARG;
     if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_scan before dp_round_begin");
+    if (int rc = dp_reads_stale(ctx, "dp_scan")) return rc;
     hipSetDevice(ctx->device);
     const int k = ctx->k;
     uint64_t bases = 0;
@@ -2774,6 +2930,7 @@ static int scan_publish(dp_ctx* ctx, const ScanRound& R, const ScanTotals& T, dp
 extern "C" int dp_scan_reads(dp_ctx* ctx, const uint8_t* ignore, uint64_t ignore_epoch, uint32_t lo, uint32_t hi, int top_level,
                              uint32_t min_seeds, const dp_scan_item* extra, uint32_t n_extra, dp_survivor_batch* out) {
     if (int rc = scan_reads_check(ctx, ignore, lo, hi, extra, n_extra, out)) return rc;
+    if (int rc = dp_reads_stale(ctx, "dp_scan_reads")) return rc;
     hipSetDevice(ctx->device);
     ScanRound R{};
     R.lo = lo, R.hi = hi, R.top_level = top_level, R.k = ctx->k, R.min_seeds = min_seeds;

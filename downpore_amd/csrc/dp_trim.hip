@@ -930,6 +930,7 @@ static int tr_resident_begin(dp_trim* t, dp_ctx* ctx, hipStream_t st, const char
     const bool own = false;
     if (!ctx) return tr_fail(t, DP_ERR_ARG, std::string(who) + ": null context");
     if (ctx->device != t->device) return tr_fail(t, DP_ERR_ARG, std::string(who) + ": the handle and the context are on different devices");
+    if (dp_reads_stale(ctx, who) != 0) return tr_fail(t, DP_ERR_STATE, dp_last_error(ctx));  // (a borrower that has not seen its owner's new read set)
     {
         std::lock_guard<std::mutex> lk(ctx->upload_mu);
         if (ctx->upload) return tr_fail(t, DP_ERR_STATE, std::string(who) + ": an upload of dp_reads_upload_rc_begin is pending on the context");

@@ -786,6 +786,13 @@ struct MapTrim;
 int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int device, std::string& paf, std::string& errText,
            MapStats* stats, std::string& error, MapTrim* trim = nullptr);
 
+// A mapper (host_map.cpp): runMap's reference side done once by mapperOpen (refSet must outlive it), its read side once per
+// mapperMap.  A batch's paf / errText are runMap's for (refSet, reads).  rc of a failed open in *rc, its text in error.
+struct Mapper;
+Mapper* mapperOpen(const ReadSet& refSet, const MapParams& p, int device, std::string& error, int* rc);
+int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error);
+void mapperClose(Mapper* m);
+
 // ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------
 struct TrimParams {  // flag table commands/trim.go:17-20
     int k = 6;

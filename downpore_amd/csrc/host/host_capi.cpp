@@ -1,6 +1,7 @@
 // The boundary of libdownpore_host.so and nothing else: every entry point include/downpore_host.h declares (read sets, `overlap`
 // round by round with the multi-GPU exchanges, `map`, `trim`).  A Go command, bench.py and the Python drivers come in here.  The
 // entry points that only tests call are in host_testhooks.cpp (dph_testhooks.h).
+#include <atomic>
 #include <algorithm>
 #include <cstring>
 
@@ -688,6 +689,53 @@ extern "C" const char* dph_map_errtext(void* h, int64_t* n) {
     *n = (int64_t)((MapH*)h)->err.size();
     return ((MapH*)h)->err.data();
 }
+// ---- a mapper: dph_map_run_ex's reference side once, its read side per batch
+namespace {
+struct MapperH {
+    Mapper* m = nullptr;
+    std::atomic<bool> busy{false};
+    ~MapperH() {
+        if (m) mapperClose(m);
+    }
+};
+}  // namespace
+extern "C" void* dph_mapper_open(void* refH, const int64_t* params, int n_params, int device) {
+    MapParams p;
+    if (!mapParamsFrom("dph_mapper_open", refH != nullptr, params, n_params, p)) return nullptr;
+    std::string error;
+    int rc = 0;
+    Mapper* m = mapperOpen(((ReadsH*)refH)->set, p, device, error, &rc);
+    if (!m) {
+        g_err = error;
+        return nullptr;
+    }
+    MapperH* h = new MapperH();
+    h->m = m;
+    return h;
+}
+extern "C" void* dph_mapper_map(void* mapperH, void* readsH) {
+    MapperH* mh = (MapperH*)mapperH;
+    if (!mh || !readsH) {
+        g_err = "dph_mapper_map: bad arguments";
+        return nullptr;
+    }
+    if (mh->busy.exchange(true)) {
+        g_err = "dph_mapper_map: DP_ERR_STATE: another call is mapping on this mapper (one batch at a time per mapper)";
+        return nullptr;
+    }
+    MapH* h = new MapH();
+    std::string error;
+    const int rc = mapperMap(mh->m, ((ReadsH*)readsH)->set, h->paf, h->err, &h->st, error);
+    mh->busy.store(false);
+    if (rc != 0) {
+        g_err = error;
+        delete h;
+        return nullptr;
+    }
+    return h;
+}
+extern "C" void dph_mapper_close(void* mapperH) { delete (MapperH*)mapperH; }
+
 // out: n_chunks,n_seeds,n_windows,n_chains,n_batches,k_scan_ms,k_map_ms
 extern "C" void dph_map_stats(void* h, double* out) {
     const MapStats& s = ((MapH*)h)->st;

@@ -598,6 +598,14 @@ double wallNow() { return std::chrono::duration<double>(std::chrono::steady_cloc
 // `return rc` correct on every way out of runMap (see there)
 struct PinnedBlock {  // the packed reads' pinned block
     uint8_t* p = nullptr;
+    size_t cap = 0;
+    bool reserve(size_t bytes) {  // (a Mapper keeps the block from batch to batch while it is large enough)
+        if (p && bytes <= cap) return true;
+        if (p) dp_host_free(p);
+        p = (uint8_t*)dp_host_alloc(bytes);
+        cap = p ? bytes : 0;
+        return p != nullptr;
+    }
     ~PinnedBlock() {
         if (p) dp_host_free(p);
     }
@@ -670,7 +678,7 @@ struct MapRun {
     // ---- what the caller gave.  upSet: the reads that go up.  Without a trim they are the reads that are mapped; with one they are
     // the raw reads, and the set that is mapped (trimmedSet) is made from them once the trim has run on the device's copy
     const ReadSet& refSet;
-    const ReadSet& upSet;
+    const ReadSet* upSetP;  // (a Mapper binds its batches one after the other: bindBatch)
     const MapParams& p;
     const int device;
     std::string& paf;
@@ -679,13 +687,15 @@ struct MapRun {
     std::string& error;
     MapTrim* const trim;
     ReadSet trimmedSet;
-    const ReadSet& reads;
+    const ReadSet* readsP;
+    const ReadSet& upSet() const { return *upSetP; }
+    const ReadSet& reads() const { return *readsP; }
     const int k;
     // the sequences mapped against: the first of the reference file (commands/map.go:34-36) or, with -all_sequences, every top-level
     // sequence of it in file order (one seed index, chunk ids running on from sequence to sequence)
     const size_t T;
     const bool prof;
-    const double tRun0;
+    double tRun0;  // (of the run, or of a Mapper's batch)
     double tMark, tLoop0 = 0;
     // ---- layout of the device read set (map_plan.hpp)
     std::vector<i64> refLens;
@@ -708,6 +718,11 @@ struct MapRun {
     uint32_t perShard = 0;
     bool sparseIndex = false;
     std::mutex infoMu;  // the mapper threads add their index's bytes to *stats
+    // ---- a Mapper (below): this run's reference side stays, batches of reads come and go
+    bool mapperMode = false;  // worker contexts are kept from batch to batch, the index estimate counts the most threads a batch may use
+    bool noChunks = false;    // no sequence is long enough for a chunk: every batch is "all unmapped" without a device call
+    std::string refText;      // the stderr lines of the reference side, in front of every batch's counts
+    int64_t regimesSeen[4] = {0, 0, 0, 0};  // the contexts count their queries for as long as they live: a batch reports what it added
     // ---- what the mapper threads leave
     size_t nThreads = 1;
     std::vector<std::string> out;  // per read, in read order, whoever mapped it
@@ -724,8 +739,8 @@ struct MapRun {
 
     MapRun(const ReadSet& refSet_, const ReadSet& upSet_, const MapParams& p_, int device_, std::string& paf_, std::string& errText_,
            MapStats* stats_, std::string& error_, MapTrim* trim_)
-        : refSet(refSet_), upSet(upSet_), p(p_), device(device_), paf(paf_), errText(errText_), stats(stats_), error(error_), trim(trim_),
-          reads(trim_ ? trimmedSet : upSet_), k(p_.k), T(p_.allSequences ? refSet_.size() : std::min<size_t>(1, refSet_.size())),
+        : refSet(refSet_), upSetP(&upSet_), p(p_), device(device_), paf(paf_), errText(errText_), stats(stats_), error(error_), trim(trim_),
+          readsP(trim_ ? &trimmedSet : &upSet_), k(p_.k), T(p_.allSequences ? refSet_.size() : std::min<size_t>(1, refSet_.size())),
           prof(dp_profile_on()), tRun0(wallNow()), tMark(tRun0), off(1, 0), index(p_.k), staging(ctx, concat) {
         memset(&ssb, 0, sizeof ssb);
         memset(&sb, 0, sizeof sb);
@@ -740,7 +755,7 @@ struct MapRun {
         error = dp_last_error(c);
         return rc;
     }
-    size_t plannedThreads() const;
+    size_t plannedThreads(size_t nReads) const;
     int64_t indexBytes(dp_ctx* c, uint64_t m) const;
     int buildIndexOn(dp_ctx* c, const dp_seq_ref* r, uint32_t n);
 
@@ -760,6 +775,11 @@ struct MapRun {
     int buildShard(Shard& sh, std::vector<uint32_t>& global, std::vector<uint32_t>& local);
     int runWorkers();
     void collectStats();
+    void packReads(const std::vector<uint64_t>& poff, size_t readsAt);
+    void unmappedBatch();
+    // the steps of a Mapper's batch
+    void bindBatch(const ReadSet& batch);
+    int replaceTail();
     void writeText();
     void writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped);
 };
@@ -799,7 +819,7 @@ void MapRun::layoutAndStage() {
     J = mapJoinChunks(p, refLens, seqs, refSet.names);
     for (size_t c = 0; c < T; c++) head += (size_t)refLens[c];
     for (const std::string& j : J.joins) head += j.size();
-    readBytes = !trim && reads.size() ? (size_t)(reads.off[reads.size()] - reads.off[0]) : 0;
+    readBytes = !trim && reads().size() ? (size_t)(reads().off[reads().size()] - reads().off[0]) : 0;
     asyncUpload = !trim && dp_tune("map_async_upload", 0) != 0;
     packedUpload = trim || (!asyncUpload && !dp_tune("map_ascii_upload", 0));
     packScalar = dp_tune("pack_scalar", 0) != 0;  // (tests: the packer without its AVX2 path)
@@ -809,33 +829,36 @@ int MapRun::allocBlocks() {
         staging.p = stagingTake(head + readBytes + 1, &staging.cap);
         return 0;
     }
-    P = mapPackedLayout(refLens, J.joins, upSet.off.data(), upSet.size(), trim != nullptr);
-    pinned.p = (uint8_t*)dp_host_alloc((size_t)P.poff.back() + 64);
-    if (!pinned.p) {
+    P = mapPackedLayout(refLens, J.joins, upSet().off.data(), upSet().size(), trim != nullptr);
+    if (!pinned.reserve((size_t)P.poff.back() + 64)) {
         error = "dp_host_alloc: no pinned memory for the packed reads";
         return DP_ERR_HIP;
     }
     return 0;
+}
+// the reads packed into the pinned block by the worker pool, read r at poff[readsAt + r]
+void MapRun::packReads(const std::vector<uint64_t>& poff, size_t readsAt) {
+    // pieces of about 2 M bases: whole reads
+    std::vector<size_t> cut(1, 0);
+    i64 acc = 0;
+    for (size_t r = 0; r < upSet().size(); r++) {
+        acc += upSet().length(r);
+        if (acc >= ((i64)2 << 20)) {
+            cut.push_back(r + 1);
+            acc = 0;
+        }
+    }
+    if (cut.back() != upSet().size()) cut.push_back(upSet().size());
+    parallelFor(cut.size() - 1, [&](size_t i) {
+        for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(upSet().seq(r), (size_t)upSet().length(r), pinned.p + poff[readsAt + r], packScalar);
+    });
 }
 // The host staging copy is made by a thread of its own while the device computes the reference's k-mer table
 void MapRun::packOrConcatenate() {
     if (packedUpload) {
         for (size_t c = 0; c < T; c++) packBases(refSet.seq(c), (size_t)refLens[c], pinned.p + P.poff[P.headAt + c], packScalar);
         for (size_t j = 0; j < J.joins.size(); j++) packBases(J.joins[j].data(), J.joins[j].size(), pinned.p + P.poff[P.headAt + T + j], packScalar);
-        // pieces of about 2 M bases: whole reads
-        std::vector<size_t> cut(1, 0);
-        i64 acc = 0;
-        for (size_t r = 0; r < upSet.size(); r++) {
-            acc += upSet.length(r);
-            if (acc >= ((i64)2 << 20)) {
-                cut.push_back(r + 1);
-                acc = 0;
-            }
-        }
-        if (cut.back() != upSet.size()) cut.push_back(upSet.size());
-        parallelFor(cut.size() - 1, [&](size_t i) {
-            for (size_t r = cut[i]; r < cut[i + 1]; r++) packBases(upSet.seq(r), (size_t)upSet.length(r), pinned.p + P.poff[P.readsAt + r], packScalar);
-        });
+        packReads(P.poff, P.readsAt);
         return;
     }
     // the reads are one contiguous block of the read set, copied (and its pages first touched) by the worker pool in 4 MiB pieces
@@ -847,15 +870,15 @@ void MapRun::packOrConcatenate() {
         memcpy(staging.p.get() + off.back(), j.data(), j.size());
         off.push_back(off.back() + (i64)j.size());
     }
-    const char* src = reads.size() ? reads.seq(0) : nullptr;
+    const char* src = reads().size() ? reads().seq(0) : nullptr;
     const size_t piece = (size_t)4 << 20, nPieces = (readBytes + piece - 1) / piece;
     char* dst = staging.p.get() + head;
     parallelFor(nPieces, [&](size_t i) {
         const size_t b = i * piece, e = std::min(readBytes, b + piece);
         memcpy(dst + b, src + b, e - b);
     });
-    const i64 shift = (i64)head - (reads.size() ? reads.off[0] : 0);
-    for (size_t r = 0; r < reads.size(); r++) off.push_back(reads.off[r + 1] + shift);
+    const i64 shift = (i64)head - (reads().size() ? reads().off[0] : 0);
+    for (size_t r = 0; r < reads().size(); r++) off.push_back(reads().off[r + 1] + shift);
 }
 
 // ---- context, reference upload, and the value table from every sequence of the reference file (map.go:45-71)
@@ -1042,11 +1065,11 @@ int MapRun::scanChunks() {
 }
 
 // mapper threads (each with a context of its own) when the index is not sharded
-size_t MapRun::plannedThreads() const {
+size_t MapRun::plannedThreads(size_t nReads) const {
     const size_t n = (size_t)dp_env_long("DP_MAP_THREADS", hostThreads() >= 16 ? 8 : hostThreads() >= 12 ? 6 : hostThreads() >= 8 ? 4 : 3, 1);
     // (fewer reads than that per thread are not worth a context; the key is a test hook)
     const size_t perThread = (size_t)std::max(1L, dp_tune("map_min_reads_per_thread", 2048));
-    return std::min(n, std::max<size_t>(1, reads.size() / perThread));
+    return std::min(n, std::max<size_t>(1, nReads / perThread));
 }
 // device bytes of an index of m chunks as dp_index_info counts them (the dense one without asking the device: its build is still queued)
 int64_t MapRun::indexBytes(dp_ctx* c, uint64_t m) const {
@@ -1074,7 +1097,7 @@ int MapRun::chooseIndexLayout() {
     perShard = mapChunksPerShard(nChunksAll, (uint32_t)nShards);  // whole 64-chunk words
     sparseIndex = p.indexLayout == 2;
     const std::vector<std::pair<int, uint64_t>> perDev =
-        mapDenseEstimate(index.seedMap.size(), nChunksAll, nShards, perShard, devs, device, nShards > 1 ? 0 : plannedThreads());
+        mapDenseEstimate(index.seedMap.size(), nChunksAll, nShards, perShard, devs, device, nShards > 1 ? 0 : plannedThreads(mapperMode ? ~(size_t)0 : reads().size()));
     std::vector<std::pair<uint64_t, uint64_t>> mem(perDev.size());  // free, total
     for (size_t i = 0; i < perDev.size(); i++) {
         if (int rc = dp_device_memory(perDev[i].first, &mem[i].first, &mem[i].second)) return failed(ctx.c, rc);
@@ -1199,7 +1222,8 @@ struct MapWorker {
 void MapWorker::run() {
     const double tt0 = wallNow();
     M.ctx = R.ctx.c;
-    if (tIdx > 0 && openContext(tt0) != 0) return;
+    if (tIdx > 0 && R.workers.v[tIdx]) M.ctx = R.workers.v[tIdx];  // (a Mapper's context of an earlier batch, refreshed by replaceTail)
+    else if (tIdx > 0 && openContext(tt0) != 0) return;
     const double tt1 = wallNow();
     loop();
     if (R.prof)
@@ -1244,7 +1268,7 @@ int MapWorker::loop() {
     const double tl0 = wallNow();
     inflight = nT >= 8 ? 2048 : std::max<size_t>(2730, 10922 / nT);
     inflight = (size_t)dp_env_long("DP_MAP_INFLIGHT", (long)inflight, 64);
-    const size_t nReads = R.reads.size();
+    const size_t nReads = R.reads().size();
     for (size_t blk = tIdx; blk * BL < nReads; blk += nT) myCount += std::min(BL, nReads - blk * BL);
     while (nextSeq < myCount || !live.empty()) {
         const double t0 = wallNow();
@@ -1273,7 +1297,7 @@ int MapWorker::loop() {
 }
 // new read tasks up to `inflight`, each run to its first window request (or completion)
 int MapWorker::startTasks() {
-    const size_t nReads = R.reads.size();
+    const size_t nReads = R.reads().size();
     while (live.size() < inflight && nextSeq < myCount) {
         const size_t nextRead = readOf(nextSeq);
         if (nextRead >= waitedBelow) {  // (the block may still be on its way to the device: dp_reads_upload_rc_begin)
@@ -1286,7 +1310,7 @@ int MapWorker::startTasks() {
         std::unique_ptr<Task> t(new Task());
         t->m = &M;
         t->read = (uint32_t)nextRead;
-        t->L = R.reads.length(nextRead);
+        t->L = R.reads().length(nextRead);
         if (freeStacks.empty()) {
             stackStore.emplace_back(new char[stackBytes]);
             freeStacks.push_back(stackStore.back().get());
@@ -1305,7 +1329,7 @@ void MapWorker::retireTasks() {
         if (live[i]->done) {
             Task& t = *live[i];
             std::string& o = R.out[t.read];
-            for (Mapping* mm : t.results) o += M.asString(*mm, R.reads.names[t.read], t.L) + "\n";
+            for (Mapping* mm : t.results) o += M.asString(*mm, R.reads().names[t.read], t.L) + "\n";
             R.nmaps[t.read] = (int)t.results.size();
             coroRelease(t.at);
             freeStacks.push_back(t.stack);
@@ -1396,11 +1420,11 @@ int MapWorker::chainWindows() {
 int MapRun::runWorkers() {
     tLoop0 = wallNow();
     if (stats) stats->t_setup_s = tLoop0 - tRun0;
-    out.assign(reads.size(), std::string());
-    nmaps.assign(reads.size(), 0);
-    nThreads = shards.v.empty() ? plannedThreads() : 1;
+    out.assign(reads().size(), std::string());
+    nmaps.assign(reads().size(), 0);
+    nThreads = shards.v.empty() ? plannedThreads(reads().size()) : 1;
     lstats.assign(nThreads, LoopStats());
-    workers.v.assign(nThreads, nullptr);
+    if (workers.v.size() < nThreads) workers.v.resize(nThreads, nullptr);  // (a Mapper's contexts of earlier batches stay in their slots)
     {
         std::vector<std::unique_ptr<MapWorker>> ws;
         for (size_t t = 0; t < nThreads; t++) ws.emplace_back(new MapWorker(*this, t, nThreads));
@@ -1421,9 +1445,13 @@ int MapRun::runWorkers() {
             if (c && dp_index_info(c, &ii) == 0)
                 for (int r = 0; r < 4; r++) stats->regimes[r] += (int64_t)ii.queries[r];
         }
+        for (int r = 0; r < 4; r++) {  // (what earlier batches of a Mapper have already reported)
+            stats->regimes[r] -= regimesSeen[r];
+            regimesSeen[r] += stats->regimes[r];
+        }
     }
     const double tJoin = wallNow();
-    workers.destroy();
+    if (!mapperMode) workers.destroy();
     if (prof) fprintf(stderr, "[map end] threads joined at %.1f ms after the loops' start, their contexts destroyed in %.1f\n", 1e3 * (tJoin - tLoop0), 1e3 * (wallNow() - tJoin));
     for (size_t t = 0; t < nThreads; t++)
         if (lstats[t].rc != 0) {
@@ -1458,9 +1486,13 @@ void MapRun::writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped) {
              (long long)multiple, (long long)total, (long long)unmapped);
     errText += line;
 }
+void MapRun::unmappedBatch() {
+    if (stats) stats->n_seeds = index.seedMap.size(), stats->t_setup_s = wallNow() - tRun0;
+    writeCounts(0, 0, 0, (i64)reads().size());
+}
 void MapRun::writeText() {
     i64 unmapped = 0, mapped = 0, multiple = 0, total = 0;
-    for (size_t r = 0; r < reads.size(); r++) {
+    for (size_t r = 0; r < reads().size(); r++) {
         paf += out[r];
         if (nmaps[r] > 0) {
             if (nmaps[r] == 1) mapped++;
@@ -1491,8 +1523,7 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
     if (trim && (rc = R.trimAndRespan())) return rc;
     if ((rc = R.scanChunks())) return rc;
     if (R.sched.items.empty()) {  // no sequence is long enough for a chunk: an empty index matches nothing, every read is unmapped
-        if (stats) stats->n_seeds = R.index.seedMap.size(), stats->t_setup_s = wallNow() - R.tRun0;
-        R.writeCounts(0, 0, 0, (i64)R.reads.size());
+        R.unmappedBatch();
         return 0;
     }
     if ((rc = R.chooseIndexLayout())) return rc;
@@ -1506,6 +1537,122 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
     if (R.prof) fprintf(stderr, "[map end] text joined in %.1f ms, context destroyed in %.1f, whole run %.1f\n", 1e3 * (tEnd0 - tText0), 1e3 * (wallNow() - tEnd0), 1e3 * (wallNow() - R.tRun0));
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// A Mapper: the reference program's NewMapper once, then MapWorker over batch after batch of reads.  It is a MapRun whose steps are
+// regrouped, none copied: open runs the steps that look at the reference alone (with an empty read set, so the one upload carries the
+// head only), and a batch runs the steps that look at the reads.  What stays from batch to batch: the main context with the head, the
+// value table, the seed index, the schedule and chunk scan, the layout choice, the index, the pinned block, and every worker context
+// a batch's thread plan has asked for so far (its round, import and dense build or borrow are done once, when it is opened).  What a
+// batch owns: its read set's binding, the packed batch in the pinned block, the tail replace and the workers' refreshes, the loops,
+// and its paf / stderr / stats.  The owners are MapRun's and go in MapRun's order when the mapper is closed.
+void MapRun::bindBatch(const ReadSet& batch) {
+    upSetP = readsP = &batch;
+    tRun0 = tMark = wallNow();
+    paf.clear();
+    errText = refText;
+    error.clear();
+    // the reference side's figures stay (chunks, seeds, index layout / bytes / builds, hits); what the loops count starts again
+    stats->n_windows = stats->n_chains = stats->n_batches = 0;
+    stats->k_scan_ms = stats->k_map_ms = stats->map_bytes = stats->scan_bytes = 0;
+    stats->t_setup_s = stats->t_scan_s = stats->t_chain_s = stats->t_host_s = 0;
+    for (int64_t& r : stats->regimes) r = 0;
+}
+// the batch packed into the pinned block, put behind the head on the device, and the worker contexts told about it
+int MapRun::replaceTail() {
+    P = mapBatchLayout(upSet().off.data(), upSet().size());
+    if (!pinned.reserve((size_t)P.poff.back() + 64)) {
+        error = "dp_host_alloc: no pinned memory for the packed reads";
+        return DP_ERR_HIP;
+    }
+    packReads(P.poff, 0);
+    mark("pack the batch");
+    if (int rc = dp_reads_replace_tail_packed_rc(ctx.c, J.firstPaired, pinned.p, P.plens.data(), (uint32_t)P.plens.size())) return failed(ctx.c, rc);
+    for (dp_ctx* wc : workers.v)
+        if (wc)
+            if (int rc = dp_ctx_refresh_shared(wc)) return failed(wc, rc);
+    mark("tail replace + refreshes");
+    return 0;
+}
+
+struct Mapper {
+    const MapParams p;  // (MapRun holds references to these: they are declared before it)
+    ReadSet none;       // the read set of the open: the head goes up alone
+    std::string paf, errText, error;
+    MapStats st;
+    MapRun R;
+    int brokenRc = 0;  // the first device error: every later batch returns it without touching the device
+    std::string brokenText;
+    Mapper(const ReadSet& refSet, const MapParams& p_, int device) : p(p_), R(refSet, none, p, device, paf, errText, &st, error, nullptr) {
+        R.mapperMode = true;
+    }
+};
+
+Mapper* mapperOpen(const ReadSet& refSet, const MapParams& p, int device, std::string& error, int* rcOut) {
+    int rc = 0;
+    auto fail = [&](int code, const std::string& text) {
+        error = text;
+        if (rcOut) *rcOut = code;
+        return (Mapper*)nullptr;
+    };
+    if (dp_env_long("DP_MAP_SHARDS", 1, 1, INT_MAX) > 1) return fail(DP_ERR_ARG, "mapper: DP_MAP_SHARDS > 1 is not supported by a mapper (use the one-shot map call)");
+    for (const char* key : {"map_ascii_upload", "map_async_upload"})
+        if (dp_tune(key, 0) != 0) return fail(DP_ERR_ARG, std::string("mapper: DP_TUNE=") + key + " is not supported by a mapper (use the one-shot map call)");
+    std::unique_ptr<Mapper> m(new Mapper(refSet, p, device));
+    MapRun& R = m->R;
+    auto failRun = [&](int code) { return fail(code, m->error); };  // (the owners give everything back, in MapRun's order)
+    if ((rc = R.check())) return failRun(rc);
+    R.layoutAndStage();
+    if ((rc = R.allocBlocks())) return failRun(rc);
+    R.concat.t = std::thread([&R] { R.packOrConcatenate(); });
+    if ((rc = R.openContext())) return failRun(rc);
+    if ((rc = R.startSeedWalk())) return failRun(rc);
+    if ((rc = R.uploadReads())) return failRun(rc);
+    if ((rc = R.scanChunks())) return failRun(rc);
+    R.noChunks = R.sched.items.empty();
+    if (!R.noChunks) {
+        if ((rc = R.chooseIndexLayout())) return failRun(rc);
+        if ((rc = R.buildIndex())) return failRun(rc);
+    } else {
+        m->st.n_seeds = R.index.seedMap.size();
+    }
+    R.refText = m->errText;
+    if (rcOut) *rcOut = 0;
+    return m.release();
+}
+
+int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
+    if (m->brokenRc) {
+        error = m->brokenText;
+        return m->brokenRc;
+    }
+    MapRun& R = m->R;
+    R.bindBatch(reads);
+    int rc = 0;
+    if (R.noChunks) {
+        R.unmappedBatch();
+    } else {
+        if ((rc = R.replaceTail()) == 0 && (rc = R.runWorkers()) == 0) {
+            R.collectStats();
+            R.writeText();
+        }
+    }
+    R.upSetP = R.readsP = &m->none;  // (the batch's read set is the caller's: nothing of it is held beyond this call)
+    if (rc) {
+        error = m->error;
+        if (rc != DP_ERR_ARG) {  // a batch refused for its arguments has touched nothing; anything else leaves the device state unknown
+            m->brokenRc = rc;
+            m->brokenText = error;
+        }
+        return rc;
+    }
+    paf.swap(m->paf);
+    errText.swap(m->errText);
+    if (stats) *stats = m->st;
+    return 0;
+}
+
+void mapperClose(Mapper* m) { delete m; }
 
 // ---- self-test of the coroutine switch (dph_testhooks.h: dph_test_coroutines): n_tasks coroutines on recycled stacks, every one adds
 // its number `yields` times with a switch back to the caller in between and touches its stack deeply; returns the sum (-1: a task

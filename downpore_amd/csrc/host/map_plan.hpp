@@ -1,6 +1,6 @@
 // The arithmetic of `downpore map` that decides what the device is asked to do (host_map.cpp: runMap and its workers), as plain
 // functions on numbers, strings and the ABI's plain structs: the 32-bit limits, the circular join chunks, the packed upload's layout,
-// the chunk schedule, a window request's scan items and the reverse strand's fix-up, the shards' seed-window merge and the dense
+// the chunk schedule, a Mapper batch's layout and device ids, a window request's scan items and the reverse strand's fix-up, the shards' seed-window merge and the dense
 // index estimate.  No device call, no environment, no thread: tests/native/map_plan_check.cpp holds every function here to the
 // oracle's Mapper, to rules written out a second time or to brute force, without a GPU.
 #pragma once
@@ -106,6 +106,15 @@ inline MapPacked mapPackedLayout(const std::vector<i64>& refLens, const std::vec
     return P;
 }
 
+// ---- a Mapper's batch (host_map.cpp: Mapper).  The head - sequences and join chunks, the device reads [0, firstPaired) - went up when
+// the mapper was opened and stays; a batch's pinned block holds the batch alone, in the same host layout (read r at the sum of the
+// 16-byte-rounded packed sizes before it), and dp_reads_replace_tail_packed_rc puts it behind the head as pairs: the forward strand of
+// batch read r is device read firstPaired + 2 r, its reverse complement the next - the ids an upload of head + batch in one go gives.
+inline MapPacked mapBatchLayout(const i64* readOff, size_t nReads) {
+    return mapPackedLayout(std::vector<i64>(), std::vector<std::string>(), readOff, nReads, false);
+}
+inline uint32_t mapBatchReadId(uint32_t firstPaired, uint32_t read, bool reverse) { return firstPaired + 2 * read + (reverse ? 1u : 0u); }
+
 // ---- chunk schedule mapping.go:79-96, canonical generation order; sequence after sequence, the chunk ids running on.  Sequence sq
 // is device read sq, its join chunk device read T + joinOf[sq].
 struct MapSchedule {
@@ -156,7 +165,7 @@ inline MapSchedule mapChunkSchedule(const MapParams& p, const std::vector<i64>& 
 // ---- the (forward, reverse complement) scan items of the window [a, b) of read `read` (L bases; device reads firstPaired + 2 read
 // and the next).  whole: the top-level read itself, not a view of it.
 inline void mapWindowItems(uint32_t firstPaired, uint32_t read, i64 L, i64 a, i64 b, bool whole, int k, dp_scan_item& f, dp_scan_item& r) {
-    const uint32_t fr = firstPaired + 2 * read, rr = fr + 1;
+    const uint32_t fr = mapBatchReadId(firstPaired, read, false), rr = mapBatchReadId(firstPaired, read, true);
     const i64 wl = b - a;
     f.read = fr;
     r.read = rr;

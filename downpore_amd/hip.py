@@ -97,7 +97,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_comm_destroy", "dp_comm_abort", "dp_allgather_blobs", "dp_gather_blobs", "dp_kindex_set_comm", "dp_kindex_digest", "dp_kindex_dump", "dp_release_device_caches", "dp_reads_upload_rc_begin", "dp_reads_upload_wait", "dp_reads_upload_packed_rc", "dp_host_alloc", "dp_host_free", "dp_comm_rank", "dp_comm_size", "dp_allgather_survivors",
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
-           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan", "dp_reads_respan_rc",
+           "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan", "dp_reads_respan_rc", "dp_reads_replace_tail_packed_rc", "dp_ctx_refresh_shared",
            "dp_debug_chain_paths"]
 
 _lib = None
@@ -222,6 +222,35 @@ class Context:
                 self.L.dp_host_free(blk)
         ln = lens.astype(np.int64)
         self.read_len = np.concatenate([ln[:first_paired], np.repeat(ln[first_paired:], 2)])
+
+    def replace_tail_packed_rc(self, keep, packed, lens, pinned=True):
+        """dp_reads_replace_tail_packed_rc: the device reads [0, keep) stay, everything behind them becomes the batch (packed, lens)
+        as (forward, reverse complement) pairs.  Borrowing contexts need refresh_shared() afterwards."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        self.L.dp_reads_replace_tail_packed_rc.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        self.L.dp_host_alloc.restype = C.c_void_p
+        self.L.dp_host_alloc.argtypes = [C.c_size_t]
+        self.L.dp_host_free.argtypes = [C.c_void_p]
+        blk = None
+        ptr = packed.ctypes.data
+        if pinned:
+            blk = self.L.dp_host_alloc(max(1, packed.size))
+            assert blk
+            C.memmove(blk, packed.ctypes.data, packed.size)
+            ptr = blk
+        try:
+            self._chk(self.L.dp_reads_replace_tail_packed_rc(self.h, keep, ptr, lens.ctypes.data, len(lens)))
+        finally:
+            if blk:
+                self.L.dp_host_free(blk)
+        self.read_len = np.concatenate([np.asarray(self.read_len[:keep], dtype=np.int64), np.repeat(lens.astype(np.int64), 2)])
+
+    def refresh_shared(self, owner):
+        """dp_ctx_refresh_shared: a borrowing context takes its owner's read set again after a tail replace."""
+        self.L.dp_ctx_refresh_shared.argtypes = [C.c_void_p]
+        self._chk(self.L.dp_ctx_refresh_shared(self.h))
+        self.read_len = np.array(owner.read_len, dtype=np.int64)
 
     def packed_read(self, r):
         nb = (int(self.read_len[r]) + 3) // 4

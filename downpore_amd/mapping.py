@@ -43,6 +43,86 @@ def _trim_block(trim):
     return front, back, T.trim_params(**kw)
 
 
+def _result_types(H):
+    """ctypes signatures of the calls that read a map handle (dph_map_run_ex's or dph_mapper_map's)."""
+    H.dph_map_free.argtypes = [C.c_void_p]
+    for f in (H.dph_map_paf, H.dph_map_errtext):
+        f.restype = C.POINTER(C.c_char)
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    H.dph_map_stats.argtypes = [C.c_void_p, C.c_void_p]
+    H.dph_map_index_info.restype = C.c_int
+    H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+
+
+def _take_result(H, h):
+    """(paf, stderr_text, stats) of a map handle, which is freed."""
+    n = C.c_int64(0)
+    paf = C.string_at(H.dph_map_paf(h, C.byref(n)), n.value).decode()
+    err = C.string_at(H.dph_map_errtext(h, C.byref(n)), n.value).decode()
+    st = np.zeros(len(MAP_STAT_FIELDS), dtype=np.float64)
+    H.dph_map_stats(h, st.ctypes.data)
+    ix = np.zeros(len(MAP_INDEX_FIELDS), dtype=np.int64)
+    got = H.dph_map_index_info(h, ix.ctypes.data, len(ix))
+    H.dph_map_free(h)
+    stats = dict(zip(MAP_STAT_FIELDS, st.tolist()))
+    info = dict(zip(MAP_INDEX_FIELDS[:got], (int(v) for v in ix[:got])))
+    info["layout"] = {1: "dense", 2: "sparse"}.get(info.get("layout", 0), "none")
+    stats["index"] = info
+    return paf, err, stats
+
+
+class Mapper:
+    """A reference opened once, batches of reads mapped against it: `with Mapper(ref) as m: paf, err, stats = m.map(reads)`.
+    The reference's sequences and join chunks, its value table, seeds, chunk scan and index are made by the constructor and stay on
+    the device; map(reads) sends the batch alone and returns what map_reads(ref, reads, ...) returns, text for text.  Arguments as
+    map_reads takes them (no trim: that path stays map_reads').  One map() at a time per mapper; DpError on use after close()."""
+
+    def __init__(self, ref, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
+                 index="auto", all_sequences=False):
+        self.h = None
+        layout = index_layout_code(index)
+        H = self.H = load_host()
+        H.dph_mapper_open.restype = C.c_void_p
+        H.dph_mapper_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        H.dph_mapper_map.restype = C.c_void_p
+        H.dph_mapper_map.argtypes = [C.c_void_p, C.c_void_p]
+        H.dph_mapper_close.argtypes = [C.c_void_p]
+        _result_types(H)
+        p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout, 1 if all_sequences else 0], dtype=np.int64)
+        self.ref = ref  # (the library reads the reference through the mapper's lifetime)
+        h = H.dph_mapper_open(ref.h, p.ctypes.data, len(p), device)
+        if not h:
+            raise DpError("dph_mapper_open: " + H.dph_last_error(None).decode())
+        self.h = h
+
+    def map(self, reads):
+        """-> (paf, stderr_text, stats) exactly as map_reads returns them for (ref, reads)."""
+        if not self.h:
+            raise DpError("Mapper.map: the mapper is closed")
+        h = self.H.dph_mapper_map(self.h, reads.h)
+        if not h:
+            raise DpError("dph_mapper_map: " + self.H.dph_last_error(None).decode())
+        return _take_result(self.H, h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.H.dph_mapper_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
               index="auto", all_sequences=False, trim=None):
     """ref / reads: downpore_amd.overlap.Reads (reference loaded with min_len=0, reads with min_len=min_length; both are
@@ -61,13 +141,7 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     H = load_host()
     H.dph_map_run_ex.restype = C.c_void_p
     H.dph_map_run_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    H.dph_map_free.argtypes = [C.c_void_p]
-    for f in (H.dph_map_paf, H.dph_map_errtext):
-        f.restype = C.POINTER(C.c_char)
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    H.dph_map_stats.argtypes = [C.c_void_p, C.c_void_p]
-    H.dph_map_index_info.restype = C.c_int
-    H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    _result_types(H)
     p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout, 1 if all_sequences else 0], dtype=np.int64)
     trim_result = None
     if trim_block is None:
@@ -85,18 +159,7 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
         if not h:
             raise DpError("dph_map_run_trim: " + H.dph_last_error(None).decode())
         trim_result = T.TrimResult(T._host(), th)
-    n = C.c_int64(0)
-    paf = C.string_at(H.dph_map_paf(h, C.byref(n)), n.value).decode()
-    err = C.string_at(H.dph_map_errtext(h, C.byref(n)), n.value).decode()
-    st = np.zeros(len(MAP_STAT_FIELDS), dtype=np.float64)
-    H.dph_map_stats(h, st.ctypes.data)
-    ix = np.zeros(len(MAP_INDEX_FIELDS), dtype=np.int64)
-    got = H.dph_map_index_info(h, ix.ctypes.data, len(ix))
-    H.dph_map_free(h)
-    stats = dict(zip(MAP_STAT_FIELDS, st.tolist()))
-    info = dict(zip(MAP_INDEX_FIELDS[:got], (int(v) for v in ix[:got])))
-    info["layout"] = {1: "dense", 2: "sparse"}.get(info.get("layout", 0), "none")
-    stats["index"] = info
+    paf, err, stats = _take_result(H, h)
     if trim_result is not None:
         stats["trim"] = trim_result
     return paf, err, stats

@@ -52,6 +52,13 @@ DP_API int dp_ctx_create(int device, dp_ctx** out);
 /* A second context on the same device that BORROWS the resident reads of `src` (no copy): lets several host threads
  * drive independent rounds concurrently, each with its own stream and per-round state.  Destroy it before `src`. */
 DP_API int dp_ctx_create_shared(dp_ctx* src, dp_ctx** out);
+/* The owner of a read set carries an epoch that every upload, respan and tail replace bumps; a borrowing context holds the epoch its
+ * copies of the read-set fields (addresses, tables, counts) were taken at.  dp_reads_replace_tail_packed_rc is the one change of the
+ * read set that is allowed while borrowers exist.  After it every borrower calls dp_ctx_refresh_shared, which copies the fields and the
+ * epoch again and voids what the borrower cached per read set; its round (seeds), imported segments and reference index, built or
+ * borrowed, stay.  Until then the borrower's dp_scan, dp_scan_reads, dp_reads_packed and the resident trim calls return DP_ERR_STATE
+ * (the text names this call) before any launch.  Call it while neither context is in another call. */
+DP_API int dp_ctx_refresh_shared(dp_ctx* ctx);
 /* Give the context's stream the device's highest (high != 0) or default scheduling priority.  For the context of a
  * latency-critical caller next to throughput work - the goroutine that runs PrepareQueries (overlap/overlap.go:157) and
  * waits for dp_select_seeds while other contexts keep the GPU busy with whole rounds.  Call it while the context is idle. */
@@ -94,6 +101,15 @@ DP_API int dp_reads_upload_rc(dp_ctx* ctx, const uint8_t* bases, const int64_t* 
  * forward ones (sequence.go:179-198).  From memory of dp_host_alloc (pinned) the bytes travel in one copy, from anywhere else through
  * the staging ring of dp_reads_upload. */
 DP_API int dp_reads_upload_packed_rc(dp_ctx* ctx, const uint8_t* packed, const uint32_t* lens, uint32_t n_reads, uint32_t first_paired);
+/* The device reads behind the first `keep` replaced by n_reads new ones, each stored as the pair (forward, reverse complement): a
+ * mapper's reference sequences and join chunks stay where they are, byte for byte, and the reads mapped against them change batch by
+ * batch.  `packed` and `lens` describe the batch alone, in the host layout of dp_reads_upload_packed_rc; the device layout behind
+ * read `keep` is the one that call gives (16-byte boundaries, bases beyond a read's end zero, 64 zero bytes behind the last read).  A
+ * block that is outgrown is replaced by a larger one, the head copied device to device.  The call voids, for the whole read set, what an
+ * upload voids (dp_scan_reads' caches, quality bytes, a k-mer position index or histogram); the value table, the round's seeds,
+ * imported segments and either reference index stay.  Borrowing contexts may exist but must be idle, and are refused until their
+ * dp_ctx_refresh_shared.  DP_ERR_ARG, before anything is touched: keep > dp_reads_count(ctx), a length above 2^31 - 1. */
+DP_API int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_reads);
 /* Pinned host memory from the library's block cache (kept across contexts up to DP_PIN_CACHE_MB; NULL: none to be had). */
 DP_API void* dp_host_alloc(size_t bytes);
 DP_API void dp_host_free(void* p);

@@ -187,6 +187,25 @@ DPH_API void dph_map_stats(void* m, double* out);
  * device's total memory, H (seed hits in chunks), contexts that built an index, then the queries by regime: 4/8-ladder (minCount
  * <= 12), 16-ladder (13 .. 24), exact count (> 24), more than 512 sets.  Writes at most cap values; returns how many it wrote. */
 DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
+/* A mapper: the reference side of dph_map_run_ex done once, batches of reads mapped against it one after the other (the reference
+ * program's NewMapper, then MapWorker over a stream of reads).
+ * dph_mapper_open   params[n_params] as dph_map_run_ex takes them.  The reference sequences and join chunks go up, the value table, the
+ *                   seeds, the chunk scan and the reference index are made, and stay until dph_mapper_close.  `ref` must outlive the
+ *                   mapper.  DP_MAP_SHARDS > 1 and DP_TUNE=map_ascii_upload / map_async_upload are refused by name (they stay with
+ *                   the one-shot call), as is everything dph_map_run_ex refuses about its parameters.  NULL on failure
+ *                   (dph_last_error(NULL)).
+ * dph_mapper_map    maps `reads` and returns a handle of dph_map_run_ex's kind (dph_map_paf, dph_map_errtext, dph_map_stats,
+ *                   dph_map_index_info, dph_map_free): PAF and stderr text are byte for byte what dph_map_run_ex gives for (ref, reads).
+ *                   Only the batch crosses the link; it replaces the previous batch behind the resident head.  Stats: chunks and
+ *                   seeds are the mapper's, the set-up seconds are this batch's time before its loops, the index bytes and builds
+ *                   are the mapper's totals so far (they grow only when a batch is the first to use more threads).  One call at a
+ *                   time per mapper: a second, concurrent one returns NULL (state error) at once.  After a batch has failed with a
+ *                   device error the mapper is broken and every later call returns that first error without touching the device; a
+ *                   batch refused for its arguments leaves it usable.  The handle is independent of the mapper and of `reads`.
+ * dph_mapper_close  gives everything back: worker contexts, then the main context, then the pinned block.  NULL is ignored. */
+DPH_API void* dph_mapper_open(void* ref, const int64_t* params, int n_params, int device);
+DPH_API void* dph_mapper_map(void* mapper, void* reads);
+DPH_API void dph_mapper_close(void* mapper);
 
 /* ---- `downpore trim`, edge stage (commands/trim.go:32-50, trim/trim.go:272-513, sequence/seqio.go:375-523) --------------------
  * reads: a read set loaded with min_len 50 (commands/trim.go:35); front / back: the adapter files loaded with min_len 0.  The read

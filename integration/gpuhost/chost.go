@@ -362,6 +362,62 @@ func RunMap(ref, reads *Reads, p MapParams, device int) (*MapResult, error) {
 	return res, nil
 }
 
+// Mapper is a reference opened once on a device (mapping.NewMapper): the sequences and join chunks, the value table, the seeds, the
+// chunk scan and the reference index stay there, and Map sends one batch of reads after the other against them.
+type Mapper struct {
+	h   unsafe.Pointer
+	ref *Reads // (the library reads the reference for as long as the mapper lives)
+}
+
+// OpenMapper does what RunMap does before it looks at a read (dph_mapper_open).  DP_MAP_SHARDS > 1 and the ASCII upload keys are
+// refused: they stay with RunMap.
+func OpenMapper(ref *Reads, p MapParams, device int) (*Mapper, error) {
+	circ := C.int64_t(0)
+	if p.Circular {
+		circ = 1
+	}
+	all := C.int64_t(0)
+	if p.AllSequences {
+		all = 1
+	}
+	params := [8]C.int64_t{circ, C.int64_t(p.K), C.int64_t(p.QuerySize), C.int64_t(p.MinLength), C.int64_t(p.ChunkSize), C.int64_t(p.SeedRate), 0, all}
+	h := C.dph_mapper_open(ref.h, &params[0], 8, C.int(device))
+	if h == nil {
+		return nil, lastError(nil, "dph_mapper_open")
+	}
+	m := &Mapper{h, ref}
+	runtime.SetFinalizer(m, func(m *Mapper) { m.Close() })
+	return m, nil
+}
+
+// Map maps one batch (reads opened with minLen = -min_length): the PAF and stderr text RunMap gives for (ref, reads).  One call at a
+// time per mapper; after a device error every later call returns that error.
+func (m *Mapper) Map(reads *Reads) (*MapResult, error) {
+	if m.h == nil {
+		return nil, errors.New("Mapper.Map: the mapper is closed")
+	}
+	h := C.dph_mapper_map(m.h, reads.h)
+	runtime.KeepAlive(reads)
+	if h == nil {
+		return nil, lastError(nil, "dph_mapper_map")
+	}
+	defer C.dph_map_free(h)
+	var n C.int64_t
+	pp := C.dph_map_paf(h, &n)
+	res := &MapResult{PAF: text(pp, n)}
+	pe := C.dph_map_errtext(h, &n)
+	res.ErrText = string(text(pe, n))
+	return res, nil
+}
+
+func (m *Mapper) Close() {
+	if m.h != nil {
+		C.dph_mapper_close(m.h)
+		m.h = nil
+	}
+	m.ref = nil
+}
+
 // TrimParams is the flag table of `downpore trim` (commands/trim.go:17-20); Middle adds the search for adapters in the middle of reads.
 type TrimParams struct {
 	K, CheckReads, AdapterThreshold, ExtraEndTrim        int
