@@ -12,6 +12,7 @@
 #include "downpore_hip.h"
 #include "dp_chunk_bound.h"  // dp_chunk_walk_bounded: the chunk parameters the device accepts
 #include "dp_env.h"  // every run-time setting: the table, dp_tune / dp_debug, and when each is read
+#include "dp_find_plan.h"  // the find stage's plan: cursor block, capacities, grids, block layouts (dp_overlap.hip)
 #include "dp_scan_flags.h"  // dp_scan_reads' host bookkeeping of the ignore flags
 
 // make COPYLOG=1: every hipMemcpyAsync of the library is counted per call site (file:line, direction, calls, bytes) and the table is
@@ -343,8 +344,7 @@ static inline const void* dp_chain_b(const dp_ctx* ctx) { return ctx->chains_pac
 uint32_t dp_find_pair_cap(const dp_ctx* ctx);
 int dp_find_complete(dp_ctx* ctx, bool* reran);
 void dp_find_stats(const dp_ctx* ctx, double* query_ms, double* chain_ms, uint64_t* query_bytes, uint64_t* chain_bytes);
-int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t** d_qmeta_out,
-                   uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out, uint32_t** d_qcnt_out = nullptr);
+dp_query_out dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf);
 // the context that holds the sparse index this one queries (itself, or the one it borrows from)
 static inline const dp_ctx* dp_index_of(const dp_ctx* ctx) { return ctx->index_src ? ctx->index_src : ctx; }
 // device bytes of a context's own sparse index (dp_sparse.hip)

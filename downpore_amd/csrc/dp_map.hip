@@ -666,17 +666,15 @@ int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_of
     if (nw == 0 || M == 0) return DP_OK;
     uint32_t* d_qmeta = nullptr;
     u64* d_words = nullptr;
-    int32_t* d_mc = nullptr;
-    uint32_t mc_n = 0;
-    uint32_t* d_qcnt_unused = nullptr;
-    int rc = DP_OK;
     const bool reused = phase == 1 && ctx->map_stage_windows == nw && ctx->map_stage_valid;
     if (reused) {
         // the reverse pass of a shard follows its forward pass on the same windows: the query stage's results are still there
         d_qmeta = (uint32_t*)ctx->d_qmeta.p;
     } else {
-        rc = dp_query_stage(ctx, w_segs, w_off, nw, 0.25, &d_qmeta, &d_words, &d_mc, &mc_n, &d_qcnt_unused);  // Matches(.., 0.25) :502-503
-        if (rc != 0) return rc;
+        const dp_query_out qo = dp_query_stage(ctx, w_segs, w_off, nw, 0.25);  // Matches(.., 0.25) :502-503
+        if (qo.rc != 0) return qo.rc;
+        d_qmeta = qo.d_qmeta;
+        d_words = qo.d_words;
         ctx->map_stage_windows = nw;
         ctx->map_stage_valid = phase == 0;
     }

@@ -20,9 +20,6 @@ typedef uint64_t u64;
 // ---------------------------------------------------------------------------------------------------------------
 // A13
 
-// the chaining stage's cursor block: 32 words (cursor, flags, totals) + 64 shards of its algorithmic-byte count (one counter
-// would be a thousand same-address atomics per kernel: 12 ns each, in a row)
-#define C_CURSOR_BYTES 640
 __global__ __launch_bounds__(256) void index_fill_kernel(const dp_seq_ref* __restrict__ refs, uint32_t n_seqs,
                                                          const int32_t* __restrict__ segs, u64* __restrict__ posting,
                                                          u64* __restrict__ seedsets, uint32_t W, uint32_t SW,
@@ -793,8 +790,8 @@ __device__ __forceinline__ void pair_scan_body(const uint32_t* __restrict__ qcnt
     if (threadIdx.x == T - 1) {
         pbase[nq] = (uint32_t)shp[T - 1];
         ibase[nq] = shi[T - 1];
-        totals[0] = shp[T - 1];
-        totals[1] = shi[T - 1];
+        totals[DP_FIND_TOT_PAIRS] = shp[T - 1];
+        totals[DP_FIND_TOT_SINTS] = shi[T - 1];
     }
 }
 
@@ -1439,8 +1436,8 @@ __device__ __forceinline__ void chain_prof_store(unsigned long long* slot, const
     slot[11] = wall_clock64();
     slot[12] = pf.bev, slot[13] = pf.nev, slot[14] = pf.nperfect, slot[15] = pf.why;
 }
-#define C_WAVES 4
-#define S_WAVES 4  // waves per workgroup of the kernels on the slim layout
+#define C_WAVES DP_FIND_C_WAVES
+#define S_WAVES DP_FIND_S_WAVES  // waves per workgroup of the kernels on the slim layout
 #define C_OPEN 500       // len(align.open)          seeds/alignment.go:299
 #define C_RESULTS 500    // len(align.results)
 #define C_POOLSTATES 10000
@@ -2546,7 +2543,7 @@ struct ChainArgs {
     u64* ibase;          // [nq + 1] first scratch int of each query (a pair's column holds nSeeds(q) ints)
     uint32_t* clist;     // [pairs] candidate (indexed-sequence index) of each pair, ascending within a query
     uint32_t* pq;        // [pairs] query of each pair
-    int pass;            // proposal pass this launch belongs to (cursor[8 + pass] != 0: a query was still open when it started)
+    int pass;            // proposal pass this launch belongs to (cursor[DP_CUR_OPEN + pass] != 0: a query was still open when it started)
     PSpec* pspec;        // [pairs]
     QState* qstate;      // [nq]
     MRec* recs;          // [pairs] final record of each pair; len 0 = no match
@@ -2555,7 +2552,7 @@ struct ChainArgs {
     uint32_t pair_cap;
     u64 sint_cap;
     uint32_t int_cap;
-    uint32_t* cursor;    // [0] packed ints used, [2] error bits, [3] overflow flag, [8 + pass] "a query is open" flags, [16..19] totals, [24 + 2 * pass + (q & 1)], pass 0 / 1: pairs left open by the pass's resolve step, [32 ..] 64 shards of the algorithmic bytes (u64)
+    uint32_t* cursor;    // the cursor block: its words are named in dp_find_plan.h (enum dp_find_cur)
     int walk_always;      // DP_CHAIN_PERFECT=0 (tests): no pair takes the perfect-chain shortcut of wave_chain_reg
     int paths;            // DP_DEBUG=chain_paths (tests): PSpec.pad of every pair says how it became final (CPATH_)
     int pack;             // 1: final chains are copied into ma/mb, densely (what a host fetch wants); 0: they stay where they were
@@ -2710,7 +2707,7 @@ __device__ int chain_pair(LW& L, CNode* __restrict__ nodes, const ChainArgs& A, 
     }
     CHAIN_TICK(DP_PROFILING && cp, *cp, cp->last, walk)
     if (tierOut) *tierOut = (uint32_t)usedTier;
-    if (lane == 0 && err) atomicOr(&A.cursor[2], err);
+    if (lane == 0 && err) atomicOr(&A.cursor[DP_CUR_ERR], err);
     if (err) resLen = 0;
     if (resLen > 0) {
         if (usedTier == 1) {  // pairs sit in the result column
@@ -2752,7 +2749,7 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
     const uint32_t waves = gridDim.x * WAVES;
     const uint32_t gw = blockIdx.x * WAVES + (threadIdx.x >> 6);
     CNode* nodes = SLIM ? (CNode*)nullptr : A.pool + (uint64_t)gw * A.pool_stride;  // (C_NODES links + the spill area of pairwise_align)
-    if (mode != 0 && (A.cursor[3] != 0 || (A.pass > 0 && A.cursor[8 + A.pass] == 0))) return;  // overflow / every query closed already
+    if (mode != 0 && (A.cursor[DP_CUR_OVERFLOW] != 0 || (A.pass > 0 && A.cursor[DP_CUR_OPEN + A.pass] == 0))) return;  // overflow / every query closed already
     // (profiling build, mode 0: per-wave sums like chain_spec_kernel's, in the slots behind the passes')
     const bool wprof = DP_PROFILING && A.prof && mode == 0;
     ChainProf pf = {};
@@ -2767,7 +2764,7 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
         const uint32_t pb = A.pbase[q];
         const u64 ib = A.ibase[q];
         if ((u64)pb + cnt > (u64)A.pair_cap || ib + (u64)cnt * nSeeds > A.sint_cap) {
-            if (lane == 0) A.cursor[3] = 1;
+            if (lane == 0) A.cursor[DP_CUR_OVERFLOW] = 1;
             continue;
         }
         int mm;
@@ -2842,8 +2839,8 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
                 len = RFL(sp.len);
             } else {
                 if (DP_PROFILING && A.prof && mode == 2 && lane == 0) {  // (what the final walk still chains, and how much of it because of the slim layout)
-                    atomicAdd(&A.cursor[20], 1u);
-                    if (spmm == -2) atomicAdd(&A.cursor[21], 1u);
+                    atomicAdd(&A.cursor[DP_CUR_CHAINED], 1u);
+                    if (spmm == -2) atomicAdd(&A.cursor[DP_CUR_MARKED], 1u);
                 }
                 len = chain_pair(L, nodes, A, aSeg, aN, aStaged, qs, qset, t, mm, ca, cb, haveMask, aMask, nullptr, wprof ? &pf : (ChainProf*)nullptr, &tier);
                 if (SLIM && len < 0) {  // needs the full layout: the query stays open at this pair (marked: slim passes skip it)
@@ -2867,7 +2864,7 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
                 off = (uint32_t)(ib + (u64)i * nSeeds);
                 algBytes += 8ull * (u64)len;
             } else if (len > 0) {
-                if (lane == 0) off = atomicAdd(&A.cursor[0], (uint32_t)len);
+                if (lane == 0) off = atomicAdd(&A.cursor[DP_CUR_INTS], (uint32_t)len);
                 off = (uint32_t)__shfl((int)off, 0, 64);
                 if ((u64)off + (u64)len <= (u64)A.int_cap) {
                     __threadfence_block();
@@ -2876,7 +2873,7 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
                         A.mb[off + x] = ld_agent(&cb[x]);
                     }
                 } else {
-                    if (lane == 0) A.cursor[3] = 1;
+                    if (lane == 0) A.cursor[DP_CUR_OVERFLOW] = 1;
                     len = 0;
                 }
                 algBytes += 8ull * (u64)len;
@@ -2894,8 +2891,8 @@ __global__ __launch_bounds__(64 * (LY != 0 ? S_WAVES : C_WAVES)) void chain_walk
         if (lane == 0) {
             QState st = {mm, i};
             A.qstate[q] = st;
-            if (algBytes) atomicAdd((unsigned long long*)(A.cursor + 32) + (q & 63u), (unsigned long long)algBytes);
-            if (mode == 0 && i < cnt) A.cursor[8] = 1u;  // a query is open ahead of proposal pass 0 (a flag: every writer stores 1)
+            if (algBytes) atomicAdd((unsigned long long*)(A.cursor + DP_CUR_ALG) + (q & (DP_CUR_ALG_SHARDS - 1u)), (unsigned long long)algBytes);
+            if (mode == 0 && i < cnt) A.cursor[DP_CUR_OPEN] = 1u;  // a query is open ahead of proposal pass 0 (a flag: every writer stores 1)
         }
         CHAIN_TICK(wprof, pf, tprev, out)
     }
@@ -2915,8 +2912,8 @@ __global__ __launch_bounds__(64 * S_WAVES) void chain_spec_kernel(const ChainArg
     const uint32_t waves = gridDim.x * WAVES;
     const uint32_t gw = blockIdx.x * WAVES + (threadIdx.x >> 6);
     // (a query that did not fit the buffers left its pairs' pq / clist unwritten: the host repeats the stage with larger ones)
-    if (A.cursor[3] != 0 || A.cursor[8 + A.pass] == 0) return;  // ... or no query is open any more
-    const uint32_t total = (uint32_t)min(totals[0], (u64)A.pair_cap);
+    if (A.cursor[DP_CUR_OVERFLOW] != 0 || A.cursor[DP_CUR_OPEN + A.pass] == 0) return;  // ... or no query is open any more
+    const uint32_t total = (uint32_t)min(totals[DP_FIND_TOT_PAIRS], (u64)A.pair_cap);
     // DP_DEBUG=chain_prof: every wave keeps its own sums (ticks of 10 ns) and stores them into its own slot of the pass - no shared
     // counters (ten thousand atomics on one word take longer than the kernel)
     const bool sprof = DP_PROFILING && A.prof;
@@ -3044,12 +3041,12 @@ __device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane) {
             const int totalLen = __shfl(incl, 63, 64);
             uint32_t off0 = 0;
             if (totalLen > 0) {
-                if (lane == 0) off0 = atomicAdd(&A.cursor[0], (uint32_t)totalLen);
+                if (lane == 0) off0 = atomicAdd(&A.cursor[DP_CUR_INTS], (uint32_t)totalLen);
                 off0 = (uint32_t)__shfl((int)off0, 0, 64);
             }
             myOff = off0 + (uint32_t)(incl - myLen);
             room = (u64)off0 + (u64)totalLen <= (u64)A.int_cap;
-            if (!room && lane == 0) A.cursor[3] = 1;
+            if (!room && lane == 0) A.cursor[DP_CUR_OVERFLOW] = 1;
         }
         if (fin) {
             int wlen = 0;
@@ -3080,10 +3077,10 @@ __device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane) {
     if (lane == 0) {
         QState o = {mm, next};
         A.qstate[q] = o;
-        if (ab) atomicAdd((unsigned long long*)(A.cursor + 32) + (q & 63u), ab);
+        if (ab) atomicAdd((unsigned long long*)(A.cursor + DP_CUR_ALG) + (q & (DP_CUR_ALG_SHARDS - 1u)), ab);
         if (next < cnt) {
-            A.cursor[9 + A.pass] = 1u;  // still open: the next pass has work (a flag)
-            if (A.pass < 2) atomicAdd(&A.cursor[24 + 2 * A.pass + (q & 1u)], cnt - next);  // (what the host sizes the next round's passes by)
+            A.cursor[DP_CUR_OPEN + 1 + A.pass] = 1u;  // still open: the next pass has work (a flag)
+            if (A.pass < 2) atomicAdd(&A.cursor[DP_CUR_LEFT_OPEN + 2 * A.pass + (q & 1u)], cnt - next);  // (what the host sizes the next round's passes by)
         }
     }
 }
@@ -3091,40 +3088,50 @@ __device__ void chain_resolve_query(const ChainArgs& A, uint32_t q, int lane) {
 __global__ __launch_bounds__(256) void chain_resolve_kernel(const ChainArgs A) {
     const int lane = dp_lane();
     const uint32_t waves = gridDim.x * (blockDim.x >> 6);
-    if (A.cursor[3] != 0 || A.cursor[8 + A.pass] == 0) return;  // buffers overflowed (stage is repeated) / no query was open before this pass
+    if (A.cursor[DP_CUR_OVERFLOW] != 0 || A.cursor[DP_CUR_OPEN + A.pass] == 0) return;  // buffers overflowed (stage is repeated) / no query was open before this pass
     for (uint32_t q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < A.nq; q += waves) chain_resolve_query(A, q, lane);
 }
 
-// What the host sends for the query stage - query offsets, query segments, the minCount table - as one block in the context's
-// pinned staging area, laid out as it will lie on the device.  Returns the block's size (0: nothing to send).
-static size_t query_block_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t* mc_n_out,
-                                uint32_t* max_seeds_out, int32_t* mc_last_out, size_t* up_off_out, size_t* up_segs_out) {
-    const uint64_t nseg = nq ? q_off[nq] : 0;
-    // int(hitFraction*float64(n)+0.5) for every n that can occur (seeds/seeds.go:351, overlap/overlap.go:356);
-    // evaluated on the host in IEEE double (this file is built with -ffp-contract=off)
-    uint32_t maxSeeds = 0;
-    for (uint32_t q = 0; q < nq; q++) maxSeeds = std::max<uint32_t>(maxSeeds, (uint32_t)((q_off[q + 1] - q_off[q]) / 2));
-    const uint32_t mc_n = std::max<uint32_t>(maxSeeds + 1, 8);
-    std::vector<int32_t> mc(mc_n);
-    for (uint32_t n = 0; n < mc_n; n++) {
-        volatile double prod = hf * (double)n;
-        volatile double sum = prod + 0.5;
-        mc[n] = (int32_t)sum;
-    }
-    const size_t up_segs = nseg * 4, up_off = ((size_t)nq + 1) * 8, up_mc = (size_t)mc_n * 4;
-    if (dev_reserve(ctx, ctx->d_qsegs, up_off + up_segs + up_mc + 64)) return 0;
+// ---------------------------------------------------------------------------------------------------------------
+// The find stage's host side.  Its arithmetic - block layouts, capacities, grids - is dp_find_plan.h.
+
+static dp_query_out query_fail(int rc) {
+    dp_query_out o = {};
+    o.rc = rc;
+    return o;
+}
+#define DPQ_HIP(call)                                                                        \
+    do {                                                                                     \
+        hipError_t _e = (call);                                                              \
+        if (_e != hipSuccess) return query_fail(dp_fail(ctx, DP_ERR_HIP, #call, _e));        \
+    } while (0)
+
+// The upload block (dp_find_upload) in the context's pinned staging area ctx->h_qup, laid out as it will lie on the device.
+struct QueryBlock {
+    int rc;
+    dp_find_upload up;
+    int32_t mc_last;  // minCount of the largest query
+    bool on_device;   // announced, and brought over by the index build's first launch: nothing to send
+};
+static int32_t query_block_mc_last(const dp_ctx* ctx, const dp_find_upload& up) {
+    return ((const int32_t*)((const uint8_t*)ctx->h_qup.p + up.off_bytes + up.segs_bytes))[up.max_seeds];
+}
+// (this file is built with -ffp-contract=off: the minCount table is evaluated on the host in IEEE double)
+static QueryBlock query_block_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf) {
+    QueryBlock b = {DP_ERR_HIP, dp_find_upload_extents(q_off, nq), 0, false};
+    const dp_find_upload& up = b.up;
+    std::vector<int32_t> mc(up.mc_n);
+    dp_find_mincount_table(hf, up.mc_n, mc.data());
+    if (dev_reserve(ctx, ctx->d_qsegs, up.bytes() + 64)) return b;
     // stage through pinned memory: copies from pageable buffers stall the stream
-    if (pin_reserve(ctx, ctx->h_qup, up_segs + up_off + up_mc + 64)) return 0;
-    uint8_t* up = (uint8_t*)ctx->h_qup.p;
-    memcpy(up, q_off, up_off);
-    memcpy(up + up_off, q_segs, up_segs);
-    memcpy(up + up_off + up_segs, mc.data(), up_mc);
-    *mc_n_out = mc_n;
-    *max_seeds_out = maxSeeds;
-    *mc_last_out = mc[maxSeeds];
-    *up_off_out = up_off;
-    *up_segs_out = up_segs;
-    return up_off + up_segs + up_mc;
+    if (pin_reserve(ctx, ctx->h_qup, up.bytes() + 64)) return b;
+    uint8_t* h = (uint8_t*)ctx->h_qup.p;
+    memcpy(h, q_off, up.off_bytes);
+    memcpy(h + up.off_bytes, q_segs, up.segs_bytes);
+    memcpy(h + up.off_bytes + up.segs_bytes, mc.data(), up.mc_bytes);
+    b.mc_last = query_block_mc_last(ctx, up);
+    b.rc = DP_OK;
+    return b;
 }
 
 // The queries of the round's coming dp_find_overlaps, announced before the index is built: they are staged now and the next
@@ -3137,103 +3144,95 @@ extern "C" int dp_query_prestage(dp_ctx* ctx, const int32_t* q_segs, const uint6
     ctx->q_pre_fetched = false;
     if (!n_queries) return DP_OK;
     hipSetDevice(ctx->device);
-    uint32_t mc_n = 0, maxSeeds = 0;
-    int32_t mcLast = 0;
-    size_t up_off = 0, up_segs = 0;
-    const size_t bytes = query_block_stage(ctx, q_segs, q_off, n_queries, hit_fraction, &mc_n, &maxSeeds, &mcLast, &up_off, &up_segs);
-    if (!bytes) return DP_ERR_HIP;
-    ctx->q_pre_bytes = bytes;
+    const QueryBlock b = query_block_stage(ctx, q_segs, q_off, n_queries, hit_fraction);
+    if (b.rc) return b.rc;
+    ctx->q_pre_bytes = b.up.bytes();
     ctx->q_pre_nq = n_queries;
     ctx->q_pre_hf = hit_fraction;
     return DP_OK;
 }
 
-// Uploads the queries, builds their seed bitsets and runs the index query (Matches -> GetSharedIDs) for all of them.
-// Leaves d_qsegs/d_qoff/d_qsets/d_cand/d_qmeta on the device.  Events ev[4]/ev[5] bracket the query kernel.
+// Is the block announced with dp_query_prestage this call's, and on the device already?  Then it is only compared.
+static bool query_block_prestaged(const dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, const dp_find_upload& up) {
+    return ctx->q_pre_bytes && ctx->q_pre_fetched && ctx->q_pre_nq == nq && ctx->q_pre_hf == hf && ctx->q_pre_bytes == up.bytes() && ctx->h_qup.p &&
+           memcmp(ctx->h_qup.p, q_off, up.off_bytes) == 0 && memcmp((const uint8_t*)ctx->h_qup.p + up.off_bytes, q_segs, up.segs_bytes) == 0;
+}
+
+// The stage's per-query output (ctx->d_qmeta, reserved) carved, and the minCount table where the upload block has it on the device.
+static int query_out_reserve(dp_ctx* ctx, uint32_t nq, const dp_find_upload& up) {
+    return dev_reserve(ctx, ctx->d_qmeta, dp_find_qmeta_layout(nq).bytes + up.mc_bytes + 64);
+}
+static dp_query_out query_out_carve(const dp_ctx* ctx, uint32_t nq, const dp_find_upload& up) {
+    const dp_find_qmeta m = dp_find_qmeta_layout(nq);
+    uint8_t* base = (uint8_t*)ctx->d_qmeta.p;
+    dp_query_out o = {};
+    o.d_qmeta = (uint32_t*)base;
+    o.d_words = (uint64_t*)(base + m.words);
+    o.d_qcnt = (uint32_t*)(base + m.qcnt);
+    o.d_mc = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up.off_bytes + up.segs_bytes);
+    o.mc_n = up.mc_n;
+    return o;
+}
+
+// One launch of query_sparse_kernel / query_kernel: the variants differ in their flags, the seed bit rows, the block to clear and the
+// BIG variants' lists
+template <bool BIG>
+static void query_sparse_launch(dp_ctx* ctx, uint32_t nq, const dp_query_out& o, uint32_t* big, uint32_t big_stride) {
+    const dp_ctx* ix = dp_index_of(ctx);
+    hipLaunchKernelGGL((query_sparse_kernel<BIG>), dim3(nq), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
+                       (const u64*)ix->d_sp_post_off.p, (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p,
+                       ctx->global_n_seqs ? ctx->global_n_seqs : ctx->n_seqs, ctx->W, o.d_mc, o.mc_n, (u64*)ctx->d_cand.p, o.d_qmeta, o.d_words,
+                       o.d_qcnt, ctx->word_base, big, big_stride);
+}
+template <bool HEAVY, bool BIG>
+static void query_launch(dp_ctx* ctx, uint32_t nq, const dp_query_out& o, uint32_t q_split, uint32_t query_dbg, u64* own_zero, uint32_t* big,
+                         uint32_t big_stride) {
+    hipLaunchKernelGGL((query_kernel<HEAVY, BIG>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
+                       (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : ctx->n_seqs, ctx->W,
+                       o.d_mc, o.mc_n, (u64*)ctx->d_cand.p, o.d_qmeta, o.d_words, o.d_qcnt, ctx->word_base,
+                       ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, BIG ? (u64*)nullptr : (u64*)ctx->d_qsets.p,
+                       ctx->SW, query_dbg, q_split, own_zero, big, big_stride);
+}
+
 // dp_query_stage on a sparse index (the query block is staged already): candidate rows as in the dense stage, no seed bit rows -
 // the windows' seed lists (window_list_kernel) instead, whose size does not grow with the seed count
-static int query_stage_sparse(dp_ctx* ctx, uint32_t nq, const uint8_t* up, size_t up_off, size_t up_segs, size_t up_mc, bool on_device, uint32_t mc_n,
-                              uint32_t maxSeeds, uint32_t** d_qmeta_out, uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out,
-                              uint32_t** d_qcnt_out) {
-    const dp_ctx* ix = dp_index_of(ctx);
-    const uint32_t W = ctx->W, M = ctx->n_seqs;
-    const uint64_t nInts = up_segs / 4;
-    if (dev_reserve(ctx, ctx->d_qmeta, (size_t)nq * 16 + (size_t)nq * 8 + (size_t)nq * 4 + (size_t)mc_n * 4 + 64)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_wlist, (size_t)(nInts / 2 + 1) * 4 + 64)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
-    uint32_t* d_qmeta = (uint32_t*)ctx->d_qmeta.p;
-    u64* d_words = (u64*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 16);
-    uint32_t* d_qcnt = (uint32_t*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 24);
-    const int32_t* d_mc = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off + up_segs);
+static dp_query_out query_stage_sparse(dp_ctx* ctx, uint32_t nq, const QueryBlock& b) {
+    const dp_find_upload& up = b.up;
+    const uint32_t W = ctx->W;
+    const uint64_t nInts = up.segs_bytes / 4;
+    if (query_out_reserve(ctx, nq, up)) return query_fail(DP_ERR_HIP);
+    if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return query_fail(DP_ERR_HIP);
+    if (dev_reserve(ctx, ctx->d_wlist, (size_t)(nInts / 2 + 1) * 4 + 64)) return query_fail(DP_ERR_HIP);
+    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return query_fail(DP_ERR_HIP);
+    const dp_query_out o = query_out_carve(ctx, nq, up);
     {
-        const dp_zero_region z[3] = {{ctx->d_cand.p, (size_t)nq * W * 8}, {d_qmeta, (size_t)nq * 28}, {ctx->d_cursor.p, C_CURSOR_BYTES}};
-        const dp_fetch_region f = {ctx->d_qsegs.p, up, up_off + up_segs + up_mc};
-        if (int rc = dp_zero_fetch_regions(ctx, z, 3, &f, on_device ? 0 : 1)) return rc;
+        const dp_zero_region z[3] = {{ctx->d_cand.p, (size_t)nq * W * 8}, {o.d_qmeta, dp_find_qmeta_layout(nq).bytes}, {ctx->d_cursor.p, C_CURSOR_BYTES}};
+        const dp_fetch_region f = {ctx->d_qsegs.p, ctx->h_qup.p, up.bytes()};
+        if (int rc = dp_zero_fetch_regions(ctx, z, 3, &f, b.on_device ? 0 : 1)) return query_fail(rc);
     }
-    DP_HIP(dp_mark(ctx, 4));
-    const uint32_t n_glob = ctx->global_n_seqs ? ctx->global_n_seqs : M;
-    hipLaunchKernelGGL((query_sparse_kernel<false>), dim3(nq), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
-                       (const u64*)ix->d_sp_post_off.p, (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W,
-                       d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)nullptr, 0u);
-    if (maxSeeds > Q_MAXSETS) {
-        const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
-        if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return DP_ERR_HIP;
-        hipLaunchKernelGGL((query_sparse_kernel<true>), dim3(nq), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
-                           (const u64*)ix->d_sp_post_off.p, (const uint32_t*)ix->d_sp_post_ids.p, (const uint32_t*)ix->d_pmeta.p, n_glob, W,
-                           d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base, (uint32_t*)ctx->d_qbig.p, stride);
+    DPQ_HIP(dp_mark(ctx, 4));
+    query_sparse_launch<false>(ctx, nq, o, nullptr, 0u);
+    if (up.max_seeds > Q_MAXSETS) {
+        const uint32_t stride = std::min<uint32_t>(up.max_seeds, Q_BIG_MAXSETS);
+        if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return query_fail(DP_ERR_HIP);
+        query_sparse_launch<true>(ctx, nq, o, (uint32_t*)ctx->d_qbig.p, stride);
     }
     if (nq) hipLaunchKernelGGL(window_list_kernel, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), 0, ctx->stream, ctx->qsegs_dev,
                                ctx->qoff_dev, nq, (uint32_t*)ctx->d_wlist.p);
-    DP_HIP(hipGetLastError());
-    DP_HIP(dp_mark(ctx, 5));
-    *d_qmeta_out = d_qmeta;
-    *d_words_out = d_words;
-    *d_mc_out = (int32_t*)d_mc;
-    *mc_n_out = mc_n;
-    if (d_qcnt_out) *d_qcnt_out = d_qcnt;
-    return DP_OK;
+    DPQ_HIP(hipGetLastError());
+    DPQ_HIP(dp_mark(ctx, 5));
+    return o;
 }
 
-int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, uint32_t** d_qmeta_out,
-                   uint64_t** d_words_out, int32_t** d_mc_out, uint32_t* mc_n_out, uint32_t** d_qcnt_out) {
-    const uint32_t W = ctx->W, SW = ctx->SW, M = ctx->n_seqs;
-    // what the host sends - query offsets, query segments, the minCount table - is one block on both sides: one copy.  Announced
-    // and on the device already (dp_query_prestage + the index build's first launch)?  Then it is only compared.
-    uint32_t mc_n = 0, maxSeeds = 0;
-    int32_t mcLast = 0;
-    size_t up_off = ((size_t)nq + 1) * 8, up_segs = (size_t)(nq ? q_off[nq] : 0) * 4;
-    bool on_device = false;
-    if (ctx->q_pre_bytes && ctx->q_pre_fetched && ctx->q_pre_nq == nq && ctx->q_pre_hf == hf && ctx->q_pre_bytes >= up_off + up_segs &&
-        ctx->h_qup.p && memcmp(ctx->h_qup.p, q_off, up_off) == 0 && memcmp((const uint8_t*)ctx->h_qup.p + up_off, q_segs, up_segs) == 0) {
-        for (uint32_t q = 0; q < nq; q++) maxSeeds = std::max<uint32_t>(maxSeeds, (uint32_t)((q_off[q + 1] - q_off[q]) / 2));
-        mc_n = std::max<uint32_t>(maxSeeds + 1, 8);
-        if (ctx->q_pre_bytes == up_off + up_segs + (size_t)mc_n * 4) {
-            mcLast = ((const int32_t*)((const uint8_t*)ctx->h_qup.p + up_off + up_segs))[maxSeeds];
-            on_device = true;
-        }
-    }
-    if (!on_device && ctx->q_pre_fetched) DP_HIP(dp_stream_sync(ctx));  // (a launch may still be copying the announced block)
-    ctx->q_pre_bytes = 0;
-    ctx->q_pre_fetched = false;
-    if (!on_device) {
-        const size_t bytes = query_block_stage(ctx, q_segs, q_off, nq, hf, &mc_n, &maxSeeds, &mcLast, &up_off, &up_segs);
-        if (!bytes) return DP_ERR_HIP;
-    }
-    const size_t up_mc = (size_t)mc_n * 4;
-    uint8_t* up = (uint8_t*)ctx->h_qup.p;
-    ctx->qoff_dev = (const u64*)ctx->d_qsegs.p;
-    ctx->qsegs_dev = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off);
-    if (ctx->index_sparse) return query_stage_sparse(ctx, nq, up, up_off, up_segs, up_mc, on_device, mc_n, maxSeeds, d_qmeta_out, d_words_out, d_mc_out,
-                                                     mc_n_out, d_qcnt_out);
-    if (dev_reserve(ctx, ctx->d_qsets, (size_t)nq * SW * 8 + 64)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_qmeta, (size_t)nq * 16 + (size_t)nq * 8 + (size_t)nq * 4 + (size_t)mc_n * 4 + 64)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return DP_ERR_HIP;
-    uint32_t* d_qmeta = (uint32_t*)ctx->d_qmeta.p;
-    u64* d_words = (u64*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 16);
-    uint32_t* d_qcnt = (uint32_t*)((uint8_t*)ctx->d_qmeta.p + (size_t)nq * 24);
-    const int32_t* d_mc = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + up_off + up_segs);
-    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
+// ... on a dense index: the queries' seed bitsets are built along, for the chaining stage's prefilter
+static dp_query_out query_stage_dense(dp_ctx* ctx, uint32_t nq, const QueryBlock& b) {
+    const dp_find_upload& up = b.up;
+    const uint32_t W = ctx->W, SW = ctx->SW;
+    if (dev_reserve(ctx, ctx->d_qsets, (size_t)nq * SW * 8 + 64)) return query_fail(DP_ERR_HIP);
+    if (query_out_reserve(ctx, nq, up)) return query_fail(DP_ERR_HIP);
+    if (dev_reserve(ctx, ctx->d_cand, (size_t)nq * W * 8 + 64)) return query_fail(DP_ERR_HIP);
+    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return query_fail(DP_ERR_HIP);
+    const dp_query_out o = query_out_carve(ctx, nq, up);
     // workgroups per query (DP_TUNE=query_split, experiments: see query_kernel)
     const int split_env = (int)dp_tune("query_split", 0);
     const uint32_t query_dbg = (uint32_t)dp_tune("query_debug", 0);
@@ -3245,51 +3244,46 @@ int dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, ui
         // the upload block from its pinned staging - no copy is handed to the runtime)
         // (with one workgroup per query - the default - the light query kernel clears its query's rows itself and this launch only
         // brings the upload block over)
-        const dp_zero_region z[4] = {{ctx->d_qsets.p, (size_t)nq * SW * 8}, {ctx->d_cand.p, (size_t)nq * W * 8}, {d_qmeta, (size_t)nq * 28},
-                                     {ctx->d_cursor.p, C_CURSOR_BYTES}};
-        const dp_fetch_region f = {ctx->d_qsegs.p, up, up_off + up_segs + up_mc};
-        if (int rc = dp_zero_fetch_regions(ctx, z, own_rows ? 0 : 4, &f, on_device ? 0 : 1)) return rc;  // (nothing at all: no launch)
+        const dp_zero_region z[4] = {{ctx->d_qsets.p, (size_t)nq * SW * 8}, {ctx->d_cand.p, (size_t)nq * W * 8},
+                                     {o.d_qmeta, dp_find_qmeta_layout(nq).bytes}, {ctx->d_cursor.p, C_CURSOR_BYTES}};
+        const dp_fetch_region f = {ctx->d_qsegs.p, ctx->h_qup.p, up.bytes()};
+        if (int rc = dp_zero_fetch_regions(ctx, z, own_rows ? 0 : 4, &f, b.on_device ? 0 : 1)) return query_fail(rc);  // (nothing at all: no launch)
     }
-    DP_HIP(dp_mark(ctx, 4));
-    hipLaunchKernelGGL((query_kernel<false>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev, ctx->qoff_dev, nq,
-                       (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W,
-                       (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
-                       ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)ctx->d_qsets.p, SW,
-                       query_dbg, q_split, own_rows ? (u64*)ctx->d_cursor.p : (u64*)nullptr, (uint32_t*)nullptr, 0u);
+    DPQ_HIP(dp_mark(ctx, 4));
     // the 16-ladder / exact-count regimes start at minCount 13: only a batch with a query of that many seeds needs the heavy variant
-    if (mcLast >= 13) hipLaunchKernelGGL((query_kernel<true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev,
-                                         ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p,
-                                         ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p,
-                                         d_qmeta, d_words, d_qcnt, ctx->word_base,
-                                         ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr,
-                                         (u64*)ctx->d_qsets.p, SW, query_dbg, q_split, (u64*)nullptr, (uint32_t*)nullptr, 0u);
-    if (maxSeeds > Q_MAXSETS) {
+    const bool heavy = b.mc_last >= 13;
+    query_launch<false, false>(ctx, nq, o, q_split, query_dbg, own_rows ? (u64*)ctx->d_cursor.p : (u64*)nullptr, nullptr, 0u);
+    if (heavy) query_launch<true, false>(ctx, nq, o, q_split, query_dbg, nullptr, nullptr, 0u);
+    if (up.max_seeds > Q_MAXSETS) {
         // a query may hold more sets than the kernel's LDS lists (round 6): the BIG variants, lists in global memory, for those queries
-        const uint32_t stride = std::min<uint32_t>(maxSeeds, Q_BIG_MAXSETS);
-        if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * q_split * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return DP_ERR_HIP;
-        hipLaunchKernelGGL((query_kernel<false, true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream, ctx->qsegs_dev,
-                           ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p, (const uint32_t*)ctx->d_pmeta.p,
-                           ctx->global_n_seqs ? ctx->global_n_seqs : M, W, (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta,
-                           d_words, d_qcnt, ctx->word_base,
-                           ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr, (u64*)nullptr, SW, query_dbg,
-                           q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
-        if (mcLast >= 13) hipLaunchKernelGGL((query_kernel<true, true>), dim3(nq * q_split), dim3(64 * Q_WAVES), 0, ctx->stream,
-                                             ctx->qsegs_dev, ctx->qoff_dev, nq, (const u64*)ctx->d_posting.p,
-                                             (const uint32_t*)ctx->d_pmeta.p, ctx->global_n_seqs ? ctx->global_n_seqs : M, W,
-                                             (const int32_t*)d_mc, mc_n, (u64*)ctx->d_cand.p, d_qmeta, d_words, d_qcnt, ctx->word_base,
-                                             ctx->chunks_on_device ? (const uint32_t*)ctx->d_nseqs.p : (const uint32_t*)nullptr,
-                                             (u64*)nullptr, SW, query_dbg, q_split, (u64*)nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+        const uint32_t stride = std::min<uint32_t>(up.max_seeds, Q_BIG_MAXSETS);
+        if (dev_reserve(ctx, ctx->d_qbig, (size_t)nq * q_split * ((size_t)stride + 2) * Q_BIG_WORDS_PER_SET * 4 + 64)) return query_fail(DP_ERR_HIP);
+        query_launch<false, true>(ctx, nq, o, q_split, query_dbg, nullptr, (uint32_t*)ctx->d_qbig.p, stride);
+        if (heavy) query_launch<true, true>(ctx, nq, o, q_split, query_dbg, nullptr, (uint32_t*)ctx->d_qbig.p, stride);
     }
-    DP_HIP(hipGetLastError());
-    DP_HIP(dp_mark(ctx, 5));
-
-    *d_qmeta_out = d_qmeta;
-    *d_words_out = d_words;
-    *d_mc_out = (int32_t*)d_mc;
-    *mc_n_out = mc_n;
-    if (d_qcnt_out) *d_qcnt_out = d_qcnt;
-    return DP_OK;
+    DPQ_HIP(hipGetLastError());
+    DPQ_HIP(dp_mark(ctx, 5));
+    return o;
 }
+
+// Uploads the queries, builds their seed bitsets and runs the index query (Matches -> GetSharedIDs) for all of them.
+// Leaves d_qsegs/d_qoff/d_qsets/d_cand/d_qmeta on the device.  Events ev[4]/ev[5] bracket the query kernel.
+dp_query_out dp_query_stage(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf) {
+    // what the host sends - query offsets, query segments, the minCount table - is one block on both sides: one copy.  Announced
+    // and on the device already (dp_query_prestage + the index build's first launch)?  Then it is only compared.
+    QueryBlock b = {DP_OK, dp_find_upload_extents(q_off, nq), 0, false};
+    b.on_device = query_block_prestaged(ctx, q_segs, q_off, nq, hf, b.up);
+    if (!b.on_device && ctx->q_pre_fetched) DPQ_HIP(dp_stream_sync(ctx));  // (a launch may still be copying the announced block)
+    ctx->q_pre_bytes = 0;
+    ctx->q_pre_fetched = false;
+    if (b.on_device) b.mc_last = query_block_mc_last(ctx, b.up);
+    else b = query_block_stage(ctx, q_segs, q_off, nq, hf);
+    if (b.rc) return query_fail(b.rc);
+    ctx->qoff_dev = (const u64*)ctx->d_qsegs.p;
+    ctx->qsegs_dev = (const int32_t*)((const uint8_t*)ctx->d_qsegs.p + b.up.off_bytes);
+    return ctx->index_sparse ? query_stage_sparse(ctx, nq, b) : query_stage_dense(ctx, nq, b);
+}
+
 
 int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out);
 
@@ -3299,152 +3293,164 @@ struct FindState {
     uint32_t nq = 0;
     int k = 0;
     uint32_t max_query_len = 0;
-    int chain_tier = 0, passes = 3;
-    uint32_t walk_blocks = 0, spec_blocks = 1024;
-    uint32_t* d_qmeta = nullptr;
-    uint32_t* d_qcnt = nullptr;
-    const int32_t* d_mc = nullptr;
-    uint32_t mc_n = 0;
-    uint64_t want_pairs = 0, want_sints = 0, want_ints = 0;
-    uint32_t pair_cap = 0, int_cap = 0;
-    uint64_t sint_cap = 0;
+    int chain_tier = 0;
+    dp_find_geom g = {};    // passes and grids
+    dp_query_out q = {};    // what the query stage left
+    dp_find_caps caps = {};
     int attempt = 0;
     bool paths = false;  // DP_DEBUG=chain_paths was set for this stage (dp_debug_chain_paths)
     float chain_ms = 0;
     bool pending = false;
     bool defer_fetch = false;  // the first attempt's read-back rides in the anchors launch of the consensus call (a pending stage)
     bool fetch_owed = false;
-    uint32_t cur[32];
+    dp_find_report rep = {};   // what the last checked attempt reported
     double query_ms = 0;
-    uint64_t query_bytes = 0, chain_bytes = 0, alg_bytes = 0;
+    uint64_t query_bytes = 0, chain_bytes = 0;
 };
+static_assert(sizeof(QState) == DP_FIND_QSTATE_BYTES, "dp_find_pbase_layout carves QState");
 void dp_find_state_free(dp_ctx* ctx) {
     delete ctx->find_state;
     ctx->find_state = nullptr;
 }
 bool dp_find_pending(const dp_ctx* ctx) { return ctx->find_state && ctx->find_state->pending; }
-uint32_t dp_find_pair_cap(const dp_ctx* ctx) { return ctx->find_state ? ctx->find_state->pair_cap : 0; }
+uint32_t dp_find_pair_cap(const dp_ctx* ctx) { return ctx->find_state ? ctx->find_state->caps.pair_cap : 0; }
+// the totals of the cursor block on the device; the pair total's low word is what match_anchor_kernel bounds its slots by
+static u64* find_totals_dev(const dp_ctx* ctx) { return (u64*)((uint32_t*)ctx->d_cursor.p + DP_CUR_TOTALS); }
+static const uint32_t* find_pair_total_dev(const dp_ctx* ctx) { return (const uint32_t*)(find_totals_dev(ctx) + DP_FIND_TOT_PAIRS); }
+// what a chaining stage reports to the host: its cursor block and the query meta block, into their pinned blocks
+static void find_report_regions(const dp_ctx* ctx, const FindState& st, dp_fetch_region f[2]) {
+    f[0] = {ctx->h_cursor.p, ctx->d_cursor.p, C_CURSOR_BYTES};
+    f[1] = {ctx->h_qm.p, st.q.d_qmeta, dp_find_qmeta_layout(st.nq).bytes};
+}
 
-// one attempt of the chaining stage with the current capacities: launches and the read-back of what it reports; no wait
-static int chain_enqueue(dp_ctx* ctx, FindState& st) {
-    if (st.attempt > 8) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps: output buffers keep overflowing");
-    const uint32_t nq = st.nq;
-    const uint32_t W = ctx->W, SW = ctx->SW;
-    uint32_t* d_cur = (uint32_t*)ctx->d_cursor.p;
-    u64* d_totals = (u64*)((uint8_t*)ctx->d_cursor.p + 64);
-    u64* d_ibase = (u64*)ctx->d_pbase.p;  // (8-byte aligned first)
-    uint32_t* d_pbase = (uint32_t*)(d_ibase + nq + 1);
-    QState* d_qstate = (QState*)(d_pbase + nq + 1 + ((nq + 1) & 1));
+// the attempt's buffers, for st.caps.want_*; then its capacities
+static int chain_reserve(dp_ctx* ctx, FindState& st) {
+    const dp_find_caps& c = st.caps;
     {
         // (a stage left pending is read by the consensus kernel before anybody knows whether it fitted its buffers: records the
         // stage did not write must at least be harmless - all-zero when the buffer is new, those of an earlier round otherwise)
         const void* before = ctx->d_mrec.p;
-        if (dev_reserve(ctx, ctx->d_mrec, (size_t)st.want_pairs * sizeof(MRec))) return DP_ERR_HIP;
+        if (dev_reserve(ctx, ctx->d_mrec, (size_t)c.want_pairs * sizeof(MRec))) return DP_ERR_HIP;
         if (ctx->d_mrec.p != before) DP_HIP(hipMemsetAsync(ctx->d_mrec.p, 0, ctx->d_mrec.cap, ctx->stream));
     }
-    if (dev_reserve(ctx, ctx->d_pspec, (size_t)st.want_pairs * sizeof(PSpec))) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_clist, (size_t)st.want_pairs * 8)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_sa, (size_t)st.want_sints * 4)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_sb, (size_t)st.want_sints * 4)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_ma, (size_t)st.want_ints * 4)) return DP_ERR_HIP;
-    if (dev_reserve(ctx, ctx->d_mb, (size_t)st.want_ints * 4)) return DP_ERR_HIP;
-    st.pair_cap = (uint32_t)std::min<uint64_t>(0xfffffff0ull, st.want_pairs);
-    st.sint_cap = st.want_sints;
-    st.int_cap = (uint32_t)std::min<uint64_t>(0xfffffff0ull, st.want_ints);
+    if (dev_reserve(ctx, ctx->d_pspec, (size_t)c.want_pairs * sizeof(PSpec))) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_clist, (size_t)c.want_pairs * 8)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_sa, (size_t)c.want_sints * 4)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_sb, (size_t)c.want_sints * 4)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_ma, (size_t)c.want_ints * 4)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_mb, (size_t)c.want_ints * 4)) return DP_ERR_HIP;
+    dp_find_caps_set(st.caps);
+    return DP_OK;
+}
+
+// the kernels' arguments for an attempt with the current capacities (pass 0; no profile buffer)
+static ChainArgs chain_args(const dp_ctx* ctx, const FindState& st) {
+    const dp_find_pbase pb = dp_find_pbase_layout(st.nq);
+    uint8_t* d_pb = (uint8_t*)ctx->d_pbase.p;
     ChainArgs A;
     A.qsegs = ctx->qsegs_dev;
     A.qoff = ctx->qoff_dev;
-    A.nq = nq;
+    A.nq = st.nq;
     A.qsets = (const u64*)ctx->d_qsets.p;
-    A.qmeta = st.d_qmeta;
-    A.qcnt = st.d_qcnt;
+    A.qmeta = st.q.d_qmeta;
+    A.qcnt = st.q.d_qcnt;
     A.cand = (const u64*)ctx->d_cand.p;
     A.refs = (const dp_seq_ref*)ctx->d_seqrefs.p;
     A.segs = (const int32_t*)ctx->d_segs.p;
     A.seedsets = (const u64*)ctx->d_seedsets.p;
-    A.W = W;
-    A.SW = SW;
-    A.mc = st.d_mc;
-    A.mc_n = st.mc_n;
+    A.W = ctx->W;
+    A.SW = ctx->SW;
+    A.mc = st.q.d_mc;
+    A.mc_n = st.q.mc_n;
     A.k = st.k;
     A.maxLength = (int)st.max_query_len;
     A.tier = st.chain_tier;
     A.pool = (CNode*)ctx->d_pool.p;
     A.pool_stride = chain_pool_stride(st.max_query_len);
-    A.pbase = d_pbase;
-    A.ibase = d_ibase;
+    A.pbase = (uint32_t*)(d_pb + pb.pbase);
+    A.ibase = (u64*)(d_pb + pb.ibase);
     A.clist = (uint32_t*)ctx->d_clist.p;
-    A.pq = A.clist + st.pair_cap;
+    A.pq = A.clist + st.caps.pair_cap;
     A.pass = 0;
     A.pspec = (PSpec*)ctx->d_pspec.p;
-    A.qstate = d_qstate;
+    A.qstate = (QState*)(d_pb + pb.qstate);
     A.recs = (MRec*)ctx->d_mrec.p;
     A.sa = (int32_t*)ctx->d_sa.p;
     A.sb = (int32_t*)ctx->d_sb.p;
     A.ma = (int32_t*)ctx->d_ma.p;
     A.mb = (int32_t*)ctx->d_mb.p;
-    {
-        // a stage whose consumers are on the device (it stays pending for dp_consensus_paf) leaves the chains in their scratch
-        // columns: no cursor atomics, no copies in the walk and resolve kernels (DP_CHAIN_PACK=1: always pack)
-        const bool always_pack = dp_env_tristate("DP_CHAIN_PACK") == 1;
-        A.pack = (st.defer_fetch && !always_pack && st.sint_cap < 0xfffffff0ull) ? 0 : 1;
-        A.walk_always = dp_env_tristate("DP_CHAIN_PERFECT") == 0 ? 1 : 0;
-        A.paths = dp_debug("chain_paths") ? 1 : 0;
-        st.paths = A.paths != 0;
-        ctx->chains_packed = A.pack != 0;
-    }
-    A.pair_cap = st.pair_cap;
-    A.sint_cap = st.sint_cap;
-    A.int_cap = st.int_cap;
-    A.cursor = d_cur;
-    const uint32_t walk0_blocks = std::max<uint32_t>(1, std::min<uint32_t>(1024, (nq + S_WAVES - 1) / S_WAVES));  // grid of the slim walk
+    // a stage whose consumers are on the device (it stays pending for dp_consensus_paf) leaves the chains in their scratch
+    // columns: no cursor atomics, no copies in the walk and resolve kernels (DP_CHAIN_PACK=1: always pack)
+    const bool always_pack = dp_env_tristate("DP_CHAIN_PACK") == 1;
+    A.pack = (st.defer_fetch && !always_pack && st.caps.sint_cap < DP_FIND_MAX_PAIRS) ? 0 : 1;
+    A.walk_always = dp_env_tristate("DP_CHAIN_PERFECT") == 0 ? 1 : 0;
+    A.paths = dp_debug("chain_paths") ? 1 : 0;
+    A.pair_cap = st.caps.pair_cap;
+    A.sint_cap = st.caps.sint_cap;
+    A.int_cap = st.caps.int_cap;
+    A.cursor = (uint32_t*)ctx->d_cursor.p;
     A.n_refs = std::max<uint32_t>(1, ctx->n_seqs);
     A.prof = nullptr;
     A.prof_walk_slot = 0;
     A.prof_stride = 0;
-    if (ctx->dbg.chain_prof) {
-        const size_t pb = ((size_t)st.passes * st.spec_blocks * S_WAVES + (size_t)walk0_blocks * S_WAVES) * 128;
-        if (dev_reserve(ctx, ctx->d_sched, pb + 128)) return DP_ERR_HIP;
-        A.prof = (unsigned long long*)ctx->d_sched.p;
-        A.prof_walk_slot = (uint32_t)(st.passes * st.spec_blocks * S_WAVES);
-        A.prof_stride = st.spec_blocks * S_WAVES;
-        DP_HIP(hipMemsetAsync(A.prof, 0, pb, ctx->stream));
-    }
-    if (st.attempt > 0) DP_HIP(hipMemsetAsync(ctx->d_cursor.p, 0, C_CURSOR_BYTES, ctx->stream));  // (attempt 0: zeroed with the query stage's buffers)
+    return A;
+}
+
+// DP_DEBUG=chain_prof: the per-wave profile slots of the attempt, zeroed
+static int chain_prof_attach(dp_ctx* ctx, const FindState& st, ChainArgs& A) {
+    if (!ctx->dbg.chain_prof) return DP_OK;
+    if (dev_reserve(ctx, ctx->d_sched, st.g.prof_bytes + DP_FIND_PROF_SLOT)) return DP_ERR_HIP;
+    A.prof = (unsigned long long*)ctx->d_sched.p;
+    A.prof_walk_slot = st.g.prof_walk_slot;
+    A.prof_stride = st.g.prof_stride;
+    DP_HIP(hipMemsetAsync(A.prof, 0, st.g.prof_bytes, ctx->stream));
+    return DP_OK;
+}
+
+// The schedule of an attempt: pair offsets, walk 0, the proposal passes (spec + resolve), the final walk.  Events ev[6]/ev[7] bracket it.
+static int chain_launch(dp_ctx* ctx, const dp_find_geom& g, ChainArgs A) {
+    u64* d_totals = find_totals_dev(ctx);
     DP_HIP(dp_mark(ctx, 6));
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)st.d_qcnt, ctx->qoff_dev, nq, d_pbase,
-                       d_ibase, d_totals);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, A.qcnt, ctx->qoff_dev, A.nq, A.pbase, A.ibase, d_totals);
     // mode 0 on the slim layout (a forced tier is the full layout's business)
-    const uint32_t spec_blocks = st.spec_blocks;
-    if (A.tier == 0 && st.passes > 0) {
-        hipLaunchKernelGGL((chain_walk_kernel<1>), dim3(walk0_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, 0);
+    if (g.slim_walk0) {
+        hipLaunchKernelGGL((chain_walk_kernel<1>), dim3(g.walk0_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, 0);
     } else {
-        hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(st.walk_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 0);
+        hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(g.walk_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 0);
     }
-    for (int ps = 0; ps < st.passes; ps++) {
+    for (int ps = 0; ps < g.passes; ps++) {
         A.pass = ps;
-        hipLaunchKernelGGL(chain_spec_kernel, dim3(spec_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, (const u64*)d_totals);
-        hipLaunchKernelGGL(chain_resolve_kernel, dim3(std::min<uint32_t>(1024, (nq + 3) / 4)), dim3(256), 0, ctx->stream, A);
+        hipLaunchKernelGGL(chain_spec_kernel, dim3(g.spec_blocks), dim3(64 * S_WAVES), 0, ctx->stream, A, (const u64*)d_totals);
+        hipLaunchKernelGGL(chain_resolve_kernel, dim3(g.resolve_blocks), dim3(256), 0, ctx->stream, A);
     }
-    A.pass = st.passes;
-    // the final walk rarely has a query to do after the passes: a quarter of the workgroups (each wants 128 KB of a CU's LDS before it
-    // can look whether there is anything to do) - a query that is still open finds a wave among 192
-    const uint32_t final_blocks = st.passes > 0 ? std::min<uint32_t>(st.walk_blocks, 48) : st.walk_blocks;
-    hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(final_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 2);
+    A.pass = g.passes;
+    hipLaunchKernelGGL((chain_walk_kernel<0>), dim3(g.final_blocks), dim3(64 * C_WAVES), 0, ctx->stream, A, 2);
     DP_HIP(hipGetLastError());
     DP_HIP(dp_mark(ctx, 7));
-    {
-        // the cursor block and the status words, per-query posting-word counts and candidate counts (a few KB) come back in any
-        // case, in the same wait: stored into their pinned blocks by one small launch of this stream (dp_zero_fetch_regions works
-        // in either direction) instead of two copies handed to the runtime
-        // (a stage that stays pending: nobody reads them before the consensus call's wait - its anchors launch, the next one of
-        // this stream, stores them instead: dp_match_anchors_launch)
-        if (st.defer_fetch && st.attempt == 0) {
-            st.fetch_owed = true;
-        } else {
-            const dp_fetch_region f[2] = {{ctx->h_cursor.p, ctx->d_cursor.p, C_CURSOR_BYTES}, {ctx->h_qm.p, st.d_qmeta, (size_t)nq * 28}};
-            if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, f, 2)) return rc;
-        }
+    return DP_OK;
+}
+
+// one attempt of the chaining stage with the current capacities: launches and the read-back of what it reports; no wait
+static int chain_enqueue(dp_ctx* ctx, FindState& st) {
+    if (st.attempt > 8) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps: output buffers keep overflowing");
+    if (int rc = chain_reserve(ctx, st)) return rc;
+    ChainArgs A = chain_args(ctx, st);
+    st.paths = A.paths != 0;
+    ctx->chains_packed = A.pack != 0;
+    if (int rc = chain_prof_attach(ctx, st, A)) return rc;
+    if (st.attempt > 0) DP_HIP(hipMemsetAsync(ctx->d_cursor.p, 0, C_CURSOR_BYTES, ctx->stream));  // (attempt 0: zeroed with the query stage's buffers)
+    if (int rc = chain_launch(ctx, st.g, A)) return rc;
+    // the cursor block and the status words, per-query posting-word counts and candidate counts (a few KB) come back in any
+    // case, in the same wait: stored into their pinned blocks by one small launch of this stream (dp_zero_fetch_regions works
+    // in either direction) instead of two copies handed to the runtime
+    // (a stage that stays pending: nobody reads them before the consensus call's wait - its anchors launch, the next one of
+    // this stream, stores them instead: dp_match_anchors_launch)
+    if (st.defer_fetch && st.attempt == 0) {
+        st.fetch_owed = true;
+    } else {
+        dp_fetch_region f[2];
+        find_report_regions(ctx, st, f);
+        if (int rc = dp_zero_fetch_regions(ctx, nullptr, 0, f, 2)) return rc;
     }
     st.attempt++;
     return DP_OK;
@@ -3452,104 +3458,100 @@ static int chain_enqueue(dp_ctx* ctx, FindState& st) {
 
 // after a wait: what did the attempt report?  *grow: a buffer was too small - capacities raised, run it again
 static int chain_check(dp_ctx* ctx, FindState& st, bool* grow) {
-    memcpy(st.cur, ctx->h_cursor.p, 128);
-    st.alg_bytes = 0;
-    for (int i = 0; i < 64; i++) st.alg_bytes += ((const uint64_t*)((const uint8_t*)ctx->h_cursor.p + 128))[i];
+    st.rep = dp_find_decode(ctx->h_cursor.p);
     st.chain_ms += dp_elapsed(ctx, 6, 7);
-    uint64_t tot_pairs, tot_sints;
-    memcpy(&tot_pairs, &st.cur[16], 8);
-    memcpy(&tot_sints, &st.cur[18], 8);
-    if (tot_pairs > 0xfffffff0ull) return dp_fail(ctx, DP_ERR_CAPACITY, "more than 2^32 (query, candidate) pairs in one round");
     *grow = false;
-    if (tot_pairs > st.pair_cap) {
-        st.want_pairs = tot_pairs + tot_pairs / 2 + 1024;
-        *grow = true;
+    switch (dp_find_caps_check(st.rep, st.caps)) {
+    case DP_FIND_TOO_MANY_PAIRS: return dp_fail(ctx, DP_ERR_CAPACITY, "more than 2^32 (query, candidate) pairs in one round");
+    case DP_FIND_FLAG_ALONE: return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps: overflow flag without a total that exceeds a buffer");
+    case DP_FIND_GROW: *grow = true; break;
+    case DP_FIND_FITS: break;
     }
-    if (tot_sints > st.sint_cap) {
-        st.want_sints = tot_sints + tot_sints / 2 + 1024;
-        *grow = true;
-    }
-    if ((uint64_t)st.cur[0] > st.int_cap) {
-        st.want_ints = std::max<uint64_t>(st.want_ints * 2, (uint64_t)st.cur[0] + 1024);
-        *grow = true;
-    }
-    if (!*grow && st.cur[3]) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps: overflow flag without a total that exceeds a buffer");
     return DP_OK;
+}
+
+// DP_DEBUG=chain_prof: the per-wave profile slots of the last attempt, summed per launch (walk 0, then every pass)
+static void chain_prof_print(dp_ctx* ctx, const FindState& st) {
+    const dp_find_geom& g = st.g;
+    std::vector<unsigned long long> h(ctx->d_sched.p ? g.prof_bytes / 8 : 0);
+    if (h.empty() || hipMemcpy(h.data(), ctx->d_sched.p, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) h.clear();
+    for (int ps = -1; ps < g.passes && !h.empty(); ps++) {
+        const size_t first = ps < 0 ? g.prof_walk_slot : (size_t)ps * g.prof_stride, n_slots = ps < 0 ? g.prof_walk_slots : g.prof_stride;
+        unsigned long long sum[16] = {0}, mx[16] = {0}, t0 = ~0ull, t1 = 0, busiest = 0, mostPairs = 0, w5[5] = {0, 0, 0, 0, 0};
+        size_t active = 0;
+        for (size_t w = 0; w < n_slots; w++) {
+            const unsigned long long* r = &h[16 * (first + w)];
+            for (int i = 0; i < 5; i++) w5[i] += (r[15] >> (12 * i)) & 0xfff;
+            if (!r[10]) continue;
+            t0 = std::min(t0, r[10]);
+            t1 = std::max(t1, r[11]);
+            if (!r[0]) continue;
+            active++;
+            for (int i = 0; i < 10; i++) sum[i] += r[i];
+            for (int i = 2; i < 10; i++) mx[i] = std::max(mx[i], r[i]);
+            for (int i = 12; i < 16; i++) sum[i] += r[i];
+            busiest = std::max(busiest, r[11] - r[10]);
+            mostPairs = std::max(mostPairs, r[0]);
+        }
+        if (!sum[0]) continue;
+        const double n = (double)sum[0], nc = (double)std::max<unsigned long long>(1, sum[1]);
+        fprintf(stderr, "[chain prof] pass %d (-1 = walk 0; its 'records' include the candidate list): %llu pairs (%llu chained) on %zu waves (at most %llu per wave), kernel span %.1f us, busiest wave %.1f us | us per pair: "
+                        "records %.2f stage a %.2f prefilter %.2f chain_pair %.2f | per chained pair: stage b + flags %.2f initial %.2f events + walk %.2f (b events %.2f us; %.1f events; %.1f %% perfect chains) out %.2f\n",
+                ps, sum[0], sum[1], active, mostPairs, (t1 - t0) / 100.0, busiest / 100.0, sum[2] / 100.0 / n, sum[3] / 100.0 / n, sum[4] / 100.0 / n,
+                sum[5] / 100.0 / n, sum[6] / 100.0 / nc, sum[7] / 100.0 / nc, sum[8] / 100.0 / nc, sum[12] / 100.0 / nc, sum[13] / nc, 100.0 * sum[14] / nc, sum[9] / 100.0 / nc);
+        fprintf(stderr, "[chain prof]   walked, not perfect: %llu size limits, %llu event 0 starts no / several chains, %llu start beyond maxBIndex, %llu seed or gap, %llu second start\n",
+                w5[0], w5[1], w5[2], w5[3], w5[4]);
+        fprintf(stderr, "[chain prof]   largest per-wave sums, us: records %.1f stage a %.1f prefilter %.1f chain_pair %.1f (stage b %.1f initial %.1f walk %.1f) out %.1f\n",
+                mx[2] / 100.0, mx[3] / 100.0, mx[4] / 100.0, mx[5] / 100.0, mx[6] / 100.0, mx[7] / 100.0, mx[8] / 100.0, mx[9] / 100.0);
+    }
+    fprintf(stderr, "[chain prof] final walk: %u pairs chained, %u of them marked for the full layout; open ahead of pass 1 / 2: %u / %u, passes %d\n",
+            st.rep.chained, st.rep.marked, dp_find_open_ahead(st.rep, 1), dp_find_open_ahead(st.rep, 2), g.passes);
 }
 
 // a checked attempt without overflow: the stage's errors, totals and statistics
 static int chain_finish(dp_ctx* ctx, FindState& st) {
+    const dp_find_report& r = st.rep;
     st.pending = false;
-    if (ctx->dbg.chain_prof && ctx->d_sched.p) {
-        const size_t waves = (size_t)st.spec_blocks * S_WAVES;
-        const size_t wwaves = (size_t)std::max<uint32_t>(1, std::min<uint32_t>(1024, (st.nq + S_WAVES - 1) / S_WAVES)) * S_WAVES;
-        std::vector<unsigned long long> h(((size_t)st.passes * waves + wwaves) * 16);
-        if (hipMemcpy(h.data(), ctx->d_sched.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            for (int ps = -1; ps < st.passes; ps++) {
-                unsigned long long sum[16] = {0}, mx[16] = {0}, t0 = ~0ull, t1 = 0, busiest = 0, mostPairs = 0;
-                size_t active = 0;
-                for (size_t w = 0; w < (ps < 0 ? wwaves : waves); w++) {
-                    const unsigned long long* r = &h[16 * (ps < 0 ? (size_t)st.passes * waves + w : (size_t)ps * waves + w)];
-                    if (!r[10]) continue;
-                    t0 = std::min(t0, r[10]);
-                    t1 = std::max(t1, r[11]);
-                    if (!r[0]) continue;
-                    active++;
-                    for (int i = 0; i < 10; i++) sum[i] += r[i];
-                    for (int i = 2; i < 10; i++) mx[i] = std::max(mx[i], r[i]);
-                    for (int i = 12; i < 16; i++) sum[i] += r[i];
-                    busiest = std::max(busiest, r[11] - r[10]);
-                    mostPairs = std::max(mostPairs, r[0]);
-                }
-                if (!sum[0]) continue;
-                const double n = (double)sum[0], nc = (double)std::max<unsigned long long>(1, sum[1]);
-                fprintf(stderr, "[chain prof] pass %d (-1 = walk 0; its 'records' include the candidate list): %llu pairs (%llu chained) on %zu waves (at most %llu per wave), kernel span %.1f us, busiest wave %.1f us | us per pair: "
-                                "records %.2f stage a %.2f prefilter %.2f chain_pair %.2f | per chained pair: stage b + flags %.2f initial %.2f events + walk %.2f (b events %.2f us; %.1f events; %.1f %% perfect chains) out %.2f\n",
-                        ps, sum[0], sum[1], active, mostPairs, (t1 - t0) / 100.0, busiest / 100.0, sum[2] / 100.0 / n, sum[3] / 100.0 / n, sum[4] / 100.0 / n,
-                        sum[5] / 100.0 / n, sum[6] / 100.0 / nc, sum[7] / 100.0 / nc, sum[8] / 100.0 / nc, sum[12] / 100.0 / nc, sum[13] / nc, 100.0 * sum[14] / nc, sum[9] / 100.0 / nc);
-                {
-                    unsigned long long w5[5] = {0, 0, 0, 0, 0};
-                    for (size_t w = 0; w < (ps < 0 ? wwaves : waves); w++) {
-                        const unsigned long long v = h[16 * (ps < 0 ? (size_t)st.passes * waves + w : (size_t)ps * waves + w) + 15];
-                        for (int i = 0; i < 5; i++) w5[i] += (v >> (12 * i)) & 0xfff;
-                    }
-                    fprintf(stderr, "[chain prof]   walked, not perfect: %llu size limits, %llu event 0 starts no / several chains, %llu start beyond maxBIndex, %llu seed or gap, %llu second start\n",
-                            w5[0], w5[1], w5[2], w5[3], w5[4]);
-                }
-                fprintf(stderr, "[chain prof]   largest per-wave sums, us: records %.1f stage a %.1f prefilter %.1f chain_pair %.1f (stage b %.1f initial %.1f walk %.1f) out %.1f\n",
-                        mx[2] / 100.0, mx[3] / 100.0, mx[4] / 100.0, mx[5] / 100.0, mx[6] / 100.0, mx[7] / 100.0, mx[8] / 100.0, mx[9] / 100.0);
-            }
-        }
-    }
-    if (ctx->dbg.chain_prof) fprintf(stderr, "[chain prof] final walk: %u pairs chained, %u of them marked for the full layout; open ahead of pass 1 / 2: %u / %u, passes %d\n",
-                            st.cur[20], st.cur[21], st.cur[24] + st.cur[25], st.cur[26] + st.cur[27], st.passes);
+    if (ctx->dbg.chain_prof) chain_prof_print(ctx, st);
     st.query_ms = dp_elapsed(ctx, 4, 5);
-    st.chain_bytes = st.alg_bytes;
-    if (st.cur[2]) {
+    st.chain_bytes = r.alg_bytes;
+    if (r.err) {
         char msg[160];
-        snprintf(msg, sizeof msg, "overlap chaining hit a reference capacity limit (bits %u: 1 reduced buffer, 2 state pool, 4 results, 8 nodes)", st.cur[2]);
+        snprintf(msg, sizeof msg, "overlap chaining hit a reference capacity limit (bits %u: 1 reduced buffer, 2 state pool, 4 results, 8 nodes)", r.err);
         return dp_fail(ctx, DP_ERR_CAPACITY, msg);
     }
     st.query_bytes = 0;
     {
         const uint32_t* qm = (const uint32_t*)ctx->h_qm.p;
-        const u64* words = (const u64*)((const uint8_t*)ctx->h_qm.p + (size_t)st.nq * 16);
+        const u64* words = (const u64*)((const uint8_t*)ctx->h_qm.p + dp_find_qmeta_layout(st.nq).words);
         for (uint32_t q = 0; q < st.nq; q++) {
-            if (qm[4 * q + 2] & 1) return dp_fail(ctx, DP_ERR_CAPACITY, "query with more than 65535 usable seeds");
+            if (qm[DP_QMETA_WORDS * q + 2] & 1) return dp_fail(ctx, DP_ERR_CAPACITY, "query with more than 65535 usable seeds");
             st.query_bytes += words[q] * 8;
         }
     }
-    ctx->chain_open_ahead[0] = st.passes >= 1 ? st.cur[24] + st.cur[25] : ~0u;
-    ctx->chain_open_ahead[1] = st.passes >= 2 ? st.cur[26] + st.cur[27] : ctx->chain_open_ahead[0];
-    uint64_t tp = 0;
-    memcpy(&tp, &st.cur[16], 8);
-    ctx->n_pairs = (uint32_t)tp;
+    ctx->chain_open_ahead[0] = st.g.passes >= 1 ? dp_find_open_ahead(r, 1) : ~0u;
+    ctx->chain_open_ahead[1] = st.g.passes >= 2 ? dp_find_open_ahead(r, 2) : ctx->chain_open_ahead[0];
+    ctx->n_pairs = (uint32_t)r.tot_pairs;
     ctx->last_nq = st.nq;
-    ctx->last_ni = st.cur[0];
-    memcpy(&ctx->last_sints, &st.cur[18], 8);
+    ctx->last_ni = r.ints;
+    ctx->last_sints = r.tot_sints;
     ctx->last_k = st.k;
     ctx->find_valid = true;
     return DP_OK;
+}
+
+// The attempt in flight, after a wait on the context's stream: check, and while a buffer was too small grow, enqueue and wait;
+// then the stage's results.  *reran: the stage was run again.
+static int chain_settle(dp_ctx* ctx, FindState& st, bool* reran) {
+    for (;;) {
+        bool grow = false;
+        if (int rc = chain_check(ctx, st, &grow)) return rc;
+        if (!grow) break;
+        *reran = true;
+        if (int rc = chain_enqueue(ctx, st)) return rc;
+        DP_HIP(dp_stream_sync(ctx));
+    }
+    return chain_finish(ctx, st);
 }
 
 // A pending chaining stage after the caller's own wait on the context's stream: evaluates the attempt; when a buffer was too
@@ -3559,15 +3561,7 @@ int dp_find_complete(dp_ctx* ctx, bool* reran) {
     *reran = false;
     FindState* st = ctx->find_state;
     if (!st || !st->pending) return DP_OK;
-    for (;;) {
-        bool grow = false;
-        if (int rc = chain_check(ctx, *st, &grow)) return rc;
-        if (!grow) break;
-        *reran = true;
-        if (int rc = chain_enqueue(ctx, *st)) return rc;
-        DP_HIP(dp_stream_sync(ctx));
-    }
-    return chain_finish(ctx, *st);
+    return chain_settle(ctx, *st, reran);
 }
 // Test hook (DP_DEBUG=chain_paths): how the context's last dp_find_overlaps dealt with every (query, candidate) pair - see
 // include/downpore_hip.h.  Waits for the context's stream.
@@ -3577,21 +3571,21 @@ extern "C" int dp_debug_chain_paths(dp_ctx* ctx, uint32_t* out3, uint32_t cap, u
     if (!st || st->pending) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: no finished dp_find_overlaps on this context");
     if (!st->paths) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: the stage ran without DP_DEBUG=chain_paths");
     hipSetDevice(ctx->device);
-    uint64_t tp = 0;
-    memcpy(&tp, &st->cur[16], 8);
+    const uint64_t tp = st->rep.tot_pairs;
+    const uint32_t pair_cap = st->caps.pair_cap;
     info4[0] = (uint32_t)st->attempt;
-    info4[1] = (uint32_t)st->passes;
-    info4[2] = st->cur[2];
-    info4[3] = st->pair_cap;
+    info4[1] = (uint32_t)st->g.passes;
+    info4[2] = st->rep.err;
+    info4[3] = pair_cap;
     *n_pairs = (uint32_t)tp;
-    if (tp > st->pair_cap) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: the last attempt did not fit its buffers");
+    if (tp > pair_cap) return dp_fail(ctx, DP_ERR_STATE, "dp_debug_chain_paths: the last attempt did not fit its buffers");
     if (tp > cap) return DP_OK;  // (the caller sizes its array by *n_pairs and asks again)
     DP_HIP(dp_stream_sync(ctx));
     std::vector<uint32_t> pq(tp), cl(tp);
     std::vector<PSpec> sp(tp);
     if (tp) {
         DP_HIP(hipMemcpy(cl.data(), ctx->d_clist.p, tp * 4, hipMemcpyDeviceToHost));
-        DP_HIP(hipMemcpy(pq.data(), (const uint32_t*)ctx->d_clist.p + st->pair_cap, tp * 4, hipMemcpyDeviceToHost));
+        DP_HIP(hipMemcpy(pq.data(), (const uint32_t*)ctx->d_clist.p + pair_cap, tp * 4, hipMemcpyDeviceToHost));
         DP_HIP(hipMemcpy(sp.data(), ctx->d_pspec.p, tp * sizeof(PSpec), hipMemcpyDeviceToHost));
     }
     for (uint64_t p = 0; p < tp; p++) {
@@ -3610,10 +3604,9 @@ void dp_find_stats(const dp_ctx* ctx, double* query_ms, double* chain_ms, uint64
     *chain_bytes = st ? st->chain_bytes : 0;
 }
 
-int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, int k,
-                          uint32_t max_query_len, int want_candidates, dp_match_batch* out) {
-    if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps before dp_round_begin");
-    hipSetDevice(ctx->device);
+// dp_find_overlaps_impl's steps
+// a call's outputs as an empty result, and the pinned blocks every outcome needs
+static int find_reset(dp_ctx* ctx, uint32_t nq, int k, dp_match_batch* out) {
     memset(out, 0, sizeof(*out));
     out->n_queries = nq;
     ctx->find_valid = false;
@@ -3621,17 +3614,46 @@ int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_
     ctx->last_nq = nq;
     ctx->last_k = k;
     if (ctx->find_state) ctx->find_state->pending = false;
-    const uint32_t M = ctx->n_seqs;
     if (pin_reserve(ctx, ctx->h_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_cand_off, ((size_t)nq + 1) * 8)) return DP_ERR_HIP;
     ((uint64_t*)ctx->h_cand_off.p)[0] = 0;
     out->cand_off = (const uint64_t*)ctx->h_cand_off.p;
     if (pin_reserve(ctx, ctx->h_moff, 16)) return DP_ERR_HIP;
-    if (pin_reserve(ctx, ctx->h_qm, (size_t)nq * 28 + 16)) return DP_ERR_HIP;
+    if (pin_reserve(ctx, ctx->h_qm, dp_find_qmeta_layout(nq).bytes + 16)) return DP_ERR_HIP;
     ((uint64_t*)ctx->h_moff.p)[0] = 0;
     out->off = (const uint64_t*)ctx->h_moff.p;
-    if (nq == 0 || M == 0) {
-        for (uint32_t q = 0; q <= nq; q++) ((uint64_t*)ctx->h_cand_off.p)[q] = 0;
+    return DP_OK;
+}
+static void find_no_candidates(dp_ctx* ctx, uint32_t nq) {
+    for (uint32_t q = 0; q <= nq; q++) ((uint64_t*)ctx->h_cand_off.p)[q] = 0;
+}
+// the stage's settings, grids and first capacities
+static int find_stage_params(dp_ctx* ctx, FindState& st, int want_candidates) {
+    st.chain_tier = (int)dp_env_long("DP_CHAIN_TIER", 0);  // tests: 2 = lds tier, 3 = one-lane tier for every pair
+    const long pass_env = dp_env_long("DP_CHAIN_PASSES", -1, 0, DP_FIND_MAX_PASSES);  // proposal passes (0 = the serial walk alone: the round-1 behaviour)
+    // spec: 1024 workgroups = 4096 persistent waves, 16 per CU: what CSlim's 8.5 KB per wave lets a CU hold
+    st.g = dp_find_geometry(st.nq, pass_env, ctx->chain_open_ahead[1], st.chain_tier, (uint32_t)std::max(1L, dp_tune("spec_blocks", 1024)));
+    if (dev_reserve(ctx, ctx->d_pool, (size_t)st.g.walk_blocks * C_WAVES * chain_pool_stride(st.max_query_len) * sizeof(CNode))) return DP_ERR_HIP;
+    // capacities: what the buffers hold now (at least a floor); a run that needs more reports its totals and is repeated
+    // with larger buffers (deterministic: same results)
+    st.caps = dp_find_caps_first(ctx->d_mrec.cap / sizeof(MRec), ctx->d_sa.cap / 4, ctx->d_ma.cap / 4);
+    st.defer_fetch = (want_candidates & 6) == 6;
+    return DP_OK;
+}
+static void find_fill_stats(const FindState& st, dp_match_batch* out) {
+    out->query_kernel_ms = st.query_ms;
+    out->chain_kernel_ms = st.chain_ms;
+    out->query_bytes = st.query_bytes;
+    out->chain_bytes = st.chain_bytes;
+}
+
+int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_off, uint32_t nq, double hf, int k,
+                          uint32_t max_query_len, int want_candidates, dp_match_batch* out) {
+    if (!ctx->round_open) return dp_fail(ctx, DP_ERR_STATE, "dp_find_overlaps before dp_round_begin");
+    hipSetDevice(ctx->device);
+    if (int rc = find_reset(ctx, nq, k, out)) return rc;
+    if (nq == 0 || ctx->n_seqs == 0) {
+        find_no_candidates(ctx, nq);
         return DP_OK;
     }
     if (!ctx->find_state) ctx->find_state = new FindState();
@@ -3640,60 +3662,29 @@ int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_
     st.nq = nq;
     st.k = k;
     st.max_query_len = max_query_len;
-    u64* d_words = nullptr;
-    int32_t* d_mc = nullptr;
-    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;  // [0..63] cursor words, [64..] totals (u64 pairs, u64 scratch ints)
-    if (dev_reserve(ctx, ctx->d_pbase, ((size_t)nq + 1) * 4 + ((size_t)nq + 1) * 8 + (size_t)nq * sizeof(QState) + (size_t)nq * 4 + 128)) return DP_ERR_HIP;
-    if (int rc = dp_query_stage(ctx, q_segs, q_off, nq, hf, &st.d_qmeta, &d_words, &d_mc, &st.mc_n, &st.d_qcnt)) return rc;
-    st.d_mc = d_mc;
-    st.chain_tier = (int)dp_env_long("DP_CHAIN_TIER", 0);  // tests: 2 = lds tier, 3 = one-lane tier for every pair
-    const long pass_env = dp_env_long("DP_CHAIN_PASSES", -1, 0, 6);  // proposal passes (0 = the serial walk alone: the round-1 behaviour)
-    st.passes = pass_env >= 0 ? (int)pass_env : 3;
-    // (round 6) the third pass is left out only when this context's previous stage left it next to nothing.  A threshold of 24 pairs - "at
-    // k = 13 it sees ~18 short pairs, which the final walk chains as well" - saved two launches a round and cost more than it saved: the
-    // final walk, one wave per QUERY, went from 13 to 53 us a launch under five slots (profiles/r06/k13_against_round5.txt).
-    if (pass_env < 0 && ctx->chain_open_ahead[1] < 2u) st.passes = 2;
-    st.walk_blocks = std::min<uint32_t>(256, (nq + C_WAVES - 1) / C_WAVES);
-    st.spec_blocks = 1024;  // 4096 persistent waves, 16 per CU: what CSlim's 8.5 KB per wave lets a CU hold
-    st.spec_blocks = (uint32_t)std::max(1L, dp_tune("spec_blocks", st.spec_blocks));
-    if (dev_reserve(ctx, ctx->d_pool, (size_t)st.walk_blocks * C_WAVES * chain_pool_stride(st.max_query_len) * sizeof(CNode))) return DP_ERR_HIP;
-    // capacities: what the buffers hold now (at least a floor); a run that needs more reports its totals and is repeated
-    // with larger buffers (deterministic: same results)
-    st.want_pairs = std::max<uint64_t>(1u << 14, ctx->d_mrec.cap / sizeof(MRec));
-    st.want_sints = std::max<uint64_t>(1u << 18, ctx->d_sa.cap / 4);
-    st.want_ints = std::max<uint64_t>(1u << 18, ctx->d_ma.cap / 4);
-    st.defer_fetch = (want_candidates & 6) == 6;
+    if (dev_reserve(ctx, ctx->d_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_pbase, dp_find_pbase_layout(nq).bytes)) return DP_ERR_HIP;
+    st.q = dp_query_stage(ctx, q_segs, q_off, nq, hf);
+    if (st.q.rc) return st.q.rc;
+    if (int rc = find_stage_params(ctx, st, want_candidates)) return rc;
     if (int rc = chain_enqueue(ctx, st)) return rc;
-    if ((want_candidates & 6) == 6) {
+    if (st.defer_fetch) {
         // bit 2: nothing of this call is read before dp_consensus_paf - the stage stays pending and is evaluated in that call's
         // wait (one wait per round less)
         st.pending = true;
-        for (uint32_t q = 0; q <= nq; q++) ((uint64_t*)ctx->h_cand_off.p)[q] = 0;
+        find_no_candidates(ctx, nq);
         return DP_OK;
     }
-    for (;;) {
-        DP_HIP(dp_stream_sync(ctx));
-        bool grow = false;
-        if (int rc = chain_check(ctx, st, &grow)) return rc;
-        if (!grow) break;
-        if (int rc = chain_enqueue(ctx, st)) return rc;
-    }
-    if (int rc = chain_finish(ctx, st)) return rc;
-    out->query_kernel_ms = st.query_ms;
-    out->chain_kernel_ms = st.chain_ms;
-    out->query_bytes = st.query_bytes;
-    out->chain_bytes = st.chain_bytes;
+    DP_HIP(dp_stream_sync(ctx));
+    bool reran = false;
+    if (int rc = chain_settle(ctx, st, &reran)) return rc;
     if (want_candidates & 2) {
-        for (uint32_t q = 0; q <= nq; q++) ((uint64_t*)ctx->h_cand_off.p)[q] = 0;
+        find_no_candidates(ctx, nq);
+        find_fill_stats(st, out);
         return DP_OK;
     }
-    const double qk = out->query_kernel_ms, ck = out->chain_kernel_ms;
-    const uint64_t qb = out->query_bytes, cb = out->chain_bytes;
-    int rc = dp_fetch_overlaps_impl(ctx, want_candidates & 1, out);
-    out->query_kernel_ms = qk;
-    out->chain_kernel_ms = ck;
-    out->query_bytes = qb;
-    out->chain_bytes = cb;
+    const int rc = dp_fetch_overlaps_impl(ctx, want_candidates & 1, out);  // (starts from an empty `out`)
+    find_fill_stats(st, out);
     return rc;
 }
 
@@ -3706,8 +3697,7 @@ int dp_match_anchors_launch(dp_ctx* ctx, const dp_fetch_region* fetch, uint32_t*
     FindState* fs = ctx->find_state;
     dp_fetch_region owed[2] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
     if (fs && fs->fetch_owed) {
-        owed[0] = {ctx->h_cursor.p, ctx->d_cursor.p, C_CURSOR_BYTES};
-        owed[1] = {ctx->h_qm.p, fs->d_qmeta, (size_t)fs->nq * 28};
+        find_report_regions(ctx, *fs, owed);
         fs->fetch_owed = false;
     }
     if (!nslots) {
@@ -3723,9 +3713,8 @@ int dp_match_anchors_launch(dp_ctx* ctx, const dp_fetch_region* fetch, uint32_t*
         F.src[i] = fr[i] ? (const unsigned long long*)fr[i]->src : nullptr;
         F.n8[i] = fr[i] ? (unsigned long long)((fr[i]->bytes + 7) / 8) : 0ull;
     }
-    const u64* d_totals = (const u64*)((const uint8_t*)ctx->d_cursor.p + 64);
     hipLaunchKernelGGL(match_anchor_kernel, dim3(std::min<uint32_t>(8192, (nslots + 3) / 4)), dim3(256), 0, ctx->stream,
-                       (const MRec*)ctx->d_mrec.p, (const uint32_t*)d_totals, nslots, (const int32_t*)dp_chain_b(ctx),
+                       (const MRec*)ctx->d_mrec.p, find_pair_total_dev(ctx), nslots, (const int32_t*)dp_chain_b(ctx),
                        (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, ctx->last_k, (int32_t*)ctx->d_manchor.p, F,
                        zero_word, (const int32_t*)dp_chain_a(ctx), (const int32_t*)ctx->qsegs_dev, (const u64*)ctx->qoff_dev,
                        (int32_t*)ctx->d_manchor.p + 2 * (size_t)nslots);
@@ -3734,8 +3723,6 @@ int dp_match_anchors_launch(dp_ctx* ctx, const dp_fetch_region* fetch, uint32_t*
     return DP_OK;
 }
 
-// Download of the chaining stage's records.  Pair slots are in canonical order already: queries ascending, candidates
-// ascending within a query.
 // Chains left in their scratch columns (ChainArgs.pack == 0), for a host consumer after all: copied into ma/mb densely, the
 // records' offsets rewritten.  One wave per record; the order of the chains in ma/mb is whatever the atomics make it (the
 // records say where each one is).
@@ -3758,46 +3745,40 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(MRec* __restrict__ recs
     }
 }
 
-int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out) {
-    if (!ctx->find_valid) return dp_fail(ctx, DP_ERR_STATE, "dp_fetch_overlaps: no chaining stage output on this context");
-    hipSetDevice(ctx->device);
-    memset(out, 0, sizeof(*out));
-    if (!ctx->chains_packed && ctx->n_pairs) {
-        // the stage left its chains in the scratch columns (its consumers were on the device): pack them now
-        const uint64_t bound = std::max<uint64_t>(1, ctx->find_state ? std::min<uint64_t>(ctx->find_state->sint_cap, ctx->last_sints) : 0);
-        if (bound > 0xfffffff0ull) return dp_fail(ctx, DP_ERR_CAPACITY, "dp_fetch_overlaps: more than 2^32 chain ints");
-        if (dev_reserve(ctx, ctx->d_ma, (size_t)bound * 4)) return DP_ERR_HIP;
-        if (dev_reserve(ctx, ctx->d_mb, (size_t)bound * 4)) return DP_ERR_HIP;
-        uint32_t* d_total = (uint32_t*)ctx->d_cursor.p;  // (the stage's cursor block is free again: word 0 counted packed ints anyway)
-        DP_HIP(hipMemsetAsync(d_total, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(chain_pack_kernel, dim3(std::min<uint32_t>(2048, (ctx->n_pairs + 3) / 4)), dim3(256), 0, ctx->stream,
-                           (MRec*)ctx->d_mrec.p, ctx->n_pairs, (const int32_t*)ctx->d_sa.p, (const int32_t*)ctx->d_sb.p,
-                           (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, d_total);
-        DP_HIP(hipGetLastError());
-        if (pin_reserve(ctx, ctx->h_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
-        DP_HIP(hipMemcpyAsync(ctx->h_cursor.p, d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
-        DP_HIP(dp_stream_sync(ctx));
-        ctx->last_ni = *(const uint32_t*)ctx->h_cursor.p;
-        ctx->chains_packed = true;
-    }
-    const uint32_t nq = ctx->last_nq, nslots = ctx->n_pairs, ni = ctx->last_ni;
-    const int k = ctx->last_k;
-    out->n_queries = nq;
-    const u64* d_totals = (const u64*)((const uint8_t*)ctx->d_cursor.p + 64);
-    if (pin_reserve(ctx, ctx->h_cand_off, ((size_t)nq + 1) * 8)) return DP_ERR_HIP;
-    out->cand_off = (const uint64_t*)ctx->h_cand_off.p;
+// dp_fetch_overlaps_impl, step 1: the stage left its chains in the scratch columns (its consumers were on the device) - pack them now
+static int fetch_pack(dp_ctx* ctx) {
+    const uint64_t bound = std::max<uint64_t>(1, ctx->find_state ? std::min<uint64_t>(ctx->find_state->caps.sint_cap, ctx->last_sints) : 0);
+    if (bound > DP_FIND_MAX_PAIRS) return dp_fail(ctx, DP_ERR_CAPACITY, "dp_fetch_overlaps: more than 2^32 chain ints");
+    if (dev_reserve(ctx, ctx->d_ma, (size_t)bound * 4)) return DP_ERR_HIP;
+    if (dev_reserve(ctx, ctx->d_mb, (size_t)bound * 4)) return DP_ERR_HIP;
+    // (the stage's cursor block is free again: the packed ints are counted where the stage would have counted them)
+    uint32_t* d_total = (uint32_t*)ctx->d_cursor.p + DP_CUR_INTS;
+    uint32_t* h_total = (uint32_t*)ctx->h_cursor.p + DP_CUR_INTS;
+    DP_HIP(hipMemsetAsync(d_total, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(chain_pack_kernel, dim3(std::min<uint32_t>(2048, (ctx->n_pairs + 3) / 4)), dim3(256), 0, ctx->stream,
+                       (MRec*)ctx->d_mrec.p, ctx->n_pairs, (const int32_t*)ctx->d_sa.p, (const int32_t*)ctx->d_sb.p,
+                       (int32_t*)ctx->d_ma.p, (int32_t*)ctx->d_mb.p, d_total);
+    DP_HIP(hipGetLastError());
+    DP_HIP(hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
+    DP_HIP(dp_stream_sync(ctx));
+    ctx->last_ni = *h_total;
+    ctx->chains_packed = true;
+    return DP_OK;
+}
+
+// step 2: records, their anchors, the packed chains and (want_candidates) the candidate list into their pinned blocks; waits
+static int fetch_download(dp_ctx* ctx, int want_candidates) {
+    const uint32_t nslots = ctx->n_pairs, ni = ctx->last_ni;
+    if (pin_reserve(ctx, ctx->h_cand_off, ((size_t)ctx->last_nq + 1) * 8)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_mrec, (size_t)nslots * sizeof(MRec) + 16)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_ta, (size_t)ni * 4 + 16)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_tb, (size_t)ni * 4 + 16)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_manchor, (size_t)nslots * 8 + 16)) return DP_ERR_HIP;
     if (dev_reserve(ctx, ctx->d_manchor, (size_t)nslots * 8 + 16)) return DP_ERR_HIP;
-    const uint32_t* h_qcnt = (const uint32_t*)((const uint8_t*)ctx->h_qm.p + (size_t)nq * 24);
-    const int32_t* ta = (const int32_t*)ctx->h_ta.p;
-    const int32_t* tb = (const int32_t*)ctx->h_tb.p;
     if (nslots) {
         hipLaunchKernelGGL(match_anchor_kernel, dim3(std::min<uint32_t>(1024, (nslots + 3) / 4)), dim3(256), 0, ctx->stream,
-                           (const MRec*)ctx->d_mrec.p, (const uint32_t*)d_totals, nslots, (const int32_t*)ctx->d_mb.p,
-                           (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, k, (int32_t*)ctx->d_manchor.p,
+                           (const MRec*)ctx->d_mrec.p, find_pair_total_dev(ctx), nslots, (const int32_t*)ctx->d_mb.p,
+                           (const dp_seq_ref*)ctx->d_seqrefs.p, (const int32_t*)ctx->d_segs.p, ctx->last_k, (int32_t*)ctx->d_manchor.p,
                            AnchorFetch{{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {0, 0, 0}}, (uint32_t*)nullptr,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, (const u64*)nullptr, (int32_t*)nullptr);
         DP_HIP(hipGetLastError());
@@ -3813,7 +3794,13 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
         if (nslots) DP_HIP(hipMemcpyAsync(ctx->h_cand_list.p, ctx->d_clist.p, (size_t)nslots * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     DP_HIP(dp_stream_sync(ctx));
-    MRec* recs = (MRec*)ctx->h_mrec.p;
+    return DP_OK;
+}
+
+// step 3, on the host: the records that hold a match, densely, each with its chain and anchors; candidate offsets
+static int fetch_compact(dp_ctx* ctx, int want_candidates, dp_match_batch* out) {
+    const uint32_t nq = ctx->last_nq, nslots = ctx->n_pairs;
+    const MRec* recs = (const MRec*)ctx->h_mrec.p;
     uint32_t nm = 0;
     uint64_t total_len = 0;
     for (uint32_t i = 0; i < nslots; i++)
@@ -3827,6 +3814,8 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
     if (pin_reserve(ctx, ctx->h_mt, (size_t)nm * 4 + 16)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_moff, ((size_t)nm + 1) * 8)) return DP_ERR_HIP;
     if (pin_reserve(ctx, ctx->h_manout, (size_t)nm * 8 + 16)) return DP_ERR_HIP;
+    const int32_t* ta = (const int32_t*)ctx->h_ta.p;
+    const int32_t* tb = (const int32_t*)ctx->h_tb.p;
     uint32_t* mq = (uint32_t*)ctx->h_mq.p;
     uint32_t* mt = (uint32_t*)ctx->h_mt.p;
     uint64_t* moff = (uint64_t*)ctx->h_moff.p;
@@ -3858,7 +3847,9 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
     out->match_b = fb;
     out->target_anchor = anchOut;
     uint64_t* co = (uint64_t*)ctx->h_cand_off.p;
+    out->cand_off = co;
     if (want_candidates) {
+        const uint32_t* h_qcnt = (const uint32_t*)((const uint8_t*)ctx->h_qm.p + dp_find_qmeta_layout(nq).qcnt);
         uint64_t p2 = 0;
         for (uint32_t q = 0; q < nq; q++) {
             co[q] = p2;
@@ -3867,9 +3858,24 @@ int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out
         co[nq] = p2;
         out->cand = (const uint32_t*)ctx->h_cand_list.p;
     } else {
-        for (uint32_t q = 0; q <= nq; q++) co[q] = 0;
+        find_no_candidates(ctx, nq);
     }
     return DP_OK;
+}
+
+// Download of the chaining stage's records.  Pair slots are in canonical order already: queries ascending, candidates
+// ascending within a query.
+int dp_fetch_overlaps_impl(dp_ctx* ctx, int want_candidates, dp_match_batch* out) {
+    if (!ctx->find_valid) return dp_fail(ctx, DP_ERR_STATE, "dp_fetch_overlaps: no chaining stage output on this context");
+    hipSetDevice(ctx->device);
+    memset(out, 0, sizeof(*out));
+    if (!ctx->chains_packed && ctx->n_pairs) {
+        if (pin_reserve(ctx, ctx->h_cursor, C_CURSOR_BYTES)) return DP_ERR_HIP;
+        if (int rc = fetch_pack(ctx)) return rc;
+    }
+    out->n_queries = ctx->last_nq;
+    if (int rc = fetch_download(ctx, want_candidates)) return rc;
+    return fetch_compact(ctx, want_candidates, out);
 }
 
 extern "C" int dp_fetch_overlaps(dp_ctx* ctx, dp_match_batch* out) {
@@ -3900,19 +3906,16 @@ extern "C" int dp_query_candidates(dp_ctx* ctx, const int32_t* q_segs, const uin
     out->cand = ctx->qc_ids.data();
     out->meta = ctx->qc_meta.data();
     if (nq == 0 || ctx->n_seqs == 0) return DP_OK;
-    uint32_t* d_qmeta = nullptr;
-    u64* d_words = nullptr;
-    int32_t* d_mc = nullptr;
-    uint32_t mc_n = 0;
     ctx->map_stage_valid = false;  // (the stage's buffers are those of dp_map_windows_shard's forward pass)
-    if (int rc = dp_query_stage(ctx, q_segs, q_off, nq, hit_fraction, &d_qmeta, &d_words, &d_mc, &mc_n, nullptr)) return rc;
+    const dp_query_out qo = dp_query_stage(ctx, q_segs, q_off, nq, hit_fraction);
+    if (qo.rc) return qo.rc;
     std::vector<u64> cw((size_t)nq * W);
-    std::vector<uint32_t> qm((size_t)nq * 4);
+    std::vector<uint32_t> qm((size_t)nq * DP_QMETA_WORDS);
     DP_HIP(hipMemcpyAsync(cw.data(), ctx->d_cand.p, cw.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    DP_HIP(hipMemcpyAsync(qm.data(), d_qmeta, qm.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DP_HIP(hipMemcpyAsync(qm.data(), qo.d_qmeta, qm.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     DP_HIP(dp_stream_sync(ctx));
     for (uint32_t q = 0; q < nq; q++) {
-        for (int j = 0; j < 3; j++) ctx->qc_meta[3 * (size_t)q + j] = qm[4 * (size_t)q + j];
+        for (int j = 0; j < 3; j++) ctx->qc_meta[3 * (size_t)q + j] = qm[DP_QMETA_WORDS * (size_t)q + j];
         for (uint32_t wi = 0; wi < W; wi++)
             for (u64 m = cw[(size_t)q * W + wi]; m; m &= m - 1) ctx->qc_ids.push_back(wi * 64 + (uint32_t)__builtin_ctzll(m));
         ctx->qc_off[q + 1] = ctx->qc_ids.size();
