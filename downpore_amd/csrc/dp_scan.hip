@@ -1220,7 +1220,7 @@ extern "C" int dp_reads_upload_packed_rc(dp_ctx* ctx, const uint8_t* packed, con
 // than the batch asked for, so a stream of batches of about one size settles after the first.
 // Contexts that borrow these reads may be alive (they must be idle: the caller orders this call against their launches); they hold the
 // old addresses until dp_ctx_refresh_shared, and the epoch bumped here makes every use before that an error code.
-static int tail_grow(dp_ctx* ctx, DevBuf& b, size_t need, size_t slack, size_t head_bytes) {
+static int tail_grow(dp_ctx* ctx, const char* who, DevBuf& b, size_t need, size_t slack, size_t head_bytes) {
     if (need <= b.cap) return 0;
     DevBuf nb;
     nb.cap = (need + slack + 255) & ~(size_t)255;
@@ -1230,44 +1230,14 @@ static int tail_grow(dp_ctx* ctx, DevBuf& b, size_t need, size_t slack, size_t h
     if (e == hipSuccess) e = dp_stream_sync(ctx);
     if (e != hipSuccess) {
         dp_dev_free(nb.p);
-        return dp_fail(ctx, DP_ERR_HIP, "dp_reads_replace_tail_packed_rc: head copy", e);
+        return dp_fail(ctx, DP_ERR_HIP, (std::string(who) + ": head copy").c_str(), e);
     }
     if (b.p) dp_dev_free(b.p);  // (idle: the stream has drained, and borrowers do not launch during a replace)
     b = nb;
     return 0;
 }
-extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_host) {
-    if (!ctx || (n_host && (!lens || !packed))) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: bad arguments") : DP_ERR_ARG;
-    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_replace_tail_packed_rc on a context that borrows its reads");
-    if (keep > ctx->n_reads) {
-        const std::string msg = "dp_reads_replace_tail_packed_rc: keep " + std::to_string(keep) + " is beyond the " + std::to_string(ctx->n_reads) + " device reads";
-        return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
-    }
-    const uint64_t nd64 = (uint64_t)keep + 2ull * n_host;
-    if (nd64 > 0x7fffffffull) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: too many reads (more than 2147483647 with the reverse strands)");
-    std::vector<uint64_t> soff((size_t)n_host + 1, 0);
-    for (uint32_t r = 0; r < n_host; r++) {
-        if (lens[r] > 0x7fffffffu) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_replace_tail_packed_rc: read length out of range");
-        soff[(size_t)r + 1] = soff[r] + ((((uint64_t)lens[r] + 3) / 4 + 15) & ~(uint64_t)15);
-    }
-    if (int rc = upload_join(ctx)) return rc;  // (a read set that was still travelling)
-    hipSetDevice(ctx->device);
-    // ---- nothing has been touched up to here.  The tail's entries of the tables:
-    const uint32_t n_dev = (uint32_t)nd64, n_tail = n_dev - keep;
-    const uint64_t pos0 = ctx->h_boff.empty() ? 0 : ctx->h_boff[keep];  // (h_boff has n_reads + 1 entries; none before the first upload)
-    uint64_t pos = pos0, total = 0;
-    for (uint32_t d = 0; d < keep; d++) total += ctx->h_len[d];
-    std::vector<uint64_t> t_boff((size_t)n_tail + 1);
-    std::vector<uint32_t> t_len(n_tail), srcmap(n_tail);
-    for (uint32_t t = 0; t < n_tail; t++) {
-        t_boff[t] = pos;
-        t_len[t] = lens[t >> 1];
-        srcmap[t] = t;  // host read t >> 1, reverse complement when bit 0 is set
-        pos += soff[(size_t)(t >> 1) + 1] - soff[t >> 1];
-        total += lens[t >> 1];
-    }
-    t_boff[n_tail] = pos;
-    // ---- what an upload voids of the previous read set: position index, histogram, quality bytes, dp_scan_reads' caches
+// what an upload voids of the previous read set: position index, histogram, quality bytes, dp_scan_reads' caches; then the epoch
+static int tail_void(dp_ctx* ctx) {
     DP_HIP(dp_stream_sync(ctx));
     dp_kindex_free(ctx);
     for (DevBuf* qb : {&ctx->d_qual, &ctx->d_qualoff, &ctx->d_hasq})
@@ -1284,16 +1254,59 @@ extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const
     ctx->flags.valid = false;
     ctx->items_ptr = nullptr;
     ctx->reads_epoch++;  // (from here on a borrower's copies may be stale: before the first block moves)
-    if (int rc = tail_grow(ctx, ctx->d_packed, (size_t)pos + 64, (size_t)(pos - pos0) / 8, (size_t)pos0)) return rc;
-    if (int rc = tail_grow(ctx, ctx->d_boff, ((size_t)n_dev + 1) * 8, (size_t)n_tail, (size_t)keep * 8)) return rc;
-    if (int rc = tail_grow(ctx, ctx->d_len, (size_t)n_dev * 4 + 4, (size_t)n_tail / 2, (size_t)keep * 4)) return rc;
+    return 0;
+}
+// the tail's entries of the host tables and the counts, once the device's are in place
+static void tail_commit(dp_ctx* ctx, uint32_t keep, const std::vector<uint64_t>& t_boff, const std::vector<uint32_t>& t_len, uint64_t total) {
     ctx->h_boff.resize((size_t)keep);
     ctx->h_boff.insert(ctx->h_boff.end(), t_boff.begin(), t_boff.end());
     ctx->h_len.resize((size_t)keep);
     ctx->h_len.insert(ctx->h_len.end(), t_len.begin(), t_len.end());
-    ctx->n_reads = n_dev;
-    ctx->packed_bytes = pos;
+    ctx->n_reads = keep + (uint32_t)t_len.size();
+    ctx->packed_bytes = t_boff.back();
     ctx->total_bases = total;
+}
+// both tail replaces from the host: every host read once (dp_reads_replace_tail_packed) or as the pair (forward, reverse complement)
+static int replace_tail_impl(dp_ctx* ctx, const char* who, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_host, bool paired) {
+    const std::string W(who);
+    if (!ctx || (n_host && (!lens || !packed))) return ctx ? dp_fail(ctx, DP_ERR_ARG, (W + ": bad arguments").c_str()) : DP_ERR_ARG;
+    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, (W + " on a context that borrows its reads").c_str());
+    if (keep > ctx->n_reads) {
+        const std::string msg = W + ": keep " + std::to_string(keep) + " is beyond the " + std::to_string(ctx->n_reads) + " device reads";
+        return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+    }
+    const uint32_t per = paired ? 2u : 1u;
+    const uint64_t nd64 = (uint64_t)keep + (uint64_t)per * n_host;
+    if (nd64 > 0x7fffffffull)
+        return dp_fail(ctx, DP_ERR_ARG, (W + (paired ? ": too many reads (more than 2147483647 with the reverse strands)" : ": too many reads (more than 2147483647)")).c_str());
+    std::vector<uint64_t> soff((size_t)n_host + 1, 0);
+    for (uint32_t r = 0; r < n_host; r++) {
+        if (lens[r] > 0x7fffffffu) return dp_fail(ctx, DP_ERR_ARG, (W + ": read length out of range").c_str());
+        soff[(size_t)r + 1] = soff[r] + ((((uint64_t)lens[r] + 3) / 4 + 15) & ~(uint64_t)15);
+    }
+    if (int rc = upload_join(ctx)) return rc;  // (a read set that was still travelling)
+    hipSetDevice(ctx->device);
+    // ---- nothing has been touched up to here.  The tail's entries of the tables:
+    const uint32_t n_dev = (uint32_t)nd64, n_tail = n_dev - keep;
+    const uint64_t pos0 = ctx->h_boff.empty() ? 0 : ctx->h_boff[keep];  // (h_boff has n_reads + 1 entries; none before the first upload)
+    uint64_t pos = pos0, total = 0;
+    for (uint32_t d = 0; d < keep; d++) total += ctx->h_len[d];
+    std::vector<uint64_t> t_boff((size_t)n_tail + 1);
+    std::vector<uint32_t> t_len(n_tail), srcmap(n_tail);
+    for (uint32_t t = 0; t < n_tail; t++) {
+        const uint32_t h = t / per;
+        t_boff[t] = pos;
+        t_len[t] = lens[h];
+        srcmap[t] = paired ? t : t << 1;  // host read << 1, reverse complement when bit 0 is set
+        pos += soff[(size_t)h + 1] - soff[h];
+        total += lens[h];
+    }
+    t_boff[n_tail] = pos;
+    if (int rc = tail_void(ctx)) return rc;
+    if (int rc = tail_grow(ctx, who, ctx->d_packed, (size_t)pos + 64, (size_t)(pos - pos0) / 8, (size_t)pos0)) return rc;
+    if (int rc = tail_grow(ctx, who, ctx->d_boff, ((size_t)n_dev + 1) * 8, (size_t)n_tail, (size_t)keep * 8)) return rc;
+    if (int rc = tail_grow(ctx, who, ctx->d_len, (size_t)n_dev * 4 + 4, (size_t)n_tail / 2, (size_t)keep * 4)) return rc;
+    tail_commit(ctx, keep, t_boff, t_len, total);
     struct Temps {
         dp_ctx* c;
         void *d_src = nullptr, *d_soff = nullptr, *d_slen = nullptr, *d_map = nullptr;
@@ -1327,6 +1340,14 @@ extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const
     DP_HIP(dp_stream_sync(ctx));  // (the tables and the caller's lens are read by copies that are through now)
     return DP_OK;
 }
+extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_host) {
+    return replace_tail_impl(ctx, "dp_reads_replace_tail_packed_rc", keep, packed, lens, n_host, true);
+}
+// the batch behind the head unpaired: device read keep + r is host read r (a mapper's raw batch, which the trim runs on before
+// dp_reads_respan_tail_rc cuts the mapped set from it)
+extern "C" int dp_reads_replace_tail_packed(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_host) {
+    return replace_tail_impl(ctx, "dp_reads_replace_tail_packed", keep, packed, lens, n_host, false);
+}
 
 // ---- dp_reads_respan with the layout of dp_reads_upload_rc (`map` with the trim in front: the trimmed reads are cut from the resident raw
 // ones and their reverse strands made in the same pass).  repack_spans_rc_kernel: one thread per output dword.  Device read lo is span
@@ -1336,6 +1357,29 @@ extern "C" int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const
 // source dword and end in the next one at most, so the byte-swapped pair is one 64-bit funnel; its top 16 bases are shifted right by the
 // overhang, reversed and complemented as in place_packed_kernel, and the bases beyond the span's end masked.  The second source dword is
 // loaded only when a base that is wanted lies in it - never past the source read's own padded end.
+// the dword of a span that starts base0 bases into it - of the span itself, or (rc) of its reverse complement; rd: the source read
+__device__ __forceinline__ uint32_t span_dword_rc(const uint32_t* __restrict__ rd, const dp_read_span sp, uint64_t base0, bool rc) {
+    if (base0 >= sp.len) return 0;
+    const uint32_t nb = (uint32_t)(sp.len - base0 < 16 ? sp.len - base0 : 16);  // bases of this dword
+    const uint32_t over = 16 - nb;                                              // reverse strand: the window's overhang, -t
+    const uint32_t first = rc ? sp.len - (uint32_t)base0 - nb : (uint32_t)base0;  // first span base wanted: max(t, 0) | base0
+    const uint32_t p = sp.start + first, sh = p & 15u;
+    const uint32_t* w = rd + (p >> 4);
+    uint64_t v = (uint64_t)__builtin_bswap32(w[0]) << 32;
+    if (sh + nb > 16) v |= __builtin_bswap32(w[1]);
+    uint32_t be = (uint32_t)((v << (2 * sh)) >> 32);  // span bases first .. first + 15, the first on top
+    if (!rc) {
+        if (nb < 16) be &= ~0u << (2 * over);
+    } else {
+        if (nb < 16) be >>= 2 * over;  // ... bases 0 .. nb - 1 at the bottom, nothing above them
+        be = __builtin_bswap32(be);
+        be = ((be & 0x0f0f0f0fu) << 4) | ((be >> 4) & 0x0f0f0f0fu);
+        be = ((be & 0x33333333u) << 2) | ((be >> 2) & 0x33333333u);  // base order reversed: span base len - 1 - base0 on top
+        be = ~be;
+        if (nb < 16) be &= ~0u << (2 * over);  // bases beyond the span's end
+    }
+    return __builtin_bswap32(be);
+}
 __global__ void repack_spans_rc_kernel(const uint32_t* __restrict__ src, const uint64_t* __restrict__ sboff, const dp_read_span* __restrict__ spans,
                                        const uint64_t* __restrict__ boff, uint32_t n_reads, uint32_t first_paired, uint32_t* __restrict__ packed,
                                        uint64_t n_dwords) {
@@ -1351,29 +1395,7 @@ __global__ void repack_spans_rc_kernel(const uint32_t* __restrict__ src, const u
     const bool rc = lo >= first_paired && ((lo - first_paired) & 1u) != 0;
     const dp_read_span sp = spans[lo < first_paired ? lo : first_paired + ((lo - first_paired) >> 1)];
     const uint64_t base0 = (byte - boff[lo]) * 4;
-    uint32_t out = 0;
-    if (base0 < sp.len) {
-        const uint32_t nb = (uint32_t)(sp.len - base0 < 16 ? sp.len - base0 : 16);  // bases of this dword
-        const uint32_t over = 16 - nb;                                              // reverse strand: the window's overhang, -t
-        const uint32_t first = rc ? sp.len - (uint32_t)base0 - nb : (uint32_t)base0;  // first span base wanted: max(t, 0) | base0
-        const uint32_t p = sp.start + first, sh = p & 15u;
-        const uint32_t* w = src + sboff[sp.read] / 4 + (p >> 4);
-        uint64_t v = (uint64_t)__builtin_bswap32(w[0]) << 32;
-        if (sh + nb > 16) v |= __builtin_bswap32(w[1]);
-        uint32_t be = (uint32_t)((v << (2 * sh)) >> 32);  // span bases first .. first + 15, the first on top
-        if (!rc) {
-            if (nb < 16) be &= ~0u << (2 * over);
-        } else {
-            if (nb < 16) be >>= 2 * over;  // ... bases 0 .. nb - 1 at the bottom, nothing above them
-            be = __builtin_bswap32(be);
-            be = ((be & 0x0f0f0f0fu) << 4) | ((be >> 4) & 0x0f0f0f0fu);
-            be = ((be & 0x33333333u) << 2) | ((be >> 2) & 0x33333333u);  // base order reversed: span base len - 1 - base0 on top
-            be = ~be;
-            if (nb < 16) be &= ~0u << (2 * over);  // bases beyond the span's end
-        }
-        out = __builtin_bswap32(be);
-    }
-    packed[d] = out;
+    packed[d] = span_dword_rc(src + sboff[sp.read] / 4, sp, base0, rc);
 }
 
 // What dp_reads_respan does, with every output read r >= first_paired stored as the pair (forward, reverse complement).  Unlike
@@ -1475,6 +1497,113 @@ extern "C" int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32
     ctx->h_len.swap(h_len);
     ctx->packed_bytes = pos;
     ctx->total_bases = total;
+    return DP_OK;
+}
+
+// ---- dp_reads_respan_rc behind a head that stays (a mapper's trimmed batch: the raw reads behind the reference sequences and join
+// chunks become the pairs (span, reverse complement) of spans of themselves).  Source and destination are the same region of the one
+// packed block, so the new tail is made in a scratch block and copied into place once the old one has been read to its end.
+// repack_spans_tail_rc_kernel: repack_spans_rc_kernel's dword (span_dword_rc), one thread per output dword of the new tail.  The search runs over the
+// NEW table from first_read on, as place_packed_kernel's tail form does; every device read from there on is one of a pair, span
+// (lo - first_read) / 2, the odd ones reverse-complemented.  The old tail is read through the old offsets: ssoff[i] is the byte the
+// read of span i began at in `src` before the call (the host knows it), so the device's table can already hold the new entries.
+// Dword d of the device layout goes to out[d - d_begin].  The second source dword is loaded only when a wanted base lies in it.
+__global__ void repack_spans_tail_rc_kernel(const uint32_t* __restrict__ src, const uint64_t* __restrict__ ssoff, const dp_read_span* __restrict__ spans,
+                                            const uint64_t* __restrict__ boff, uint32_t n_reads, uint32_t first_read, uint32_t* __restrict__ out,
+                                            uint64_t d_begin, uint64_t n_dwords) {
+    const uint64_t d = d_begin + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_dwords) return;
+    const uint64_t byte = d * 4;
+    uint32_t lo = first_read, hi = n_reads;  // binary search: last device read with boff[r] <= byte
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (boff[mid] <= byte) lo = mid;
+        else hi = mid;
+    }
+    const bool rc = ((lo - first_read) & 1u) != 0;
+    const uint32_t si = (lo - first_read) >> 1;
+    const dp_read_span sp = spans[si];
+    const uint64_t base0 = (byte - boff[lo]) * 4;
+    out[d - d_begin] = span_dword_rc(src + ssoff[si] / 4, sp, base0, rc);
+}
+
+// The reads behind `keep` replaced by the pairs (span, reverse complement) of n_out spans of those same reads.  What it leaves alone,
+// what it voids and what it asks of borrowing contexts is dp_reads_replace_tail_packed_rc's.
+extern "C" int dp_reads_respan_tail_rc(dp_ctx* ctx, uint32_t keep, const dp_read_span* spans, uint32_t n_out) {
+    static const char* const who = "dp_reads_respan_tail_rc";
+    if (!ctx || (n_out && !spans)) return ctx ? dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan_tail_rc: bad arguments") : DP_ERR_ARG;
+    if (ctx->borrowed_reads) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_tail_rc on a context that borrows its reads");
+    {
+        std::lock_guard<std::mutex> lk(ctx->upload_mu);
+        if (ctx->upload) return dp_fail(ctx, DP_ERR_STATE, "dp_reads_respan_tail_rc while an upload of dp_reads_upload_rc_begin is pending");
+    }
+    if (keep > ctx->n_reads) {
+        const std::string msg = "dp_reads_respan_tail_rc: keep " + std::to_string(keep) + " is beyond the " + std::to_string(ctx->n_reads) + " device reads";
+        return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+    }
+    const uint64_t nd64 = (uint64_t)keep + 2ull * n_out;
+    if (nd64 > 0x7fffffffull) return dp_fail(ctx, DP_ERR_ARG, "dp_reads_respan_tail_rc: too many reads (more than 2147483647 with the reverse strands)");
+    const uint32_t n_dev = (uint32_t)nd64, n_tail = n_dev - keep;
+    const uint64_t pos0 = ctx->h_boff.empty() ? 0 : ctx->h_boff[keep];
+    uint64_t pos = pos0, total = 0;
+    for (uint32_t d = 0; d < keep; d++) total += ctx->h_len[d];
+    std::vector<uint64_t> t_boff((size_t)n_tail + 1), ssoff(n_out);
+    std::vector<uint32_t> t_len(n_tail);
+    for (uint32_t i = 0; i < n_out; i++) {
+        const dp_read_span& sp = spans[i];
+        if (sp.read < keep) {
+            const std::string msg = "dp_reads_respan_tail_rc: span " + std::to_string(i) + " names read " + std::to_string(sp.read) + " of the head (keep " + std::to_string(keep) + ")";
+            return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+        }
+        if (sp.read >= ctx->n_reads || (uint64_t)sp.start + sp.len > ctx->h_len[sp.read]) {
+            const std::string msg = "dp_reads_respan_tail_rc: span " + std::to_string(i) + " lies outside its read";
+            return dp_fail(ctx, DP_ERR_ARG, msg.c_str());
+        }
+        ssoff[i] = ctx->h_boff[sp.read];
+        for (uint32_t strand = 0; strand < 2; strand++) {
+            t_boff[2 * (size_t)i + strand] = pos;
+            t_len[2 * (size_t)i + strand] = sp.len;
+            pos += ((uint64_t)(sp.len + 3) / 4 + 15) & ~(uint64_t)15;
+            total += sp.len;
+        }
+    }
+    t_boff[n_tail] = pos;
+    hipSetDevice(ctx->device);
+    // ---- nothing has been touched up to here
+    if (int rc = tail_void(ctx)) return rc;
+    struct Temps {
+        dp_ctx* c;
+        void *d_new = nullptr, *d_spans = nullptr, *d_ssoff = nullptr;
+        ~Temps() {
+            hipStreamSynchronize(c->stream);
+            for (void* q : {d_new, d_spans, d_ssoff})
+                if (q) dp_dev_free(q);
+        }
+    } T{ctx};
+    // the tables first: the kernel reads the old tail through ssoff, not through the device's offsets
+    if (int rc = tail_grow(ctx, who, ctx->d_boff, ((size_t)n_dev + 1) * 8, (size_t)n_tail, (size_t)keep * 8)) return rc;
+    if (int rc = tail_grow(ctx, who, ctx->d_len, (size_t)n_dev * 4 + 4, (size_t)n_tail / 2, (size_t)keep * 4)) return rc;
+    DP_HIP(hipMemcpyAsync((uint64_t*)ctx->d_boff.p + keep, t_boff.data(), ((size_t)n_tail + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_tail) DP_HIP(hipMemcpyAsync((uint32_t*)ctx->d_len.p + keep, t_len.data(), (size_t)n_tail * 4, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t new_bytes = pos - pos0;
+    if (new_bytes) {
+        DP_HIP(dp_dev_malloc(&T.d_new, (size_t)new_bytes));
+        DP_HIP(dp_dev_malloc(&T.d_spans, (size_t)n_out * sizeof(dp_read_span)));
+        DP_HIP(dp_dev_malloc(&T.d_ssoff, (size_t)n_out * 8));
+        DP_HIP(hipMemcpyAsync(T.d_spans, spans, (size_t)n_out * sizeof(dp_read_span), hipMemcpyHostToDevice, ctx->stream));
+        DP_HIP(hipMemcpyAsync(T.d_ssoff, ssoff.data(), (size_t)n_out * 8, hipMemcpyHostToDevice, ctx->stream));
+        const uint64_t d_begin = pos0 / 4, n_dwords = pos / 4;
+        hipLaunchKernelGGL(repack_spans_tail_rc_kernel, dim3((uint32_t)((n_dwords - d_begin + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)ctx->d_packed.p, (const uint64_t*)T.d_ssoff, (const dp_read_span*)T.d_spans, (const uint64_t*)ctx->d_boff.p, n_dev,
+                           keep, (uint32_t*)T.d_new, d_begin, n_dwords);
+        DP_HIP(hipGetLastError());
+        DP_HIP(dp_stream_sync(ctx));  // the old tail has been read to its end: only now may its block grow or be written
+    }
+    if (int rc = tail_grow(ctx, who, ctx->d_packed, (size_t)pos + 64, (size_t)new_bytes / 8, (size_t)pos0)) return rc;
+    if (new_bytes) DP_HIP(hipMemcpyAsync((uint8_t*)ctx->d_packed.p + pos0, T.d_new, (size_t)new_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    DP_HIP(hipMemsetAsync((uint8_t*)ctx->d_packed.p + pos, 0, 64, ctx->stream));
+    DP_HIP(dp_stream_sync(ctx));
+    tail_commit(ctx, keep, t_boff, t_len, total);
     return DP_OK;
 }
 

@@ -791,6 +791,11 @@ int runMap(const ReadSet& refSet, const ReadSet& reads, const MapParams& p, int 
 struct Mapper;
 Mapper* mapperOpen(const ReadSet& refSet, const MapParams& p, int device, std::string& error, int* rc);
 int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error);
+// The batch trimmed first, on the device's copy (dph_mapper_map_trim): trim->raw goes behind the head packed and unpaired
+// (dp_reads_replace_tail_packed), runTrim runs on it with the head's size as its base id, trimmedReadSet (minimum length: the mapper's
+// minLength) gives the set that is mapped, and dp_reads_respan_tail_rc cuts it from the raw tail with its reverse strands.  paf /
+// errText are runMap's for (refSet, raw, trim).  A trim that fails for its parameters or its input leaves the mapper usable.
+int mapperMap(Mapper* m, MapTrim& trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error);
 void mapperClose(Mapper* m);
 
 // ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------
@@ -852,9 +857,12 @@ void trimHostMatch(const int32_t* cSeg, int cN, const int32_t* aSeg, int aN, int
 bool trimBuildIndex(const ReadSet& front, const ReadSet& back, int k, TrimIndex& ix, std::string& error);
 // the whole edge stage on HIP device `device`; reads receives ignore / frontTrim / backTrim.  0, or < 0 with `error` (-2: no read of 200 bases)
 // resident: a context on `device` that holds `reads` as uploaded by dp_reads_upload - both stages then take their bases from it (read ids
-// and spans go up instead of bases) and nothing is written: res.out stays empty and the log has no "Writing" line (trimmedReadSet)
+// and spans go up instead of bases) and nothing is written: res.out stays empty and the log has no "Writing" line (trimmedReadSet).
+// residentBase: the context holds host read r as device read residentBase + r (a mapper's batch behind its head); only the id lists and
+// spans that go up are offset.  kTrimDeviceFailed: a device call failed (every other failure is about the parameters or the input)
+const int kTrimDeviceFailed = -3;
 int runTrim(ReadSet& reads, const ReadSet& front, const ReadSet& back, const TrimParams& p, int device, TrimResult& res, std::string& error,
-            dp_ctx* resident = nullptr);
+            dp_ctx* resident = nullptr, uint32_t residentBase = 0);
 // the read set `downpore trim`'s output gives when it is read back with minimum length minLen - without writing it - and the span of
 // `raw` (the reads the trim ran on) behind each of its records; pure host code
 void trimmedReadSet(const ReadSet& raw, const TrimResult& res, i64 minLen, bool himem, ReadSet& out, std::vector<dp_read_span>& spans);

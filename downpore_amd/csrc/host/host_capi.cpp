@@ -987,6 +987,40 @@ extern "C" void* dph_map_run_trim(void* refH, void* readsH, void* frontH, void* 
     *trim_out = th;
     return h;
 }
+// dph_mapper_map with the trim in front, per batch: the raw reads go behind the mapper's resident head once, packed; both trim stages run on
+// that copy; the trimmed read set (the mapper's minimum length) is cut from it on the device with its reverse strands and mapped.
+// *trim_out: the trim run's handle, as dph_map_run_trim gives it.
+extern "C" void* dph_mapper_map_trim(void* mapperH, void* readsH, void* frontH, void* backH, const int64_t* trim_params, int n_trim, void** trim_out) {
+    if (trim_out) *trim_out = nullptr;
+    MapperH* mh = (MapperH*)mapperH;
+    MapTrim mt;
+    if (!mh || !readsH || !frontH || !backH || !trim_out || !trimParamsFrom(trim_params, n_trim, mt.params)) {
+        g_err = "dph_mapper_map_trim: bad arguments (8 trim parameters, or 14 with the middle stage's)";
+        return nullptr;
+    }
+    if (mh->busy.exchange(true)) {
+        g_err = "dph_mapper_map_trim: DP_ERR_STATE: another call is mapping on this mapper (one batch at a time per mapper)";
+        return nullptr;
+    }
+    MapH* h = new MapH();
+    TrimH* th = new TrimH();
+    th->reads = &((ReadsH*)readsH)->set;
+    mt.raw = th->reads;
+    mt.front = &((ReadsH*)frontH)->set;
+    mt.back = &((ReadsH*)backH)->set;
+    mt.res = &th->res;
+    std::string error;
+    const int rc = mapperMap(mh->m, mt, h->paf, h->err, &h->st, error);
+    mh->busy.store(false);
+    if (rc != 0) {
+        g_err = error;
+        delete h;
+        delete th;
+        return nullptr;
+    }
+    *trim_out = th;
+    return h;
+}
 extern "C" const char* dph_trim_output(void* h, int64_t* n) {
     *n = (int64_t)((TrimH*)h)->res.out.size();
     return ((TrimH*)h)->res.out.data();

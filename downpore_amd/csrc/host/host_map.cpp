@@ -778,8 +778,11 @@ struct MapRun {
     void packReads(const std::vector<uint64_t>& poff, size_t readsAt);
     void unmappedBatch();
     // the steps of a Mapper's batch
-    void bindBatch(const ReadSet& batch);
+    void bindBatch(const ReadSet& batch, bool trimmed = false);
+    int packBatch();
+    int refreshWorkers();
     int replaceTail();
+    int replaceTailTrimmed(MapTrim& t);
     void writeText();
     void writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped);
 };
@@ -1545,9 +1548,12 @@ int runMap(const ReadSet& refSet, const ReadSet& upSet, const MapParams& p, int 
 // value table, the seed index, the schedule and chunk scan, the layout choice, the index, the pinned block, and every worker context
 // a batch's thread plan has asked for so far (its round, import and dense build or borrow are done once, when it is opened).  What a
 // batch owns: its read set's binding, the packed batch in the pinned block, the tail replace and the workers' refreshes, the loops,
-// and its paf / stderr / stats.  The owners are MapRun's and go in MapRun's order when the mapper is closed.
-void MapRun::bindBatch(const ReadSet& batch) {
-    upSetP = readsP = &batch;
+// and its paf / stderr / stats.  A batch that is trimmed first (mapperMap with a MapTrim) has replaceTailTrimmed in replaceTail's place:
+// the raw batch behind the head unpaired, runTrim on it, and the trimmed set cut from the raw tail with its reverse strands.
+// The owners are MapRun's and go in MapRun's order when the mapper is closed.
+void MapRun::bindBatch(const ReadSet& batch, bool trimmed) {
+    upSetP = &batch;
+    readsP = trimmed ? &trimmedSet : &batch;  // (a trimmed batch goes up raw and is mapped as trimmedReadSet gives it)
     tRun0 = tMark = wallNow();
     paf.clear();
     errText = refText;
@@ -1559,7 +1565,7 @@ void MapRun::bindBatch(const ReadSet& batch) {
     for (int64_t& r : stats->regimes) r = 0;
 }
 // the batch packed into the pinned block, put behind the head on the device, and the worker contexts told about it
-int MapRun::replaceTail() {
+int MapRun::packBatch() {
     P = mapBatchLayout(upSet().off.data(), upSet().size());
     if (!pinned.reserve((size_t)P.poff.back() + 64)) {
         error = "dp_host_alloc: no pinned memory for the packed reads";
@@ -1567,11 +1573,42 @@ int MapRun::replaceTail() {
     }
     packReads(P.poff, 0);
     mark("pack the batch");
-    if (int rc = dp_reads_replace_tail_packed_rc(ctx.c, J.firstPaired, pinned.p, P.plens.data(), (uint32_t)P.plens.size())) return failed(ctx.c, rc);
+    return 0;
+}
+int MapRun::refreshWorkers() {
     for (dp_ctx* wc : workers.v)
         if (wc)
             if (int rc = dp_ctx_refresh_shared(wc)) return failed(wc, rc);
+    return 0;
+}
+int MapRun::replaceTail() {
+    if (int rc = packBatch()) return rc;
+    if (int rc = dp_reads_replace_tail_packed_rc(ctx.c, J.firstPaired, pinned.p, P.plens.data(), (uint32_t)P.plens.size())) return failed(ctx.c, rc);
+    if (int rc = refreshWorkers()) return rc;
     mark("tail replace + refreshes");
+    return 0;
+}
+// A batch that is trimmed first: the raw reads go behind the head unpaired (raw read r is device read firstPaired + r), the trim runs
+// on that copy, and the trimmed set with its reverse strands is cut from the raw tail in place of it - the ids replaceTail gives.
+// DP_ERR_ARG: the trim failed for its parameters or its input; whatever the tail holds then, the next batch replaces it.
+int MapRun::replaceTailTrimmed(MapTrim& t) {
+    if (int rc = packBatch()) return rc;
+    const uint32_t base = J.firstPaired;
+    if (int rc = dp_reads_replace_tail_packed(ctx.c, base, pinned.p, P.plens.data(), (uint32_t)P.plens.size())) return failed(ctx.c, rc);
+    mark("tail replace (raw reads)");
+    std::string trimError;
+    if (int rc = runTrim(*t.raw, *t.front, *t.back, t.params, device, *t.res, trimError, ctx.c, base)) {
+        error = trimError;
+        return rc == kTrimDeviceFailed ? DP_ERR_HIP : DP_ERR_ARG;
+    }
+    mark("trim on resident reads");
+    std::vector<dp_read_span> cut;
+    trimmedReadSet(*t.raw, *t.res, p.minLength, t.raw->himem, trimmedSet, cut);
+    mark("trimmed read set");
+    const std::vector<dp_read_span> spans = mapTailSpans(cut, base);
+    if (int rc = dp_reads_respan_tail_rc(ctx.c, base, spans.data(), (uint32_t)spans.size())) return failed(ctx.c, rc);
+    if (int rc = refreshWorkers()) return rc;
+    mark("respan + reverse strands + refreshes");
     return 0;
 }
 
@@ -1621,26 +1658,29 @@ Mapper* mapperOpen(const ReadSet& refSet, const MapParams& p, int device, std::s
     return m.release();
 }
 
-int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
+namespace {
+// one batch: trim == nullptr maps `reads` as they are; with a trim `reads` is the raw set (trim->raw)
+int mapperBatch(Mapper* m, const ReadSet& reads, MapTrim* trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
     if (m->brokenRc) {
         error = m->brokenText;
         return m->brokenRc;
     }
     MapRun& R = m->R;
-    R.bindBatch(reads);
+    R.bindBatch(reads, trim != nullptr);
     int rc = 0;
-    if (R.noChunks) {
-        R.unmappedBatch();
+    if (R.noChunks) {  // (the trim still runs: its result is the caller's, and the counts are of the trimmed set)
+        if (!trim || (rc = R.replaceTailTrimmed(*trim)) == 0) R.unmappedBatch();
     } else {
-        if ((rc = R.replaceTail()) == 0 && (rc = R.runWorkers()) == 0) {
+        if ((rc = trim ? R.replaceTailTrimmed(*trim) : R.replaceTail()) == 0 && (rc = R.runWorkers()) == 0) {
             R.collectStats();
             R.writeText();
         }
     }
     R.upSetP = R.readsP = &m->none;  // (the batch's read set is the caller's: nothing of it is held beyond this call)
+    R.trimmedSet = ReadSet();
     if (rc) {
         error = m->error;
-        if (rc != DP_ERR_ARG) {  // a batch refused for its arguments has touched nothing; anything else leaves the device state unknown
+        if (rc != DP_ERR_ARG) {  // a batch refused for its arguments (or its trim's) leaves nothing the next batch does not replace; anything else leaves the device state unknown
             m->brokenRc = rc;
             m->brokenText = error;
         }
@@ -1650,6 +1690,13 @@ int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& er
     errText.swap(m->errText);
     if (stats) *stats = m->st;
     return 0;
+}
+}  // namespace
+int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
+    return mapperBatch(m, reads, nullptr, paf, errText, stats, error);
+}
+int mapperMap(Mapper* m, MapTrim& trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
+    return mapperBatch(m, *trim.raw, &trim, paf, errText, stats, error);
 }
 
 void mapperClose(Mapper* m) { delete m; }

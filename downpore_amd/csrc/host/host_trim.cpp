@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include "host_util.hpp"
+#include "map_plan.hpp"
 
 namespace dph {
 
@@ -83,10 +84,14 @@ void extractEnds(const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b) {
 
 // One edge call over the reads [lo, hi): their ends extracted here and sent, or - with `resident`, a context that holds `reads` - spelled on
 // the device from the packed reads, the eligible reads' ids being all that goes up.  `up` receives the bytes sent.
-int edgeCall(dp_trim* h, dp_ctx* resident, const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b, int mode, int minMatch, int threshold, dp_trim_rec* recs,
-             uint64_t* counts, uint8_t* enabled, double* tms, double* up) {
+int edgeCall(dp_trim* h, dp_ctx* resident, uint32_t base, const ReadSet& reads, size_t lo, size_t hi, EdgeBatch& b, int mode, int minMatch, int threshold,
+             dp_trim_rec* recs, uint64_t* counts, uint8_t* enabled, double* tms, double* up) {
     if (resident) {
         *up = 4.0 * (double)b.reads.size();
+        if (base) {  // (the context holds host read r as device read base + r)
+            const std::vector<uint32_t> ids = mapTailIds(b.reads, base);
+            return dp_trim_edges_resident(h, resident, ids.data(), (uint32_t)ids.size(), mode, minMatch, threshold, recs, counts, enabled, tms);
+        }
         return dp_trim_edges_resident(h, resident, b.reads.data(), (uint32_t)b.reads.size(), mode, minMatch, threshold, recs, counts, enabled, tms);
     }
     *up = (double)b.ends.size();
@@ -592,7 +597,7 @@ TrimDev setupDevice(const TrimIndex& ix, int device, std::string& error) {
 
 // the middle stage's device half over the plan `mp`: scan every planned chunk for its seed count, cut the flush batches, then per batch
 // scan -> index -> candidates -> matching kernel, and the host's Match for the pairs the kernel listed
-bool midDevice(dp_trim* h, dp_ctx* resident, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, MidPlan& mp, std::vector<int32_t>& seedCounts,
+bool midDevice(dp_trim* h, dp_ctx* resident, uint32_t base, const ReadSet& reads, const TrimIndex& ix, const TrimParams& p, MidPlan& mp, std::vector<int32_t>& seedCounts,
                std::vector<TrimMidRec>& recs, TrimResult& res, std::string& error) {
     const size_t nC = mp.plan.size();
     seedCounts.assign(nC, 0);
@@ -604,14 +609,14 @@ bool midDevice(dp_trim* h, dp_ctx* resident, const ReadSet& reads, const TrimInd
     std::vector<dp_read_span> spans;
     double tms[2];
     // chunks [lo, hi) cut from the trimmed reads and scanned in one call; their segments stay on the device.  With `resident` the chunks
-    // are named as spans of the reads that context holds, in the coordinates of the uploaded read.
+    // are named as spans of the reads that context holds (host read r is its read base + r), in the coordinates of the uploaded read.
     auto scan = [&](size_t lo, size_t hi) -> bool {
         cnt.assign(hi - lo, 0);
         if (resident) {
             spans.clear();
             for (size_t c = lo; c < hi; c++) {
                 const TrimChunk& ch = mp.plan[c];
-                spans.push_back(dp_read_span{ch.read, (uint32_t)(reads.frontTrim[ch.read] + ch.start), (uint32_t)(ch.end - ch.start)});
+                spans.push_back(dp_read_span{mapTailId(base, ch.read), (uint32_t)(reads.frontTrim[ch.read] + ch.start), (uint32_t)(ch.end - ch.start)});
             }
             if (!devOk(dp_trim_scan_chunks_resident(h, resident, spans.data(), (uint32_t)spans.size(), cnt.data(), tms) == 0, h, error)) return false;
             res.bytes_up += (double)(spans.size() * sizeof(dp_read_span));
@@ -890,7 +895,7 @@ int applyTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const
 }
 
 int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const TrimParams& p, int device, TrimResult& res, std::string& error,
-            dp_ctx* resident) {
+            dp_ctx* resident, uint32_t residentBase) {
     res = TrimResult();
     TrimIndex ix;
     if (!trimBuildIndex(front0, back0, p.k, ix, error)) return -1;
@@ -904,14 +909,14 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         std::vector<uint8_t> enabled(front0.size() + back0.size(), 0);
         if (!enabled.empty()) {
             const TrimDev h = setupDevice(ix, device, error);
-            if (!h) return -1;
+            if (!h) return kTrimDeviceFailed;
             for (size_t lo = 0; lo < nCheck; lo += batchReads) {
                 const size_t hi = std::min(nCheck, lo + batchReads);
                 double up;
                 edgeBatch(reads, lo, hi, resident != nullptr, eb);
-                if (!devOk(edgeCall(h.get(), resident, reads, lo, hi, eb, DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr, enabled.data(), tms, &up) == 0,
+                if (!devOk(edgeCall(h.get(), resident, residentBase, reads, lo, hi, eb, DP_TRIM_MODE_DETERMINE, 0, p.adapterThreshold, nullptr, nullptr, enabled.data(), tms, &up) == 0,
                            h.get(), error))
-                    return -1;
+                    return kTrimDeviceFailed;
                 res.k_determine_ms += tms[1];
             }
         }
@@ -928,7 +933,7 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
     TrimDev h(nullptr, dp_trim_release);
     if (nA) {
         h = setupDevice(ix, device, error);
-        if (!h) return -1;
+        if (!h) return kTrimDeviceFailed;
     }
     for (size_t lo = 0; lo < reads.size(); lo += batchReads) {
         const double t0 = now();
@@ -940,8 +945,8 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         recs.resize(2 * eligible.size(), dp_trim_rec{kEdgeSize, 0, 0, 0, 0, 0});  // (no adapters at all: what findMatches returns)
         if (h && !eb.reads.empty()) {
             double up;
-            if (!devOk(edgeCall(h.get(), resident, reads, lo, hi, eb, DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms, &up) == 0, h.get(), error))
-                return -1;
+            if (!devOk(edgeCall(h.get(), resident, residentBase, reads, lo, hi, eb, DP_TRIM_MODE_TRIM, 3, 0, recs.data() + 2 * at, counts.data(), nullptr, tms, &up) == 0, h.get(), error))
+                return kTrimDeviceFailed;
             res.upload_ms += tms[0];
             res.kernel_ms += tms[1];
             res.download_ms += tms[2];
@@ -955,7 +960,8 @@ int runTrim(ReadSet& reads, const ReadSet& front0, const ReadSet& back0, const T
         MidPlan mp;
         std::vector<int32_t> seedCounts;
         std::vector<TrimMidRec> midRecs;
-        if (!midBuildPlan(reads, p, mp, error) || !midDevice(h.get(), resident, reads, ix, p, mp, seedCounts, midRecs, res, error)) return -1;
+        if (!midBuildPlan(reads, p, mp, error)) return -1;
+        if (!midDevice(h.get(), resident, residentBase, reads, ix, p, mp, seedCounts, midRecs, res, error)) return kTrimDeviceFailed;
         TrimMidInput mid;
         mid.seedCounts = seedCounts.data();
         mid.nChunks = seedCounts.size();

@@ -1,6 +1,6 @@
 // The arithmetic of `downpore map` that decides what the device is asked to do (host_map.cpp: runMap and its workers), as plain
 // functions on numbers, strings and the ABI's plain structs: the 32-bit limits, the circular join chunks, the packed upload's layout,
-// the chunk schedule, a Mapper batch's layout and device ids, a window request's scan items and the reverse strand's fix-up, the shards' seed-window merge and the dense
+// the chunk schedule, a Mapper batch's layout and device ids (a trimmed batch's raw ids too), a window request's scan items and the reverse strand's fix-up, the shards' seed-window merge and the dense
 // index estimate.  No device call, no environment, no thread: tests/native/map_plan_check.cpp holds every function here to the
 // oracle's Mapper, to rules written out a second time or to brute force, without a GPU.
 #pragma once
@@ -114,6 +114,20 @@ inline MapPacked mapBatchLayout(const i64* readOff, size_t nReads) {
     return mapPackedLayout(std::vector<i64>(), std::vector<std::string>(), readOff, nReads, false);
 }
 inline uint32_t mapBatchReadId(uint32_t firstPaired, uint32_t read, bool reverse) { return firstPaired + 2 * read + (reverse ? 1u : 0u); }
+// A batch that is trimmed first goes behind the head raw and unpaired (dp_reads_replace_tail_packed): raw read r is device read
+// base + r with base = firstPaired, and that is the id the trim's resident calls and dp_reads_respan_tail_rc are given - the eligible
+// reads' id list, the middle stage's chunk spans, and the spans trimmedReadSet cut from the raw reads.  Starts and lengths stay.
+inline uint32_t mapTailId(uint32_t base, uint32_t read) { return base + read; }
+inline std::vector<uint32_t> mapTailIds(const std::vector<uint32_t>& reads, uint32_t base) {
+    std::vector<uint32_t> ids(reads.size());
+    for (size_t i = 0; i < reads.size(); i++) ids[i] = mapTailId(base, reads[i]);
+    return ids;
+}
+inline std::vector<dp_read_span> mapTailSpans(const std::vector<dp_read_span>& cut, uint32_t base) {
+    std::vector<dp_read_span> spans(cut);
+    for (dp_read_span& sp : spans) sp.read = mapTailId(base, sp.read);
+    return spans;
+}
 
 // ---- chunk schedule mapping.go:79-96, canonical generation order; sequence after sequence, the chunk ids running on.  Sequence sq
 // is device read sq, its join chunk device read T + joinOf[sq].

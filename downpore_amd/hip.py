@@ -98,6 +98,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_index_build_sparse", "dp_index_borrow", "dp_index_info", "dp_device_memory", "dp_query_candidates",
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
            "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan", "dp_reads_respan_rc", "dp_reads_replace_tail_packed_rc", "dp_ctx_refresh_shared",
+           "dp_reads_replace_tail_packed", "dp_reads_respan_tail_rc",
            "dp_debug_chain_paths"]
 
 _lib = None
@@ -223,12 +224,10 @@ class Context:
         ln = lens.astype(np.int64)
         self.read_len = np.concatenate([ln[:first_paired], np.repeat(ln[first_paired:], 2)])
 
-    def replace_tail_packed_rc(self, keep, packed, lens, pinned=True):
-        """dp_reads_replace_tail_packed_rc: the device reads [0, keep) stay, everything behind them becomes the batch (packed, lens)
-        as (forward, reverse complement) pairs.  Borrowing contexts need refresh_shared() afterwards."""
+    def _replace_tail(self, call, keep, packed, lens, pinned):
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        self.L.dp_reads_replace_tail_packed_rc.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        call.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         self.L.dp_host_alloc.restype = C.c_void_p
         self.L.dp_host_alloc.argtypes = [C.c_size_t]
         self.L.dp_host_free.argtypes = [C.c_void_p]
@@ -240,11 +239,31 @@ class Context:
             C.memmove(blk, packed.ctypes.data, packed.size)
             ptr = blk
         try:
-            self._chk(self.L.dp_reads_replace_tail_packed_rc(self.h, keep, ptr, lens.ctypes.data, len(lens)))
+            self._chk(call(self.h, keep, ptr, lens.ctypes.data, len(lens)))
         finally:
             if blk:
                 self.L.dp_host_free(blk)
-        self.read_len = np.concatenate([np.asarray(self.read_len[:keep], dtype=np.int64), np.repeat(lens.astype(np.int64), 2)])
+        return lens.astype(np.int64)
+
+    def replace_tail_packed_rc(self, keep, packed, lens, pinned=True):
+        """dp_reads_replace_tail_packed_rc: the device reads [0, keep) stay, everything behind them becomes the batch (packed, lens)
+        as (forward, reverse complement) pairs.  Borrowing contexts need refresh_shared() afterwards."""
+        ln = self._replace_tail(self.L.dp_reads_replace_tail_packed_rc, keep, packed, lens, pinned)
+        self.read_len = np.concatenate([np.asarray(self.read_len[:keep], dtype=np.int64), np.repeat(ln, 2)])
+
+    def replace_tail_packed(self, keep, packed, lens, pinned=True):
+        """dp_reads_replace_tail_packed: replace_tail_packed_rc without the reverse strands - device read keep + r is batch read r."""
+        ln = self._replace_tail(self.L.dp_reads_replace_tail_packed, keep, packed, lens, pinned)
+        self.read_len = np.concatenate([np.asarray(self.read_len[:keep], dtype=np.int64), ln])
+
+    def respan_tail_rc(self, keep, spans):
+        """dp_reads_respan_tail_rc: the reads behind `keep` replaced by the (forward, reverse complement) pairs of spans of themselves -
+        uint32 [n, 3] = (device read >= keep, start, len), any order, a read any number of times.  The head stays byte for byte;
+        borrowing contexts need refresh_shared() afterwards."""
+        sp = np.ascontiguousarray(spans, dtype=np.uint32).reshape(-1, 3)
+        self.L.dp_reads_respan_tail_rc.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        self._chk(self.L.dp_reads_respan_tail_rc(self.h, keep, sp.ctypes.data if len(sp) else None, len(sp)))
+        self.read_len = np.concatenate([np.asarray(self.read_len[:keep], dtype=np.int64), np.repeat(sp[:, 2].astype(np.int64), 2)])
 
     def refresh_shared(self, owner):
         """dp_ctx_refresh_shared: a borrowing context takes its owner's read set again after a tail replace."""

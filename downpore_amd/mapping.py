@@ -75,7 +75,8 @@ class Mapper:
     """A reference opened once, batches of reads mapped against it: `with Mapper(ref) as m: paf, err, stats = m.map(reads)`.
     The reference's sequences and join chunks, its value table, seeds, chunk scan and index are made by the constructor and stay on
     the device; map(reads) sends the batch alone and returns what map_reads(ref, reads, ...) returns, text for text.  Arguments as
-    map_reads takes them (no trim: that path stays map_reads').  One map() at a time per mapper; DpError on use after close()."""
+    map_reads takes them, its trim among them, per batch: map(raw, trim=dict(front=..., back=..., ...)) trims the batch first on the
+    device's copy, as map_reads(ref, raw, trim=...) does.  One map() at a time per mapper; DpError on use after close()."""
 
     def __init__(self, ref, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
                  index="auto", all_sequences=False):
@@ -86,6 +87,8 @@ class Mapper:
         H.dph_mapper_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         H.dph_mapper_map.restype = C.c_void_p
         H.dph_mapper_map.argtypes = [C.c_void_p, C.c_void_p]
+        H.dph_mapper_map_trim.restype = C.c_void_p
+        H.dph_mapper_map_trim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         H.dph_mapper_close.argtypes = [C.c_void_p]
         _result_types(H)
         p = np.array([1 if circular else 0, k, query_size, min_length, chunk_size, seed_rate, layout, 1 if all_sequences else 0], dtype=np.int64)
@@ -95,14 +98,30 @@ class Mapper:
             raise DpError("dph_mapper_open: " + H.dph_last_error(None).decode())
         self.h = h
 
-    def map(self, reads):
-        """-> (paf, stderr_text, stats) exactly as map_reads returns them for (ref, reads)."""
-        if not self.h:
+    def map(self, reads, trim=None):
+        """-> (paf, stderr_text, stats) exactly as map_reads returns them for (ref, reads), or with trim - the dict map_reads takes,
+        `reads` then being the raw set loaded with min_len=50 - for (ref, reads, trim=trim): the batch goes up once, 2-bit packed,
+        both trim stages run on the device's copy behind the resident reference, and the reads that are mapped are cut from it on
+        the device (dph_mapper_map_trim); stats["trim"] is the trim's TrimResult (keep `reads` alive while it is in use).  A trim
+        refused for its parameters or its input raises DpError and leaves the mapper usable."""
+        trim_block = None if trim is None else _trim_block(trim)  # (refused before any library call)
+        if not getattr(self, "h", None):
             raise DpError("Mapper.map: the mapper is closed")
-        h = self.H.dph_mapper_map(self.h, reads.h)
+        if trim_block is None:
+            h = self.H.dph_mapper_map(self.h, reads.h)
+            if not h:
+                raise DpError("dph_mapper_map: " + self.H.dph_last_error(None).decode())
+            return _take_result(self.H, h)
+        from . import trim as T
+        front, back, tp = trim_block
+        th = C.c_void_p()
+        h = self.H.dph_mapper_map_trim(self.h, reads.h, front.h, back.h, tp.ctypes.data, len(tp), C.byref(th))
         if not h:
-            raise DpError("dph_mapper_map: " + self.H.dph_last_error(None).decode())
-        return _take_result(self.H, h)
+            raise DpError("dph_mapper_map_trim: " + self.H.dph_last_error(None).decode())
+        trim_result = T.TrimResult(T._host(), th)
+        paf, err, stats = _take_result(self.H, h)
+        stats["trim"] = trim_result
+        return paf, err, stats
 
     def close(self):
         if getattr(self, "h", None):

@@ -110,6 +110,10 @@ DP_API int dp_reads_upload_packed_rc(dp_ctx* ctx, const uint8_t* packed, const u
  * imported segments and either reference index stay.  Borrowing contexts may exist but must be idle, and are refused until their
  * dp_ctx_refresh_shared.  DP_ERR_ARG, before anything is touched: keep > dp_reads_count(ctx), a length above 2^31 - 1. */
 DP_API int dp_reads_replace_tail_packed_rc(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_reads);
+/* dp_reads_replace_tail_packed_rc without the reverse strands: the batch goes behind the head unpaired, device read keep + r is host
+ * read r (a mapper's raw batch, which the trim's resident calls then see under the ids keep + r).  Host layout, device layout, what
+ * stays, what is voided, the borrowers' rule and the refusals (by this call's name; at most 2^31 - 1 device reads) are that call's. */
+DP_API int dp_reads_replace_tail_packed(dp_ctx* ctx, uint32_t keep, const uint8_t* packed, const uint32_t* lens, uint32_t n_reads);
 /* Pinned host memory from the library's block cache (kept across contexts up to DP_PIN_CACHE_MB; NULL: none to be had). */
 DP_API void* dp_host_alloc(size_t bytes);
 DP_API void dp_host_free(void* p);
@@ -728,6 +732,15 @@ DP_API int dp_reads_respan(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_ou
  * the reference's value table before its reads arrive; dp_reads_upload_rc leaves that table in place and so does this call (the
  * histogram, which counted the old set, is dropped as dp_reads_upload_rc drops it). */
 DP_API int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32_t n_out, uint32_t first_paired);
+/* The device reads behind the first `keep` replaced by the pairs (span, reverse complement) of n_out spans of those same reads: device
+ * read keep + 2 i is span i, keep + 2 i + 1 its reverse strand, bases as dp_reads_respan_rc makes them, layout as above.  The head
+ * - bytes and table entries of the reads [0, keep) - is not touched.  Spans may come in any order and name a read any number of times;
+ * n_out = 0 leaves the head alone.  The new tail is made beside the old one and copied into place once the old one has been read, so
+ * source and destination may overlap as they like.  Borrowing contexts, what stays and what is voided: as
+ * dp_reads_replace_tail_packed_rc.  Refused, each with a message that starts with the call's name, and with nothing changed:
+ * keep > dp_reads_count(ctx), a span that names a read of the head, a span outside its read, more than 2^31 - 1 device reads
+ * (DP_ERR_ARG); a context that borrows its reads, a pending dp_reads_upload_rc_begin (DP_ERR_STATE). */
+DP_API int dp_reads_respan_tail_rc(dp_ctx* ctx, uint32_t keep, const dp_read_span* spans, uint32_t n_out);
 
 #ifdef __cplusplus
 }

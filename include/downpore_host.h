@@ -202,9 +202,21 @@ DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
  *                   time per mapper: a second, concurrent one returns NULL (state error) at once.  After a batch has failed with a
  *                   device error the mapper is broken and every later call returns that first error without touching the device; a
  *                   batch refused for its arguments leaves it usable.  The handle is independent of the mapper and of `reads`.
+ * dph_mapper_map_trim  dph_mapper_map with `trim` in front of it, per batch: reads is the raw read set (loaded with trim's minimum
+ *                   length 50); front / back, trim_params[n_trim] and *trim_out are as dph_map_run_trim documents them; the result
+ *                   handle is of dph_mapper_map's kind, and its PAF and stderr text are byte for byte dph_map_run_trim's for (ref,
+ *                   reads, front, back, trim_params) with the mapper's parameters.  The batch crosses the link once, 2-bit packed: it
+ *                   goes behind the resident head unpaired (dp_reads_replace_tail_packed), both trim stages run on that copy under
+ *                   the ids behind the head, and dp_reads_respan_tail_rc cuts the trimmed set (minimum length: the mapper's
+ *                   params[3]) from it with its reverse strands; the head is not touched.  Adapters are determined per batch.  Bad
+ *                   arguments return NULL with a text that starts "dph_mapper_map_trim: bad arguments" and leave the mapper
+ *                   usable; so does a trim that fails for its parameters or its input (k outside 3..8, chunk_size <= 100 with the
+ *                   middle stage, no read long enough), whether or not the raw batch had gone up.  A device error breaks the mapper
+ *                   as in dph_mapper_map.  *trim_out = NULL on every failure.
  * dph_mapper_close  gives everything back: worker contexts, then the main context, then the pinned block.  NULL is ignored. */
 DPH_API void* dph_mapper_open(void* ref, const int64_t* params, int n_params, int device);
 DPH_API void* dph_mapper_map(void* mapper, void* reads);
+DPH_API void* dph_mapper_map_trim(void* mapper, void* reads, void* front, void* back, const int64_t* trim_params, int n_trim, void** trim_out);
 DPH_API void dph_mapper_close(void* mapper);
 
 /* ---- `downpore trim`, edge stage (commands/trim.go:32-50, trim/trim.go:272-513, sequence/seqio.go:375-523) --------------------

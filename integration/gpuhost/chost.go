@@ -429,18 +429,16 @@ type TrimParams struct {
 	FlushSeeds                                           int
 }
 
-// RunMapTrim is RunMap with `downpore trim` in front, on one upload (dph_map_run_trim): reads = the raw read set opened with minLen 50,
-// front / back = the adapter files opened with minLen 0.  The reads go up once, packed; the trim runs on the device's copy; the PAF is
-// what RunMap prints for the read set `trim` would write, read back with minLen = p.MinLength.  The second result is the trim's log
-// (without the line about writing).  The parameter blocks and the handle slot live in this frame for the length of the call, and the
-// four read sets are kept from their finalizers until it has returned.
-func RunMapTrim(ref, reads, front, back *Reads, tp TrimParams, p MapParams, device int) (*MapResult, string, error) {
-	b := func(v bool) C.int64_t {
-		if v {
-			return 1
-		}
-		return 0
+func boolParam(v bool) C.int64_t {
+	if v {
+		return 1
 	}
+	return 0
+}
+
+// trimParamBlock is the trim parameter block of dph_map_run_trim and dph_mapper_map_trim: 8 values, or 14 with the middle stage's.
+func trimParamBlock(tp TrimParams) ([14]C.int64_t, C.int) {
+	b := boolParam
 	trim := [14]C.int64_t{C.int64_t(tp.K), C.int64_t(tp.CheckReads), C.int64_t(tp.AdapterThreshold), C.int64_t(tp.ExtraEndTrim), b(tp.TagAdapters),
 		b(tp.RequirePairs), b(tp.DetermineAdapters), C.int64_t(tp.Verbosity), b(tp.Middle), C.int64_t(tp.ChunkSize), C.int64_t(tp.MiddleThreshold),
 		C.int64_t(tp.ExtraMiddleTrim), b(tp.DiscardMiddle), C.int64_t(tp.FlushSeeds)}
@@ -448,6 +446,17 @@ func RunMapTrim(ref, reads, front, back *Reads, tp TrimParams, p MapParams, devi
 	if tp.Middle {
 		nTrim = 14
 	}
+	return trim, nTrim
+}
+
+// RunMapTrim is RunMap with `downpore trim` in front, on one upload (dph_map_run_trim): reads = the raw read set opened with minLen 50,
+// front / back = the adapter files opened with minLen 0.  The reads go up once, packed; the trim runs on the device's copy; the PAF is
+// what RunMap prints for the read set `trim` would write, read back with minLen = p.MinLength.  The second result is the trim's log
+// (without the line about writing).  The parameter blocks and the handle slot live in this frame for the length of the call, and the
+// four read sets are kept from their finalizers until it has returned.
+func RunMapTrim(ref, reads, front, back *Reads, tp TrimParams, p MapParams, device int) (*MapResult, string, error) {
+	b := boolParam
+	trim, nTrim := trimParamBlock(tp)
 	params := [8]C.int64_t{b(p.Circular), C.int64_t(p.K), C.int64_t(p.QuerySize), C.int64_t(p.MinLength), C.int64_t(p.ChunkSize), C.int64_t(p.SeedRate), 0, b(p.AllSequences)}
 	// (as in RunMap: cgo pins what the pointer arguments point to for the length of the call, and the library keeps none of them)
 	var th unsafe.Pointer
@@ -458,6 +467,36 @@ func RunMapTrim(ref, reads, front, back *Reads, tp TrimParams, p MapParams, devi
 	if h == nil {
 		runtime.KeepAlive(reads)
 		return nil, "", lastError(nil, "dph_map_run_trim")
+	}
+	defer C.dph_map_free(h)
+	var n C.int64_t
+	pp := C.dph_map_paf(h, &n)
+	res := &MapResult{PAF: text(pp, n)}
+	pe := C.dph_map_errtext(h, &n)
+	res.ErrText = string(text(pe, n))
+	pl := C.dph_trim_errtext(th, &n)
+	trimLog := string(text(pl, n))
+	C.dph_trim_free(th)
+	runtime.KeepAlive(reads) // (the trim handle points into the raw read set)
+	return res, trimLog, nil
+}
+
+// MapTrim is Map with `downpore trim` in front, per batch (dph_mapper_map_trim): reads = the raw batch opened with minLen 50, front /
+// back = the adapter files opened with minLen 0.  The batch goes up once, packed, behind the mapper's resident reference; the trim runs
+// on the device's copy; the PAF is what RunMapTrim prints for (ref, reads, front, back, tp) with the mapper's parameters.  The second
+// result is the trim's log.  A trim refused for its parameters or its input returns an error and leaves the mapper usable.
+func (m *Mapper) MapTrim(reads, front, back *Reads, tp TrimParams) (*MapResult, string, error) {
+	if m.h == nil {
+		return nil, "", errors.New("Mapper.MapTrim: the mapper is closed")
+	}
+	trim, nTrim := trimParamBlock(tp)
+	var th unsafe.Pointer
+	h := C.dph_mapper_map_trim(m.h, reads.h, front.h, back.h, &trim[0], nTrim, &th)
+	runtime.KeepAlive(front)
+	runtime.KeepAlive(back)
+	if h == nil {
+		runtime.KeepAlive(reads)
+		return nil, "", lastError(nil, "dph_mapper_map_trim")
 	}
 	defer C.dph_map_free(h)
 	var n C.int64_t
