@@ -37,6 +37,7 @@ struct PinBuf {
 struct dp_kindex;
 
 struct FindState;
+struct AlignState;
 struct dp_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -147,6 +148,7 @@ struct dp_ctx {
     bool cons_huge = false;                  // a window of an earlier round did not fit the large consensus layout: the huge one follows it from now on
     uint32_t cons_prev_pairs = 0;            // pairs of the previous round's chaining stage (output bound of a pending one)
     struct FindState* find_state = nullptr;  // dp_overlap.hip: the chaining stage between launch and evaluation
+    struct AlignState* align_state = nullptr;  // dp_align.hip: the results of the last dp_align_spans (host memory) and its events
     bool timing_on = true;
     uint64_t round_serial = 0;
 
@@ -337,6 +339,7 @@ int dp_find_overlaps_impl(dp_ctx* ctx, const int32_t* q_segs, const uint64_t* q_
 int dp_map_windows_impl(dp_ctx* ctx, const int32_t* w_segs, const uint64_t* w_off, const uint32_t* w_len, uint32_t nw, int k,
                         dp_chain_batch* out, int phase = 2, int32_t* thr_io = nullptr);
 void dp_find_state_free(dp_ctx* ctx);
+void dp_align_state_free(dp_ctx* ctx);  // dp_align.hip
 bool dp_find_pending(const dp_ctx* ctx);
 // where the chaining stage's final chains are: MRec.off indexes these two arrays (a side, b side)
 static inline const void* dp_chain_a(const dp_ctx* ctx) { return ctx->chains_packed ? ctx->d_ma.p : ctx->d_sa.p; }

@@ -774,6 +774,9 @@ struct MapStats {
     // index, queries per regime (4/8-ladder, 16-ladder, exact count, more than 512 sets)
     int64_t index_layout = 0, index_bytes = 0, dense_estimate = 0, device_total = 0, hits = 0, index_builds = 0;
     int64_t regimes[4] = {0, 0, 0, 0};
+    // base-level alignment of a Mapper's batch (dph_map_align_info): lines, aligned, over max_edits, out of range, DP cells computed,
+    // band doublings, kernel microseconds, trace-back bytes; zeros for a batch mapped without it
+    int64_t align[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 // Runs the whole command on HIP device `device`: reference = first sequence of refSet (top-level, cache=false; every sequence of it
 // with p.allSequences), reads top-level.  paf receives the PAF lines (read order), errText the reference's stderr lines.
@@ -796,6 +799,10 @@ int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& er
 // minLength) gives the set that is mapped, and dp_reads_respan_tail_rc cuts it from the raw tail with its reverse strands.  paf /
 // errText are runMap's for (refSet, raw, trim).  A trim that fails for its parameters or its input leaves the mapper usable.
 int mapperMap(Mapper* m, MapTrim& trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error);
+// mapperMap with NM and cg tags behind every line (dph_mapper_map_align): trim == nullptr maps `reads`, else trim->raw is
+// trimmed first as above.  maxEdits outside 1 .. 32768 is refused before the batch touches anything and leaves the mapper usable.
+int mapperMapAlign(Mapper* m, const ReadSet* reads, MapTrim* trim, int64_t maxEdits, std::string& paf, std::string& errText, MapStats* stats,
+                   std::string& error);
 void mapperClose(Mapper* m);
 
 // ---- trim.Trimmer, edge stage / `downpore trim` (trim/trim.go, commands/trim.go; host_trim.cpp) -------------------------------

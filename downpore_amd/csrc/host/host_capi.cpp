@@ -1021,6 +1021,53 @@ extern "C" void* dph_mapper_map_trim(void* mapperH, void* readsH, void* frontH, 
     *trim_out = th;
     return h;
 }
+// dph_mapper_map (no trim arguments) or dph_mapper_map_trim with NM and cg tags behind every line of the batch: align_params[0] = max_edits.
+extern "C" void* dph_mapper_map_align(void* mapperH, void* readsH, void* frontH, void* backH, const int64_t* trim_params, int n_trim, void** trim_out,
+                                      const int64_t* align_params, int n_align) {
+    if (trim_out) *trim_out = nullptr;
+    MapperH* mh = (MapperH*)mapperH;
+    const bool noTrim = !frontH && !backH && !trim_params && n_trim == 0;
+    MapTrim mt;
+    if (!mh || !readsH || !align_params || n_align != 1 || (!noTrim && (!frontH || !backH || !trim_out || !trimParamsFrom(trim_params, n_trim, mt.params)))) {
+        g_err = "dph_mapper_map_align: bad arguments (no trim: front, back and trim_params NULL and n_trim 0, else 8 or 14 trim parameters; one align parameter)";
+        return nullptr;
+    }
+    if (align_params[0] < 1 || align_params[0] > 32768) {
+        g_err = "dph_mapper_map_align: bad arguments: max_edits " + std::to_string((long long)align_params[0]) + " (1 .. 32768)";
+        return nullptr;
+    }
+    if (mh->busy.exchange(true)) {
+        g_err = "dph_mapper_map_align: DP_ERR_STATE: another call is mapping on this mapper (one batch at a time per mapper)";
+        return nullptr;
+    }
+    MapH* h = new MapH();
+    TrimH* th = noTrim ? nullptr : new TrimH();
+    if (th) {
+        th->reads = &((ReadsH*)readsH)->set;
+        mt.raw = th->reads;
+        mt.front = &((ReadsH*)frontH)->set;
+        mt.back = &((ReadsH*)backH)->set;
+        mt.res = &th->res;
+    }
+    std::string error;
+    const int rc = mapperMapAlign(mh->m, &((ReadsH*)readsH)->set, th ? &mt : nullptr, align_params[0], h->paf, h->err, &h->st, error);
+    mh->busy.store(false);
+    if (rc != 0) {
+        g_err = error;
+        delete h;
+        delete th;
+        return nullptr;
+    }
+    if (th) *trim_out = th;
+    return h;
+}
+// out: lines, aligned, over max_edits, out of range, DP cells computed, band doublings, kernel microseconds, trace-back bytes
+extern "C" int dph_map_align_info(void* h, int64_t* out, int cap) {
+    const MapStats& s = ((MapH*)h)->st;
+    const int n = std::max(0, std::min(cap, 8));
+    for (int i = 0; i < n; i++) out[i] = s.align[i];
+    return n;
+}
 extern "C" const char* dph_trim_output(void* h, int64_t* n) {
     *n = (int64_t)((TrimH*)h)->res.out.size();
     return ((TrimH*)h)->res.out.data();

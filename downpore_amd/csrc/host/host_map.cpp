@@ -14,6 +14,7 @@
 
 #include "dph.hpp"
 #include "host_util.hpp"
+#include "align_plan.hpp"
 #include "map_plan.hpp"
 
 #define DPH_CORO_IMPLEMENTATION  // (the switch routine itself lives in this translation unit)
@@ -728,6 +729,10 @@ struct MapRun {
     std::vector<std::string> out;  // per read, in read order, whoever mapped it
     std::vector<int> nmaps;
     std::vector<LoopStats> lstats;
+    // ---- base-level alignment of a Mapper's batch (alignMappings): off unless the batch asked for it
+    bool alignOn = false;
+    uint32_t maxEdits = (uint32_t)kAlignMaxEditsDefault;
+    std::vector<std::vector<AlignLine>> lines;  // per read, the mappings behind out[r]'s lines in their order
     // ---- the owners, declared in the reverse of the order they must go in (everything above outlives them all):
     PinnedBlock pinned;     // 7. freed last: the packing thread writes it
     ThreadJoiner concat;    // 6. the packing / concatenating thread (it touches no context)
@@ -783,6 +788,7 @@ struct MapRun {
     int refreshWorkers();
     int replaceTail();
     int replaceTailTrimmed(MapTrim& t);
+    int alignMappings();
     void writeText();
     void writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped);
 };
@@ -1333,6 +1339,13 @@ void MapWorker::retireTasks() {
             Task& t = *live[i];
             std::string& o = R.out[t.read];
             for (Mapping* mm : t.results) o += M.asString(*mm, R.reads().names[t.read], t.L) + "\n";
+            if (R.alignOn)  // what the alignment needs of each line: its spans are worked out once every read has retired
+                for (Mapping* mm : t.results) {
+                    AlignLine ln;
+                    ln.L = t.L, ln.queryOffset = mm->QueryOffset, ln.queryInset = mm->QueryInset;
+                    ln.start = mm->Start, ln.end = mm->End, ln.rc = mm->RC, ln.ref = mm->ref;
+                    R.lines[t.read].push_back(ln);
+                }
             R.nmaps[t.read] = (int)t.results.size();
             coroRelease(t.at);
             freeStacks.push_back(t.stack);
@@ -1425,6 +1438,7 @@ int MapRun::runWorkers() {
     if (stats) stats->t_setup_s = tLoop0 - tRun0;
     out.assign(reads().size(), std::string());
     nmaps.assign(reads().size(), 0);
+    lines.assign(alignOn ? reads().size() : 0, std::vector<AlignLine>());
     nThreads = shards.v.empty() ? plannedThreads(reads().size()) : 1;
     lstats.assign(nThreads, LoopStats());
     if (workers.v.size() < nThreads) workers.v.resize(nThreads, nullptr);  // (a Mapper's contexts of earlier batches stay in their slots)
@@ -1481,6 +1495,62 @@ void MapRun::collectStats() {
     stats->t_scan_s = tScan;
     stats->t_chain_s = tChain;
     stats->t_host_s = (wallNow() - tLoop0) - tScan - tChain;
+}
+
+// ---- NM and cg tags behind every line of the batch.  The mappings are finished and both strands of every read and the
+// reference sequences are resident: each line's spans (align_plan.hpp) become one item of dp_align_spans on the main context - forward
+// read firstPaired + 2 r, its reverse strand + 1, reference sequence c - and the tags go behind the line's column 12.  A line out of
+// range or over max_edits keeps its twelve columns and is counted.
+int MapRun::alignMappings() {
+    const double t0 = wallNow();
+    std::vector<dp_align_item> items;
+    std::vector<int64_t> itemOf;  // per line in (read, line) order: its item, -1 = out of range
+    i64 nLines = 0, outOfRange = 0, aligned = 0, over = 0;
+    for (size_t r = 0; r < lines.size(); r++)
+        for (const AlignLine& ln : lines[r]) {
+            nLines++;
+            AlignSpan sp;
+            if (!alignSpanOf(ln, refLens[(size_t)ln.ref], p.circular, sp)) {
+                outOfRange++;
+                itemOf.push_back(-1);
+                continue;
+            }
+            itemOf.push_back((int64_t)items.size());
+            items.push_back(alignItemOf(sp, J.firstPaired, (uint32_t)r, ln.rc, ln.ref));
+        }
+    dp_align_batch ab;
+    memset(&ab, 0, sizeof ab);
+    if (!items.empty())
+        if (int rc = dp_align_spans(ctx.c, items.data(), (uint32_t)items.size(), maxEdits, p.circular ? 1 : 0, &ab)) return failed(ctx.c, rc);
+    size_t at = 0;
+    std::string tagged;
+    for (size_t r = 0; r < lines.size(); r++) {
+        if (lines[r].empty()) continue;
+        tagged.clear();
+        size_t b = 0;
+        for (size_t li = 0; li < lines[r].size(); li++, at++) {
+            const size_t e = out[r].find('\n', b);
+            tagged.append(out[r], b, e - b);
+            if (itemOf[at] >= 0) {
+                const dp_align_rec& rec = ab.recs[itemOf[at]];
+                if (rec.nm >= 0) {
+                    tagged += alignTags(rec.nm, ab.runs + rec.run_off, rec.n_runs);
+                    aligned++;
+                } else {
+                    over++;
+                }
+            }
+            tagged += '\n';
+            b = e + 1;
+        }
+        out[r].swap(tagged);
+    }
+    if (stats) {
+        const int64_t v[8] = {nLines, aligned, over, outOfRange, (int64_t)ab.cells, (int64_t)ab.doublings, (int64_t)(1e3 * ab.kernel_ms), (int64_t)ab.tb_bytes};
+        for (int i = 0; i < 8; i++) stats->align[i] = v[i];
+    }
+    if (prof) fprintf(stderr, "[map align] %lld lines, %zu items, %.1f ms (kernels %.1f ms)\n", (long long)nLines, items.size(), 1e3 * (wallNow() - t0), ab.kernel_ms);
+    return 0;
 }
 
 void MapRun::writeCounts(i64 mapped, i64 multiple, i64 total, i64 unmapped) {
@@ -1563,6 +1633,7 @@ void MapRun::bindBatch(const ReadSet& batch, bool trimmed) {
     stats->k_scan_ms = stats->k_map_ms = stats->map_bytes = stats->scan_bytes = 0;
     stats->t_setup_s = stats->t_scan_s = stats->t_chain_s = stats->t_host_s = 0;
     for (int64_t& r : stats->regimes) r = 0;
+    for (int64_t& a : stats->align) a = 0;
 }
 // the batch packed into the pinned block, put behind the head on the device, and the worker contexts told about it
 int MapRun::packBatch() {
@@ -1660,12 +1731,19 @@ Mapper* mapperOpen(const ReadSet& refSet, const MapParams& p, int device, std::s
 
 namespace {
 // one batch: trim == nullptr maps `reads` as they are; with a trim `reads` is the raw set (trim->raw)
-int mapperBatch(Mapper* m, const ReadSet& reads, MapTrim* trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
+int mapperBatch(Mapper* m, const ReadSet& reads, MapTrim* trim, const int64_t* maxEdits, std::string& paf, std::string& errText, MapStats* stats,
+                std::string& error) {
     if (m->brokenRc) {
         error = m->brokenText;
         return m->brokenRc;
     }
+    if (maxEdits && (*maxEdits < 1 || *maxEdits > kAlignMaxEditsLimit)) {  // (refused before the batch touches anything)
+        error = "map align: max_edits " + std::to_string((long long)*maxEdits) + " (1 .. 32768)";
+        return DP_ERR_ARG;
+    }
     MapRun& R = m->R;
+    R.alignOn = maxEdits != nullptr;
+    R.maxEdits = maxEdits ? (uint32_t)*maxEdits : (uint32_t)kAlignMaxEditsDefault;
     R.bindBatch(reads, trim != nullptr);
     int rc = 0;
     if (R.noChunks) {  // (the trim still runs: its result is the caller's, and the counts are of the trimmed set)
@@ -1673,11 +1751,12 @@ int mapperBatch(Mapper* m, const ReadSet& reads, MapTrim* trim, std::string& paf
     } else {
         if ((rc = trim ? R.replaceTailTrimmed(*trim) : R.replaceTail()) == 0 && (rc = R.runWorkers()) == 0) {
             R.collectStats();
-            R.writeText();
+            if (!R.alignOn || (rc = R.alignMappings()) == 0) R.writeText();
         }
     }
     R.upSetP = R.readsP = &m->none;  // (the batch's read set is the caller's: nothing of it is held beyond this call)
     R.trimmedSet = ReadSet();
+    R.lines.clear();
     if (rc) {
         error = m->error;
         if (rc != DP_ERR_ARG) {  // a batch refused for its arguments (or its trim's) leaves nothing the next batch does not replace; anything else leaves the device state unknown
@@ -1693,10 +1772,14 @@ int mapperBatch(Mapper* m, const ReadSet& reads, MapTrim* trim, std::string& paf
 }
 }  // namespace
 int mapperMap(Mapper* m, const ReadSet& reads, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
-    return mapperBatch(m, reads, nullptr, paf, errText, stats, error);
+    return mapperBatch(m, reads, nullptr, nullptr, paf, errText, stats, error);
 }
 int mapperMap(Mapper* m, MapTrim& trim, std::string& paf, std::string& errText, MapStats* stats, std::string& error) {
-    return mapperBatch(m, *trim.raw, &trim, paf, errText, stats, error);
+    return mapperBatch(m, *trim.raw, &trim, nullptr, paf, errText, stats, error);
+}
+int mapperMapAlign(Mapper* m, const ReadSet* reads, MapTrim* trim, int64_t maxEdits, std::string& paf, std::string& errText, MapStats* stats,
+                   std::string& error) {
+    return mapperBatch(m, trim ? *trim->raw : *reads, trim, &maxEdits, paf, errText, stats, error);
 }
 
 void mapperClose(Mapper* m) { delete m; }

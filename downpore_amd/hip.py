@@ -88,6 +88,16 @@ class IndexInfo(C.Structure):  # dp_index_info_t
                 ("device_bytes", C.c_uint64), ("entries", C.c_uint64), ("queries", C.c_uint64 * 4)]
 
 
+class AlignBatch(C.Structure):  # dp_align_batch
+    _fields_ = [("n", C.c_uint32), ("recs", C.c_void_p), ("runs", C.POINTER(C.c_uint32)), ("n_runs", C.c_uint64), ("cells", C.c_uint64),
+                ("tb_bytes", C.c_uint64), ("doublings", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+ALIGN_ITEM = np.dtype([("q_read", np.uint32), ("q_off", np.uint32), ("q_len", np.uint32), ("t_read", np.uint32), ("t_off", np.uint32),
+                       ("t_len", np.uint32)])  # dp_align_item
+ALIGN_REC = np.dtype([("nm", np.int32), ("n_runs", np.uint32), ("run_off", np.uint64)])  # dp_align_rec
+
+
 #: every entry point include/downpore_hip.h declares (checked by the CPU-side symbol test)
 SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_priority", "dp_ctx_destroy", "dp_last_error", "dp_reads_upload", "dp_reads_packed",
            "dp_reads_count", "dp_reads_total_bases", "dp_kmer_histogram", "dp_kmer_values", "dp_round_begin", "dp_scan", "dp_scan_prepare", "dp_scan_reads", "dp_index_build",
@@ -99,7 +109,7 @@ SYMBOLS = ["dp_version", "dp_ctx_create", "dp_ctx_create_shared", "dp_ctx_set_pr
            "dp_trim_setup", "dp_trim_edges", "dp_trim_release", "dp_trim_error", "dp_trim_scan_chunks",
            "dp_trim_chunk_segments", "dp_trim_search", "dp_trim_edges_resident", "dp_trim_scan_chunks_resident", "dp_reads_respan", "dp_reads_respan_rc", "dp_reads_replace_tail_packed_rc", "dp_ctx_refresh_shared",
            "dp_reads_replace_tail_packed", "dp_reads_respan_tail_rc",
-           "dp_debug_chain_paths"]
+           "dp_debug_chain_paths", "dp_align_spans"]
 
 _lib = None
 
@@ -594,3 +604,19 @@ class Context:
         self._chk(self.L.dp_map_windows_shard(self.h, ws.ctypes.data, wo.ctypes.data, wl.ctypes.data, len(wo) - 1, k, phase, t.ctypes.data,
                                               C.byref(b)))
         return self._chains(b), t
+
+    # ---- base-level alignment of spans of the resident reads
+    def align_spans(self, items, max_edits=4096, circular=False):
+        """dp_align_spans: items = rows (q_read, q_off, q_len, t_read, t_off, t_len) over the resident reads.  Returns dict nm (int32
+        [n], -1 = over max_edits), cigar (list of strings, "" where nm is -1), runs (list of uint32 arrays len << 2 | op), cells,
+        tb_bytes, doublings, kernel_ms."""
+        it = np.ascontiguousarray(np.asarray(items, dtype=np.uint32).reshape(-1, 6))
+        b = AlignBatch()
+        self.L.dp_align_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(AlignBatch)]
+        self._chk(self.L.dp_align_spans(self.h, it.ctypes.data if len(it) else None, len(it), int(max_edits), 1 if circular else 0, C.byref(b)))
+        n = b.n
+        recs = np.frombuffer(C.string_at(b.recs, n * ALIGN_REC.itemsize), dtype=ALIGN_REC) if n else np.zeros(0, dtype=ALIGN_REC)
+        runs = _arr(b.runs, b.n_runs, np.uint32)
+        per = [runs[int(r["run_off"]):int(r["run_off"]) + int(r["n_runs"])] for r in recs]
+        return dict(nm=recs["nm"].astype(np.int32), runs=per, cigar=["".join("%d%s" % (int(x) >> 2, "MID?"[int(x) & 3]) for x in pr) for pr in per],
+                    cells=int(b.cells), tb_bytes=int(b.tb_bytes), doublings=int(b.doublings), kernel_ms=float(b.kernel_ms))

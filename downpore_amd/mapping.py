@@ -11,6 +11,8 @@ MAP_STAT_FIELDS = ["n_chunks", "n_seeds", "n_windows", "n_chains", "n_batches", 
 #: dph_map_index_info's values, in order (the "index" entry of the stats)
 MAP_INDEX_FIELDS = ["layout", "index_bytes", "dense_estimate", "device_total", "hits", "index_builds", "q_ladder8", "q_ladder16",
                     "q_exact", "q_big"]
+#: dph_map_align_info's values, in order (the "align" entry of map_aligned's stats)
+MAP_ALIGN_FIELDS = ["lines", "aligned", "over_max_edits", "out_of_range", "cells", "band_doublings", "kernel_us", "traceback_bytes"]
 INDEX_LAYOUTS = {"auto": 0, "dense": 1, "sparse": 2}
 
 
@@ -54,8 +56,8 @@ def _result_types(H):
     H.dph_map_index_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 
 
-def _take_result(H, h):
-    """(paf, stderr_text, stats) of a map handle, which is freed."""
+def _take_result(H, h, align=False):
+    """(paf, stderr_text, stats) of a map handle, which is freed; align: with stats["align"] (dph_map_align_info)."""
     n = C.c_int64(0)
     paf = C.string_at(H.dph_map_paf(h, C.byref(n)), n.value).decode()
     err = C.string_at(H.dph_map_errtext(h, C.byref(n)), n.value).decode()
@@ -63,11 +65,18 @@ def _take_result(H, h):
     H.dph_map_stats(h, st.ctypes.data)
     ix = np.zeros(len(MAP_INDEX_FIELDS), dtype=np.int64)
     got = H.dph_map_index_info(h, ix.ctypes.data, len(ix))
+    al = np.zeros(len(MAP_ALIGN_FIELDS), dtype=np.int64)
+    if align:
+        H.dph_map_align_info.restype = C.c_int
+        H.dph_map_align_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        H.dph_map_align_info(h, al.ctypes.data, len(al))
     H.dph_map_free(h)
     stats = dict(zip(MAP_STAT_FIELDS, st.tolist()))
     info = dict(zip(MAP_INDEX_FIELDS[:got], (int(v) for v in ix[:got])))
     info["layout"] = {1: "dense", 2: "sparse"}.get(info.get("layout", 0), "none")
     stats["index"] = info
+    if align:
+        stats["align"] = dict(zip(MAP_ALIGN_FIELDS, (int(v) for v in al)))
     return paf, err, stats
 
 
@@ -121,6 +130,39 @@ class Mapper:
         trim_result = T.TrimResult(T._host(), th)
         paf, err, stats = _take_result(self.H, h)
         stats["trim"] = trim_result
+        return paf, err, stats
+
+    def map_aligned(self, reads, trim=None, max_edits=4096):
+        """map(reads, trim) with the base-level alignment of every PAF line behind its column 12: "\\tNM:i:<edit distance>\\tcg:Z:<CIGAR>"
+        (unit costs, M for matches and mismatches, gaps at the left end of a tie), computed on the device over the reads
+        and the reference it holds anyway (dph_mapper_map_align).  Columns 1 - 12, the lines' order, the stderr text and every other
+        stats key are map's.  A line whose edit distance exceeds max_edits (1 .. 32768) or whose coordinates lie outside its read or
+        sequence gets no tags; stats["align"] counts them (MAP_ALIGN_FIELDS).  A refused max_edits raises DpError and leaves the mapper
+        usable."""
+        trim_block = None if trim is None else _trim_block(trim)
+        if isinstance(max_edits, bool) or not isinstance(max_edits, (int, np.integer)) or not 1 <= int(max_edits) <= 32768:
+            raise DpError("Mapper.map_aligned: max_edits must be an integer in 1 .. 32768, not %r" % (max_edits,))
+        if not getattr(self, "h", None):
+            raise DpError("Mapper.map_aligned: the mapper is closed")
+        H = self.H
+        H.dph_mapper_map_align.restype = C.c_void_p
+        H.dph_mapper_map_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int]
+        ap = np.array([int(max_edits)], dtype=np.int64)
+        th = C.c_void_p()
+        if trim_block is None:
+            h = H.dph_mapper_map_align(self.h, reads.h, None, None, None, 0, C.byref(th), ap.ctypes.data, 1)
+        else:
+            front, back, tp = trim_block
+            h = H.dph_mapper_map_align(self.h, reads.h, front.h, back.h, tp.ctypes.data, len(tp), C.byref(th), ap.ctypes.data, 1)
+        if not h:
+            raise DpError("dph_mapper_map_align: " + H.dph_last_error(None).decode())
+        trim_result = None
+        if trim_block is not None:
+            from . import trim as T
+            trim_result = T.TrimResult(T._host(), th)
+        paf, err, stats = _take_result(H, h, align=True)
+        if trim_result is not None:
+            stats["trim"] = trim_result
         return paf, err, stats
 
     def close(self):
@@ -182,3 +224,14 @@ def map_reads(ref, reads, circular=True, k=11, query_size=1000, min_length=500, 
     if trim_result is not None:
         stats["trim"] = trim_result
     return paf, err, stats
+
+
+def map_reads_aligned(ref, reads, circular=True, k=11, query_size=1000, min_length=500, chunk_size=10000, seed_rate=40, device=0,
+                      index="auto", all_sequences=False, trim=None, max_edits=4096):
+    """map_reads with NM and cg tags behind every PAF line (Mapper.map_aligned): opens a Mapper on `ref`, maps the one batch `reads`
+    and closes it.  Because it goes through a Mapper, DP_MAP_SHARDS > 1 and the ASCII upload keys (DP_TUNE=map_ascii_upload /
+    map_async_upload) are not available to it: they are refused by name, as Mapper refuses them.  Returns (paf, stderr_text, stats)
+    with stats["align"]."""
+    with Mapper(ref, circular=circular, k=k, query_size=query_size, min_length=min_length, chunk_size=chunk_size, seed_rate=seed_rate,
+                device=device, index=index, all_sequences=all_sequences) as m:
+        return m.map_aligned(reads, trim=trim, max_edits=max_edits)

@@ -742,6 +742,42 @@ DP_API int dp_reads_respan_rc(dp_ctx* ctx, const dp_read_span* spans, uint32_t n
  * (DP_ERR_ARG); a context that borrows its reads, a pending dp_reads_upload_rc_begin (DP_ERR_STATE). */
 DP_API int dp_reads_respan_tail_rc(dp_ctx* ctx, uint32_t keep, const dp_read_span* spans, uint32_t n_out);
 
+/* ---- base-level alignment of spans of the resident reads (dp_align.hip) ------------------------------------------
+ * Item x aligns Q = bases [q_off, q_off + q_len) of resident read q_read (m = q_len) globally against T = t_len bases of resident read
+ * t_read from t_off on (n = t_len); with circular != 0 target base j is base (t_off + j) mod len(t_read), so a target may run over the
+ * read's end and t_off may equal the read's length.  The bases are the 2-bit codes the device holds.
+ * recs[x].nm is the unit-cost edit distance D[m][n] (D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (Q[i-1] != T[j-1]),
+ * D[i-1][j] + 1, D[i][j-1] + 1)), or -1 when it exceeds max_edits (1 .. 32768): such an item has no runs.  Otherwise runs[run_off ..
+ * run_off + n_runs) is the canonical CIGAR, one word len << 2 | op per run, op 0 = M (match or mismatch), 1 = I (consumes the query),
+ * 2 = D: the walk back from (m, n) over the FULL matrix that takes, at (i, j), M if i, j > 0 and D[i-1][j-1] + (Q[i-1] != T[j-1]) ==
+ * D[i][j], else I if i > 0 and D[i-1][j] + 1 == D[i][j], else D; equal neighbours merged.  The device computes a band of diagonals
+ * that starts 64 beyond |m - n| on either side and doubles while the result does not prove that every optimal path lies inside it;
+ * the proof makes the banded walk the full matrix's.  Inside the limits nothing but a device error fails: there is no "did not fit".
+ * cells: DP cells computed over all attempts; doublings: band doublings over all items; tb_bytes: trace-back bytes written (2 bits
+ * per cell, from dp_dev_malloc blocks sized against the device's free memory, pairs going in groups); kernel_ms: the kernels' time.
+ * The result arrays are host memory of the context, valid until its next dp_align_spans or its end.
+ * DP_ERR_ARG before any launch: max_edits outside 1 .. 32768; an item with a read id beyond the set, q_len or t_len 0 or above 2^20, a
+ * query span outside its read, a target span outside its read (linear) or longer than it / starting beyond its end (circular).
+ * DP_ERR_STATE: a borrowing context that has not refreshed, a pending dp_reads_upload_rc_begin. */
+typedef struct {
+    uint32_t q_read, q_off, q_len, t_read, t_off, t_len;
+} dp_align_item;
+typedef struct {
+    int32_t nm;       /* -1: over max_edits */
+    uint32_t n_runs;
+    uint64_t run_off; /* into dp_align_batch.runs */
+} dp_align_rec;
+typedef struct {
+    uint32_t n;
+    const dp_align_rec* recs; /* [n] */
+    const uint32_t* runs;     /* [n_runs] len << 2 | op */
+    uint64_t n_runs;
+    uint64_t cells, tb_bytes;
+    uint32_t doublings;
+    double kernel_ms;
+} dp_align_batch;
+DP_API int dp_align_spans(dp_ctx* ctx, const dp_align_item* items, uint32_t n, uint32_t max_edits, int circular, dp_align_batch* out);
+
 #ifdef __cplusplus
 }
 #endif

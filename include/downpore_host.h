@@ -213,10 +213,30 @@ DPH_API int dph_map_index_info(void* m, int64_t* out, int cap);
  *                   usable; so does a trim that fails for its parameters or its input (k outside 3..8, chunk_size <= 100 with the
  *                   middle stage, no read long enough), whether or not the raw batch had gone up.  A device error breaks the mapper
  *                   as in dph_mapper_map.  *trim_out = NULL on every failure.
+ * dph_mapper_map_align  dph_mapper_map, or dph_mapper_map_trim, with the base-level alignment of every PAF line of the batch behind its
+ *                   column 12: "\tNM:i:<edit distance>\tcg:Z:<CIGAR>" (what `minimap2 -c` prints; M covers matches and mismatches).
+ *                   front == back == trim_params == NULL and n_trim == 0 (trim_out is then not written beyond a NULL) mean no trim;
+ *                   otherwise those arguments and *trim_out are exactly dph_mapper_map_trim's.  align_params[0] = max_edits (1 ..
+ *                   32768; 4096 is the usual choice), n_align == 1.  The rule, per line: the query is columns 3 - 4 of
+ *                   the read ('-': their reverse complement), the target End - Start bases from Start (plus the sequence's length when
+ *                   the mapper is circular and that is negative; positions wrap on a circular mapper); NM is the unit-cost edit distance
+ *                   of the two, the CIGAR the canonical walk dp_align_spans documents (gaps go to the left end of a tie).  A line whose
+ *                   coordinates lie outside its read or sequence, or whose spans exceed 2^20 bases, gets no tags (out of range), as
+ *                   does a line whose NM exceeds max_edits.  Columns 1 - 12, the order of the lines, the stderr text and dph_map_stats
+ *                   are dph_mapper_map's (dph_mapper_map_trim's), byte for byte.  The alignment runs on the device (dp_align_spans)
+ *                   over the reads and reference the mapper holds there anyway.  Bad arguments (a max_edits outside its range among
+ *                   them) return NULL with a text that starts "dph_mapper_map_align: bad arguments" and leave the mapper usable; a
+ *                   device error breaks it, as in dph_mapper_map.
+ * dph_map_align_info  out[0..7] of a map handle = PAF lines, lines aligned, lines over max_edits, lines out of range, DP cells
+ *                   computed, band doublings, kernel microseconds, trace-back bytes written; all zero for a handle made without
+ *                   alignment.  Writes at most cap values; returns how many it wrote.
  * dph_mapper_close  gives everything back: worker contexts, then the main context, then the pinned block.  NULL is ignored. */
 DPH_API void* dph_mapper_open(void* ref, const int64_t* params, int n_params, int device);
 DPH_API void* dph_mapper_map(void* mapper, void* reads);
 DPH_API void* dph_mapper_map_trim(void* mapper, void* reads, void* front, void* back, const int64_t* trim_params, int n_trim, void** trim_out);
+DPH_API void* dph_mapper_map_align(void* mapper, void* reads, void* front, void* back, const int64_t* trim_params, int n_trim, void** trim_out,
+                                   const int64_t* align_params, int n_align);
+DPH_API int dph_map_align_info(void* m, int64_t* out, int cap);
 DPH_API void dph_mapper_close(void* mapper);
 
 /* ---- `downpore trim`, edge stage (commands/trim.go:32-50, trim/trim.go:272-513, sequence/seqio.go:375-523) --------------------

@@ -510,3 +510,36 @@ func (m *Mapper) MapTrim(reads, front, back *Reads, tp TrimParams) (*MapResult, 
 	runtime.KeepAlive(reads) // (the trim handle points into the raw read set)
 	return res, trimLog, nil
 }
+
+// AlignInfo is what dph_map_align_info reports of a batch mapped with MapAlign.
+type AlignInfo struct {
+	Lines, Aligned, OverMaxEdits, OutOfRange, Cells, BandDoublings, KernelMicros, TracebackBytes int64
+}
+
+// MapAlign is Map with the base-level alignment of every PAF line behind its column 12 (dph_mapper_map_align): "\tNM:i:<edit
+// distance>\tcg:Z:<CIGAR>", unit costs, M for matches and mismatches, computed on the device over the reads and the reference the mapper
+// holds there anyway.  Columns 1 - 12, the order of the lines and the stderr text are Map's.  A line whose edit distance exceeds
+// maxEdits (1 .. 32768; 4096 is the usual choice) or whose coordinates lie outside its read or sequence gets no tags; the AlignInfo
+// counts them.  A refused maxEdits returns an error and leaves the mapper usable.
+func (m *Mapper) MapAlign(reads *Reads, maxEdits int) (*MapResult, *AlignInfo, error) {
+	if m.h == nil {
+		return nil, nil, errors.New("Mapper.MapAlign: the mapper is closed")
+	}
+	align := [1]C.int64_t{C.int64_t(maxEdits)}
+	var th unsafe.Pointer
+	h := C.dph_mapper_map_align(m.h, reads.h, nil, nil, nil, 0, &th, &align[0], 1)
+	runtime.KeepAlive(reads)
+	if h == nil {
+		return nil, nil, lastError(nil, "dph_mapper_map_align")
+	}
+	defer C.dph_map_free(h)
+	var n C.int64_t
+	pp := C.dph_map_paf(h, &n)
+	res := &MapResult{PAF: text(pp, n)}
+	pe := C.dph_map_errtext(h, &n)
+	res.ErrText = string(text(pe, n))
+	var v [8]C.int64_t
+	C.dph_map_align_info(h, &v[0], 8)
+	info := &AlignInfo{int64(v[0]), int64(v[1]), int64(v[2]), int64(v[3]), int64(v[4]), int64(v[5]), int64(v[6]), int64(v[7])}
+	return res, info, nil
+}
