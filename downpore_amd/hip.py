@@ -316,7 +316,24 @@ class Context:
     def kmer_values(self, k):
         out = np.zeros(4 ** k, dtype=np.float64)
         self._chk(self.L.dp_kmer_values(self.h, k, out.ctypes.data))
+        self.n_values = len(out)
         return out
+
+    def values_codes(self, width):
+        """The resident table of kmer_values as one code per k-mer (dp_values_download_codes8 for width 1, dp_values_download_codes for
+        width 2): its own count where it has a value, 0 where it has none, clamped to 255 / 65535.  -> (codes, total, overflow): total =
+        the sum of all counts, overflow = 1 when a valued k-mer counts more than 254 / 65535.  DpError for a table that was uploaded."""
+        if width not in (1, 2):
+            raise ValueError("values_codes: width is 1 or 2")
+        n = getattr(self, "n_values", 0)
+        if not n:
+            raise DpError("values_codes: no value table resident")
+        call = self.L.dp_values_download_codes8 if width == 1 else self.L.dp_values_download_codes
+        call.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        codes = np.zeros(n, dtype=np.uint8 if width == 1 else np.uint16)
+        total, overflow = C.c_uint64(0), C.c_int(0)
+        self._chk(call(self.h, codes.ctypes.data, n, C.byref(total), C.byref(overflow)))
+        return codes, int(total.value), int(overflow.value)
 
     # ---- A18: the parallel part of AddSingleSeeds
     def single_seed_candidates(self, read, k, seed_rate):
@@ -383,6 +400,7 @@ class Context:
         v = np.ascontiguousarray(values, dtype=np.float64)
         self.L.dp_values_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         self._chk(self.L.dp_values_upload(self.h, v.ctypes.data, len(v)))
+        self.n_values = len(v)
 
     def select_seeds(self, windows, k, num_seeds):
         """windows: (read, start, length in bases) rows -> uint32 [n, num_seeds] k-mers in insertion-list order."""
